@@ -127,7 +127,56 @@ def valu_profile(world):
             "cycles_per_valu_instr": big.get("cycles_per_valu_instr")}
 
 
-def measure_sfm3(size, steps, warmup, dev=None, pencil=0, listener=True, lanczos=False):
+DUMP_BUDGET = 60 << 20           # --dump-outputs: bytes of array data in all (the .npy headers stay well inside 64 MB)
+DUMP_SEED = 20240917             # the fixed sample of cells when a full copy of the grids would not fit the budget
+
+
+def _save_finite(out, name, v, dtype):
+    """One output as <name>.npy, finite: the library's "no value" is NaN (cvhip.h), so a floating array is written with its
+    non-finite entries set to 0 and <name>_valid.npy beside it (1 where the value was finite, 0 where it was not)."""
+    v = np.asarray(v)
+    if np.issubdtype(v.dtype, np.floating):
+        ok = np.isfinite(v)
+        np.save(out / f"{name}_valid.npy", ok.astype(dtype))
+        v = np.where(ok, v, 0)
+    np.save(out / f"{name}.npy", v.astype(dtype))
+
+
+def dump_outputs(out_dir, grids, extra=None):
+    """--dump-outputs: what the timed path handed its caller in its last step, as finite float32 / float64 .npy files in
+    out_dir.  grids: name -> (xy int32 (H, W, 2), corr f32 (H, W)), torch tensors or numpy arrays, all of one shape;
+    written as <name>_xy.npy / <name>_corr.npy + <name>_corr_valid.npy (float32: coordinates below 2^24 are exact; (-1, -1)
+    = no match).  When their full copies would not fit DUMP_BUDGET, the same fixed, seeded sample of cells is taken from
+    every grid and its flat row-major indices are written to sample_index.npy.  extra: name -> small array, written as
+    float64 (+ <name>_valid.npy for floating arrays)."""
+    import torch
+
+    out = Path(out_dir)
+    out.mkdir(parents=True, exist_ok=True)
+    extra = {k: np.asarray(v) for k, v in (extra or {}).items()}
+    budget = DUMP_BUDGET - sum(2 * 8 * v.size for v in extra.values())
+    idx = None
+    if grids:
+        shapes = {tuple(xy.shape[:2]) for xy, _ in grids.values()}
+        if len(shapes) != 1:
+            raise ValueError(f"--dump-outputs: grids of different shapes {shapes}")
+        n = int(np.prod(next(iter(shapes))))
+        if 16 * n * len(grids) > budget:   # x, y, score, score valid: 16 B per cell and grid; the index 8 B per sampled cell
+            k = budget // (16 * len(grids) + 8)
+            idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=k, replace=False))
+            np.save(out / "sample_index.npy", idx.astype(np.float64))
+    for name, (xy, corr) in grids.items():
+        xy, corr = torch.as_tensor(xy), torch.as_tensor(corr)
+        if idx is not None:
+            sel = torch.from_numpy(idx).to(xy.device)
+            xy, corr = xy.reshape(-1, 2)[sel], corr.reshape(-1)[sel]
+        _save_finite(out, f"{name}_xy", xy.cpu().numpy(), np.float32)
+        _save_finite(out, f"{name}_corr", corr.cpu().numpy(), np.float32)
+    for name, v in extra.items():
+        _save_finite(out, name, v, np.float64)
+
+
+def measure_sfm3(size, steps, warmup, dev=None, pencil=0, listener=True, lanczos=False, dump_dir=None):
     """BASELINE config 5 ("3-image perspective SFM: ORB + RANSAC F-matrix on GPU + pairwise dense correlation"):
     three synthetic size^2 perspective views, resident in HBM as u8 pyramids; one step = per-level ORB on the three
     images, 3 x matcher (threshold 48), 3 x perspective find_ransac (device RANSAC + LM refit), 3 x dense correlation
@@ -164,6 +213,16 @@ def measure_sfm3(size, steps, warmup, dev=None, pencil=0, listener=True, lanczos
             acc[k] = acc.get(k, 0.0) + v
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    if dump_dir is not None:   # the last step's results, as reconstruct_pairs returned them
+        grids, extra = {}, {}
+        for (i, j), e in res["pairs"].items():
+            if e["f"] is not None:
+                extra[f"pair{i}{j}_f"] = e["f"]
+                extra[f"pair{i}{j}_inliers"] = e["inliers"]
+            extra[f"pair{i}{j}_matches"] = e["matches"]
+            if "xy" in e:
+                grids[f"pair{i}{j}"] = (e["xy"], e["corr"])
+        dump_outputs(dump_dir, grids, extra)
     for (i, j), e in res["pairs"].items():
         n_pairs += e["f"] is not None
         matches.append(int(len(e["matches"])))
@@ -188,7 +247,7 @@ def measure_sfm3(size, steps, warmup, dev=None, pencil=0, listener=True, lanczos
 def bench_sfm3(args):
     """`--config sfm3`: config 5 as a line of its own (a secondary line, not the headline metric)."""
     size = 2048 if args.size == 4096 else args.size
-    m = measure_sfm3(size, args.steps, args.warmup, pencil=args.pencil)
+    m = measure_sfm3(size, args.steps, args.warmup, pencil=args.pencil, dump_dir=args.dump_outputs)
     print(json.dumps({
         "metric": f"Mpixels/s dense correlation, 3 x {size}x{size} perspective views (3 pairs), config 5", "secondary": True,
         "value": m["dense_mpixels_per_s"], "unit": "Mpixels/s", "n_gpus": 1, "steps": args.steps,
@@ -232,7 +291,14 @@ def main():
                     help="profiling runs (scripts/_run_prof.sh): skip the untimed candidate-counting step, so that every step of the "
                          "run launches the same kernel instantiations; the line then carries no candidate count")
     ap.add_argument("--sweep-tilts", default="3,10,30,45,60,90", help="tilts (degrees) of geometry_sweep")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy in float32 / float64 "
+                         "(grids larger than the 64 MB budget: a fixed, seeded sample of their cells)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
     if args.config == "sfm3":
         return bench_sfm3(args)
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -421,6 +487,8 @@ def main():
         step(timed=last)
     fence()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:   # the last timed step's grid, before anything below reuses out_xy / out_corr
+        dump_outputs(args.dump_outputs, {"grid": (out_xy, out_corr)})
     l0_ms = sum(a.elapsed_time(b) for a, b in l0_events) / max(len(l0_events), 1)
     ktimes_last = pc.get_kernel_times()
     search_ms_local = ktimes_last["search"]["ms"]  # the box-kernel launches of ONE step (the first pass runs the
