@@ -47,6 +47,8 @@ SIGNATURES = {
     "cvhip_complete_packed": (C.c_int, [_vp, C.c_int, _vp, _vp]),
     "cvhip_triangulate_affine": (C.c_int, [_vp, _vp, _vp, C.c_uint64, C.POINTER(C.c_uint64)]),
     "cvhip_extend_tracks": (C.c_int, [_vp, _vp, C.c_uint64, _u32, _vp, _vp, _vp, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "cvhip_triangulate_perspective": (C.c_int, [_vp, _vp, C.c_uint64, _u32, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp,
+                                                C.POINTER(C.c_uint64), _vp, _vp, _vp, PROGRESS_FN, _vp]),
     "cvhip_ctx_set_row_shard": (C.c_int, [_vp, _u32, _u32, ALLGATHER_FN, _vp]),
     "cvhip_ctx_set_row_band": (C.c_int, [_vp, _u32, _u32]),
     "cvhip_rccl_unique_id": (C.c_int, [_vp]),

@@ -233,3 +233,43 @@ def match_count(xy) -> int:
     if hasattr(xy, "data_ptr"):
         return int((xy[..., 0] >= 0).sum().item())
     return int((np.asarray(xy)[..., 0] >= 0).sum())
+
+
+def reconstruct_perspective_surface(device, pyramids, pairs_result, cameras, bundle_adjustment: bool = True,
+                                    progress=None):
+    """The perspective tail of `reconstruct` for n views: reconstruct_dense's pair loop (reconstruction.rs:668-730) -
+    for img1 in order, for every later img2 whose pair has an F in `pairs_result` (reconstruct_pairs' output; its
+    dense grids are not needed, dense=False is enough), the dense correlation and extend_tracks into one track table
+    (triangulation.rs:1330-1419) - then triangulate_all (:817-865) with the given cameras [(K, R, t)] per image: DLT
+    points, filter_outliers and, unless bundle_adjustment is False (--no-bundle-adjustment), the bundle adjustment.
+    Departures, as stated in DESIGN.md: the cameras come from the caller (no P3P / recover_pose), merge_tracks
+    (:1421-1540, run after every img1 at :728) is skipped, and max_points (a random subset) stays with the caller.
+    -> dict: surface (triangulation.Surface), tracks (the whole table), timings_ms per stage (dense, tracks,
+    triangulate)."""
+    from . import triangulation
+
+    rec = ImageReconstruction(device, ProjectionMode.Perspective)
+    n = len(pyramids)
+    shapes = [(int(p[0].shape[1]), int(p[0].shape[0])) for p in pyramids]
+    tri = triangulation.PerspectiveTriangulation(n, shapes, bundle_adjustment=bundle_adjustment)
+    mode = correlation.ProjectionMode(int(ProjectionMode.Perspective))
+    for i in range(n):
+        for j in range(i + 1, n):
+            entry = pairs_result["pairs"].get((i, j))
+            if entry is None or entry["f"] is None:
+                continue  # no matches between the images: no correlation (reconstruction.rs:702-707)
+            pc = correlation.PointCorrelations(device, shapes[i], shapes[j], entry["f"], mode)
+            try:
+                def run(pc=pc, pi=pyramids[i], pj=pyramids[j]):
+                    steps = correlation.optimal_scale_steps(*shapes[i])
+                    for s in range(steps + 1):
+                        k = steps - s
+                        pc.correlate_images(pi[k], pj[k], 1.0 / float(1 << k))
+                    return pc.complete()
+
+                rec._timed("dense", run)
+                rec._timed("tracks", lambda pc=pc, i=i, j=j: tri.add_image_pair_dense(i, j, pc))
+            finally:
+                pc.close()
+    surface = rec._timed("triangulate", lambda: tri.triangulate_all(device, cameras, progress=progress))
+    return {"surface": surface, "tracks": tri.tracks, "timings_ms": dict(rec.timings_ms)}

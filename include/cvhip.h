@@ -39,6 +39,7 @@ extern "C" {
 #define CVHIP_ERR_UNSUPPORTED (-3) /* valid in the reference, not supported here (documented) */
 #define CVHIP_ERR_NOMEM (-4)
 #define CVHIP_ERR_NO_MODEL (-5)    /* RANSAC: "Not enough matches" / "No reliable matches found" (RansacError) */
+#define CVHIP_ERR_NO_SURFACE (-6)  /* perspective triangulation: the reference's TriangulationError messages */
 
 typedef struct cvhip_device cvhip_device;
 typedef struct cvhip_ctx cvhip_ctx;
@@ -180,6 +181,37 @@ int cvhip_triangulate_affine(cvhip_ctx *ctx, double *out_points3d, uint32_t *out
 int cvhip_extend_tracks(cvhip_ctx *ctx, const int32_t *track_p1, uint64_t n_tracks, uint32_t max_dimension2,
                         int32_t *out_track_p2, uint32_t *out_new_p1, uint32_t *out_new_p2, uint64_t cap,
                         uint64_t *out_n_new);
+
+/* Dense consumer, perspective pipeline, last step - replaces PerspectiveTriangulation::triangulate_all (triangulation.rs:817-865)
+ * with the cameras given by the caller (pose recovery, recover_pose / find_projection_matrix :1033-1278, and merge_tracks
+ * :1421-1540 are not part of it):
+ *  - triangulate_track (:867-911) for every track: the 2k x 4 DLT system of its k seen views in camera order, the right
+ *    singular vector of the smallest singular value (nalgebra's `svd` sorts them in decreasing order, so the reference's
+ *    `v_t.row(nrows - 1)`); rejected if k < 2 or |w| < 1e-4; the point is xyz / w.
+ *  - filter_outliers (:1559-1593): dropped if a seen view has point_depth <= 0 (:492-500), if it has no pair of rays
+ *    (rays shorter than f64::EPSILON skipped, min_ray_angle_cos :996-1031) or if the smallest |cos| between its rays is
+ *    above cos(0.5 deg); the survivors keep their order (`retain`).
+ *  - bundle_adjustment != 0 (the reference's default; --no-bundle-adjustment = 0): BundleAdjustment::optimize
+ *    (:1675-2148) over all survivors and all cameras, with its Levenberg-Marquardt control as written, up to 100
+ *    iterations; every reduction in a fixed order, so two calls give the same bits.
+ * tracks: n x m x 2 int32 (x, y), (-1, -1) where the track has no point in that image.  K, R: m x 9 row-major, t: m x 3
+ * (X_cam = R X + t).  As for the reference's initial pair (:727-740) the DLT projects with K [R | t] as given, while
+ * filter_outliers and the bundle adjustment use the Camera that Camera::from_matrix (:414-466, including its 180 degree
+ * branch) derives - whose angle is atan2(2 sin, cos) of R's as the reference writes it.
+ * Out: out_points (n_kept x 3), out_index (n_kept: the row of each kept track in `tracks`) - both with room for n -,
+ * per camera the refined r (3), t (3) and projection K [R | t] (12) (each may be NULL), *out_n = n_kept.  Optional
+ * (NULL = not wanted): *out_iterations = the LM iterations run, out_history[100] = 1 accepted / 0 rejected step per
+ * iteration (0xFF after the last), out_residual_norms[2] = |residual| before and after (NaN without bundle adjustment).
+ * progress (may be NULL): iter / 100 before every iteration (:2054-2056), on the calling thread.
+ * Errors: CVHIP_ERR_NO_SURFACE "Failed to compute delta vector" (the LU solve of S fails) / "Levenberg-Marquardt failed
+ * to converge" (100 iterations); CVHIP_ERR_UNSUPPORTED above CVHIP_TRIANGULATE_MAX_CAMERAS cameras.  Tracks, outputs:
+ * host or device pointers. */
+#define CVHIP_TRIANGULATE_MAX_CAMERAS 8
+int cvhip_triangulate_perspective(cvhip_device *dev, const int32_t *tracks, uint64_t n, uint32_t m, const double *K,
+                                  const double *R, const double *t, int bundle_adjustment, double *out_points,
+                                  uint64_t *out_index, double *out_r, double *out_t, double *out_projection,
+                                  uint64_t *out_n, uint32_t *out_iterations, uint8_t *out_history,
+                                  double *out_residual_norms, cvhip_progress_fn progress, void *user);
 
 /* Row sharding (multi-GPU): restrict the SEARCH passes of this context to shard `num` of `den`
  * equal row chunks of the searched level image: rows [num*rps, min((num+1)*rps, h_level)) with

@@ -1,0 +1,183 @@
+"""Perspective triangulation on the device (cvhip_triangulate_perspective, cybervision_amd/triangulation.py) against the
+CPU restatement (tests/ref_triangulation.py): DLT + filter_outliers on analytic track tables, the bundle adjustment, the
+determinism of its reductions, the errors, and config 5's scene end to end at 512^2 and 2048^2."""
+import time
+
+import numpy as np
+import pytest
+
+import ref_triangulation as rt
+import tri_scenes
+from cybervision_amd import _lib, reconstruction, synth, triangulation
+
+
+def run_device(dev, tracks, cams, bundle_adjustment):
+    m = tracks.shape[1]
+    tri = triangulation.PerspectiveTriangulation(m, [(2048, 2048)] * m, bundle_adjustment=bundle_adjustment)
+    tri.tracks = np.ascontiguousarray(tracks, dtype=np.int32)
+    return tri.triangulate_all(dev, cams)
+
+
+def rel_err(a, b):
+    return np.linalg.norm(np.asarray(a) - np.asarray(b), axis=-1) / np.maximum(np.linalg.norm(np.asarray(b), axis=-1), 1e-300)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("m", [2, 3, 4, 8])
+def test_triangulate_and_filter_match_restatement(gpu_device, m):
+    """triangulate_track + filter_outliers (triangulation.rs:867-911, 1559-1593), no bundle adjustment, ~100 k tracks with
+    1-view tracks, parallel rays (|w| ~ 0), points behind a camera and near-duplicate views: the same kept set in the
+    same order, points to 1e-9.  No track's deciding quantity lies within 1e-9 of its threshold (listed otherwise)."""
+    cams = tri_scenes.rig(m, near_duplicate=m > 2)
+    tracks = tri_scenes.track_table(cams, 100_000, seed=m)
+    close = tri_scenes.near_threshold(tracks, cams)
+    assert len(close) == 0, f"tracks at a threshold: {close[:20].tolist()}"
+    ref_idx, ref_pts, _, _ = rt.triangulate_all(tracks, cams, bundle_adjustment=False)
+    surf = run_device(gpu_device, tracks, cams, False)
+    # every branch is exercised and decides some tracks
+    k = (tracks[..., 0] >= 0).sum(axis=1)
+    kept = np.zeros(len(tracks), dtype=bool)
+    kept[ref_idx] = True
+    assert (k < 2).any() and not kept[k < 2].any()
+    assert 0.3 * len(tracks) < len(ref_idx) < 0.9 * len(tracks)
+    assert np.array_equal(surf.track_index, ref_idx)
+    assert (rel_err(surf.points, ref_pts) <= 1e-9).all(), rel_err(surf.points, ref_pts).max()
+    assert surf.ba_iterations == 0 and np.isnan(surf.ba_residual_norms[0])
+
+
+def _ba_case(dev):
+    _, pert, tracks = tri_scenes.ba_scene(20_000)
+    return pert, tracks, run_device(dev, tracks, pert, True)
+
+
+@pytest.mark.gpu
+def test_bundle_adjustment_matches_restatement(gpu_device):
+    """BundleAdjustment::optimize (:2042-2147) on 20 k tracks, 3 cameras with perturbed poses and integer (sub-pixel
+    noisy) observations: the same number of LM iterations, the same accept / reject sequence, cameras and points to
+    1e-6, the final residual norm to 1e-9.  (As the reference writes the update every step is rejected - see
+    tests/test_triangulation_ref.py - so the sequence is all rejections until the delta test ends the loop.)"""
+    pert, tracks, surf = _ba_case(gpu_device)
+    idx, pts, cams, ba = rt.triangulate_all(tracks, pert, bundle_adjustment=True)
+    assert np.array_equal(surf.track_index, idx)
+    assert surf.ba_iterations == len(ba.history)
+    assert surf.ba_history == [int(h) for h in ba.history]
+    assert (rel_err(surf.points, pts) <= 1e-6).all()
+    for dc, rc in zip(surf.cameras, cams):
+        assert np.allclose(dc.r, rc.r, rtol=1e-6, atol=1e-12)
+        assert np.allclose(dc.t, rc.t, rtol=1e-6, atol=1e-12)
+        assert np.allclose(dc.projection, rc.projection(), rtol=1e-6, atol=1e-9)
+    assert abs(surf.ba_residual_norms[1] - ba.final_residual_norm) <= 1e-9 * ba.final_residual_norm
+
+
+@pytest.mark.gpu
+def test_bundle_adjustment_is_deterministic(gpu_device):
+    """Two runs of the bundle adjustment case give the same bits (fixed-order reductions)."""
+    _, _, a = _ba_case(gpu_device)
+    _, _, b = _ba_case(gpu_device)
+    assert np.array_equal(a.track_index, b.track_index)
+    assert a.points.tobytes() == b.points.tobytes()
+    assert a.ba_history == b.ba_history and a.ba_residual_norms == b.ba_residual_norms
+    for ca, cb in zip(a.cameras, b.cameras):
+        assert ca.r.tobytes() == cb.r.tobytes() and ca.t.tobytes() == cb.t.tobytes()
+
+
+@pytest.mark.gpu
+def test_errors(gpu_device):
+    """Fewer than two views everywhere: every track is rejected (:881-883) and, as in the reference (an empty
+    bundle adjustment returns at :2050), the surface is empty - not an error; the cameras are from_matrix's.  More than
+    CVHIP_TRIANGULATE_MAX_CAMERAS cameras: CVHIP_ERR_UNSUPPORTED.  A progress listener sees iter / 100 (:2054-2056)."""
+    cams = tri_scenes.rig(3)
+    tracks = tri_scenes.track_table(cams, 10_000, seed=9)
+    single = tracks.copy()
+    single[:, 1:] = -1
+    surf = run_device(gpu_device, single, cams, True)
+    assert len(surf.points) == 0 and surf.ba_iterations == 0
+    for dc, (K, R, t) in zip(surf.cameras, cams):
+        rc = rt.Camera.from_matrix(K, R, t)
+        assert np.allclose(dc.r, rc.r, atol=1e-15) and np.allclose(dc.projection, rc.projection(), rtol=1e-14)
+    cams9 = tri_scenes.rig(9)
+    with pytest.raises(_lib.CvhipError) as err:
+        run_device(gpu_device, tri_scenes.track_table(cams9, 1000, seed=1), cams9, False)
+    assert err.value.code == -3
+    pert, btracks = tri_scenes.ba_scene(2000)[1:]
+    seen = []
+    tri = triangulation.PerspectiveTriangulation(3, [(2048, 2048)] * 3)
+    tri.tracks = btracks
+    surf = tri.triangulate_all(gpu_device, pert, progress=seen.append)
+    # one report per pass of the loop: the decided steps, and the last pass, which the delta test ends (:2079-2083)
+    assert seen == [np.float32(i / 100.0) for i in range(surf.ba_iterations + 1)]
+
+
+def ground_truth_depth_error(points, K, size):
+    """|z - Z0(p0)| / Z0(p0) per point, p0 = the point's pixel in view 0 (camera 0 is the identity: z is its depth)."""
+    q = points @ K.T
+    x, y = q[:, 0] / q[:, 2], q[:, 1] / q[:, 2]
+    inside = (x >= 0) & (x < size) & (y >= 0) & (y < size)
+    z0 = synth._sfm_depth(x[inside], y[inside], size)
+    return np.abs(points[inside, 2] - z0) / z0
+
+
+@pytest.mark.gpu
+def test_sfm3_surface_512_matches_restatement(gpu_device):
+    """Config 5 at 512^2: reconstruct_pairs' sparse stage, then reconstruct_perspective_surface with the true cameras
+    and bundle adjustment on; the same track table through the restatement gives the same surface: the same kept set
+    and accept / reject sequence, the final residual norm to 1e-6, points and cameras to 1e-4.  (The reference's
+    update is uphill - tests/test_triangulation_ref.py - and its first step is so large that, on this scene, it lands
+    lower and is accepted: it carries the points ~2000 scene units away, and the rounding of the 18 x 18 solve with
+    them - measured 3.2e-5 at most on the points, 2.5e-7 on the residual - so the bounds here are looser than the
+    1e-6 / 1e-9 of the all-rejected case above.)  The triangulation itself (no bundle adjustment) against the scene's
+    ground truth: median relative depth error below 3 %."""
+    size = 512
+    views, K, poses = synth.make_sfm_views(size)
+    steps = synth.optimal_scale_steps(size, size)
+    pyrs = [synth.box_pyramid(v, steps) for v in views]
+    pairs = reconstruction.reconstruct_pairs(gpu_device, pyrs, dense=False)
+    cams = [(K, R, t) for R, t in poses]
+    out = reconstruction.reconstruct_perspective_surface(gpu_device, pyrs, pairs, cams, bundle_adjustment=True)
+    surf, table = out["surface"], out["tracks"]
+    assert len(table) > 50_000 and len(surf.points) > 0.5 * len(table)
+    idx, pts, rcams, ba = rt.triangulate_all(table, cams, bundle_adjustment=True)
+    assert np.array_equal(surf.track_index, idx)
+    assert surf.ba_history == [int(h) for h in ba.history]
+    assert abs(surf.ba_residual_norms[1] - ba.final_residual_norm) <= 1e-6 * ba.final_residual_norm
+    assert (rel_err(surf.points, pts) <= 1e-4).all(), rel_err(surf.points, pts).max()
+    for dc, rc in zip(surf.cameras, rcams):
+        assert np.allclose(dc.r, rc.r, rtol=1e-4, atol=1e-12) and np.allclose(dc.t, rc.t, rtol=1e-4, atol=1e-12)
+    plain = run_device(gpu_device, table, cams, False)
+    assert np.array_equal(plain.track_index, surf.track_index)
+    err = ground_truth_depth_error(plain.points, K, size)
+    err_ba = ground_truth_depth_error(surf.points, K, size)
+    print(f"512^2: {len(table)} tracks, {len(surf.points)} kept, median depth error {np.median(err):.4f} "
+          f"({np.median(err_ba):.4f} after the bundle adjustment, history {surf.ba_history}), timings {out['timings_ms']}")
+    assert np.median(err) < 0.03
+
+
+@pytest.mark.gpu
+def test_sfm3_surface_2048_properties(gpu_device):
+    """Config 5 at 2048^2 (no restatement: size-independent properties): most tracks kept, the reprojection RMS after
+    the bundle adjustment not above the one before, the median relative depth error of the triangulation (no bundle
+    adjustment) against the ground truth below 2 %; wall time reported.  The RMS is the bundle adjustment's own, taken
+    with Camera::from_matrix's cameras, whose rotation angle is atan2(2 sin, cos) of the given one
+    (tests/test_triangulation_ref.py): ~1.7 px before, so no sub-pixel bound holds for the reference's residual."""
+    size = 2048
+    views, K, poses = synth.make_sfm_views(size)
+    steps = synth.optimal_scale_steps(size, size)
+    pyrs = [synth.box_pyramid(v, steps) for v in views]
+    pairs = reconstruction.reconstruct_pairs(gpu_device, pyrs, dense=False)
+    cams = [(K, R, t) for R, t in poses]
+    t0 = time.perf_counter()
+    out = reconstruction.reconstruct_perspective_surface(gpu_device, pyrs, pairs, cams, bundle_adjustment=True)
+    wall = time.perf_counter() - t0
+    surf, table = out["surface"], out["tracks"]
+    n_obs = int((surf.tracks[..., 0] >= 0).sum())
+    rms_before, rms_after = (v / np.sqrt(n_obs) for v in surf.ba_residual_norms)
+    plain = run_device(gpu_device, table, cams, False)
+    err = ground_truth_depth_error(plain.points, K, size)
+    err_ba = ground_truth_depth_error(surf.points, K, size)
+    print(f"2048^2: {len(table)} tracks, {len(surf.points)} kept ({len(surf.points) / len(table):.3f}), reprojection RMS "
+          f"{rms_before:.4f} -> {rms_after:.4f} px over {n_obs} observations, LM history {surf.ba_history}, median depth "
+          f"error {np.median(err):.4f} ({np.median(err_ba):.4f} after the bundle adjustment), wall {wall:.2f} s, "
+          f"timings {out['timings_ms']}")
+    assert len(surf.points) > 0.5 * len(table)
+    assert rms_after <= rms_before
+    assert np.median(err) < 0.02

@@ -1,0 +1,98 @@
+"""The CPU restatement of the perspective triangulation stage (tests/ref_triangulation.py) on its own: DLT recovery, the
+Rodrigues round trip of Camera::from_matrix and the bundle adjustment's behaviour as the reference writes it."""
+import math
+
+import numpy as np
+import pytest
+
+import ref_triangulation as rt
+import tri_scenes
+
+
+def test_dlt_recovers_noise_free_points():
+    """triangulate_track (triangulation.rs:867-911) on exact (float) projections: the points come back to ~1e-9."""
+    from cybervision_amd import synth
+
+    K, poses = synth.sfm_cameras(2048)
+    cams = [rt.Camera.from_matrix(K, R, t) for R, t in poses]
+    P = np.stack([c.projection() for c in cams])
+    rng = np.random.default_rng(3)
+    X = np.stack([rng.uniform(-0.4, 0.4, 2000), rng.uniform(-0.4, 0.4, 2000), rng.uniform(0.85, 1.0, 2000)], axis=1)
+    tracks = np.zeros((2000, 3, 2))
+    for j in range(3):
+        q = X @ P[j][:, :3].T + P[j][:, 3]
+        tracks[:, j] = q[:, :2] / q[:, 2:3]
+    tracks[:500, 2] = -1.0  # two views only
+    pts, ok, _ = rt.triangulate_tracks(tracks, P)
+    assert ok.all()
+    rel = np.linalg.norm(pts - X, axis=1) / np.linalg.norm(X, axis=1)
+    assert rel.max() < 1e-9, rel.max()
+
+
+AXES = [(0, 0, 1), (1, 0, 0), (0, 1, 0), (1, 1, 0), (1, -2, 3), (0, -1, 1)]
+# 180 degrees only about axes whose matrix_r is exactly symmetric in f64 (s = 0): elsewhere s is ~1e-16, not below
+# f64::EPSILON, and the reference's general branch divides rounding noise by it - no axis to recover
+CASES = [(a, t) for a in AXES for t in (0.0, 1e-3, 0.7, 2.5)] + [(a, math.pi) for a in AXES[:4]]
+
+
+@pytest.mark.parametrize("axis,angle", CASES)
+def test_from_matrix_of_matrix_r(axis, angle):
+    """Camera::from_matrix (:414-466) of matrix_r(theta u) (:475-485).  As the reference writes it, rho (:419-423) is the
+    DIFFERENCE a21 - a12 = 2 sin(theta) u, so the axis comes back but the angle is atan2(2 sin(theta), cos(theta)): the
+    round trip is exact at 0 and at 180 degrees (the branch of :433-461 and its sign convention), not in between."""
+    u = np.asarray(axis, dtype=np.float64)
+    u = u / np.linalg.norm(u)
+    R = rt.matrix_r(u * angle)
+    cam = rt.Camera.from_matrix(np.eye(3), R, np.zeros(3))
+    if angle == 0.0:
+        assert (cam.r == 0).all()
+    elif angle == math.pi:
+        assert abs(np.linalg.norm(cam.r) - math.pi) < 1e-12
+        expected = u * math.pi
+        if expected[0] < 0 or (abs(expected[0]) < rt.EPS and expected[1] < 0) or \
+                (abs(expected[0]) < rt.EPS and abs(expected[1]) < rt.EPS and expected[2] < 0):
+            expected = -expected
+        assert np.allclose(cam.r, expected, atol=1e-12)
+        assert np.allclose(rt.matrix_r(cam.r), R, atol=1e-12)
+    else:
+        assert np.allclose(cam.r, u * math.atan2(2.0 * math.sin(angle), math.cos(angle)), atol=1e-12)
+
+
+def test_exact_180_degree_rotation_takes_its_branch():
+    """diag(1, -1, -1) is exactly 180 degrees about x: s = 0 and c = -1, so from_matrix takes the branch of :433-461."""
+    cam = rt.Camera.from_matrix(np.eye(3), np.diag([1.0, -1.0, -1.0]), np.zeros(3))
+    assert np.allclose(cam.r, [math.pi, 0.0, 0.0], atol=0)
+    assert np.allclose(rt.matrix_r(cam.r), np.diag([1.0, -1.0, -1.0]), atol=1e-15)
+
+
+def test_bundle_adjustment_as_written_reaches_found_without_raising_the_residual():
+    """BundleAdjustment::optimize (:2042-2147) on a perturbed scene: it reaches "found" and never raises the residual.
+    As the reference writes it the step is ADDED (update_params, :2012-2040) although delta = (J^T J + mu I)^-1 J^T r with
+    r = projected - observed (:1781-1786) points uphill, so every step is rejected and mu grows until the delta test
+    (:2079-2083) ends the loop - the surface keeps the input points and cameras.  The same loop with the step's sign
+    turned does lower the residual, which is what pins the diagnosis."""
+    _, pert, tracks = tri_scenes.ba_scene(1500)
+    cams = tri_scenes.ref_cameras(pert)
+    idx, pts = rt.triangulate_and_filter(tracks, cams, [rt.given_projection(*c) for c in pert])
+    assert len(idx) > 1000
+    ba = rt.BundleAdjustment(cams, tracks[idx], pts)
+    before = ba.residual_norm_squared()
+    ba.optimize()
+    assert ba.final_residual_norm ** 2 <= before
+    assert len(ba.history) > 0 and not any(ba.history)  # all rejected
+    assert np.array_equal(ba.points, pts)
+
+    turned = rt.BundleAdjustment(cams, tracks[idx], pts)
+    step = turned.delta_step
+
+    def downhill():
+        da, db = step()
+        return -da, -db
+
+    turned.delta_step = downhill
+    try:
+        turned.optimize()
+    except rt.TriangulationError:
+        pass  # (100 iterations are not always enough for the turned loop; only its residual matters here)
+    assert any(turned.history)
+    assert turned.residual_norm_squared() < 0.5 * before

@@ -1,0 +1,118 @@
+"""Analytic scenes for the perspective triangulation tests: cameras (K, R, t) and integer track tables that exercise every
+branch of triangulate_track / filter_outliers (triangulation.rs:867-911, 1559-1593)."""
+from __future__ import annotations
+
+import math
+
+import numpy as np
+
+import ref_triangulation as rt
+
+
+def rot_y(a):
+    c, s = math.cos(a), math.sin(a)
+    return np.array([[c, 0.0, s], [0.0, 1.0, 0.0], [-s, 0.0, c]])
+
+
+def rig(m, size=2048, near_duplicate=True):
+    """m cameras [(K, R, t)] looking at (0, 0, 5): camera 0 at the origin (R = I); camera 1 with R = I too, 0.01 to the
+    side (near-duplicate: its rays and camera 0's are within 0.5 degrees at the scene) or 0.5 when near_duplicate is off;
+    the others on an arc of radius 5 around the scene centre, 12 to 40 degrees to either side."""
+    f = 0.5 * size
+    K = np.array([[f, 0.0, size / 2.0], [0.0, f, size / 2.0], [0.0, 0.0, 1.0]])
+    cams = [(K, np.eye(3), np.zeros(3)), (K, np.eye(3), np.array([-0.01 if near_duplicate else -0.5, 0.0, 0.0]))]
+    for j in range(2, m):
+        theta = math.radians((12.0 + 28.0 * (j - 2) / max(m - 3, 1)) * (1 if j % 2 else -1))
+        C = np.array([5.0 * math.sin(theta), 0.2 * (j % 3 - 1), 5.0 - 5.0 * math.cos(theta)])
+        R = rot_y(-theta)
+        cams.append((K, R, -R @ C))
+    return cams
+
+
+def project(cam, X):
+    K, R, t = cam
+    q = (X @ R.T + t) @ K.T
+    return q[:, :2] / q[:, 2:3]
+
+
+def observe(cams, X, mask):
+    """Rounded projections where mask (and the projection is a valid non-negative pixel), else (-1, -1)."""
+    n, m = len(X), len(cams)
+    out = np.full((n, m, 2), -1, dtype=np.int32)
+    for j, cam in enumerate(cams):
+        with np.errstate(all="ignore"):
+            p = np.round(project(cam, X))
+        good = mask[:, j] & np.all(np.isfinite(p), axis=1) & np.all((p >= 0) & (p < 1e6), axis=1)
+        out[good, j] = p[good].astype(np.int32)
+    return out
+
+
+def track_table(cams, n, seed):
+    """~n tracks: 60 % regular points seen in a random subset of >= 2 views, 10 % seen in one view only, 10 % the same
+    pixel in cameras 0 and 1 (parallel rays: |w| ~ 0), 10 % scattered through a large box (many behind a camera),
+    10 % seen by cameras 0 and 1 only (near-duplicate views: the ray-angle test).  Rows shuffled."""
+    rng = np.random.default_rng(seed)
+    m = len(cams)
+    parts = []
+    n_reg = int(0.6 * n)
+    X = np.stack([rng.uniform(-1.5, 1.5, n_reg), rng.uniform(-1.5, 1.5, n_reg), rng.uniform(3.5, 6.5, n_reg)], axis=1)
+    mask = rng.random((n_reg, m)) < 0.7
+    mask[np.arange(n_reg), rng.integers(0, m, n_reg)] = True
+    mask[np.arange(n_reg), (rng.integers(1, m, n_reg) + rng.integers(0, m, n_reg)) % m] = True
+    parts.append(observe(cams, X, mask))
+    n10 = n // 10
+    X = np.stack([rng.uniform(-1.5, 1.5, n10), rng.uniform(-1.5, 1.5, n10), rng.uniform(3.5, 6.5, n10)], axis=1)
+    mask = np.zeros((n10, m), dtype=bool)
+    mask[np.arange(n10), rng.integers(0, m, n10)] = True
+    parts.append(observe(cams, X, mask))
+    pix = np.stack([rng.integers(0, 2048, n10), rng.integers(0, 2048, n10)], axis=1).astype(np.int32)
+    t = np.full((n10, m, 2), -1, dtype=np.int32)
+    t[:, 0] = pix
+    t[:, 1] = pix
+    parts.append(t)
+    X = np.stack([rng.uniform(-8, 8, n10), rng.uniform(-3, 3, n10), rng.uniform(-4, 10, n10)], axis=1)
+    parts.append(observe(cams, X, np.ones((n10, m), dtype=bool)))
+    X = np.stack([rng.uniform(-1.5, 1.5, n10), rng.uniform(-1.5, 1.5, n10), rng.uniform(3.5, 6.5, n10)], axis=1)
+    mask = np.zeros((n10, m), dtype=bool)
+    mask[:, :2] = True
+    parts.append(observe(cams, X, mask))
+    table = np.concatenate(parts)
+    return np.ascontiguousarray(table[rng.permutation(len(table))])
+
+
+def ref_cameras(cams):
+    return [rt.Camera.from_matrix(K, R, t) for K, R, t in cams]
+
+
+def near_threshold(tracks, cams, tol=1e-9):
+    """Rows whose deciding quantity lies within tol (relative) of its threshold: |w| vs 1e-4, the smallest depth of a seen
+    view vs 0, the smallest |cos| between rays vs cos(0.5 deg)."""
+    rc = ref_cameras(cams)
+    P = np.stack([rt.given_projection(*c) for c in cams])
+    pts, ok, w_abs = rt.triangulate_tracks(tracks, P)
+    _, depth_min, min_cos = rt.filter_decisions(tracks, pts, ok, rc)
+    thr = math.cos(rt.MIN_ANGLE_BETWEEN_RAYS)
+    close = np.abs(w_abs - rt.PERSPECTIVE_SCALE_THRESHOLD) <= tol * rt.PERSPECTIVE_SCALE_THRESHOLD
+    close |= ok & (np.abs(depth_min) <= tol * np.maximum(1.0, np.linalg.norm(np.where(ok[:, None], pts, 0.0), axis=1)))
+    close |= ok & (np.abs(min_cos - thr) <= tol)
+    return np.nonzero(close)[0]
+
+
+def ba_scene(n, seed=5, size=2048):
+    """n tracks over synth.sfm_cameras-like cameras (3 views), every track seen in 2 or 3 views with integer (so
+    sub-pixel-noisy) observations, and the cameras 2 and 3 perturbed by ~1e-3 in r and t.  -> (true cams, perturbed
+    cams, tracks)."""
+    from cybervision_amd import synth
+
+    rng = np.random.default_rng(seed)
+    K, poses = synth.sfm_cameras(size)
+    cams = [(K, R, t) for R, t in poses]
+    X = np.stack([rng.uniform(-0.4, 0.4, n), rng.uniform(-0.4, 0.4, n), rng.uniform(0.85, 1.0, n)], axis=1)
+    mask = np.ones((n, 3), dtype=bool)
+    mask[np.arange(n), rng.integers(0, 3, n)] = rng.random(n) < 0.5
+    tracks = observe(cams, X, mask)
+    pert = [cams[0]]
+    for K_, R, t in cams[1:]:
+        dR = rt.matrix_r(rng.normal(0.0, 1e-3, 3))
+        pert.append((K_, dR @ R, t + rng.normal(0.0, 1e-3, 3)))
+    return cams, pert, tracks
