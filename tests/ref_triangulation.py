@@ -248,6 +248,7 @@ class BundleAdjustment:
         self.covariance = 1.0
         self.mu = INITIAL_MU
         self.history = []  # accept (True) / reject (False) per finished iteration
+        self.rhos = []  # the rho that decided each of them
 
     def _d_projection(self, X, j):
         """point_projected and d_projection_hpoint (:1698-1704), [n, 2, 3]."""
@@ -373,7 +374,7 @@ class BundleAdjustment:
         """:2042-2147 -> refined cameras; raises TriangulationError."""
         residual_ns = self.residual_norm_squared()
         g_a, g_b = self.jt_residual()
-        self.final_residual_norm = math.sqrt(residual_ns)
+        self.initial_residual_norm = self.final_residual_norm = math.sqrt(residual_ns)
         if abs(max(g_a.max(), g_b.max())) <= GRADIENT_EPSILON:  # .max().abs() (:2050)
             return self.cameras
         self.mu = INITIAL_MU
@@ -398,6 +399,7 @@ class BundleAdjustment:
             new_ns = self.residual_norm_squared()
             rho_den = float(delta_a @ (delta_a * self.mu + g_a)) + float(np.sum(delta_b * (delta_b * self.mu + g_b)))
             rho = (residual_ns - new_ns) / rho_den
+            self.rhos.append(rho)
             if rho > 0.0:
                 self.history.append(True)
                 converged = math.sqrt(residual_ns) - math.sqrt(new_ns) < RESIDUAL_REDUCTION_EPSILON * math.sqrt(residual_ns)

@@ -23,7 +23,7 @@ def rel_err(a, b):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("m", [2, 3, 4, 8])
+@pytest.mark.parametrize("m", [2, 3, 4, 5, 6, 7, 8])
 def test_triangulate_and_filter_match_restatement(gpu_device, m):
     """triangulate_track + filter_outliers (triangulation.rs:867-911, 1559-1593), no bundle adjustment, ~100 k tracks with
     1-view tracks, parallel rays (|w| ~ 0), points behind a camera and near-duplicate views: the same kept set in the
@@ -106,6 +106,67 @@ def test_errors(gpu_device):
     surf = tri.triangulate_all(gpu_device, pert, progress=seen.append)
     # one report per pass of the loop: the decided steps, and the last pass, which the delta test ends (:2079-2083)
     assert seen == [np.float32(i / 100.0) for i in range(surf.ba_iterations + 1)]
+
+
+def _compare_ba(surf, idx, pts, cams, ba, tol, tol_res):
+    """The device's bundle adjustment against the restatement's: the kept set, the iteration count, the exact accept /
+    reject sequence, both residual norms to tol_res, points, and each camera's r, t and projection to tol (relative to
+    the largest element: a step moves every component, the small ones by as much as the large)."""
+    assert np.array_equal(surf.track_index, idx)
+    assert surf.ba_iterations == len(ba.history)
+    assert surf.ba_history == [int(h) for h in ba.history]
+    for dn, rn in zip(surf.ba_residual_norms, (ba.initial_residual_norm, ba.final_residual_norm)):
+        assert abs(dn - rn) <= tol_res * rn, (dn, rn)
+    assert (rel_err(surf.points, pts) <= tol).all(), rel_err(surf.points, pts).max()
+    for j, (dc, rc) in enumerate(zip(surf.cameras, cams)):
+        assert tri_scenes.vec_close(dc.r, rc.r, tol, 1e-12), j
+        assert tri_scenes.vec_close(dc.t, rc.t, tol, 1e-12), j
+        assert tri_scenes.vec_close(dc.projection, rc.projection(), tol, 1e-9), j
+
+
+def _case_id(case):
+    m, n, seed, far, accepts = case
+    return f"m{m}-n{n}-seed{seed}-{'accepts' if accepts else 'rejects'}"
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("case", tri_scenes.BA_RIG_CASES, ids=_case_id)
+def test_bundle_adjustment_every_camera_count(gpu_device, case):
+    """BundleAdjustment::optimize (:2042-2147) with every camera count the kernels are instantiated for (M = 2..8),
+    ~20 k tracks over tri_scenes.ba_rig_scene: each track seen in 2..m views, the rest missing (the obs.x < 0 residual,
+    V summed over every view, seen or not), the cameras 1..m-1 perturbed.  M >= 5 runs the second camera group of
+    ba_jtr_kernel; M = 8 the 48 x 48 LU.  Compared as test_bundle_adjustment_matches_restatement: the kept set, the
+    iteration count, the exact accept / reject sequence, both residual norms, points and cameras, at that test's 1e-6
+    (points, cameras) and 1e-9 (residual norms).  Every scene is all-rejected (tri_scenes.BA_RIG_CASES says why); every
+    rho is at least 0.1 away from 0 and keeps its sign under a reversed summation order (tests/test_triangulation_ref.py)."""
+    m, n, seed, far, accepts = case
+    _, given, tracks = tri_scenes.ba_case_scene(case)
+    idx, pts, cams, ba = tri_scenes.ba_restatement(given, tracks)
+    assert any(ba.history) == accepts
+    surf = run_device(gpu_device, tracks, given, True)
+    print(f"m={m}: {len(idx)} kept, history {surf.ba_history}")
+    _compare_ba(surf, idx, pts, cams, ba, 1e-6, 1e-9)
+
+
+@pytest.mark.gpu
+def test_bundle_adjustment_past_one_grid(gpu_device):
+    """The bundle adjustment with more than MAX_GRID = 1024 blocks of 256 kept tracks, so every thread of
+    ba_schur_kernel, ba_step_kernel and ba_jtr_kernel walks its grid-stride loop more than once: 3 cameras, 270 k
+    tracks, all-rejected.  Compared with the restatement as above (1e-6, 1e-9).  Two device runs give the same bits."""
+    case = tri_scenes.BA_GRID_CASE
+    _, given, tracks = tri_scenes.ba_case_scene(case)
+    idx, pts, cams, ba = tri_scenes.ba_restatement(given, tracks)
+    assert len(idx) > tri_scenes.GRID_STRIDE_TRACKS and any(ba.history) == case[4]
+    a = run_device(gpu_device, tracks, given, True)
+    print(f"{len(idx)} kept, history {a.ba_history}")
+    _compare_ba(a, idx, pts, cams, ba, 1e-6, 1e-9)
+    b = run_device(gpu_device, tracks, given, True)
+    assert np.array_equal(a.track_index, b.track_index)
+    assert a.points.tobytes() == b.points.tobytes()
+    assert a.ba_history == b.ba_history and a.ba_residual_norms == b.ba_residual_norms
+    for ca, cb in zip(a.cameras, b.cameras):
+        assert ca.r.tobytes() == cb.r.tobytes() and ca.t.tobytes() == cb.t.tobytes()
+        assert ca.projection.tobytes() == cb.projection.tobytes()
 
 
 def ground_truth_depth_error(points, K, size):

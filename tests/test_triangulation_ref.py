@@ -96,3 +96,45 @@ def test_bundle_adjustment_as_written_reaches_found_without_raising_the_residual
         pass  # (100 iterations are not always enough for the turned loop; only its residual matters here)
     assert any(turned.history)
     assert turned.residual_norm_squared() < 0.5 * before
+
+
+SCENE_CASES = tri_scenes.BA_RIG_CASES + [tri_scenes.BA_GRID_CASE]
+
+
+@pytest.mark.parametrize("case", SCENE_CASES, ids=lambda c: f"m{c[0]}-n{c[1]}-seed{c[2]}")
+def test_ba_scene_claims(case, monkeypatch):
+    """What the device tests rely on for each bundle-adjustment scene: no track's DLT / filter decision lies within 1e-9
+    of its threshold, the restatement reaches "found", every V it pseudo-inverts keeps its singular values far above the
+    f64::EPSILON cut-off, the history has accepted steps exactly where the case claims
+    them, every rho is at least RHO_MARGIN away from 0, the grid-stride case keeps more than 1024 * 256 tracks, and - so that the device's other summation order
+    cannot tip any decision - the restatement with its reductions over the kept tracks in reversed order gives the same
+    accept / reject sequence, with points, cameras and residual norm within a fifth of the device test's bound."""
+    m, n, seed, far, accepts = case
+    _, given, tracks = tri_scenes.ba_case_scene(case)
+    close = tri_scenes.near_threshold(tracks, given)
+    assert len(close) == 0, f"tracks at a threshold: {close[:20].tolist()}"
+    smallest = []  # the smallest singular value of every V the loop pseudo-inverts (:1797)
+    pinv3 = rt._pinv3
+
+    def recording_pinv3(v):
+        smallest.append(float(np.linalg.svd(v, compute_uv=False)[:, -1].min()))
+        return pinv3(v)
+
+    monkeypatch.setattr(rt, "_pinv3", recording_pinv3)
+    idx, pts, cams, ba = tri_scenes.ba_restatement(given, tracks)  # raises unless "found"
+    monkeypatch.setattr(rt, "_pinv3", pinv3)
+    # the f64::EPSILON cut-off never engages, so the device's adjugate inverse is the pseudo-inverse (DESIGN.md 4.8)
+    assert min(smallest) > 1e6 * rt.EPS, min(smallest)
+    assert any(ba.history) == accepts, ba.history
+    assert min(abs(r) for r in ba.rhos) >= tri_scenes.RHO_MARGIN, ba.rhos
+    if case == tri_scenes.BA_GRID_CASE:
+        assert len(idx) > tri_scenes.GRID_STRIDE_TRACKS
+    tol, tol_res = 1e-6, 1e-9  # the device test's bounds
+    _, rpts, rcams, rba = tri_scenes.ba_restatement(given, tracks, order=np.arange(len(idx))[::-1])
+    assert rba.history == ba.history
+    assert abs(rba.final_residual_norm - ba.final_residual_norm) <= 0.2 * tol_res * ba.final_residual_norm
+    rel = np.linalg.norm(rpts - pts, axis=1) / np.linalg.norm(pts, axis=1)
+    assert rel.max() <= 0.2 * tol, rel.max()
+    for a, b in zip(rcams, cams):
+        assert tri_scenes.vec_close(a.r, b.r, 0.2 * tol, 1e-12) and tri_scenes.vec_close(a.t, b.t, 0.2 * tol, 1e-12)
+        assert tri_scenes.vec_close(a.projection(), b.projection(), 0.2 * tol, 1e-9)

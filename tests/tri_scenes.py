@@ -116,3 +116,80 @@ def ba_scene(n, seed=5, size=2048):
         dR = rt.matrix_r(rng.normal(0.0, 1e-3, 3))
         pert.append((K_, dR @ R, t + rng.normal(0.0, 1e-3, 3)))
     return cams, pert, tracks
+
+
+def ba_rig_scene(m, n, seed, perturb=True, far=0.1):
+    """n tracks over rig(m, near_duplicate=False) (no camera pair the ray-angle test drops whole): points of the box
+    [-1.5, 1.5]^2 x [3.5, 6.5], a fraction `far` of them scattered through track_table's large box instead (some far
+    or behind a camera: the tracks that can make the reference's uphill first step land lower), each seen in a uniform
+    number of 2..m views (a random subset; the others (-1, -1)) with integer observations; with perturb, the cameras
+    1..m-1 perturbed by ~1e-3 in r and t as ba_scene's.  -> (true cams, cams given to the triangulation, tracks)."""
+    rng = np.random.default_rng(seed)
+    cams = rig(m, near_duplicate=False)
+    n_far = int(far * n)
+    X = np.stack([rng.uniform(-1.5, 1.5, n), rng.uniform(-1.5, 1.5, n), rng.uniform(3.5, 6.5, n)], axis=1)
+    X[:n_far] = np.stack([rng.uniform(-8, 8, n_far), rng.uniform(-3, 3, n_far), rng.uniform(-4, 10, n_far)], axis=1)
+    k = rng.integers(2, m + 1, n)
+    order = np.argsort(rng.random((n, m)), axis=1)
+    mask = np.zeros((n, m), dtype=bool)
+    np.put_along_axis(mask, order, np.arange(m)[None, :] < k[:, None], axis=1)
+    tracks = observe(cams, X, mask)
+    given = [cams[0]]
+    for K, R, t in cams[1:]:
+        if perturb:
+            dR = rt.matrix_r(rng.normal(0.0, 1e-3, 3))
+            given.append((K, dR @ R, t + rng.normal(0.0, 1e-3, 3)))
+        else:
+            given.append((K, R, t))
+    return cams, given, np.ascontiguousarray(tracks[rng.permutation(n)])
+
+
+# The bundle-adjustment scenes of tests/test_triangulation_gpu.py, (m, n, seed, far, accepts): ba_rig_scene(m, n, seed,
+# far=far), and whether its LM history holds accepted steps.  Seeds picked on the CPU; tests/test_triangulation_ref.py
+# checks each scene's claims.  Every scene here is all-rejected: no scene tried has an accepted step that the
+# restatement reproduces when only its rounding changes (reductions in reversed track order, or V inverted by
+# np.linalg.inv instead of the SVD pseudo-inverse) - the history itself changes, or the points move by O(1).  Tried:
+# ba_rig_scene with m = 2..8, seeds 1..16, far 0 / 0.01 / 0.02 / 0.03 / 0.05 / 0.1, n = 20 k and 270 k; rig(m,
+# near_duplicate=False) with track_table(cams, 20 k, seed), true cameras, m = 3..8, seeds 1, 2, 3, 5, 8 (among them the
+# 8-camera seed-8 scene with 3 accepts: reversed order moves its points by 54x their norm); rig sizes 16, 64, 256.  The
+# accepts come from tracks whose V is ill-conditioned (condition numbers up to 4.5e12) and, with 4 or more cameras, from
+# S + mu I solved at mu = 1e-3 against entries ~1e10 in its near-null directions.
+BA_RIG_CASES = [
+    (2, 20_000, 11, 0.0, False),
+    (3, 20_000, 3, 0.0, False),
+    (4, 20_000, 1, 0.0, False),
+    (5, 20_000, 8, 0.0, False),
+    (6, 20_000, 1, 0.1, False),
+    (7, 20_000, 3, 0.0, False),
+    (8, 20_000, 5, 0.0, False),
+]
+# more than MAX_GRID (1024) blocks of 256 kept tracks: the grid-stride loops of the bundle-adjustment kernels
+BA_GRID_CASE = (3, 270_000, 2, 0.0, False)
+GRID_STRIDE_TRACKS = 1024 * 256
+# every rho of a scene at least this far from 0: the decisions then do not hang on the rounding of rho itself (an
+# all-rejected scene's rhos are O(1) or larger; a scene whose rho was 2e-3 at one step took the other branch on the device)
+RHO_MARGIN = 0.1
+
+
+def vec_close(a, b, rtol, atol):
+    """max |a - b| <= rtol max |b| + atol (relative to the largest element of b)."""
+    a, b = np.asarray(a), np.asarray(b)
+    return float(np.abs(a - b).max()) <= rtol * float(np.abs(b).max()) + atol
+
+
+def ba_case_scene(case):
+    m, n, seed, far, _ = case
+    return ba_rig_scene(m, n, seed, far=far)
+
+
+def ba_restatement(given, tracks, order=None):
+    """triangulate_all with the bundle adjustment on, its reductions run over the kept tracks in `order` (a permutation
+    of them; None = track order) -> (kept indices, points, cameras, BundleAdjustment), points in track order."""
+    cams = ref_cameras(given)
+    idx, pts = rt.triangulate_and_filter(tracks, cams, [rt.given_projection(*c) for c in given])
+    order = np.arange(len(idx)) if order is None else np.asarray(order)
+    ba = rt.BundleAdjustment(cams, np.asarray(tracks)[idx][order], pts[order])
+    out = ba.optimize()
+    points = np.empty_like(ba.points)
+    points[order] = ba.points
+    return idx, points, out, ba
