@@ -13,13 +13,18 @@ N > 1: the SAME pair is row-sharded over the ranks (strong scaling), bands are a
 with RCCL after every sharded search pass; every rank ends with the full, identical grid.
 
 Prints ONE JSON line on rank 0 (contract in the task statement), with `roofline` for the
-dominant kernel (search3_box_kernel, timed live with HIP events on its own stream) and
-`cpu_baseline` (the C restatement of the reference's --mode=cpu path, oracle/, timed on this
-node's host cores on a bounded sample).  At N = 1 the same line also carries, measured after the
-timed region: `readback` (SURVEY 8(d)'s t_dense with the final grid landing in page-locked HOST
-memory - per pair, and with the transfer of one pair under the search of the next),
-`geometry_sweep` (the same 4096^2 workload with the epipolar lines tilted by 3 .. 90 degrees) and
-`sfm3` (BASELINE config 5, per-stage times).
+dominant kernel (search3_box_kernel, timed live with HIP events on its own stream, in the last
+timed step; its candidate count comes from the first warm-up step, which runs with the counter on).
+A plain run does nothing else: set-up, warm-up, the timed steps, --dump-outputs, the line.
+
+--full adds everything that takes runs of its own, after the timed region: `kernel_ms_per_step`
+(one more, fully instrumented step), `cpu_baseline` (the C restatement of the reference's
+--mode=cpu path, oracle/, timed on this node's host cores on a bounded sample) and, at N > 1, the
+sharded result checked against an unsharded run.  At N = 1 it also adds `readback` (SURVEY 8(d)'s
+t_dense with the final grid landing in page-locked HOST memory - per pair, and with the transfer of
+one pair under the search of the next), `boundary_path` (the reference's own call sequence),
+`pair_pipeline`, `geometry_sweep` (the same 4096^2 workload with the epipolar lines tilted by
+3 .. 90 degrees) and `sfm3` (BASELINE config 5, per-stage times).
 
 `python bench.py --gpus N` without a launcher starts the N ranks itself (torch.distributed.run as a
 child process, before anything touches the GPU) and exits with its code.
@@ -280,17 +285,22 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--size", type=int, default=4096, help="image side (default: BASELINE's 4096)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure and check what the headline does not need: per-kernel times, the CPU "
+                         "baseline, the sharded-vs-unsharded check (N > 1) and, at N = 1, readback / boundary_path / pair_pipeline / "
+                         "geometry_sweep / sfm3")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--simulate-shard", default="", help="num/den: time one rank's share of a den-GPU band-mode run on 1 GPU")
-    ap.add_argument("--cpu-sample", type=int, default=512, help="side of the first crop timed on the CPU")
+    ap.add_argument("--cpu-sample", type=int, default=512, help="--full: side of the first crop timed on the CPU")
     ap.add_argument("--config", default="dense4096", choices=["dense4096", "sfm3"],
                     help="dense4096 (default): the headline metric; sfm3: BASELINE config 5, a secondary line")
     ap.add_argument("--pencil", type=int, default=0, choices=[0, 1], help="--config sfm3: 7-point pencil (0 = the reference's thin-SVD rows, 1 = null space)")
-    ap.add_argument("--no-extras", action="store_true", help="skip readback / geometry_sweep / sfm3 in the headline line")
+    ap.add_argument("--no-extras", action="store_true",
+                    help="--full: skip readback / boundary_path / pair_pipeline / geometry_sweep / sfm3 in the headline line")
     ap.add_argument("--no-count-step", action="store_true",
                     help="profiling runs (scripts/_run_prof.sh): skip the untimed candidate-counting step, so that every step of the "
                          "run launches the same kernel instantiations; the line then carries no candidate count")
-    ap.add_argument("--sweep-tilts", default="3,10,30,45,60,90", help="tilts (degrees) of geometry_sweep")
+    ap.add_argument("--sweep-tilts", default="3,10,30,45,60,90", help="--full: tilts (degrees) of geometry_sweep")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last timed step returned as DIR/<name>.npy in float32 / float64 "
                          "(grids larger than the 64 MB budget: a fixed, seeded sample of their cells)")
@@ -346,7 +356,14 @@ def main():
         return [resident(p) for p in pa], [resident(p) for p in pb]
 
     d1, d2 = resident_pyramids()
-    img1, img2 = d1[0].cpu().numpy(), d2[0].cpu().numpy()  # host copies of the pair, for the CPU baseline
+    # The pair is complete in HBM before the library's handle is made and its first run is enqueued, in every run (the
+    # host copies below used to make this point).  The first runs feed the library's stats-ahead self-check
+    # (cvhip_internal.hpp, StatsAhead), which times them; enqueued under the pyramid build, the timed steps measured
+    # 0.5 % slower.
+    torch.cuda.synchronize()
+    cpu_baseline = args.full and world == 1 and not args.no_cpu_baseline
+    if cpu_baseline:
+        img1, img2 = d1[0].cpu().numpy(), d2[0].cpu().numpy()  # host copies of the pair, for the CPU baseline
     level_dims = [(int(p.shape[1]), int(p.shape[0]), int(q.shape[1]), int(q.shape[0])) for p, q in zip(d1, d2)]
 
     stream = torch.cuda.current_stream()
@@ -464,7 +481,7 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    # one counting pass (untimed): candidates evaluated per step, needed for the flop count
+    # one counting pass (untimed, the first of the --warmup steps): candidates evaluated per step, needed for the flop count
     cand_local = 0
     if not args.no_count_step:
         pc.set_profiling(False, True)
@@ -493,14 +510,16 @@ def main():
     ktimes_last = pc.get_kernel_times()
     search_ms_local = ktimes_last["search"]["ms"]  # the box-kernel launches of ONE step (the first pass runs the
     search_launches = ktimes_last["search"]["launches"]  # candidate filter: class "search_filter", not counted here)
-    # per-class breakdown of one more (untimed) step
-    pc.set_profiling(1, False)
-    step()
-    fence()
-    ktimes = pc.get_kernel_times()
-    pc.set_profiling(0, False)
+    ktimes = None
+    if args.full:
+        # per-class breakdown of one more (untimed) step
+        pc.set_profiling(1, False)
+        step()
+        fence()
+        ktimes = pc.get_kernel_times()
+        pc.set_profiling(0, False)
 
-    extras = world == 1 and sim is None and not args.no_extras
+    extras = args.full and world == 1 and sim is None and not args.no_extras
     readback = geometry_sweep = sfm3 = boundary_path = None
     if extras:
         # ---- t_dense INCLUDING the final readback of the forward grid into host memory
@@ -774,7 +793,7 @@ def main():
                                                                       "ransac_inliers": lz["ransac_inliers"], "dense_matches": lz["dense_matches"]}}
 
     sharded_ok = None
-    if world > 1:
+    if world > 1 and args.full:
         # the sharded result of the last step against an unsharded run of the same pair in this process (the rank that
         # holds the gathered grid: rank 0 with the library's gather-to-root, every rank with an all-gather)
         pc1 = correlation.PointCorrelations(dev, (W, H), (W, H), synth.F_HORIZONTAL, correlation.ProjectionMode.Affine)
@@ -887,12 +906,12 @@ def main():
             # level in result bands); `value` is the HBM -> HBM rate the task's bench contract asks for (inputs and grid resident)
             "value_survey_8d": readback["mpixels_per_s_with_readback_banded"] if readback else None,
             "roofline": roofline,
-            # every kernel class, from one extra fully instrumented step after the timed region
-            "kernel_ms_per_step": {k: round(v["ms"], 4) for k, v in ktimes.items()},
+            # --full: every kernel class, from one extra fully instrumented step after the timed region
+            **({"kernel_ms_per_step": {k: round(v["ms"], 4) for k, v in ktimes.items()}} if ktimes is not None else {}),
             # the full-resolution level alone (non-first pass: the dominant level), this rank's share of the rows
             "level0": {"ms": round(l0_ms, 4), "mpixels_per_s": round(mpx / world / (l0_ms / 1e3), 1) if l0_ms > 0 else None},
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if cpu_baseline:
             from oracle import cvref  # CPU oracle: only as the reported baseline, never on the product path
 
             cores = os.cpu_count() or 1
@@ -930,8 +949,9 @@ def main():
             result["boundary_path"] = boundary_path
         if world > 1:
             result["collective"] = collective
-            result["ranks_seen"] = ranks_seen
-            result["sharded_equals_unsharded"] = sharded_ok
+            if args.full:
+                result["ranks_seen"] = ranks_seen
+                result["sharded_equals_unsharded"] = sharded_ok
         if rehearsal:
             result["rehearsal"] = f"{backend}: all {world} ranks on one GPU, gather staged through the host - not a measurement"
         print(json.dumps(result), flush=True)

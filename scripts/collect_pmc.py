@@ -1,11 +1,11 @@
 #!/usr/bin/env python3
-"""Turn a rocprofv3 --pmc SQ pass of `bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-extras --no-count-step` into
+"""Turn a rocprofv3 --pmc SQ pass of `bench.py --full --steps 1 --warmup 1 --no-cpu-baseline --no-extras --no-count-step` into
 profiles/<tag>_pmc.json: per kernel INSTANTIATION (template arguments kept: `search3_box_kernel<false, false, false>` is the
 timed one, `<true, ...>` the candidate-counting one - they are different kernels), summed over the launches of ONE bench
 step.  The profiled run must hold identical steps only (--no-count-step: timed step + instrumented step = 2).
 
     rocprofv3 --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_ACTIVE_INST_VALU SQ_WAIT_ANY SQ_ACTIVE_INST_ANY \
-              GRBM_GUI_ACTIVE -d <dir> --output-format csv -- python3 bench.py --steps 1 --warmup 1 --no-cpu-baseline
+              GRBM_GUI_ACTIVE -d <dir> --output-format csv -- python3 bench.py --full --steps 1 --warmup 1 --no-cpu-baseline --no-extras --no-count-step
     collect_pmc.py <dir> <out.json> <steps_in_run>
 
 Derived per kernel: valu_busy = SQ_ACTIVE_INST_VALU * 4 / (SIMDs * GRBM_GUI_ACTIVE / XCDs)  - SQ_ACTIVE_* count

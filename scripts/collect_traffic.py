@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Turn two rocprofv3 PMC runs of `bench.py --steps 1 --warmup 1 --no-cpu-baseline`
+"""Turn two rocprofv3 PMC runs of `bench.py --full --steps 1 --warmup 1 --no-cpu-baseline --no-extras --no-count-step`
 (one with --pmc FETCH_SIZE, one with --pmc WRITE_SIZE, as MI355X_MICROARCH.md prescribes:
 separate passes) into profiles/<tag>_traffic.json.
 
