@@ -246,6 +246,12 @@ class PointCorrelations:
         return {"candidates": arr[0], "exact_evals": arr[1], "multi_contender_pixels": arr[2],
                 "whole_corridor_pixels": arr[3]}
 
+    def get_box_counters(self, reset: bool = True):
+        """cvhip_ctx_get_box_counters: diagnostics of the stepped box walk (needs set_profiling(_, True))."""
+        arr = (C.c_uint64 * 4)()
+        _lib.check(_lib.lib().cvhip_ctx_get_box_counters(self._h, arr, int(reset)), "cvhip_ctx_get_box_counters")
+        return {"waves65_rowmajor": arr[0], "waves65_transposed": arr[1], "max_steps": arr[2]}
+
     def set_borrow_inputs(self, borrow: bool):
         """Device-resident level images are used in place (no copy): the caller guarantees 64 readable bytes after
         the last pixel of each and keeps them unchanged until the call's work has completed (include/cvhip.h)."""

@@ -191,8 +191,14 @@
     // integer row there (affine F: the lanes' lines are parallel and - for a consistent pair - coincide, so that happens
     // where the line itself passes a row).  A window that is wider than needed only costs its planes: a lane re-derives its
     // OWN first plane, with the reference's expression, where a candidate of its passes the filter (the hit branch below).
+    // The table has one step per lane, and the wide plan's boxes are up to ISP - 63 = 65 steps wide (eligibility below):
+    // the one step past the lanes - step 64 - has its window in a wave-uniform word of its own (a lane number of 64
+    // would wrap to lane 0, whose window on a sloped line holds other rows).
+    constexpr int STEP_TABLE = 64;
+    static_assert(ISP - 63 <= STEP_TABLE + 1, "a stepped wave walks at most the table's steps and step_last");
     int wave_planes = mxy - mny + 1; // never more than the wave's box is tall
     uint32_t step_tbl = 0u;          // lane t: {first plane of step t relative to mny | planes << 16}
+    uint32_t step_last = 0u;         // the same for step 64 (wave-uniform)
     if (STEP && wave_step) {
         constexpr double FX = 262144.0; // 2^18
         double ga = 0.5, gc = 0.0;
@@ -221,14 +227,18 @@
             cmin_i = wave_min_i32(has ? ci : 0x7FFFFFFF);
             cmax_i = wave_max_i32(has ? ci : -0x7FFFFFFF);
         }
-        const int t = (int)lane; // (t >= 0: the products below keep their order)
-        int lo = (amin - 1 + t * (cmin_i - 1)) >> 18, hi = (amax + 2 + t * (cmax_i + 2)) >> 18;
-        // every lane's true first plane lies inside its own [lov, lov_hi] and so inside the wave's box
-        lo = max(lo, 0);
-        hi = max(min(hi, mxy - (2 * cs + 1 + wave_loose) + 1 - mny), lo);
-        const int np = hi - lo + 2 * cs + 1 + wave_loose;
-        step_tbl = (uint32_t)lo | ((uint32_t)np << 16);
-        wave_planes = min(wave_planes, wave_max_i32(t <= mxx - mnx ? np : 0));
+        const auto window = [&](int t) -> uint32_t { // (t >= 0: the products below keep their order)
+            int lo = (amin - 1 + t * (cmin_i - 1)) >> 18, hi = (amax + 2 + t * (cmax_i + 2)) >> 18;
+            // every lane's true first plane lies inside its own [lov, lov_hi] and so inside the wave's box
+            lo = max(lo, 0);
+            hi = max(min(hi, mxy - (2 * cs + 1 + wave_loose) + 1 - mny), lo);
+            return (uint32_t)lo | ((uint32_t)(hi - lo + 2 * cs + 1 + wave_loose) << 16);
+        };
+        const int t = (int)lane;
+        step_tbl = window(t);
+        step_last = window(STEP_TABLE);
+        wave_planes = min(wave_planes, max(wave_max_i32(t <= mxx - mnx ? (int)(step_tbl >> 16) : 0),
+                                           mxx - mnx >= STEP_TABLE ? (int)(step_last >> 16) : 0));
     }
     __syncthreads(); // bb initialised
     if (lane == 0) {
@@ -286,6 +296,15 @@
             worklist_push(declined, TR ? (V0 | (tid.x << 16) | 0x40000000u) : ((uint32_t)U0 | (tid.y << 16)));
         }
         return;
+    }
+    if constexpr (COUNT && STEP) {
+        // diagnostics (cvhip_ctx_get_box_counters; counters 4..7, apart from the four above): the stepped waves that
+        // walk one step past the table's 64 lanes, and the most steps any stepped wave walks
+        if (counters && lane == 0 && wave_step && wave_has) {
+            const int nst = mxx - mnx + 1;
+            if (nst == STEP_TABLE + 1) atomicAdd(&counters[TR ? 5 : 4], 1ull);
+            atomicMax(&counters[6], (unsigned long long)nst);
+        }
     }
     const int NPL = H > 9 ? S3_MAXH : (H > 5 ? 9 : 5); // planes staged (lean: group A = 0..4, group B = 5..8)
     if (dbg & 256) return; // profiling: per-pixel setup and box reduction only
@@ -593,8 +612,8 @@
             int bl = lov, s0 = ws0, n = wn;
             if (wave_step) {
                 if (!__builtin_amdgcn_ballot_w64(mx)) continue; // nobody searches this step
-                // the wave's window at this step, from the table settled in setup (lane `step` holds it)
-                const uint32_t tw = (uint32_t)__builtin_amdgcn_readlane((int)step_tbl, step);
+                // the wave's window at this step, from the table settled in setup (lane `step` holds it; step 64: step_last)
+                const uint32_t tw = step < STEP_TABLE ? (uint32_t)__builtin_amdgcn_readlane((int)step_tbl, step) : step_last;
                 s0 = ws0 + (int)(tw & 0xFFFFu);
                 n = (int)(tw >> 16);
                 if (COUNT && stepped && mx) {

@@ -1546,7 +1546,7 @@ template <bool STEP, bool WIDE = true> struct S3Plan {
     static constexpr int TAIL_OFF = 4 * S3_COLS * 16;                // (lean) [4][128] u32: rows 16..19
     static constexpr int IS_OFF = TAIL_OFF + 4 * S3_COLS * TAIL_BYTES; // (lean) [MAXH + 3][128] uint2: candidate statistics
     static constexpr int LDS_BYTES = IS_OFF + (MAXH + 3) * S3_COLS * 8;
-    // Stepped plan, two widths: boxes of up to 61 steps (128 lines, 128 cells per statistics row) where the lines are
+    // Stepped plan, two widths: boxes of up to 65 - colshift steps (128 lines, 128 cells per statistics row) where the lines are
     // shallow enough for that to leave five workgroups per CU; up to 33 steps (100 lines, 96 cells) for steeper lines,
     // whose boxes are taller - the statistics rows are what fills the LDS.
     static constexpr int LINES = STEP && !WIDE ? 100 : S3_COLS;      // target lines staged per workgroup

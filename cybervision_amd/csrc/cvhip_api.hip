@@ -509,7 +509,7 @@ static int plan_pass(cvhip_ctx *c, int a, int b, uint32_t lw1, uint32_t lh1, uin
     } else if (v3 && !c->force_box) {
         v3 = f_major > 0.0;
     }
-    // The first pass searches the whole line: its displacement boxes are wider than the box kernel's 61 steps, every
+    // The first pass searches the whole line: its displacement boxes are wider than the box kernel's 65 steps, every
     // workgroup would decline - straight to the candidate filter (one launch less on the latency-bound coarsest level).
     if (first_pass && !c->force_box) v3 = false;
     if (v3) {
@@ -528,7 +528,7 @@ static int plan_pass(cvhip_ctx *c, int a, int b, uint32_t lw1, uint32_t lh1, uin
             const uint32_t H = (uint32_t)std::ceil(std::min(slope, 1.0) * 32.0) + wv + 3u;
             p.box_sh = std::min(H + 3u, 44u);
             p.box_pd = std::min(((H + 26u + 3u) >> 2) | 1u, 39u);
-            // boxes up to 61 steps wide where that still leaves five workgroups per CU (160 KB of LDS), else up to 33
+            // boxes up to 65 steps wide where that still leaves five workgroups per CU (160 KB of LDS), else up to 33
             p.box_wide = 128u * p.box_pd * 4u + p.box_sh * 128u * 8u <= 32u * 1024u ? 1u : 0u;
         }
     }
@@ -911,9 +911,9 @@ int cvhip_ctx_create(cvhip_device *dev, uint32_t w1, uint32_t h1, uint32_t w2, u
         if (e == hipSuccess) e = hipMalloc(&c->contenders, c->max_px * sizeof(unsigned long long));
         if (e == hipSuccess) e = hipMalloc(&c->contenders_rev, c->max_px * sizeof(unsigned long long));
         if (e == hipSuccess) e = hipMalloc(&c->work, (8 + 4 * c->work_cap) * sizeof(uint32_t));
-        if (e == hipSuccess) e = hipMalloc(&c->d_cand, 4 * sizeof(unsigned long long));
+        if (e == hipSuccess) e = hipMalloc(&c->d_cand, cvhip_ctx::N_COUNTERS * sizeof(unsigned long long));
     }
-    if (e == hipSuccess) e = hipMemsetAsync(c->d_cand, 0, 4 * sizeof(unsigned long long), dev->d.stream);
+    if (e == hipSuccess) e = hipMemsetAsync(c->d_cand, 0, cvhip_ctx::N_COUNTERS * sizeof(unsigned long long), dev->d.stream);
     for (int d = 0; d < 2 && e == hipSuccess; d++)
         e = hipMemsetAsync(c->img[d], 0, img_pool_bytes(c->max_px), dev->d.stream);
     // (host level images are uploaded on the handle's COPY stream: it must not overtake the clearing above)
@@ -1706,7 +1706,7 @@ int cvhip_ctx_get_profile(cvhip_ctx *ctx, uint32_t *launches, double *search_ms,
             ctx->prof_launches[i] = 0;
             ctx->prof_ms[i] = 0.0;
         }
-        CVHIP_TRY_HIP(hipMemset(ctx->d_cand, 0, 4 * sizeof(unsigned long long)));
+        CVHIP_TRY_HIP(hipMemset(ctx->d_cand, 0, cvhip_ctx::N_COUNTERS * sizeof(unsigned long long)));
     }
     return CVHIP_OK;
 }
@@ -1735,10 +1735,23 @@ int cvhip_ctx_get_counters(cvhip_ctx *ctx, uint64_t out[4], int reset)
     CVHIP_TRY(flush_level_calls(ctx));
     CVHIP_TRY(set_device(ctx->dev));
     CVHIP_TRY_HIP(hipStreamSynchronize(ctx->dev->d.stream));
-    unsigned long long v[4] = {0, 0, 0, 0};
+    unsigned long long v[cvhip_ctx::N_COUNTERS] = {};
     CVHIP_TRY_HIP(hipMemcpy(v, ctx->d_cand, sizeof(v), hipMemcpyDeviceToHost));
     for (int i = 0; i < 4; i++) out[i] = (uint64_t)v[i];
-    if (reset) CVHIP_TRY_HIP(hipMemset(ctx->d_cand, 0, sizeof(v)));
+    if (reset) CVHIP_TRY_HIP(hipMemset(ctx->d_cand, 0, 4 * sizeof(unsigned long long))); // (the box counters stay)
+    return CVHIP_OK;
+}
+
+int cvhip_ctx_get_box_counters(cvhip_ctx *ctx, uint64_t out[4], int reset)
+{
+    if (!ctx || !out) return fail(CVHIP_ERR_INVALID, "null argument");
+    CVHIP_TRY(flush_level_calls(ctx));
+    CVHIP_TRY(set_device(ctx->dev));
+    CVHIP_TRY_HIP(hipStreamSynchronize(ctx->dev->d.stream));
+    unsigned long long v[cvhip_ctx::N_COUNTERS] = {};
+    CVHIP_TRY_HIP(hipMemcpy(v, ctx->d_cand, sizeof(v), hipMemcpyDeviceToHost));
+    for (int i = 0; i < 4; i++) out[i] = (uint64_t)v[4 + i];
+    if (reset) CVHIP_TRY_HIP(hipMemset(ctx->d_cand + 4, 0, 4 * sizeof(unsigned long long)));
     return CVHIP_OK;
 }
 

@@ -476,6 +476,8 @@ struct cvhip_ctx {
     BandPlan band[16];
 
     int time_kernels = 0, count_candidates = 0;
+    // device counters of the counting search instantiations: [0..3] cvhip_ctx_get_counters, [4..7] cvhip_ctx_get_box_counters
+    static constexpr int N_COUNTERS = 8;
     unsigned long long *d_cand = nullptr;
     // kernel classes timed with HIP events when time_kernels is set
     enum { K_STATS = 0, K_RANGE, K_SEARCH, K_EXACT, K_CROSS, K_EXPAND, K_FILTER, K_COUNT };

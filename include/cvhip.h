@@ -322,8 +322,14 @@ int cvhip_ctx_get_kernel_times(cvhip_ctx *ctx, double ms[7], uint32_t launches[7
  * out[0] candidates that passed the reference's bounds/stdev tests (== candidates above),
  * out[1] exact 121-term f32 evaluations, out[2] pixels whose filter band held 2..4 contenders,
  * out[3] pixels that re-evaluated their whole corridor exactly (tile too large for LDS, or more
- * than 4 contenders).  Synchronises. */
+ * than 4 contenders).  reset clears these four only (cvhip_ctx_get_profile's reset clears every counter).
+ * Synchronises. */
 int cvhip_ctx_get_counters(cvhip_ctx *ctx, uint64_t out[4], int reset);
+/* Diagnostics of the stepped box walk since the last reset (needs count_candidates = 1; kept apart from the
+ * counters above, which they do not change): out[0] stepped waves of row-major tiles whose own displacement range
+ * is 65 steps (one more than the walk's 64-lane step table), out[1] the same for transposed tiles, out[2] the
+ * most steps any stepped wave walked, out[3] 0.  reset clears these four only.  Synchronises. */
+int cvhip_ctx_get_box_counters(cvhip_ctx *ctx, uint64_t out[4], int reset);
 /* Select the search kernel: 1 = every candidate through the exact serial f32 chain, 2 = exact-integer
  * filter per candidate + exact re-evaluation of the contenders, 3 (default) = the same filter evaluated
  * as displacement-plane box sums for whole row segments where the epipolar lines keep one major axis, with 2 for

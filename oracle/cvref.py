@@ -47,6 +47,7 @@ def _load(so: Path):
         L.cvref_corr_cross_check.argtypes = [C.c_void_p, C.c_float, C.c_int]
         L.cvref_corr_end_level.argtypes = [C.c_void_p]
         L.cvref_corr_get.argtypes = [C.c_void_p, C.c_int, _i32p, _f32p]
+        L.cvref_corr_set_range_out.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
         L.cvref_corr_candidates.restype = C.c_uint64
         L.cvref_corr_candidates.argtypes = [C.c_void_p]
         L.cvref_corr_optimal_scale_steps.restype = C.c_uint32
@@ -116,6 +117,7 @@ class Corr:
         self._h = self._lib.cvref_corr_new(self.w1, self.h1, self.w2, self.h2, F, projection, self.nthreads)
         if not self._h:
             raise MemoryError("cvref_corr_new")
+        self._export = [None, None]
 
     def close(self):
         if self._h:
@@ -152,6 +154,19 @@ class Corr:
         corr = np.empty((h, w), dtype=np.float32)
         self._lib.cvref_corr_get(self._h, direction, xy, corr)
         return xy, corr
+
+    def export_ranges(self, direction: int = 0):
+        """From now on every step in `direction` records each pixel's search range and epipolar line: see ranges()."""
+        n = self.w1 * self.h1 if direction == 0 else self.w2 * self.h2
+        r, line = np.full(2 * n, -1, dtype=np.int32), np.zeros(4 * n, dtype=np.float64)
+        self._export[direction] = (r, line)
+        self._lib.cvref_corr_set_range_out(self._h, direction, r.ctypes.data, line.ctypes.data)
+
+    def ranges(self, direction: int, lw: int, lh: int):
+        """The last step's (direction, level of lw x lh pixels): ([lh, lw, 2] int32 search range [r0, r1), -1 where the
+        pixel was not searched; [lh, lw, 4] float64 epipolar line coeff_x, coeff_y, add_x, add_y)."""
+        r, line = self._export[direction]
+        return r[:2 * lw * lh].reshape(lh, lw, 2).copy(), line[:4 * lw * lh].reshape(lh, lw, 4).copy()
 
     @property
     def candidates(self) -> int:

@@ -44,6 +44,8 @@ struct cvref_corr {
     double F[9];
     int nthreads;
     _Atomic uint64_t candidates;
+    int32_t *range_out[2]; /* optional per-direction export of the next steps' search ranges (test infrastructure) */
+    double *line_out[2];
 };
 
 /* ---- Rust numeric-cast semantics ------------------------------------------------ */
@@ -257,6 +259,8 @@ typedef struct {
     const float *avg2, *stdev2;
     cell_t *out_data;          /* w1*h1 level-sized */
     double **scratch;          /* per-thread STDEV_RANGE (mod.rs:477) */
+    int32_t *range_out;        /* optional: [r0, r1) per level pixel, -1 where no search (cvref_corr_set_range_out) */
+    double *line_out;          /* optional: the epipolar line per level pixel */
     size_t *scratch_cap;
     _Atomic uint64_t cand;
 } step_t;
@@ -420,6 +424,17 @@ static void correlate_point(step_t *s, size_t px, size_t py, cell_t *out_point, 
     } else if (!estimate_search_range(s, px, py, &e, CORRIDOR_START, corridor_end, &r0, &r1, tid)) {
         return;
     }
+    if (s->range_out) {
+        size_t k = (size_t)s->w1 * py + px;
+        s->range_out[2 * k] = (int32_t)r0;
+        s->range_out[2 * k + 1] = (int32_t)r1;
+        if (s->line_out) {
+            s->line_out[4 * k] = e.coeff_x;
+            s->line_out[4 * k + 1] = e.coeff_y;
+            s->line_out[4 * k + 2] = e.add_x;
+            s->line_out[4 * k + 3] = e.add_y;
+        }
+    }
 
     best_match best = {0, 0, 0, 0, 0.0f};
     ptrdiff_t cs = (ptrdiff_t)pc->corridor_size;
@@ -526,6 +541,10 @@ int cvref_corr_step(cvref_corr *c, const uint8_t *img1, uint32_t lw1, uint32_t l
     s.out_data = out_data;
     s.scratch = scratch;
     s.scratch_cap = scratch_cap;
+    s.range_out = c->range_out[dir];
+    s.line_out = c->line_out[dir];
+    if (s.range_out)
+        for (size_t i = 0; i < 2 * n1; i++) s.range_out[i] = -1;
     atomic_init(&s.cand, 0);
 
     parallel_rows(lh1, nt, step_row, &s); /* mod.rs:288-304 */
@@ -646,6 +665,12 @@ void cvref_corr_get(const cvref_corr *c, int dir, int32_t *xy, float *corr)
             corr[i] = NAN;
         }
     }
+}
+
+void cvref_corr_set_range_out(cvref_corr *c, int dir, int32_t *r0r1, double *line)
+{
+    c->range_out[dir] = r0r1;
+    c->line_out[dir] = line;
 }
 
 uint64_t cvref_corr_candidates(const cvref_corr *c) { return atomic_load(&c->candidates); }

@@ -7,6 +7,7 @@ from pathlib import Path
 import numpy as np
 import pytest
 
+import box_scenes
 import cases
 from cybervision_amd import correlation, synth
 
@@ -30,7 +31,8 @@ def assert_same_grid(got, want, what):
     assert np.isnan(gc[~valid]).all()
 
 
-def run_gpu(dev, c, fused=True, both=False, version=None, counters=None, range_mode=None, exact_scores=None):
+def run_gpu(dev, c, fused=True, both=False, version=None, counters=None, range_mode=None, exact_scores=None,
+            box_counters=None):
     """exact_scores: None = on exactly when the reverse grid is read (its scores are only the reference's bits under
     cvhip_ctx_set_exact_scores; the forward grid of the last level always is)."""
     p1, p2 = cases.pyramids(c)
@@ -51,6 +53,8 @@ def run_gpu(dev, c, fused=True, both=False, version=None, counters=None, range_m
         fwd = pc.complete(correlation.CorrelationDirection.Forward)
         if counters is not None:
             counters.update(pc.get_counters())
+            if box_counters is not None:
+                box_counters.update(pc.get_box_counters())
         if both:
             return fwd, pc.complete(correlation.CorrelationDirection.Reverse)
         return fwd
@@ -1398,3 +1402,28 @@ def test_sizes_beyond_the_benchmark_equal_exact_kernel(gpu_device, w, h, tilt):
         assert 0.8 < float(valid.float().mean()) < 0.95
         assert torch.equal(xy, xy1)
         assert torch.equal(corr.view(torch.int32)[valid], corr1.view(torch.int32)[valid])
+
+
+@pytest.mark.parametrize("version", [3, 4])
+@pytest.mark.parametrize("name", sorted(box_scenes.SCENES))
+def test_stepped_walk_past_64_steps(gpu_device, oracle, name, version):
+    """Waves of the stepped box walk whose displacement range is 65 steps - one more than the lanes of the walk's step
+    table - along lines that change row over them (tests/box_scenes.py; test_box_scenes.py shows it from the oracle's
+    ranges): the grids of the timed instantiation, and of the counting one with the oracle's candidate count."""
+    c = box_scenes.make_scene(name)
+    p1, p2 = cases.pyramids(c)
+    _, _, cand = oracle.correlate_dense(p1, p2, c["F"], c["projection"], 8)
+    want_f, want_r = run_oracle(oracle, c, both=True)
+    got_f, got_r = run_gpu(gpu_device, c, both=True, version=version)
+    assert_same_grid(got_f, want_f, f"{name} v{version} forward")
+    assert_same_grid(got_r, want_r, f"{name} v{version} reverse")
+    cnt, box = {}, {}
+    got_f, got_r = run_gpu(gpu_device, c, both=True, version=version, counters=cnt, box_counters=box)
+    print(name, version, cnt, box)
+    assert_same_grid(got_f, want_f, f"{name} v{version} forward, counters")
+    assert_same_grid(got_r, want_r, f"{name} v{version} reverse, counters")
+    assert cnt["candidates"] == cand, (cnt, cand)
+    # the case is reached - and walked: no wave is wider than 65 steps, and some are exactly that
+    own, other = ("waves65_transposed", "waves65_rowmajor") if c["transposed"] else ("waves65_rowmajor", "waves65_transposed")
+    assert box[own] >= 1 and box[other] == 0, box
+    assert box["max_steps"] == 65, box
