@@ -98,6 +98,19 @@ SIGNATURES = {
     "cvhip_optimize_perspective_f": (C.c_int, [_vp, _vp, _u32, _vp, _vp]),
     "cvhip_optimize_perspective_f_device": (C.c_int, [_vp, _vp, _vp, _u32, _vp, _vp]),
     "cvhip_ransac_score": (C.c_int, [_vp, _vp, _u32, _vp, _u32, C.c_double, _vp, _vp]),
+    "cvhip_triangulate_perspective_cameras": (C.c_int, [_vp, _vp, C.c_uint64, _u32, _vp, _vp, _vp, _vp, C.c_int, _vp, _vp,
+                                                        _vp, _vp, _vp, C.POINTER(C.c_uint64), C.POINTER(_u32), _vp, _vp,
+                                                        PROGRESS_FN, _vp]),
+    "cvhip_extend_tracks_matches": (C.c_int, [_vp, _vp, C.c_uint64, _u32, _u32, _vp, C.c_uint64, _u32, _vp, _vp, _vp,
+                                              C.c_uint64, C.POINTER(C.c_uint64)]),
+    "cvhip_triangulate_tracks": (C.c_int, [_vp, _vp, C.c_uint64, _u32, _vp, _vp, _vp, _vp]),
+    "cvhip_find_projection_matrix": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_uint64, _vp, C.POINTER(C.c_double), _vp,
+                                               _vp]),
+    "cvhip_recover_pose": (C.c_int, [_vp, _vp, C.c_uint64, _u32, _vp, _vp, _vp, _vp, _u32, _vp, _u32, C.c_uint64, _vp, _vp,
+                                     _vp, C.POINTER(_u32), C.POINTER(C.c_double), C.POINTER(_u32), _vp, PROGRESS_FN,
+                                     _vp]),
+    "cvhip_recover_pose_models": (C.c_int, [_vp, _vp, C.c_uint64, _u32, _vp, _vp, _vp, _vp, _u32, _vp, _u32, _vp, _u32, _vp,
+                                            _vp, _vp, _vp]),
 }
 
 

@@ -8,7 +8,9 @@
 // and every remaining Some cell starts a new track, in scan order (:1397-1416).  Integer only: bit-exact.
 #include "cvhip_internal.hpp"
 
+#include <algorithm>
 #include <string>
+#include <vector>
 
 namespace cvhip {
 
@@ -203,6 +205,69 @@ extern "C" int cvhip_extend_tracks(cvhip_ctx *ctx, const int32_t *track_p1, uint
     if (cap && !n1_dev && d_n1) (void)hipFree(d_n1);
     if (cap && !n2_dev && d_n2) (void)hipFree(d_n2);
     if (e != hipSuccess) return fail(CVHIP_ERR_DEVICE, std::string("extend_tracks: ") + hipGetErrorString(e));
+    if (h_oob) return fail(CVHIP_ERR_INVALID, "Index out of bounds (a merged match lies outside the image-1 grid; the reference panics here, data.rs:61-64)");
+    *out_n_new = h_total;
+    return CVHIP_OK;
+}
+
+// extend_tracks (triangulation.rs:1330-1419) with the grid add_image_pair_sparse builds from a pair's RANSAC inliers
+// (:628-633): image-1 shape w1 x h1, cell (x1, y1) = Some(x2, y2), a later duplicate of a point overwriting an earlier one.
+// The grid is uploaded as full-resolution cells and runs through the dense path's kernels above.
+extern "C" int cvhip_extend_tracks_matches(cvhip_device *dev, const uint32_t *inliers, uint64_t n_inliers, uint32_t w1,
+                                           uint32_t h1, const int32_t *track_p1, uint64_t n_tracks, uint32_t max_dimension2,
+                                           int32_t *out_track_p2, uint32_t *out_new_p1, uint32_t *out_new_p2, uint64_t cap,
+                                           uint64_t *out_n_new)
+{
+    if (!dev || !out_n_new || (n_inliers && !inliers)) return fail(CVHIP_ERR_INVALID, "null argument");
+    if (n_tracks && (!track_p1 || !out_track_p2)) return fail(CVHIP_ERR_INVALID, "track arrays are null");
+    if (cap && (!out_new_p1 || !out_new_p2)) return fail(CVHIP_ERR_INVALID, "new-track arrays are null");
+    if (w1 == 0 || h1 == 0 || w1 > 65535 || h1 > 65535) return fail(CVHIP_ERR_INVALID, "extend_tracks_matches: image size");
+    std::vector<uint32_t> cells((size_t)w1 * h1, CELL_NONE);
+    for (uint64_t i = 0; i < n_inliers; i++) {
+        const uint32_t *m = inliers + 4 * i;
+        // (x2, y2) are packed in 16 bits each, and 0xFFFF / 0xFFFF would read as the empty cell: 65535 is rejected too
+        if (m[0] >= w1 || m[1] >= h1 || m[2] >= 65535 || m[3] >= 65535)
+            return fail(CVHIP_ERR_INVALID, "extend_tracks_matches: an inlier lies outside the image-1 grid");
+        cells[(size_t)m[1] * w1 + m[0]] = m[2] | (m[3] << 16);
+    }
+    CVHIP_TRY_HIP(hipSetDevice(dev->d.ordinal));
+    hipStream_t s = dev->d.stream;
+    const size_t n = (size_t)w1 * h1;
+    const uint32_t nblocks = (uint32_t)((n + 255) / 256);
+    uint32_t *d_cells = nullptr, *d_counts = nullptr, *d_n1 = nullptr, *d_n2 = nullptr;
+    uint8_t *d_removed = nullptr;
+    int2 *d_tp1 = nullptr, *d_tp2 = nullptr;
+    const size_t capw = (size_t)std::max<uint64_t>(cap, 1);
+    hipError_t e = hipMalloc(&d_cells, n * 4);
+    if (e == hipSuccess) e = hipMalloc(&d_removed, n);
+    if (e == hipSuccess) e = hipMalloc(&d_counts, ((size_t)nblocks + 2) * 4);
+    if (e == hipSuccess) e = hipMalloc(&d_tp1, std::max<uint64_t>(n_tracks, 1) * sizeof(int2));
+    if (e == hipSuccess) e = hipMalloc(&d_tp2, std::max<uint64_t>(n_tracks, 1) * sizeof(int2));
+    if (e == hipSuccess) e = hipMalloc(&d_n1, capw * 8);
+    if (e == hipSuccess) e = hipMalloc(&d_n2, capw * 8);
+    uint32_t *total = d_counts + nblocks, *oob = d_counts + nblocks + 1;
+    if (e == hipSuccess) e = hipMemcpyAsync(d_cells, cells.data(), n * 4, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemsetAsync(d_removed, 0, n, s);
+    if (e == hipSuccess) e = hipMemsetAsync(oob, 0, 4, s);
+    if (e == hipSuccess && n_tracks) e = hipMemcpyAsync(d_tp1, track_p1, n_tracks * sizeof(int2), hipMemcpyHostToDevice, s);
+    // EXTEND_TRACKS_SEARCH_RADIUS = 3, TRACKS_RADIUS_DENOMINATOR = 1000 (triangulation.rs:16, 19, 1346-1350)
+    const uint32_t radius = max_dimension2 > 1000 ? (uint32_t)((uint64_t)3 * max_dimension2 / 1000) : 3u;
+    uint32_t h_total = 0, h_oob = 0;
+    if (e == hipSuccess) {
+        launch_extend_tracks_match(d_cells, w1, h1, 0, w1, h1, d_tp1, n_tracks, radius, d_tp2, d_removed, oob, s);
+        launch_extend_tracks_new(d_cells, w1, h1, 0, w1, h1, d_removed, d_counts, total, d_n1, d_n2, cap, s);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(&h_total, total, 4, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(&h_oob, oob, 4, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess && n_tracks) e = hipMemcpyAsync(out_track_p2, d_tp2, n_tracks * sizeof(int2), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    const uint64_t written = h_total < cap ? h_total : cap;
+    if (e == hipSuccess && written) e = hipMemcpy(out_new_p1, d_n1, (size_t)written * 8, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && written) e = hipMemcpy(out_new_p2, d_n2, (size_t)written * 8, hipMemcpyDeviceToHost);
+    for (void *p : {(void *)d_cells, (void *)d_removed, (void *)d_counts, (void *)d_tp1, (void *)d_tp2, (void *)d_n1, (void *)d_n2})
+        if (p) (void)hipFree(p);
+    if (e != hipSuccess) return fail(CVHIP_ERR_DEVICE, std::string("extend_tracks_matches: ") + hipGetErrorString(e));
     if (h_oob) return fail(CVHIP_ERR_INVALID, "Index out of bounds (a merged match lies outside the image-1 grid; the reference panics here, data.rs:61-64)");
     *out_n_new = h_total;
     return CVHIP_OK;

@@ -3,6 +3,7 @@
 // All arithmetic is f64, as in the reference.  Every reduction runs in a fixed order (fixed grid, per-thread sums in
 // track order, wave shuffles, LDS, then the per-block partials in block order), so two runs are bit-identical.
 #include "cvhip_internal.hpp"
+#include "tri_common.hpp"
 
 #include <cmath>
 #include <cstring>
@@ -10,8 +11,6 @@
 namespace {
 
 constexpr int MAXC = CVHIP_TRIANGULATE_MAX_CAMERAS;
-constexpr double F64_EPS = 2.220446049250313e-16;         // f64::EPSILON
-constexpr double PERSPECTIVE_SCALE_THRESHOLD = 0.0001;    // triangulation.rs:20
 constexpr int BA_MAX_ITERATIONS = 100;                    // :15 BUNDLE_ADJUSTMENT_MAX_ITERATIONS
 constexpr double BA_INITIAL_MU = 1e-3;                    // :1687
 constexpr double BA_GRADIENT_EPSILON = 1e-12;             // :1688
@@ -31,21 +30,6 @@ struct TriCam {
     double Dr[3][9];
     double cr[3][3];
 };
-
-// Camera::matrix_r (:475-485)
-__host__ __device__ inline void matrix_r(const double r[3], double R[9])
-{
-    double theta = sqrt(r[0] * r[0] + r[1] * r[1] + r[2] * r[2]);
-    if (fabs(theta) < F64_EPS) {
-        for (int i = 0; i < 9; i++) R[i] = (i % 4 == 0) ? 1.0 : 0.0;
-        return;
-    }
-    double u[3] = {r[0] / theta, r[1] / theta, r[2] / theta};
-    double c = cos(theta), s = sin(theta);
-    double ux[9] = {0.0, -u[2], u[1], u[2], 0.0, -u[0], -u[1], u[0], 0.0};
-    for (int i = 0; i < 3; i++)
-        for (int j = 0; j < 3; j++) R[3 * i + j] = ((i == j ? c : 0.0) + (1.0 - c) * u[i] * u[j]) + ux[3 * i + j] * s;
-}
 
 // Camera::{matrix_r, center, projection} (:475-507) and the camera-only parts of jacobian_a (:1706-1743)
 __host__ __device__ inline void cam_setup(TriCam &c, const double K[9], const double r[3], const double t[3])
@@ -193,10 +177,7 @@ __device__ inline double block_max(double v, double *lds)
 }
 
 // ---- triangulate_track (:867-911) + filter_outliers (:1559-1593), one track per lane ----------------------------------
-// A (2k x 4, rows P.row(2) x - P.row(0), P.row(2) y - P.row(1) over the seen views in camera order) is reduced to the 4 x 4
-// triangular R of its QR decomposition by Givens rotations (same right singular vectors and singular values, A^T A is
-// never formed), then a one-sided Jacobi SVD of R gives V; the right singular vector of the smallest singular value is
-// the point.
+// The DLT (Givens QR of the 2k x 4 system, one-sided Jacobi SVD of its R) is tri_common.hpp's, shared with pose recovery.
 template <int M>
 __global__ __launch_bounds__(BLOCK) void tri_dlt_filter_kernel(const int2 *__restrict__ tracks, uint64_t n,
                                                                const TriCam *__restrict__ cams, double cos_threshold,
@@ -208,75 +189,18 @@ __global__ __launch_bounds__(BLOCK) void tri_dlt_filter_kernel(const int2 *__res
     double X[3] = {0.0, 0.0, 0.0};
     if (i < n) {
         double R[16];
-        for (int k = 0; k < 16; k++) R[k] = 0.0;
+        dlt_init(R);
         int seen = 0;
 #pragma unroll
         for (int j = 0; j < M; j++) {
             int2 o = tracks[i * M + j];
             if (o.x < 0) continue;
             seen++;
-            const double *P = cams[j].Pg;
-            for (int rr = 0; rr < 2; rr++) {
-                double xv = rr == 0 ? (double)o.x : (double)o.y;
-                double a[4];
-                for (int c = 0; c < 4; c++) a[c] = P[8 + c] * xv - P[4 * rr + c];
-                for (int c = 0; c < 4; c++) {
-                    double h = hypot(R[5 * c], a[c]);
-                    if (h == 0.0) continue;
-                    double cs = R[5 * c] / h, sn = a[c] / h;
-                    for (int l = c; l < 4; l++) {
-                        double t1 = cs * R[4 * c + l] + sn * a[l];
-                        a[l] = cs * a[l] - sn * R[4 * c + l];
-                        R[4 * c + l] = t1;
-                    }
-                    a[c] = 0.0;
-                }
-            }
+            dlt_fold_view(R, cams[j].Pg, (double)o.x, (double)o.y);
         }
         if (seen >= 2) {
-            double V[16];
-            for (int k = 0; k < 16; k++) V[k] = (k % 5 == 0) ? 1.0 : 0.0;
-            for (int sweep = 0; sweep < 40; sweep++) {
-                bool rotated = false;
-                for (int p = 0; p < 3; p++)
-                    for (int q = p + 1; q < 4; q++) {
-                        double al = 0.0, be = 0.0, ga = 0.0;
-                        for (int r = 0; r < 4; r++) {
-                            al += R[4 * r + p] * R[4 * r + p];
-                            be += R[4 * r + q] * R[4 * r + q];
-                            ga += R[4 * r + p] * R[4 * r + q];
-                        }
-                        if (ga == 0.0 || fabs(ga) <= 1e-17 * sqrt(al * be)) continue;
-                        rotated = true;
-                        double zeta = (be - al) / (2.0 * ga);
-                        double t = (zeta >= 0.0 ? 1.0 : -1.0) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
-                        double c = 1.0 / sqrt(1.0 + t * t), s = c * t;
-                        for (int r = 0; r < 4; r++) {
-                            double rp = R[4 * r + p], rq = R[4 * r + q];
-                            R[4 * r + p] = c * rp - s * rq;
-                            R[4 * r + q] = s * rp + c * rq;
-                            double vp = V[4 * r + p], vq = V[4 * r + q];
-                            V[4 * r + p] = c * vp - s * vq;
-                            V[4 * r + q] = s * vp + c * vq;
-                        }
-                    }
-                if (!rotated) break;
-            }
-            int best = 0;
-            double best_n = INFINITY;
-            for (int c = 0; c < 4; c++) {
-                double s2 = 0.0;
-                for (int r = 0; r < 4; r++) s2 += R[4 * r + c] * R[4 * r + c];
-                if (s2 < best_n) best_n = s2, best = c;
-            }
             double v4[4];
-            for (int r = 0; r < 4; r++) v4[r] = V[4 * r + best];
-            double nv = sqrt(v4[0] * v4[0] + v4[1] * v4[1] + v4[2] * v4[2] + v4[3] * v4[3]);
-            double w = v4[3] / nv;
-            if (!(fabs(w) < PERSPECTIVE_SCALE_THRESHOLD)) { // :896-898
-                for (int k = 0; k < 3; k++) X[k] = (v4[k] / nv) / w; // remove_row(3).unscale(w) (:906-907)
-                ok = 1;
-            }
+            ok = dlt_solve(R, v4, X) ? 1 : 0;
         }
         if (ok) {
             // filter_outliers: every seen view has the point in front (point_depth, :492-500; :1568-1578)
@@ -755,52 +679,6 @@ bool tri_dev_ptr(const void *p)
     return attr.type == hipMemoryTypeDevice || attr.type == hipMemoryTypeManaged;
 }
 
-// Camera::from_matrix (:414-466): Rodrigues after Tomasi, with its 180 degree branch.  As written, rho = (a21 - a12, ..)
-// is 2 sin(theta) u (Tomasi's is sin(theta) u), so the angle comes out as atan2(2 sin(theta), cos(theta)): a camera
-// built from R rotates by more than R unless theta is 0 or 180 degrees.  Kept: the reference's cameras are these.
-void from_matrix(const double *Rm, double r[3])
-{
-    auto R = [&](int i, int j) { return Rm[3 * i + j]; };
-    double a[9];
-    for (int i = 0; i < 3; i++)
-        for (int j = 0; j < 3; j++) a[3 * i + j] = (R(i, j) - R(j, i)) / 2.0;
-    double rho[3] = {a[7] - a[5], a[2] - a[6], a[3] - a[1]};
-    double s = std::sqrt(rho[0] * rho[0] + rho[1] * rho[1] + rho[2] * rho[2]);
-    double c = ((R(0, 0) + R(1, 1)) + R(2, 2) - 1.0) / 2.0;
-    if (std::fabs(s) < F64_EPS && std::fabs(c - 1.0) < F64_EPS) {
-        r[0] = r[1] = r[2] = 0.0;
-    } else if (std::fabs(s) < F64_EPS && std::fabs(c + 1.0) < F64_EPS) {
-        int v_i = 0;
-        double v_norm = 0.0;
-        for (int col = 0; col < 3; col++) {
-            double x = R(0, col) + (col == 0), y = R(1, col) + (col == 1), z = R(2, col) + (col == 2);
-            double nn = std::sqrt(x * x + y * y + z * z);
-            if (nn > v_norm) v_i = col, v_norm = nn;
-        }
-        double v[3] = {R(0, v_i) + (v_i == 0), R(1, v_i) + (v_i == 1), R(2, v_i) + (v_i == 2)};
-        double vn = std::sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
-        for (int k = 0; k < 3; k++) r[k] = (v[k] / vn) * M_PI;
-        double rn = std::sqrt(r[0] * r[0] + r[1] * r[1] + r[2] * r[2]);
-        if (std::fabs(rn - M_PI) < F64_EPS &&
-            ((std::fabs(r[0]) < F64_EPS && std::fabs(r[1]) < F64_EPS && r[2] < 0.0) || (std::fabs(r[0]) < F64_EPS && r[1] < 0.0) ||
-             r[0] < 0.0))
-            for (int k = 0; k < 3; k++) r[k] = -r[k];
-    } else {
-        double theta = std::atan2(s, c);
-        for (int k = 0; k < 3; k++) r[k] = (rho[k] / s) * theta;
-    }
-}
-
-// k * [R | t] (:737-740): the projection triangulate_tracks uses for a camera given as matrices
-void given_projection(const double *K, const double *R, const double *t, double P[12])
-{
-    for (int i = 0; i < 3; i++)
-        for (int j = 0; j < 4; j++) {
-            double a0 = j < 3 ? R[j] : t[0], a1 = j < 3 ? R[3 + j] : t[1], a2 = j < 3 ? R[6 + j] : t[2];
-            P[4 * i + j] = K[3 * i] * a0 + K[3 * i + 1] * a1 + K[3 * i + 2] * a2;
-        }
-}
-
 struct Bufs {
     int2 *tracks = nullptr;
     double *pts = nullptr, *Xn = nullptr, *gb = nullptr, *kept = nullptr, *part = nullptr, *part_max = nullptr, *sums = nullptr;
@@ -822,6 +700,7 @@ struct Args {
     uint64_t n;
     uint32_t m;
     const double *K, *R, *t;
+    const double *rv, *P; // cvhip_triangulate_perspective_cameras: the cameras' r and projections as held (else NULL)
     int bundle_adjustment;
     double *out_points;
     uint64_t *out_index;
@@ -850,6 +729,11 @@ int run(const Args &a)
     const uint32_t nb = (uint32_t)((n + BLOCK - 1) / BLOCK);
     TriCam hc[M];
     for (int j = 0; j < M; j++) {
+        if (a.rv) { // a camera as the reference holds it: r and the projection the DLT uses, both given
+            cam_setup(hc[j], a.K + 9 * j, a.rv + 3 * j, a.t + 3 * j);
+            std::memcpy(hc[j].Pg, a.P + 12 * j, 96);
+            continue;
+        }
         double r[3];
         from_matrix(a.R + 9 * j, r);
         cam_setup(hc[j], a.K + 9 * j, r, a.t + 3 * j);
@@ -964,14 +848,15 @@ int run(const Args &a)
 
 } // namespace
 
-extern "C" int cvhip_triangulate_perspective(cvhip_device *dev, const int32_t *tracks, uint64_t n, uint32_t m, const double *K,
-                                             const double *R, const double *t, int bundle_adjustment, double *out_points,
-                                             uint64_t *out_index, double *out_r, double *out_t, double *out_projection,
-                                             uint64_t *out_n, uint32_t *out_iterations, uint8_t *out_history,
-                                             double *out_residual_norms, cvhip_progress_fn progress, void *user)
+namespace {
+int triangulate_perspective(cvhip_device *dev, const int32_t *tracks, uint64_t n, uint32_t m, const double *K,
+                            const double *R, const double *rv, const double *P, const double *t, int bundle_adjustment,
+                            double *out_points, uint64_t *out_index, double *out_r, double *out_t, double *out_projection,
+                            uint64_t *out_n, uint32_t *out_iterations, uint8_t *out_history, double *out_residual_norms,
+                            cvhip_progress_fn progress, void *user)
 {
     using cvhip::fail;
-    if (!dev || !K || !R || !t || !out_n || (n && (!tracks || !out_points || !out_index)))
+    if (!dev || !K || (!R && !(rv && P)) || !t || !out_n || (n && (!tracks || !out_points || !out_index)))
         return fail(CVHIP_ERR_INVALID, "null argument");
     if (m < 2) return fail(CVHIP_ERR_INVALID, "triangulate_perspective: at least two cameras are needed");
     if (m > CVHIP_TRIANGULATE_MAX_CAMERAS)
@@ -982,7 +867,8 @@ extern "C" int cvhip_triangulate_perspective(cvhip_device *dev, const int32_t *t
         for (uint32_t j = 0; j < m; j++) {
             double r[3];
             TriCam c;
-            from_matrix(R + 9 * j, r);
+            if (rv) std::memcpy(r, rv + 3 * j, 24);
+            else from_matrix(R + 9 * j, r);
             cam_setup(c, K + 9 * j, r, t + 3 * j);
             if (out_r) std::memcpy(out_r + 3 * j, c.r, 24);
             if (out_t) std::memcpy(out_t + 3 * j, c.t, 24);
@@ -995,7 +881,7 @@ extern "C" int cvhip_triangulate_perspective(cvhip_device *dev, const int32_t *t
     }
     hipError_t e = hipSetDevice(dev->d.ordinal);
     if (e != hipSuccess) return fail(CVHIP_ERR_DEVICE, std::string("hipSetDevice: ") + hipGetErrorString(e));
-    Args a{dev, tracks, n, m, K, R, t, bundle_adjustment, out_points, out_index, out_r, out_t, out_projection, out_n,
+    Args a{dev, tracks, n, m, K, R, t, rv, P, bundle_adjustment, out_points, out_index, out_r, out_t, out_projection, out_n,
            out_iterations, out_history, out_residual_norms, progress, user};
     switch (m) {
     case 2: return run<2>(a);
@@ -1006,4 +892,31 @@ extern "C" int cvhip_triangulate_perspective(cvhip_device *dev, const int32_t *t
     case 7: return run<7>(a);
     default: return run<8>(a);
     }
+}
+} // namespace
+
+extern "C" int cvhip_triangulate_perspective(cvhip_device *dev, const int32_t *tracks, uint64_t n, uint32_t m, const double *K,
+                                             const double *R, const double *t, int bundle_adjustment, double *out_points,
+                                             uint64_t *out_index, double *out_r, double *out_t, double *out_projection,
+                                             uint64_t *out_n, uint32_t *out_iterations, uint8_t *out_history,
+                                             double *out_residual_norms, cvhip_progress_fn progress, void *user)
+{
+    if (!R) return cvhip::fail(CVHIP_ERR_INVALID, "null argument");
+    return triangulate_perspective(dev, tracks, n, m, K, R, nullptr, nullptr, t, bundle_adjustment, out_points, out_index,
+                                   out_r, out_t, out_projection, out_n, out_iterations, out_history, out_residual_norms,
+                                   progress, user);
+}
+
+extern "C" int cvhip_triangulate_perspective_cameras(cvhip_device *dev, const int32_t *tracks, uint64_t n, uint32_t m,
+                                                     const double *K, const double *r, const double *t,
+                                                     const double *projection, int bundle_adjustment, double *out_points,
+                                                     uint64_t *out_index, double *out_r, double *out_t,
+                                                     double *out_projection, uint64_t *out_n, uint32_t *out_iterations,
+                                                     uint8_t *out_history, double *out_residual_norms,
+                                                     cvhip_progress_fn progress, void *user)
+{
+    if (!r || !projection) return cvhip::fail(CVHIP_ERR_INVALID, "null argument");
+    return triangulate_perspective(dev, tracks, n, m, K, nullptr, r, projection, t, bundle_adjustment, out_points,
+                                   out_index, out_r, out_t, out_projection, out_n, out_iterations, out_history,
+                                   out_residual_norms, progress, user);
 }

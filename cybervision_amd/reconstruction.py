@@ -273,3 +273,88 @@ def reconstruct_perspective_surface(device, pyramids, pairs_result, cameras, bun
                 pc.close()
     surface = rec._timed("triangulate", lambda: tri.triangulate_all(device, cameras, progress=progress))
     return {"surface": surface, "tracks": tri.tracks, "timings_ms": dict(rec.timings_ms)}
+
+
+def recover_camera_poses(device, tri, seed: int = 0, log=None):
+    """recover_camera_poses (reconstruction.rs:627-666) over a PerspectiveTriangulation whose sparse pairs are in: calls
+    recover_next_cameras until it places no more images; an image whose recover_pose fails is skipped (the reference prints
+    the error and goes on).  Then complete_sparse_triangulation.  -> (camera_order, per-call info)."""
+    from . import _lib
+
+    order, info = [], []
+    while True:
+        try:
+            images = tri.recover_next_cameras(device, seed=seed + len(info))
+        except _lib.CvhipError as exc:  # "Failed to recover pose for next image"
+            info.append({"error": str(exc), **(tri.last_pose or {})})
+            if log is not None:
+                log(f"Failed to recover pose for next image: {exc}")
+            continue
+        if not images:
+            break
+        info.append({"images": images, **((tri.last_pose or {}) if len(images) == 1 else {})})
+        order.extend(images)
+    tri.complete_sparse_triangulation()
+    return order, info
+
+
+def reconstruct_perspective(device, pyramids, K, bundle_adjustment: bool = True, seed: int = 0, pairs_result=None,
+                            progress=None):
+    """The perspective `reconstruct` in the reference's order for n views (reconstruction.rs:261-277, 380-395, 627-752):
+    the sparse stage per pair (ORB, matcher, RANSAC - reconstruct_pairs with dense=False, or the caller's `pairs_result`),
+    add_image_pair_sparse for every pair with an F (a pair that fails is skipped), recover_camera_poses, the dense
+    correlation and extend_tracks of the pairs of linked images only, and triangulate_all with the recovered cameras.
+    K: one 3 x 3 matrix for every view, or one per view.  merge_tracks and max_points stay out.
+    -> dict: surface, camera_order, poses (per recover call), initial_pair, sparse ({pair: (p2, score, the short tracks scored)}), sparse_tracks (the
+    table before complete_sparse_triangulation), tracks, cameras, projections, pairs, timings_ms."""
+    from . import triangulation
+
+    n = len(pyramids)
+    Ks = [np.asarray(K[i] if np.ndim(K) == 3 else K, dtype=np.float64) for i in range(n)]
+    if pairs_result is None:
+        pairs_result = reconstruct_pairs(device, pyramids, ProjectionMode.Perspective, seed=seed, dense=False)
+    rec = ImageReconstruction(device, ProjectionMode.Perspective)
+    shapes = [(int(p[0].shape[1]), int(p[0].shape[0])) for p in pyramids]
+    tri = triangulation.PerspectiveTriangulation(n, shapes, bundle_adjustment=bundle_adjustment, calibration=Ks)
+    from . import _lib
+
+    sparse = {}
+    for (i, j), entry in sorted(pairs_result["pairs"].items()):
+        if entry["f"] is None:
+            continue
+        try:
+            p2, score = rec._timed("sparse", lambda i=i, j=j, e=entry: tri.add_image_pair_sparse(device, i, j, e["f"],
+                                                                                               e["inliers"]))
+            sparse[(i, j)] = (p2, score, tri.last_short)
+        except _lib.CvhipError:
+            continue
+    initial = tri.best_initial_pair
+    sparse_tracks = tri.tracks.copy()
+    order, poses = rec._timed("poses", lambda: recover_camera_poses(device, tri, seed=seed))
+    linked = set(order)
+    mode = correlation.ProjectionMode(int(ProjectionMode.Perspective))
+    for i in range(n):
+        if i not in linked:
+            continue
+        for j in range(i + 1, n):
+            entry = pairs_result["pairs"].get((i, j))
+            if j not in linked or entry is None or entry["f"] is None:
+                continue
+            pc = correlation.PointCorrelations(device, shapes[i], shapes[j], entry["f"], mode)
+            try:
+                def run(pc=pc, pi=pyramids[i], pj=pyramids[j], i=i):
+                    steps = correlation.optimal_scale_steps(*shapes[i])
+                    for s in range(steps + 1):
+                        k = steps - s
+                        pc.correlate_images(pi[k], pj[k], 1.0 / float(1 << k))
+                    return pc.complete()
+
+                rec._timed("dense", run)
+                rec._timed("tracks", lambda pc=pc, i=i, j=j: tri.add_image_pair_dense(i, j, pc))
+            finally:
+                pc.close()
+    surface = rec._timed("triangulate", lambda: tri.triangulate_all_recovered(device, progress=progress))
+    return {"surface": surface, "camera_order": order, "poses": poses, "initial_pair": initial, "sparse": sparse,
+            "sparse_tracks": sparse_tracks, "tracks": tri.tracks,
+            "cameras": list(tri.cameras), "projections": list(tri.projections), "pairs": pairs_result,
+            "timings_ms": dict(rec.timings_ms)}

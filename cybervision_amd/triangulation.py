@@ -1,7 +1,8 @@
 """PerspectiveTriangulation (src/triangulation.rs:604-1593) over the C ABI: the dense track table that
 extend_tracks builds pair by pair, and triangulate_all (:817-865) - DLT points, filter_outliers and the bundle
-adjustment - in one call of cvhip_triangulate_perspective.  The cameras are the caller's: pose recovery
-(recover_pose / find_projection_matrix, :1033-1278) and merge_tracks (:1421-1540) are not part of this module.
+adjustment - in one call of cvhip_triangulate_perspective - and the sparse half that recovers the cameras
+(add_image_pair_sparse, recover_next_cameras, :620-811): find_projection_matrix, triangulate_tracks and the P3P RANSAC of
+recover_pose run on the device.  merge_tracks (:1421-1540) is not part of this module.
 No compute in Python - the track table's bookkeeping and the calls only.
 """
 from __future__ import annotations
@@ -40,14 +41,187 @@ class Surface:
 
 
 class PerspectiveTriangulation:
-    """The dense half of PerspectiveTriangulation: tracks [n, images_count, 2] int32, (-1, -1) = no point."""
+    """PerspectiveTriangulation: tracks [n, images_count, 2] int32, (-1, -1) = no point; the sparse half places the cameras."""
 
-    def __init__(self, images_count: int, image_shapes, bundle_adjustment: bool = True):
-        """image_shapes: (width, height) per image (image_shapes, :604-617)."""
+    def __init__(self, images_count: int, image_shapes, bundle_adjustment: bool = True, calibration=None):
+        """image_shapes: (width, height) per image; calibration: K per image (set_image_data, :604-617, 700-703)."""
         self.images_count = int(images_count)
         self.image_shapes = [tuple(int(v) for v in s) for s in image_shapes]
         self.bundle_adjustment = bool(bundle_adjustment)
         self.tracks = np.full((0, self.images_count, 2), -1, dtype=np.int32)
+        n = self.images_count
+        self.calibration = [None if calibration is None else np.ascontiguousarray(calibration[i], dtype=np.float64)
+                            for i in range(n)]
+        self.projections = [None] * n   # 3 x 4, calibrated
+        self.cameras = [None] * n       # (K, r, t) per placed image: the Camera as the reference holds it
+        self.points = np.zeros((0, 3))  # point3d of every track (valid where points_ok)
+        self.points_ok = np.zeros(0, dtype=bool)
+        self.best_initial_p2 = None
+        self.best_initial_r2 = None     # Camera::from_matrix's r of best_initial_p2's rotation
+        self.best_initial_kp2 = None    # k2 * best_initial_p2, as the library computed it
+        self.best_initial_score = None
+        self.best_initial_pair = None
+        self.remaining_images = list(range(n))
+        self.last_pose = None           # what the last recover_pose call returned (count, error, batches)
+
+    # ---- sparse half ---------------------------------------------------------------------------------------------------
+    def _extend_tracks_matches(self, device, image1_index, image2_index, inliers):
+        """extend_tracks (:1330-1419) with add_image_pair_sparse's inlier grid (:628-638), on the device."""
+        inl = np.ascontiguousarray(np.asarray(inliers, dtype=np.uint32).reshape(-1, 4))
+        w1, h1 = self.image_shapes[image1_index]
+        max_dimension = max(self.image_shapes[image2_index])
+        tp1 = np.ascontiguousarray(self.tracks[:, image1_index])
+        n = len(tp1)
+        tp2 = np.full((max(n, 1), 2), -1, dtype=np.int32)
+        cap = max(len(inl), 1)
+        new_p1 = np.zeros((cap, 2), dtype=np.uint32)
+        new_p2 = np.zeros((cap, 2), dtype=np.uint32)
+        n_new = C.c_uint64(0)
+        p = lambda a: C.c_void_p(a.ctypes.data)  # noqa: E731
+        _lib.check(_lib.lib().cvhip_extend_tracks_matches(device.handle, p(inl), len(inl), w1, h1, p(tp1) if n else None, n,
+                                                          max_dimension, p(tp2) if n else None, p(new_p1), p(new_p2), cap,
+                                                          C.byref(n_new)), "cvhip_extend_tracks_matches")
+        tp2 = tp2[:n]
+        fill = (self.tracks[:, image2_index, 0] < 0) & (tp2[:, 0] >= 0)
+        self.tracks[fill, image2_index] = tp2[fill]
+        k = n_new.value
+        new = np.full((k, self.images_count, 2), -1, dtype=np.int32)
+        new[:, image1_index] = new_p1[:k].astype(np.int32)
+        new[:, image2_index] = new_p2[:k].astype(np.int32)
+        self.tracks = np.concatenate([self.tracks, new])
+        self.points = np.concatenate([self.points, np.zeros((k, 3))])
+        self.points_ok = np.concatenate([self.points_ok, np.zeros(k, dtype=bool)])
+
+    def add_image_pair_sparse(self, device, image1_index: int, image2_index: int, f, inliers):
+        """add_image_pair_sparse (:620-688): extend_tracks with the inliers ([k, 4] x1, y1, x2, y2), then
+        find_projection_matrix over the tracks seen in both images; the first pair with a strictly higher score becomes the
+        initial pair.  -> (p2 [3, 4] = [r | t], score)."""
+        self._extend_tracks_matches(device, image1_index, image2_index, inliers)  # (before the calibration check, :628-655)
+        k1, k2 = self.calibration[image1_index], self.calibration[image2_index]
+        if k1 is None or k2 is None:
+            raise _lib.CvhipError(-1, "add_image_pair_sparse", "Missing calibration matrix")
+        both = (self.tracks[:, image1_index, 0] >= 0) & (self.tracks[:, image2_index, 0] >= 0)
+        short = np.ascontiguousarray(self.tracks[both][:, [image1_index, image2_index]])
+        self.last_short = short
+        p2, r2, kp2 = np.zeros((3, 4)), np.zeros(3), np.zeros((3, 4))
+        score = C.c_double(0.0)
+        p = lambda a: C.c_void_p(a.ctypes.data)  # noqa: E731
+        F = np.ascontiguousarray(f, dtype=np.float64)
+        _lib.check(_lib.lib().cvhip_find_projection_matrix(device.handle, p(F), p(k1), p(k2), p(short) if len(short) else None,
+                                                           len(short), p(p2), C.byref(score), p(r2), p(kp2)),
+                   "cvhip_find_projection_matrix")
+        if self.best_initial_score is None or score.value > self.best_initial_score:
+            self.best_initial_p2 = p2
+            self.best_initial_r2 = r2
+            self.best_initial_kp2 = kp2
+            self.best_initial_pair = (image1_index, image2_index)
+            self.best_initial_score = score.value
+        return p2, score.value
+
+    def triangulate_tracks(self, device):
+        """triangulate_tracks (:905-911): every track's point from the images that have a projection (device)."""
+        n, m = len(self.tracks), self.images_count
+        has = np.array([pr is not None for pr in self.projections], dtype=np.uint8)
+        P = np.ascontiguousarray(np.stack([pr if pr is not None else np.zeros((3, 4)) for pr in self.projections]))
+        pts = np.zeros((max(n, 1), 3))
+        ok = np.zeros(max(n, 1), dtype=np.uint8)
+        p = lambda a: C.c_void_p(a.ctypes.data)  # noqa: E731
+        tr = np.ascontiguousarray(self.tracks)
+        _lib.check(_lib.lib().cvhip_triangulate_tracks(device.handle, p(tr) if n else None, n, m, p(P), p(has),
+                                                       p(pts) if n else None, p(ok) if n else None),
+                   "cvhip_triangulate_tracks")
+        self.points, self.points_ok = pts[:n], ok[:n].astype(bool)
+
+    def recover_next_cameras(self, device, seed: int = 0, progress=None):
+        """recover_next_cameras (:710-811) -> the images whose cameras were placed ([] when none is left).  The first call
+        places the initial pair (camera 1 at the origin, camera 2 from best_initial_p2); every later call takes the
+        remaining image seen by the most triangulated tracks - max_by_key keeps the LAST of equal counts - and runs
+        recover_pose for it; the tracks are re-triangulated after every placed camera.  Raises CvhipError
+        (CVHIP_ERR_NO_SURFACE, "Unable to find projection matrix") when recover_pose fails; that image stays unplaced."""
+        self.last_pose = None
+        if self.best_initial_pair is not None:
+            i1, i2 = self.best_initial_pair
+            k1, k2 = self.calibration[i1], self.calibration[i2]
+            p2 = self.best_initial_p2
+            # camera1 = from_matrix(k1, I, 0): r = 0, p1 = k1 [I | 0]; camera2 = from_matrix(k2, p2[:, :3], p2[:, 3]), whose r
+            # and k2 p2 cvhip_find_projection_matrix returned (:720-752); k1 [I | 0] is k1 next to a zero column, no arithmetic
+            self.projections[i1] = np.hstack([k1, np.zeros((3, 1))])
+            self.cameras[i1] = (k1, np.zeros(3), np.zeros(3))
+            self.projections[i2] = self.best_initial_kp2.copy()
+            self.cameras[i2] = (k2, self.best_initial_r2.copy(), p2[:, 3].copy())
+            self.triangulate_tracks(device)
+            self.remaining_images = [i for i in self.remaining_images if i not in (i1, i2)]
+            self.best_initial_pair = None
+            return [i1, i2]
+        seen = self.tracks[..., 0] >= 0
+        linked = self.points_ok & seen[:, self.remaining_images].any(axis=1) if self.remaining_images else self.points_ok
+        counts = {i: int((linked & seen[:, i]).sum()) for i in self.remaining_images}
+        if not self.remaining_images:
+            return []
+        best = self.remaining_images[0]
+        for i in self.remaining_images:  # max_by_key: the last maximum
+            if counts[i] >= counts[best]:
+                best = i
+        self.remaining_images = [i for i in self.remaining_images if i != best]
+        K = self.calibration[best]
+        n, m = len(self.tracks), self.images_count
+        has = np.array([pr is not None for pr in self.projections], dtype=np.uint8)
+        P = np.ascontiguousarray(np.stack([pr if pr is not None else np.zeros((3, 4)) for pr in self.projections]))
+        r, t, proj = np.zeros(3), np.zeros(3), np.zeros((3, 4))
+        cnt, err, batches = C.c_uint32(0), C.c_double(0.0), C.c_uint32(0)
+        winner = np.full(3, -1, dtype=np.int32)
+        cb = _lib.PROGRESS_FN(lambda _user, pos: progress(pos)) if progress is not None else _lib.NULL_PROGRESS
+        p = lambda a: C.c_void_p(a.ctypes.data)  # noqa: E731
+        tr = np.ascontiguousarray(self.tracks)
+        pts = np.ascontiguousarray(self.points)
+        ok = np.ascontiguousarray(self.points_ok.astype(np.uint8))
+        rc = _lib.lib().cvhip_recover_pose(device.handle, p(tr) if n else None, n, m, p(pts) if n else None,
+                                           p(ok) if n else None, p(P), p(has), best, p(np.ascontiguousarray(K)),
+                                           max(self.image_shapes[best]), int(seed), p(r), p(t), p(proj), C.byref(cnt),
+                                           C.byref(err), C.byref(batches), p(winner), cb, None)
+        self.last_pose = {"image": best, "count": int(cnt.value), "error": float(err.value), "batches": int(batches.value),
+                          "linked": counts[best], "winner": tuple(int(v) for v in winner), "r": r.copy(), "t": t.copy(),
+                          "projection": proj.copy()}
+        _lib.check(rc, "cvhip_recover_pose")
+        self.cameras[best] = (K, r, t)
+        self.projections[best] = proj
+        self.triangulate_tracks(device)
+        return [best]
+
+    def complete_sparse_triangulation(self):
+        """complete_sparse_triangulation (:813-815): the tracks go, the cameras stay."""
+        self.tracks = np.full((0, self.images_count, 2), -1, dtype=np.int32)
+        self.points = np.zeros((0, 3))
+        self.points_ok = np.zeros(0, dtype=bool)
+
+    def triangulate_all_recovered(self, device, progress=None) -> Surface:
+        """triangulate_all (:817-865) with the recovered cameras and projections (cvhip_triangulate_perspective_cameras);
+        images without a camera are pruned (prune_projections, :913-938)."""
+        keep = [i for i in range(self.images_count) if self.projections[i] is not None]
+        tracks = np.ascontiguousarray(self.tracks[:, keep])
+        m, n = len(keep), len(tracks)
+        K = np.ascontiguousarray(np.stack([self.cameras[i][0].reshape(9) for i in keep]))
+        R = np.ascontiguousarray(np.stack([self.cameras[i][1].reshape(3) for i in keep]))
+        t = np.ascontiguousarray(np.stack([self.cameras[i][2].reshape(3) for i in keep]))
+        P = np.ascontiguousarray(np.stack([self.projections[i] for i in keep]))
+        pts = np.zeros((max(n, 1), 3), dtype=np.float64)
+        idx = np.zeros(max(n, 1), dtype=np.uint64)
+        out_r, out_t, out_p = np.zeros((m, 3)), np.zeros((m, 3)), np.zeros((m, 3, 4))
+        out_n, iters = C.c_uint64(0), C.c_uint32(0)
+        history = np.zeros(BUNDLE_ADJUSTMENT_MAX_ITERATIONS, dtype=np.uint8)
+        norms = np.zeros(2)
+        cb = _lib.PROGRESS_FN(lambda _user, pos: progress(pos)) if progress is not None else _lib.NULL_PROGRESS
+        p = lambda a: C.c_void_p(a.ctypes.data)  # noqa: E731
+        _lib.check(_lib.lib().cvhip_triangulate_perspective_cameras(
+            device.handle, p(tracks) if n else None, n, m, p(K), p(R), p(t), p(P), int(self.bundle_adjustment), p(pts),
+            p(idx), p(out_r), p(out_t), p(out_p), C.byref(out_n), C.byref(iters), p(history), p(norms), cb, None),
+            "cvhip_triangulate_perspective_cameras")
+        k = out_n.value
+        index = idx[:k].astype(np.int64)
+        return Surface(points=pts[:k].copy(), track_index=index, tracks=tracks[index],
+                       cameras=[Camera(out_r[j].copy(), out_t[j].copy(), out_p[j].copy()) for j in range(m)],
+                       ba_iterations=int(iters.value), ba_history=[int(h) for h in history[:iters.value]],
+                       ba_residual_norms=(float(norms[0]), float(norms[1])))
 
     def add_image_pair_dense(self, image1_index: int, image2_index: int, pc):
         """extend_tracks (:1330-1419) with the completed grid of a pair's PointCorrelations `pc`: every track with a point

@@ -213,6 +213,77 @@ int cvhip_triangulate_perspective(cvhip_device *dev, const int32_t *tracks, uint
                                   uint64_t *out_n, uint32_t *out_iterations, uint8_t *out_history,
                                   double *out_residual_norms, cvhip_progress_fn progress, void *user);
 
+/* The same as cvhip_triangulate_perspective, with each camera given as the reference holds it after pose recovery
+ * (PerspectiveTriangulation::{cameras, projections}, triangulation.rs:604-617, 727-752, 805-808): r (m x 3, the Camera's
+ * axis-angle, as from_matrix made it), t (m x 3), K (m x 9) and projection (m x 12, what triangulate_tracks projects
+ * with).  For a P3P camera the projection is K [matrix_r(from_matrix(R)) | t], not K [R | t], which the entry above
+ * cannot express.  Outputs, limits and errors as above. */
+int cvhip_triangulate_perspective_cameras(cvhip_device *dev, const int32_t *tracks, uint64_t n, uint32_t m,
+                                          const double *K, const double *r, const double *t, const double *projection,
+                                          int bundle_adjustment, double *out_points, uint64_t *out_index, double *out_r,
+                                          double *out_t, double *out_projection, uint64_t *out_n,
+                                          uint32_t *out_iterations, uint8_t *out_history, double *out_residual_norms,
+                                          cvhip_progress_fn progress, void *user);
+
+/* ------------------------------------------------------------------------------------------
+ * Pose recovery, perspective pipeline (sparse stage).  All f64 on the device (csrc/pose_kernels.hip).
+ * tracks: n x m x 2 int32, (-1, -1) = no point; m <= CVHIP_TRIANGULATE_MAX_CAMERAS.  projections: m x 12 row-major
+ * (3 x 4, calibrated), used where has_projection[j] != 0.  Host pointers unless stated. */
+
+/* extend_tracks (triangulation.rs:1330-1419) with the grid add_image_pair_sparse builds from a pair's inliers
+ * (:620-638): inliers n_inliers x 4 uint32 (x1, y1, x2, y2); cell (x1, y1) of the w1 x h1 image-1 grid = (x2, y2), a later
+ * duplicate overwriting an earlier one.  Then as cvhip_extend_tracks: out_track_p2 per existing track, the remaining
+ * cells as new tracks in scan order (at most cap written, *out_n_new = their number).  Integer only, bit-exact.  The cells
+ * pack (x2, y2) in 16 bits each: image-2 coordinates 0..65534 (CVHIP_ERR_INVALID otherwise). */
+int cvhip_extend_tracks_matches(cvhip_device *dev, const uint32_t *inliers, uint64_t n_inliers, uint32_t w1, uint32_t h1,
+                                const int32_t *track_p1, uint64_t n_tracks, uint32_t max_dimension2, int32_t *out_track_p2,
+                                uint32_t *out_new_p1, uint32_t *out_new_p2, uint64_t cap, uint64_t *out_n_new);
+
+/* triangulate_tracks (triangulation.rs:867-911) with the images that have a projection: per track the DLT of its seen
+ * views among them; out_ok[i] = 0 (None) with fewer than 2 such views or |w| < 1e-4, else out_points[i] = xyz / w. */
+int cvhip_triangulate_tracks(cvhip_device *dev, const int32_t *tracks, uint64_t n, uint32_t m, const double *projections,
+                             const uint8_t *has_projection, double *out_points, uint8_t *out_ok);
+
+/* find_projection_matrix (triangulation.rs:940-994): E = K2^T F K1 projected onto diag(1, 1, 0); the candidates
+ * (r1, u3), (r1, -u3), (r2, u3), (r2, -u3) of its SVD (3 x 3 SVDs on the host); each scored by the short tracks (n x 2 x 2
+ * int32: the points in images 1 and 2) that triangulate with K1 [I | 0], K2 [r | t], have z > 0 and lie in front of
+ * Camera::from_matrix(K2, r, t) (cheirality, on the device).  out_P2 = [r | t] (12, uncalibrated) of the highest count -
+ * the LAST of equal counts, as Rust's max_by; the candidates' order follows the SVD's sign choices, so a tie between
+ * candidates is not pinned - and *out_score = that count.  out_r2 (3, may be NULL): the r of Camera::from_matrix(K2, r, t)
+ * for the winner - recover_next_cameras' camera 2 of the initial pair (:729-736); out_KP2 (12, may be NULL): K2 [r | t], the
+ * projection it stores for that camera (:737-740). */
+int cvhip_find_projection_matrix(cvhip_device *dev, const double *F, const double *K1, const double *K2,
+                                 const int32_t *short_tracks, uint64_t n, double *out_P2, double *out_score, double *out_r2,
+                                 double *out_KP2);
+
+/* recover_pose (triangulation.rs:1033-1144): the P3P RANSAC (Nakano, BMVC 2019) for image `image_index` over its linked
+ * tracks - the rows with ok[i] != 0 (points[i], n x 3, from cvhip_triangulate_tracks) and a point in that image, in table
+ * order.  K^-1 is pseudo_inverse(K).  Up to 100 batches of 1000 hypotheses; hypothesis h of batch b draws its 3 samples
+ * from the counter-based generator of DESIGN.md 4.9 keyed on (seed, b, h); each root of solve_quartic gives a pose whose
+ * camera Camera::from_matrix(K, R, t) is checked on the 3 samples (RANSAC_INLIERS_T * max_dimension) and scored on all
+ * linked tracks (count below RANSAC_T * max_dimension, error = the largest such error / count).  Best: higher count,
+ * then lower error; on an exact tie the lowest (hypothesis, root), and the result carried from earlier batches before
+ * any of a later batch.  Early exit after a batch with count >= 95 % of the linked tracks.  Out: out_r (3, the Camera's
+ * r), out_t (3), out_projection (12) = K [matrix_r(r) | t], *out_count, *out_error, *out_batches, out_winner (3: batch,
+ * hypothesis, root slot of the winner; -1 while the initial result is carried) - each may be NULL.
+ * progress (may be NULL): 0.02 + 0.98 * hypotheses done / 100000 after every batch.
+ * Errors: CVHIP_ERR_NO_SURFACE "Unable to find projection matrix" with fewer than 3 linked tracks or a final count not
+ * above 70 % of them (the outputs then hold the best found). */
+int cvhip_recover_pose(cvhip_device *dev, const int32_t *tracks, uint64_t n, uint32_t m, const double *points,
+                       const uint8_t *ok, const double *projections, const uint8_t *has_projection, uint32_t image_index,
+                       const double *K, uint32_t max_dimension, uint64_t seed, double *out_r, double *out_t,
+                       double *out_projection, uint32_t *out_count, double *out_error, uint32_t *out_batches,
+                       int32_t *out_winner, cvhip_progress_fn progress, void *user);
+
+/* Test hook of recover_pose's hot path: B caller-chosen sample triples (sample_idx: 3 linked-track indices each) through
+ * the same kernels.  Per sample and root slot (B x 4, the quartic's root order): out_pose 27 doubles (R 9, t 3, the
+ * Camera's r 3, projection 12; NaN where the slot has no pose), out_status 0 = no pose, 1 = rejected by the 3-sample
+ * check, 2 = scored; out_count / out_error the score (0 / NaN unless scored). */
+int cvhip_recover_pose_models(cvhip_device *dev, const int32_t *tracks, uint64_t n, uint32_t m, const double *points,
+                              const uint8_t *ok, const double *projections, const uint8_t *has_projection,
+                              uint32_t image_index, const double *K, uint32_t max_dimension, const uint32_t *sample_idx,
+                              uint32_t B, double *out_pose, int8_t *out_status, uint32_t *out_count, double *out_error);
+
 /* Row sharding (multi-GPU): restrict the SEARCH passes of this context to shard `num` of `den`
  * equal row chunks of the searched level image: rows [num*rps, min((num+1)*rps, h_level)) with
  * rps = ceil(h_level / den).  Rows outside the band keep whatever the level grid holds until
