@@ -111,6 +111,7 @@ SIGNATURES = {
                                      _vp]),
     "cvhip_recover_pose_models": (C.c_int, [_vp, _vp, C.c_uint64, _u32, _vp, _vp, _vp, _vp, _u32, _vp, _u32, _vp, _u32, _vp,
                                             _vp, _vp, _vp]),
+    "cvhip_merge_tracks": (C.c_int, [_vp, _vp, C.c_uint64, _u32, _u32, _u32, _u32, _vp, _vp, C.POINTER(C.c_uint64), _vp]),
 }
 
 

@@ -6,6 +6,7 @@
 // FIRST minimum in row-major scan order, :1362-1382) and takes that match's image-2 point; the merged points are
 // then cleared from the remaining grid - at the MATCHED point's coordinates, as the reference does (:1391-1393) -
 // and every remaining Some cell starts a new track, in scan order (:1397-1416).  Integer only: bit-exact.
+// Also PerspectiveTriangulation::merge_tracks (:1421-1540), the pass that reconstruct_dense runs after each image's pairs.
 #include "cvhip_internal.hpp"
 
 #include <algorithm>
@@ -125,6 +126,235 @@ void launch_extend_tracks_new(const uint32_t *cells, uint32_t lw, uint32_t lh, u
                            block_counts, cap, out_new_p1, out_new_p2);
 }
 
+// ---- merge_tracks (triangulation.rs:1421-1540), DESIGN.md 4.10 ---------------------------------------------------------
+// The reference's AverageTrack folds start every step from a fresh vector (:523-583), so each fold returns the points of
+// the LAST element it folded: the "average" of a cell is its highest row, the vertical window's is the last track of its
+// bottom cell (row yhi - 1), and the area track A of cell p is last[x*, yhi - 1] with x* the highest column of
+// [px - r, min(px + r, w)) that has any track in rows [py - r, yhi).  A cell is kept iff every track in it can_merge
+// (:347-368) with A, and then yields a copy of its highest row; cells in row-major order.  Integer only: bit-exact.
+// Counters (MergeCounters): tracks with a point in image i, occupied cells, cells whose A is empty, invalid point.
+struct MergeCounters {
+    uint32_t present, cells, empty_area, bad, total;
+};
+
+// the number of true `f` in a block of 256 lanes (every lane of the block calls it)
+__device__ __forceinline__ uint32_t block_count_256(bool f, uint32_t *wsum)
+{
+    const unsigned long long b = __ballot(f);
+    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = (uint32_t)__popcll(b);
+    __syncthreads();
+    return wsum[0] + wsum[1] + wsum[2] + wsum[3];
+}
+
+// one lane per track: validate the row (a point is present iff x >= 0 and y >= 0; exactly one negative coordinate, or an
+// image-i point outside w x h, is an error) and scatter row + 1 into its image-i cell; the highest row wins (0 = empty).
+// present_part[block] = the block's tracks with a point in image i (summed by merge_tracks_sum_kernel: a counter shared
+// by every wave would serialise the kernel on one address)
+__global__ __launch_bounds__(256) void merge_tracks_scatter_kernel(const int2 *__restrict__ tracks, unsigned long long n, uint32_t m,
+                                                                   uint32_t image_index, uint32_t w, uint32_t h,
+                                                                   uint32_t *__restrict__ last, uint32_t *__restrict__ present_part,
+                                                                   MergeCounters *__restrict__ cnt)
+{
+    const unsigned long long t = (unsigned long long)blockIdx.x * 256 + threadIdx.x;
+    bool present = false;
+    if (t < n) {
+        const int2 *row = tracks + t * m;
+        bool bad = false;
+        for (uint32_t j = 0; j < m; j++) {
+            const int2 p = row[j];
+            bad |= (p.x < 0) != (p.y < 0);
+        }
+        const int2 p = row[image_index];
+        if (p.x >= 0 && p.y >= 0) {
+            if ((uint32_t)p.x < w && (uint32_t)p.y < h) {
+                atomicMax(&last[(size_t)p.y * w + p.x], (uint32_t)t + 1u);
+                present = true;
+            } else {
+                bad = true;
+            }
+        }
+        if (bad) atomicOr(&cnt->bad, 1u);
+    }
+    __shared__ uint32_t wsum[4];
+    const uint32_t c = block_count_256(present, wsum);
+    if (threadIdx.x == 0) present_part[blockIdx.x] = c;
+}
+
+// column occupancy: occ[y, x] = 1 iff a cell of column x in rows [max(y - r, 0), min(y + r, h)) holds a track.  One lane
+// per (column, chunk of MERGE_ROWS rows): neighbouring lanes read neighbouring cells, and the window slides down the chunk
+constexpr uint32_t MERGE_ROWS = 64;
+__global__ __launch_bounds__(256) void merge_tracks_column_kernel(const uint32_t *__restrict__ last, uint32_t w, uint32_t h,
+                                                                  uint32_t r, uint8_t *__restrict__ occ)
+{
+    const size_t g = (size_t)blockIdx.x * 256 + threadIdx.x;
+    const uint32_t chunks = (h + MERGE_ROWS - 1) / MERGE_ROWS;
+    if (g >= (size_t)w * chunks) return;
+    const uint32_t x = (uint32_t)(g % w), y0 = (uint32_t)(g / w) * MERGE_ROWS, y1 = min(y0 + MERGE_ROWS, h);
+    uint32_t count = 0;
+    for (uint32_t y = y0 > r ? y0 - r : 0u, hi = min(y0 + r, h); y < hi; y++) count += last[(size_t)y * w + x] != 0;
+    for (uint32_t y = y0; y < y1; y++) {
+        occ[(size_t)y * w + x] = count != 0;
+        if (y + r < h) count += last[(size_t)(y + r) * w + x] != 0;
+        if (y >= r) count -= last[(size_t)(y - r) * w + x] != 0;
+    }
+}
+
+// one lane per cell: area[c] = A (row + 1 of the area track, 0 = empty) and keep[c] = occupied; per block the occupied
+// cells and those whose A is empty
+__global__ __launch_bounds__(256) void merge_tracks_area_kernel(const uint32_t *__restrict__ last, const uint8_t *__restrict__ occ,
+                                                                uint32_t w, uint32_t h, uint32_t r, uint32_t *__restrict__ area,
+                                                                uint8_t *__restrict__ keep, uint32_t *__restrict__ cells_part,
+                                                                uint32_t *__restrict__ empty_part)
+{
+    const size_t c = (size_t)blockIdx.x * 256 + threadIdx.x;
+    bool occupied = false, empty = false;
+    if (c < (size_t)w * h) {
+        occupied = last[c] != 0;
+        keep[c] = occupied;
+        if (occupied) {
+            const uint32_t px = (uint32_t)(c % w), py = (uint32_t)(c / w);
+            const uint32_t xlo = px > r ? px - r : 0u, xhi = min(px + r, w), yhi = min(py + r, h);
+            const uint8_t *orow = occ + (size_t)py * w;
+            uint32_t xs = xhi - 1;
+            while (xs > xlo && !orow[xs]) xs--; // column px itself qualifies (r >= 2), so the walk ends by px
+            const uint32_t a = last[(size_t)(yhi - 1) * w + xs];
+            area[c] = a;
+            empty = a == 0;
+        }
+    }
+    __shared__ uint32_t wsum[8];
+    const uint32_t nc = block_count_256(occupied, wsum);
+    const uint32_t ne = block_count_256(empty, wsum + 4);
+    if (threadIdx.x == 0) {
+        cells_part[blockIdx.x] = nc;
+        empty_part[blockIdx.x] = ne;
+    }
+}
+
+// one block: the per-block counts of the scatter and area kernels into MergeCounters, in a fixed order
+__global__ __launch_bounds__(1024) void merge_tracks_sum_kernel(const uint32_t *__restrict__ present_part, uint32_t tblocks,
+                                                                const uint32_t *__restrict__ cells_part,
+                                                                const uint32_t *__restrict__ empty_part, uint32_t cblocks,
+                                                                MergeCounters *__restrict__ cnt)
+{
+    uint32_t v[3] = {0, 0, 0};
+    for (uint32_t i = threadIdx.x; i < tblocks; i += 1024) v[0] += present_part[i];
+    for (uint32_t i = threadIdx.x; i < cblocks; i += 1024) {
+        v[1] += cells_part[i];
+        v[2] += empty_part[i];
+    }
+    __shared__ uint32_t part[3][16];
+    for (int k = 0; k < 3; k++) {
+        for (int s = 32; s > 0; s >>= 1) v[k] += __shfl_down(v[k], s, 64);
+        if ((threadIdx.x & 63) == 0) part[k][threadIdx.x >> 6] = v[k];
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint32_t sum[3] = {0, 0, 0};
+        for (int k = 0; k < 3; k++)
+            for (int wv = 0; wv < 16; wv++) sum[k] += part[k][wv];
+        cnt->present = sum[0];
+        cnt->cells = sum[1];
+        cnt->empty_area = sum[2];
+    }
+}
+
+// one lane per track with a point in image i: can_merge with its cell's area track over the m images, or keep[c] = 0
+__global__ __launch_bounds__(256) void merge_tracks_check_kernel(const int2 *__restrict__ tracks, unsigned long long n, uint32_t m,
+                                                                 uint32_t image_index, uint32_t w, uint32_t h,
+                                                                 unsigned long long max_distance_sqr,
+                                                                 const uint32_t *__restrict__ area, uint8_t *__restrict__ keep)
+{
+    const unsigned long long t = (unsigned long long)blockIdx.x * 256 + threadIdx.x;
+    if (t >= n) return;
+    const int2 *row = tracks + t * m;
+    const int2 p = row[image_index];
+    if (p.x < 0 || p.y < 0 || (uint32_t)p.x >= w || (uint32_t)p.y >= h) return;
+    const size_t c = (size_t)p.y * w + p.x;
+    const uint32_t a = area[c];
+    if (!a) return; // an empty area track has no point in any image: can_merge holds
+    const int2 *arow = tracks + (unsigned long long)(a - 1) * m;
+    for (uint32_t j = 0; j < m; j++) {
+        const int2 p1 = row[j], p2 = arow[j];
+        if (p1.x < 0 || p1.y < 0 || p2.x < 0 || p2.y < 0) continue;
+        const unsigned long long dx = (unsigned long long)(p1.x > p2.x ? p1.x - p2.x : p2.x - p1.x);
+        const unsigned long long dy = (unsigned long long)(p1.y > p2.y ? p1.y - p2.y : p2.y - p1.y);
+        if (dx * dx + dy * dy > max_distance_sqr) {
+            keep[c] = 0;
+            return;
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void merge_tracks_count_kernel(const uint8_t *__restrict__ keep, size_t cells,
+                                                                 uint32_t *__restrict__ block_counts)
+{
+    const size_t c = (size_t)blockIdx.x * 256 + threadIdx.x;
+    const bool f = c < cells && keep[c];
+    __shared__ uint32_t wsum[4];
+    const unsigned long long b = __ballot(f);
+    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = (uint32_t)__popcll(b);
+    __syncthreads();
+    if (threadIdx.x == 0) block_counts[blockIdx.x] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+}
+
+// kept cells in row-major order: out_rows[k] = the cell's highest row, out_tracks[k] = that row (either may be null).
+// Nothing is written when the scatter found an invalid point.
+__global__ __launch_bounds__(256) void merge_tracks_write_kernel(const int2 *__restrict__ tracks, uint32_t m,
+                                                                 const uint32_t *__restrict__ last,
+                                                                 const uint8_t *__restrict__ keep, size_t cells,
+                                                                 const uint32_t *__restrict__ block_offsets,
+                                                                 const MergeCounters *__restrict__ cnt,
+                                                                 unsigned long long *__restrict__ out_rows,
+                                                                 int2 *__restrict__ out_tracks)
+{
+    const size_t c = (size_t)blockIdx.x * 256 + threadIdx.x;
+    const bool f = c < cells && keep[c];
+    __shared__ uint32_t wsum[4];
+    const unsigned long long b = __ballot(f);
+    const uint32_t lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    if (lane == 0) wsum[wv] = (uint32_t)__popcll(b);
+    __syncthreads();
+    if (!f || cnt->bad) return;
+    unsigned long long off = block_offsets[blockIdx.x];
+    for (uint32_t v = 0; v < wv; v++) off += wsum[v];
+    off += (unsigned long long)__popcll(b & ((1ull << lane) - 1ull));
+    const unsigned long long src = last[c] - 1u;
+    if (out_rows) out_rows[off] = src;
+    if (out_tracks)
+        for (uint32_t j = 0; j < m; j++) out_tracks[off * m + j] = tracks[src * m + j];
+}
+
+void launch_merge_tracks(const int2 *tracks, unsigned long long n, uint32_t m, uint32_t image_index, uint32_t w, uint32_t h,
+                         uint32_t r, unsigned long long max_distance_sqr, uint32_t *last, uint8_t *occ, uint32_t *area,
+                         uint8_t *keep, uint32_t *block_counts, uint32_t *present_part, uint32_t *cells_part,
+                         uint32_t *empty_part, MergeCounters *cnt, unsigned long long *out_rows, int2 *out_tracks,
+                         hipStream_t s)
+{
+    const size_t cells = (size_t)w * h;
+    const uint32_t cblocks = (uint32_t)((cells + 255) / 256);
+    const unsigned tblocks = (unsigned)((n + 255) / 256);
+    const size_t col_lanes = (size_t)w * ((h + MERGE_ROWS - 1) / MERGE_ROWS);
+    if (n) {
+        hipLaunchKernelGGL(merge_tracks_scatter_kernel, dim3(tblocks), dim3(256), 0, s, tracks, n, m, image_index, w, h, last,
+                           present_part, cnt);
+    }
+    hipLaunchKernelGGL(merge_tracks_column_kernel, dim3((unsigned)((col_lanes + 255) / 256)), dim3(256), 0, s, last, w, h, r, occ);
+    hipLaunchKernelGGL(merge_tracks_area_kernel, dim3(cblocks), dim3(256), 0, s, last, occ, w, h, r, area, keep, cells_part,
+                       empty_part);
+    hipLaunchKernelGGL(merge_tracks_sum_kernel, dim3(1), dim3(1024), 0, s, present_part, (uint32_t)tblocks, cells_part, empty_part,
+                       cblocks, cnt);
+    if (n) {
+        hipLaunchKernelGGL(merge_tracks_check_kernel, dim3(tblocks), dim3(256), 0, s, tracks, n, m, image_index, w, h,
+                           max_distance_sqr, area, keep);
+    }
+    hipLaunchKernelGGL(merge_tracks_count_kernel, dim3(cblocks), dim3(256), 0, s, keep, cells, block_counts);
+    launch_scan_u32(block_counts, cblocks, &cnt->total, s);
+    if (out_rows || out_tracks)
+        hipLaunchKernelGGL(merge_tracks_write_kernel, dim3(cblocks), dim3(256), 0, s, tracks, m, last, keep, cells, block_counts,
+                           cnt, out_rows, out_tracks);
+}
+
 } // namespace cvhip
 
 using namespace cvhip;
@@ -172,19 +402,23 @@ extern "C" int cvhip_extend_tracks(cvhip_ctx *ctx, const int32_t *track_p1, uint
     const uint32_t radius = max_dimension2 > 1000 ? (uint32_t)((uint64_t)3 * max_dimension2 / 1000) : 3u;
     const bool tp1_dev = n_tracks ? on_device(track_p1) : true, tp2_dev = n_tracks ? on_device(out_track_p2) : true;
     const bool n1_dev = cap ? on_device(out_new_p1) : true, n2_dev = cap ? on_device(out_new_p2) : true;
-    int2 *d_tp1 = reinterpret_cast<int2 *>(const_cast<int32_t *>(track_p1)), *d_tp2 = reinterpret_cast<int2 *>(out_track_p2);
-    uint32_t *d_n1 = out_new_p1, *d_n2 = out_new_p2;
+    // scratch copies of host arrays (only these are freed; the caller's pointers are chosen at launch)
+    int2 *s_tp1 = nullptr, *s_tp2 = nullptr;
+    uint32_t *s_n1 = nullptr, *s_n2 = nullptr;
     hipError_t e = hipMemsetAsync(removed, 0, n, s);
     if (e == hipSuccess) e = hipMemsetAsync(oob, 0, sizeof(uint32_t), s);
     if (e == hipSuccess && !tp1_dev) {
-        e = hipMalloc(&d_tp1, n_tracks * sizeof(int2));
-        if (e == hipSuccess) e = hipMemcpyAsync(d_tp1, track_p1, n_tracks * sizeof(int2), hipMemcpyHostToDevice, s);
+        e = hipMalloc(&s_tp1, n_tracks * sizeof(int2));
+        if (e == hipSuccess) e = hipMemcpyAsync(s_tp1, track_p1, n_tracks * sizeof(int2), hipMemcpyHostToDevice, s);
     }
-    if (e == hipSuccess && !tp2_dev) e = hipMalloc(&d_tp2, n_tracks * sizeof(int2));
-    if (e == hipSuccess && cap && !n1_dev) e = hipMalloc(&d_n1, (size_t)cap * 2 * sizeof(uint32_t));
-    if (e == hipSuccess && cap && !n2_dev) e = hipMalloc(&d_n2, (size_t)cap * 2 * sizeof(uint32_t));
+    if (e == hipSuccess && !tp2_dev) e = hipMalloc(&s_tp2, n_tracks * sizeof(int2));
+    if (e == hipSuccess && cap && !n1_dev) e = hipMalloc(&s_n1, (size_t)cap * 2 * sizeof(uint32_t));
+    if (e == hipSuccess && cap && !n2_dev) e = hipMalloc(&s_n2, (size_t)cap * 2 * sizeof(uint32_t));
     uint32_t h_total = 0, h_oob = 0;
     if (e == hipSuccess) {
+        const int2 *d_tp1 = tp1_dev ? reinterpret_cast<const int2 *>(track_p1) : s_tp1;
+        int2 *d_tp2 = tp2_dev ? reinterpret_cast<int2 *>(out_track_p2) : s_tp2;
+        uint32_t *d_n1 = n1_dev ? out_new_p1 : s_n1, *d_n2 = n2_dev ? out_new_p2 : s_n2;
         launch_extend_tracks_match(ds.cells[ds.cur], ds.lw, ds.lh, ds.k, ds.gw, ds.gh, d_tp1, n_tracks, radius, d_tp2, removed,
                                    oob, s);
         launch_extend_tracks_new(ds.cells[ds.cur], ds.lw, ds.lh, ds.k, ds.gw, ds.gh, removed, counts, total, d_n1, d_n2, cap, s);
@@ -192,18 +426,16 @@ extern "C" int cvhip_extend_tracks(cvhip_ctx *ctx, const int32_t *track_p1, uint
     }
     if (e == hipSuccess) e = hipMemcpyAsync(&h_total, total, sizeof(uint32_t), hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipMemcpyAsync(&h_oob, oob, sizeof(uint32_t), hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess && n_tracks && !tp2_dev)
-        e = hipMemcpyAsync(out_track_p2, d_tp2, n_tracks * sizeof(int2), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess && n_tracks && s_tp2)
+        e = hipMemcpyAsync(out_track_p2, s_tp2, n_tracks * sizeof(int2), hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     const uint64_t written = h_total < cap ? h_total : cap;
-    if (e == hipSuccess && written && !n1_dev)
-        e = hipMemcpy(out_new_p1, d_n1, (size_t)written * 2 * sizeof(uint32_t), hipMemcpyDeviceToHost);
-    if (e == hipSuccess && written && !n2_dev)
-        e = hipMemcpy(out_new_p2, d_n2, (size_t)written * 2 * sizeof(uint32_t), hipMemcpyDeviceToHost);
-    if (!tp1_dev && d_tp1) (void)hipFree(d_tp1);
-    if (!tp2_dev && d_tp2) (void)hipFree(d_tp2);
-    if (cap && !n1_dev && d_n1) (void)hipFree(d_n1);
-    if (cap && !n2_dev && d_n2) (void)hipFree(d_n2);
+    if (e == hipSuccess && written && s_n1)
+        e = hipMemcpy(out_new_p1, s_n1, (size_t)written * 2 * sizeof(uint32_t), hipMemcpyDeviceToHost);
+    if (e == hipSuccess && written && s_n2)
+        e = hipMemcpy(out_new_p2, s_n2, (size_t)written * 2 * sizeof(uint32_t), hipMemcpyDeviceToHost);
+    for (void *p : {(void *)s_tp1, (void *)s_tp2, (void *)s_n1, (void *)s_n2})
+        if (p) (void)hipFree(p);
     if (e != hipSuccess) return fail(CVHIP_ERR_DEVICE, std::string("extend_tracks: ") + hipGetErrorString(e));
     if (h_oob) return fail(CVHIP_ERR_INVALID, "Index out of bounds (a merged match lies outside the image-1 grid; the reference panics here, data.rs:61-64)");
     *out_n_new = h_total;
@@ -270,5 +502,81 @@ extern "C" int cvhip_extend_tracks_matches(cvhip_device *dev, const uint32_t *in
     if (e != hipSuccess) return fail(CVHIP_ERR_DEVICE, std::string("extend_tracks_matches: ") + hipGetErrorString(e));
     if (h_oob) return fail(CVHIP_ERR_INVALID, "Index out of bounds (a merged match lies outside the image-1 grid; the reference panics here, data.rs:61-64)");
     *out_n_new = h_total;
+    return CVHIP_OK;
+}
+
+// merge_tracks (triangulation.rs:1421-1540) for image `image_index` of shape width x height over the n x m x 2 table;
+// kernels above.  Scratch is taken per call, as cvhip_extend_tracks_matches does.
+extern "C" int cvhip_merge_tracks(cvhip_device *dev, const int32_t *tracks, uint64_t n, uint32_t m, uint32_t image_index,
+                                  uint32_t width, uint32_t height, uint64_t *out_rows, int32_t *out_tracks, uint64_t *out_n,
+                                  uint64_t *out_stats)
+{
+    if (!dev || !out_n || (n && !tracks)) return fail(CVHIP_ERR_INVALID, "null argument");
+    if (image_index >= m) return fail(CVHIP_ERR_INVALID, "merge_tracks: image_index >= m");
+    if (m > CVHIP_TRIANGULATE_MAX_CAMERAS) return fail(CVHIP_ERR_UNSUPPORTED, "merge_tracks: more than CVHIP_TRIANGULATE_MAX_CAMERAS images");
+    if (width == 0 || height == 0) return fail(CVHIP_ERR_INVALID, "merge_tracks: image size");
+    // row + 1 and the cell offsets are 32-bit
+    if (n >= 0xFFFFFFFFull || (uint64_t)width * height >= 0xFFFFFFFFull)
+        return fail(CVHIP_ERR_UNSUPPORTED, "merge_tracks: more than 2^32 - 2 tracks or cells");
+    CVHIP_TRY_HIP(hipSetDevice(dev->d.ordinal));
+    hipStream_t s = dev->d.stream;
+    // MERGE_TRACKS_SEARCH_RADIUS = 2, MERGE_TRACKS_MAX_DISTANCE = 10, TRACKS_RADIUS_DENOMINATOR = 1000 (:17-19, 1431-1443)
+    const uint64_t md = std::max(width, height);
+    const uint32_t r = md > 1000 ? (uint32_t)(2 * md / 1000) : 2u;
+    const unsigned long long d2 = md > 1000 ? 10ull * 10ull * md / 1000 : 100ull;
+    const size_t cells = (size_t)width * height, row_bytes = (size_t)m * 2 * sizeof(int32_t);
+    const uint32_t cblocks = (uint32_t)((cells + 255) / 256);
+    const bool tr_dev = n ? on_device(tracks) : true;
+    const bool rows_dev = out_rows ? on_device(out_rows) : true, otr_dev = out_tracks ? on_device(out_tracks) : true;
+    uint32_t *d_last = nullptr, *d_area = nullptr, *d_counts = nullptr, *d_parts = nullptr;
+    uint8_t *d_occ = nullptr, *d_keep = nullptr;
+    MergeCounters *d_cnt = nullptr;
+    // scratch copies of host tables and outputs (only these are freed; the caller's pointers are chosen at launch)
+    int2 *s_tr = nullptr, *s_otr = nullptr;
+    unsigned long long *s_rows = nullptr;
+    const size_t nw = (size_t)std::max<uint64_t>(n, 1);
+    hipError_t e = hipMalloc(&d_last, cells * 4);
+    if (e == hipSuccess) e = hipMalloc(&d_area, cells * 4);
+    if (e == hipSuccess) e = hipMalloc(&d_occ, cells);
+    if (e == hipSuccess) e = hipMalloc(&d_keep, cells);
+    const size_t tblocks = (size_t)((n + 255) / 256);
+    if (e == hipSuccess) e = hipMalloc(&d_counts, (size_t)cblocks * 4);
+    if (e == hipSuccess) e = hipMalloc(&d_parts, (tblocks + 2 * (size_t)cblocks) * 4);
+    if (e == hipSuccess) e = hipMalloc(&d_cnt, sizeof(MergeCounters));
+    if (e == hipSuccess && !tr_dev) e = hipMalloc(&s_tr, nw * row_bytes);
+    if (e == hipSuccess && out_rows && !rows_dev) e = hipMalloc(&s_rows, nw * sizeof(unsigned long long));
+    if (e == hipSuccess && out_tracks && !otr_dev) e = hipMalloc(&s_otr, nw * row_bytes);
+    if (e == hipSuccess) e = hipMemsetAsync(d_last, 0, cells * 4, s);
+    if (e == hipSuccess) e = hipMemsetAsync(d_cnt, 0, sizeof(MergeCounters), s);
+    if (e == hipSuccess && n && !tr_dev) e = hipMemcpyAsync(s_tr, tracks, (size_t)n * row_bytes, hipMemcpyHostToDevice, s);
+    MergeCounters h_cnt{};
+    if (e == hipSuccess) {
+        const int2 *d_tr = tr_dev ? reinterpret_cast<const int2 *>(tracks) : s_tr;
+        unsigned long long *d_rows = !out_rows ? nullptr : rows_dev ? reinterpret_cast<unsigned long long *>(out_rows) : s_rows;
+        int2 *d_otr = !out_tracks ? nullptr : otr_dev ? reinterpret_cast<int2 *>(out_tracks) : s_otr;
+        launch_merge_tracks(d_tr, n, m, image_index, width, height, r, d2, d_last, d_occ, d_area, d_keep, d_counts, d_parts + 2 * cblocks,
+                            d_parts, d_parts + cblocks, d_cnt, d_rows, d_otr, s);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(&h_cnt, d_cnt, sizeof(MergeCounters), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    const uint64_t k = h_cnt.total;
+    if (e == hipSuccess && !h_cnt.bad && k && s_rows)
+        e = hipMemcpy(out_rows, s_rows, (size_t)k * sizeof(unsigned long long), hipMemcpyDeviceToHost);
+    if (e == hipSuccess && !h_cnt.bad && k && s_otr) e = hipMemcpy(out_tracks, s_otr, (size_t)k * row_bytes, hipMemcpyDeviceToHost);
+    for (void *p : {(void *)d_last, (void *)d_area, (void *)d_occ, (void *)d_keep, (void *)d_counts, (void *)d_parts, (void *)d_cnt,
+                    (void *)s_tr, (void *)s_rows, (void *)s_otr})
+        if (p) (void)hipFree(p);
+    if (e != hipSuccess) return fail(CVHIP_ERR_DEVICE, std::string("merge_tracks: ") + hipGetErrorString(e));
+    if (h_cnt.bad)
+        return fail(CVHIP_ERR_INVALID, "merge_tracks: a point has exactly one negative coordinate, or an image-i point lies "
+                                       "outside the image (the reference panics here, data.rs:61-64)");
+    *out_n = k;
+    if (out_stats) {
+        out_stats[0] = h_cnt.present;
+        out_stats[1] = h_cnt.cells;
+        out_stats[2] = (uint64_t)h_cnt.cells - k;
+        out_stats[3] = h_cnt.empty_area;
+    }
     return CVHIP_OK;
 }

@@ -236,16 +236,17 @@ def match_count(xy) -> int:
 
 
 def reconstruct_perspective_surface(device, pyramids, pairs_result, cameras, bundle_adjustment: bool = True,
-                                    progress=None):
+                                    progress=None, merge_tracks: bool = False):
     """The perspective tail of `reconstruct` for n views: reconstruct_dense's pair loop (reconstruction.rs:668-730) -
     for img1 in order, for every later img2 whose pair has an F in `pairs_result` (reconstruct_pairs' output; its
     dense grids are not needed, dense=False is enough), the dense correlation and extend_tracks into one track table
     (triangulation.rs:1330-1419) - then triangulate_all (:817-865) with the given cameras [(K, R, t)] per image: DLT
     points, filter_outliers and, unless bundle_adjustment is False (--no-bundle-adjustment), the bundle adjustment.
-    Departures, as stated in DESIGN.md: the cameras come from the caller (no P3P / recover_pose), merge_tracks
-    (:1421-1540, run after every img1 at :728) is skipped, and max_points (a random subset) stays with the caller.
-    -> dict: surface (triangulation.Surface), tracks (the whole table), timings_ms per stage (dense, tracks,
-    triangulate)."""
+    merge_tracks=True is the reference's flow: merge_tracks (:1421-1540, run after every img1 at reconstruction.rs:726) after each
+    image's pairs, every view counting as linked; False (the default) skips it.  Departures, as stated
+    in DESIGN.md: the cameras come from the caller (no P3P / recover_pose), and max_points (a random subset) stays with
+    the caller.  -> dict: surface (triangulation.Surface), tracks (the whole table), timings_ms per stage (dense,
+    tracks, merge, triangulate); with merge_tracks, merges (per image: PerspectiveTriangulation.merge_tracks' counts)."""
     from . import triangulation
 
     rec = ImageReconstruction(device, ProjectionMode.Perspective)
@@ -253,6 +254,7 @@ def reconstruct_perspective_surface(device, pyramids, pairs_result, cameras, bun
     shapes = [(int(p[0].shape[1]), int(p[0].shape[0])) for p in pyramids]
     tri = triangulation.PerspectiveTriangulation(n, shapes, bundle_adjustment=bundle_adjustment)
     mode = correlation.ProjectionMode(int(ProjectionMode.Perspective))
+    merges = []
     for i in range(n):
         for j in range(i + 1, n):
             entry = pairs_result["pairs"].get((i, j))
@@ -271,8 +273,13 @@ def reconstruct_perspective_surface(device, pyramids, pairs_result, cameras, bun
                 rec._timed("tracks", lambda pc=pc, i=i, j=j: tri.add_image_pair_dense(i, j, pc))
             finally:
                 pc.close()
+        if merge_tracks:
+            merges.append(rec._timed("merge", lambda i=i: tri.merge_tracks(device, i)))
     surface = rec._timed("triangulate", lambda: tri.triangulate_all(device, cameras, progress=progress))
-    return {"surface": surface, "tracks": tri.tracks, "timings_ms": dict(rec.timings_ms)}
+    out = {"surface": surface, "tracks": tri.tracks, "timings_ms": dict(rec.timings_ms)}
+    if merge_tracks:
+        out["merges"] = merges
+    return out
 
 
 def recover_camera_poses(device, tri, seed: int = 0, log=None):
@@ -299,14 +306,17 @@ def recover_camera_poses(device, tri, seed: int = 0, log=None):
 
 
 def reconstruct_perspective(device, pyramids, K, bundle_adjustment: bool = True, seed: int = 0, pairs_result=None,
-                            progress=None):
+                            progress=None, merge_tracks: bool = False):
     """The perspective `reconstruct` in the reference's order for n views (reconstruction.rs:261-277, 380-395, 627-752):
     the sparse stage per pair (ORB, matcher, RANSAC - reconstruct_pairs with dense=False, or the caller's `pairs_result`),
     add_image_pair_sparse for every pair with an F (a pair that fails is skipped), recover_camera_poses, the dense
     correlation and extend_tracks of the pairs of linked images only, and triangulate_all with the recovered cameras.
-    K: one 3 x 3 matrix for every view, or one per view.  merge_tracks and max_points stay out.
+    merge_tracks=True is the reference's flow: merge_tracks (triangulation.rs:1421-1540) after every linked image's
+    pairs, the last linked image included (reconstruction.rs:726); False (the default) skips it.
+    K: one 3 x 3 matrix for every view, or one per view.  max_points stays out.
     -> dict: surface, camera_order, poses (per recover call), initial_pair, sparse ({pair: (p2, score, the short tracks scored)}), sparse_tracks (the
-    table before complete_sparse_triangulation), tracks, cameras, projections, pairs, timings_ms."""
+    table before complete_sparse_triangulation), tracks, cameras, projections, pairs, timings_ms; with merge_tracks, merges
+    (per linked image: PerspectiveTriangulation.merge_tracks' counts)."""
     from . import triangulation
 
     n = len(pyramids)
@@ -333,6 +343,7 @@ def reconstruct_perspective(device, pyramids, K, bundle_adjustment: bool = True,
     order, poses = rec._timed("poses", lambda: recover_camera_poses(device, tri, seed=seed))
     linked = set(order)
     mode = correlation.ProjectionMode(int(ProjectionMode.Perspective))
+    merges = []
     for i in range(n):
         if i not in linked:
             continue
@@ -353,8 +364,13 @@ def reconstruct_perspective(device, pyramids, K, bundle_adjustment: bool = True,
                 rec._timed("tracks", lambda pc=pc, i=i, j=j: tri.add_image_pair_dense(i, j, pc))
             finally:
                 pc.close()
+        if merge_tracks:
+            merges.append(rec._timed("merge", lambda i=i: tri.merge_tracks(device, i)))
     surface = rec._timed("triangulate", lambda: tri.triangulate_all_recovered(device, progress=progress))
-    return {"surface": surface, "camera_order": order, "poses": poses, "initial_pair": initial, "sparse": sparse,
-            "sparse_tracks": sparse_tracks, "tracks": tri.tracks,
-            "cameras": list(tri.cameras), "projections": list(tri.projections), "pairs": pairs_result,
-            "timings_ms": dict(rec.timings_ms)}
+    out = {"surface": surface, "camera_order": order, "poses": poses, "initial_pair": initial, "sparse": sparse,
+           "sparse_tracks": sparse_tracks, "tracks": tri.tracks,
+           "cameras": list(tri.cameras), "projections": list(tri.projections), "pairs": pairs_result,
+           "timings_ms": dict(rec.timings_ms)}
+    if merge_tracks:
+        out["merges"] = merges
+    return out

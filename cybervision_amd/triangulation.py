@@ -2,7 +2,8 @@
 extend_tracks builds pair by pair, and triangulate_all (:817-865) - DLT points, filter_outliers and the bundle
 adjustment - in one call of cvhip_triangulate_perspective - and the sparse half that recovers the cameras
 (add_image_pair_sparse, recover_next_cameras, :620-811): find_projection_matrix, triangulate_tracks and the P3P RANSAC of
-recover_pose run on the device.  merge_tracks (:1421-1540) is not part of this module.
+recover_pose run on the device - and merge_tracks (:1421-1540, cvhip_merge_tracks), which reconstruct_dense runs after
+each linked image's pairs.
 No compute in Python - the track table's bookkeeping and the calls only.
 """
 from __future__ import annotations
@@ -235,6 +236,26 @@ class PerspectiveTriangulation:
         new[:, image1_index] = new_p1.astype(np.int32)
         new[:, image2_index] = new_p2.astype(np.int32)
         self.tracks = np.concatenate([self.tracks, new])
+
+    def merge_tracks(self, device, image_index: int) -> dict:
+        """merge_tracks (:1421-1540) for image `image_index` on the device (cvhip_merge_tracks): the table
+        becomes one copy of the highest row of every kept cell of that image, in row-major order of the cells; tracks
+        without a point in the image are dropped.  The trailing triangulate_tracks (:1538) is not run: triangulate_all
+        re-triangulates every track first (:822), and the dense stage keeps no points (`self.points` stays as it is).
+        -> {image, rows_in, rows_out, present, cells, rejected, empty_area}."""
+        n, m = len(self.tracks), self.images_count
+        w, h = self.image_shapes[image_index]
+        tr = np.ascontiguousarray(self.tracks)
+        out = np.empty((max(n, 1), m, 2), dtype=np.int32)
+        out_n = C.c_uint64(0)
+        stats = np.zeros(4, dtype=np.uint64)
+        p = lambda a: C.c_void_p(a.ctypes.data)  # noqa: E731
+        _lib.check(_lib.lib().cvhip_merge_tracks(device.handle, p(tr) if n else None, n, m, int(image_index), w, h, None,
+                                                 p(out), C.byref(out_n), p(stats)), "cvhip_merge_tracks")
+        k = out_n.value
+        self.tracks = out[:k]
+        return {"image": int(image_index), "rows_in": n, "rows_out": k, "present": int(stats[0]), "cells": int(stats[1]),
+                "rejected": int(stats[2]), "empty_area": int(stats[3])}
 
     def prune_projections(self, cameras):
         """prune_projections (:913-938): images without a camera are dropped and the track columns remapped (kept in

@@ -184,7 +184,7 @@ int cvhip_extend_tracks(cvhip_ctx *ctx, const int32_t *track_p1, uint64_t n_trac
 
 /* Dense consumer, perspective pipeline, last step - replaces PerspectiveTriangulation::triangulate_all (triangulation.rs:817-865)
  * with the cameras given by the caller (pose recovery, recover_pose / find_projection_matrix :1033-1278, and merge_tracks
- * :1421-1540 are not part of it):
+ * :1421-1540 - cvhip_merge_tracks below - are not part of it):
  *  - triangulate_track (:867-911) for every track: the 2k x 4 DLT system of its k seen views in camera order, the right
  *    singular vector of the smallest singular value (nalgebra's `svd` sorts them in decreasing order, so the reference's
  *    `v_t.row(nrows - 1)`); rejected if k < 2 or |w| < 1e-4; the point is xyz / w.
@@ -224,6 +224,25 @@ int cvhip_triangulate_perspective_cameras(cvhip_device *dev, const int32_t *trac
                                           double *out_t, double *out_projection, uint64_t *out_n,
                                           uint32_t *out_iterations, uint8_t *out_history, double *out_residual_norms,
                                           cvhip_progress_fn progress, void *user);
+
+/* merge_tracks (triangulation.rs:1421-1540; reconstruct_dense runs it after each linked image's pairs, reconstruction.rs:726)
+ * for image `image_index` of shape width x height, as the reference computes it: its AverageTrack folds
+ * return the LAST element folded, so with r = 2 * md / 1000 and d^2 = 100 * md / 1000 (md = max(width, height) > 1000;
+ * else 2 and 100), for every cell p of image i that holds tracks: A = the highest row in cell (x*, yhi - 1), yhi =
+ * min(py + r, height), x* = the highest column of [px - r, min(px + r, width)) with a track in rows [py - r, yhi) (lower
+ * bounds saturate at 0); the cell is kept iff every track in it can_merge with A (in every image where both have a point,
+ * dx^2 + dy^2 <= d^2), and yields a copy of its highest row.  Tracks without a point in image i are dropped.
+ * tracks: n x m x 2 int32, a point present iff x >= 0 and y >= 0.  Out (each with room for n, each may be NULL): out_rows
+ * = the source row of each merged track, out_tracks = those rows (n_out x m x 2), in row-major order of their cells;
+ * *out_n = n_out.  out_stats[4] (may be NULL): tracks with a point in image i, occupied cells, cells rejected by can_merge,
+ * cells whose A has no point.  The trailing triangulate_tracks (:1538) is not part of it.  Integer only, bit-exact.
+ * Errors (nothing written): CVHIP_ERR_INVALID for image_index >= m, a point with exactly one negative coordinate or an
+ * image-i point outside width x height (the reference panics there, data.rs:61-64); CVHIP_ERR_UNSUPPORTED above
+ * CVHIP_TRIANGULATE_MAX_CAMERAS images or with 2^32 - 1 or more tracks or cells.  tracks, out_rows, out_tracks: host or
+ * device pointers; out_n and out_stats: host memory. */
+int cvhip_merge_tracks(cvhip_device *dev, const int32_t *tracks, uint64_t n, uint32_t m, uint32_t image_index,
+                       uint32_t width, uint32_t height, uint64_t *out_rows, int32_t *out_tracks, uint64_t *out_n,
+                       uint64_t *out_stats);
 
 /* ------------------------------------------------------------------------------------------
  * Pose recovery, perspective pipeline (sparse stage).  All f64 on the device (csrc/pose_kernels.hip).
