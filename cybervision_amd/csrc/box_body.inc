@@ -90,6 +90,13 @@
         const double cmn = major_x ? e.cy : e.cx, amn = major_x ? e.ay : e.ax;
         const int omn = major_x ? e.oy : e.ox;
         const double vf = cmn * (double)r0 + amn, vl = STEP ? cmn * (double)(r1 - 1) + amn : vf;
+        // Lean plan: where v - cs and v + cs share a binade (8 < v - cs, v + cs < 1e9) every v + off is exact (an integer
+        // added inside one binade), so with stripes that advance by +1 the loop below would find them consecutive from
+        // floor(v - cs), which it computes first.  All lines but those within cs rows of 16, 32, ... 2^k skip it.
+        const double vlo0 = vf - (double)cs, vhi0 = vf + (double)cs;
+        const bool closed = !STEP && omn == 1 && vlo0 > 8.0 && vhi0 < 1.0e9 && (__double2hiint(vlo0) ^ __double2hiint(vhi0)) < (1 << 20);
+        if (closed) m0 = m0l = (uint32_t)floor(vlo0);
+        else
         for (int off = -cs; off <= cs; off++) {
             // The lean instantiation is only launched for exactly axis-parallel lines (minor coefficient +-0): the
             // minor coordinate (+-0 * i + add) + off then does not depend on i, so the far end need not be evaluated.
@@ -174,8 +181,22 @@
     const int lou = TR ? loy : lox, lov = TR ? lox : loy, lov_hi = TR ? lox_hi : loy_hi;
     const uint32_t wu = TR ? wy : wx, wv = TR ? wx : wy;
     // wave-uniform bounds of the wave's displacement box
-    const int mnx = wave_min_i32(has ? lou : 0x7FFFFFFF), mny = wave_min_i32(has ? lov : 0x7FFFFFFF);
-    const int mxx = wave_max_i32(has ? lou + (int)wu - 1 : -0x7FFFFFFF), mxy = wave_max_i32(has ? lov_hi + (int)wv - 1 : -0x7FFFFFFF);
+    const int mnx = wave_min_i32(has ? lou : 0x7FFFFFFF), mxx = wave_max_i32(has ? lou + (int)wu - 1 : -0x7FFFFFFF);
+    // (across the planes - the lean plan's row of parallel lines: almost always the same two integers on every lane, one
+    // comparison instead of two reductions)
+    int mny = 0x7FFFFFFF, mxy = -0x7FFFFFFF;
+    {
+        const unsigned long long hm = __builtin_amdgcn_ballot_w64(has);
+        const int fl = (int)__builtin_ctzll(hm | (1ull << 63));
+        const int lo_f = __builtin_amdgcn_readlane(lov, fl), hi_f = __builtin_amdgcn_readlane(lov_hi + (int)wv - 1, fl);
+        if (__builtin_amdgcn_ballot_w64(has && (lov != lo_f || lov_hi + (int)wv - 1 != hi_f))) {
+            mny = wave_min_i32(has ? lov : 0x7FFFFFFF);
+            mxy = wave_max_i32(has ? lov_hi + (int)wv - 1 : -0x7FFFFFFF);
+        } else if (hm) {
+            mny = lo_f;
+            mxy = hi_f;
+        }
+    }
     const int need = wave_max_i32(has ? (int)min(wu * wv, 0x3FFFFFFFu) : 0);
     const bool wave_has = mxx >= mnx;
     const bool wave_odd = __any(active && !(simple || stepped));
@@ -494,9 +515,9 @@
             const int r = u / isp, c = u - r * isp;
             const int gv = (int)V0 + dy0 + r, gu = gu0 + c;
             const int gx = TR ? gv : gu, gy = TR ? gu : gv;
-            // {-window sum, f32 stdev - the lean plan: its reciprocal (v_rcp_f32: within an ulp, far inside what limk is shaved by)};
+            // {-window sum, f32 stdev - the lean plan: its reciprocal (v_rcp_f32: within an ulp, part of the approximate score, see record())};
             // centres outside the image or skipped by the reference (stdev non-finite or < min_stdev, mod.rs:430-441) get +inf - the
-            // lean plan: 0 - and never reach limk > 0
+            // lean plan: 0 - and never pass the pre-screen
             uint2 v = make_uint2(0u, NO_CAND);
             if (gy >= 0 && gy < (int)p.h2 && gx >= 0 && gx < (int)p.w2) {
                 const uint2 tt = istats2[(size_t)gy * p.w2 + (size_t)gx];
@@ -539,45 +560,60 @@
     }
     const uint32_t s1 = has ? (istats1[pix].x & 0x7FFFFFFFu) : 0u;
     const float k1 = ps.st1.y * (float)(KERNEL_POINT_COUNT * KERNEL_POINT_COUNT); // 121*121*sd1
-    const float c1 = 1.0f / k1;
-    const float k1s = k1 * (1.0f - 9.5367431640625e-7f); // (the pre-screen's bound is shaved by 2^-20: it absorbs the roundings below)
     __syncthreads();
 
     unsigned long long word = 0ull;
     uint2 cell = make_uint2(CELL_NONE, 0x7FC00000u);
-    uint32_t evaluated = 0, multi = 0, whole = 0, exact_evals = 0;
-    float runmax = -__builtin_inff();
+    uint32_t evaluated = 0, whole = 0, exact_evals = 0;
     const float thr_lo = p.threshold - S2_DELTA;
+    // Contender bookkeeping, in the pre-screen's own domain.  A candidate's x = (float)N * r - the exact product, r = the
+    // rounded 1 / sd2 (lean plan: the staged table's; stepped plan: v_rcp_f32 of the staged stdev) - stands for its approximate
+    // score g = x / k1; g has fewer roundings than the chain's own f32 steps allow for, so |f - g| <= DELTA holds for it.  The
+    // state is one number per lane, T = max(T0, fl(R + D)), R the largest x recorded so far:
+    //     D  = k1 * (2 DELTA + 2^-20)   the band, widened by 2^-20 (16 ulp of a score) for the roundings below
+    //     T0 = fl(lam + 2 D),  lam = thr_lo * k1 shaved by 2^-18 of itself and 2^-20 D
+    // Pre-screen (walk and hit branch): fl(x - T) >= -2 D - one fma against the state, no bound to rebuild.
+    // Restart (the list starts anew with this candidate): fl(x - T) > 0, i.e. x > T exactly.
+    // Record: T = max(T, fl(x + D)) - one fma and one v_max_f32; the lean plan's code is a scalar (plane << 7 | step) that the
+    // lane turns into the reference's (stripe << 11 | i - r0) after the walk, the stepped plans' codes are built per lane.
+    // The invariant the exact phase needs: every candidate with g >= max(G - 2 DELTA, thr_lo), G = R_final / k1, reaches it
+    // (is on the final list, or the list overflowed).  The roundings that enter, with |x|, |R| < 1.01 k1 (|g| <= 1 + DELTA):
+    // fl(R + D), fl(T - 2 D), the stepped plans' fl(limk sd2) and the fmas each within 1.02 k1 2^-24 (the reciprocal's error is
+    // inside x, hence inside g), D itself within D 2^-24 - together below 8 k1 2^-24 of the 2^-20 k1 in D.  So (a) a candidate
+    // that fails the pre-screen has x < T - 2 D + 3 k1 2^-24: below R - 2 DELTA k1 where T = fl(R + D), below thr_lo k1 where
+    // T = T0 (the shaves of lam exceed T0's rounding at any threshold); (b) a restart has x_new > fl(R + D) >= R + D -
+    // 1.02 k1 2^-24, so everything it drops lies below x_new - 2 DELTA k1 <= R_final - 2 DELTA k1.  The few candidates the
+    // widening lets through only join the list.  (A pixel's first record at x <= T0 - rare: g within 2 DELTA of thr_lo - starts
+    // the list through the append path.)  For thr_lo > 1e-10 lam > 2^-23 D, so T0 > 2 D and the lean plan's cells without a
+    // candidate (r = 0: x = 0) never pass, as before.  Lanes without candidates have T = +inf.
+    const float D = k1 * (2.0f * S2_DELTA + 9.5367431640625e-7f), M = -2.0f * D;
+    const auto start_of = [&]() -> float {
+        float lam = thr_lo * k1;
+        lam -= fabsf(lam) * 3.814697265625e-6f + D * 9.5367431640625e-7f;
+        return lam + 2.0f * D;
+    };
+    float T = has ? start_of() : __builtin_inff();
+    float limk = T + M; // (stepped plans: the walk's bound on (float)N / sd2, kept beside T)
+    // bits 15 j: the codes, oldest first; bits 60..63: how many were recorded (S2_K + 1: more than the list holds)
     unsigned long long clist = 0ull;
-    uint32_t count = 0;
-    // acceptance band in the integer domain, as in search2_filter_kernel; lanes without candidates never pass
-    // A candidate passes the pre-screen where (float)N * (1 / sd2) >= limk = max(runmax - 2 DELTA, thr_lo) * k1 * (1 - 2^-20) (lean plan;
-    // stepped plan: (float)N >= limk * sd2): with g = (float)N / sd2 * c1 the approximate score, every candidate with g >=
-    // max(runmax - 2 DELTA, thr_lo) does (the roundings of g, c1, the reciprocal and limk together stay below 8 * 2^-24 of the
-    // 2^-20), and the few it lets through just below that bound only join the list of contenders that the exact phase re-evaluates
-    // - so record() does not test g against the bound again.  (Round 5: the bound is not re-derived on entry, the maxima are the
-    // plain instruction, the lean plan's reciprocal comes from the staged table instead of a quarter-rate v_rcp_f32 per record:
-    // a record body went from 28 vector instructions and a reciprocal to 19.)
-    float limk = has ? thr_lo * k1s : __builtin_inff();
     const auto max_f32 = [](float a, float b) -> float { // v_max_f32 as it is: no operand is ever a NaN here, and fmaxf()
         float r;                                          // spends an instruction per operand on quieting signalling ones
         asm("v_max_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
         return r;
     };
-    auto record = [&](float g, uint32_t code) {
-        // The rule: a candidate clearly above everything recorded so far (by more than the band) starts the list anew -
-        // nearly every record is that, so it is a path of its own (two moves); appending inside the band - the variable
-        // 64-bit shift, the count's cap - is a real branch that almost no wave takes.
-        if (g > runmax + 2.0f * S2_DELTA) {
-            clist = (unsigned long long)code;
-            count = 1u;
+    auto record = [&](bool restart, float t, uint32_t code) { // t = fl(x + D)
+        // Nearly every record is a restart, so it is a path of its own (one 64-bit move); appending inside the band - the
+        // variable 64-bit shift, the count's cap - is a real branch that almost no wave takes.
+        if (restart) {
+            clist = (1ull << 60) | code;
         } else {
+            uint32_t count = (uint32_t)(clist >> 60);
             asm volatile("" : "+v"(count)); // (keeps the two paths apart: as selects the append costs every record its dozen operations)
             if (count < (uint32_t)S2_K) clist |= (unsigned long long)code << (15u * count);
-            count = min(count + 1u, (uint32_t)S2_K + 1u);
+            clist = (clist & ((1ull << 60) - 1ull)) | ((unsigned long long)min(count + 1u, (uint32_t)S2_K + 1u) << 60);
         }
-        runmax = max_f32(runmax, g);
-        limk = max_f32(runmax - 2.0f * S2_DELTA, thr_lo) * k1s;
+        T = max_f32(T, t);
+        if (STEP) limk = T + M;
     };
 
     // mod.rs:424-429 for stripe -cs at displacement dx, the reference's own operations: this lane's first plane at that step.
@@ -602,7 +638,7 @@
         // Inside out: from the middle of the wave's displacement range up to its end, then from the middle down to
         // its start.  The ranges are centred on the positions predicted by the previous level, so the best matches
         // sit around the middle and are met first; the near-misses next to them (which pass the initial threshold
-        // and would each cost a trip through the hit branch) then come after limk has risen.  Any order is exact.
+        // and would each cost a trip through the hit branch) then come after the bound has risen.  Any order is exact.
         const int mid = nsteps >> 1;
         for (int t = 0; t < nsteps; t++) {
             const int step = t < nsteps - mid ? mid + t : nsteps - 1 - t;
@@ -663,20 +699,21 @@
                     num[q] = __mul24((int)s12, KERNEL_POINT_COUNT) + __mul24((int)s1, (int)is2.x);
                     rs[q] = __uint_as_float(is2.y);
                 }
-                // one branch for the group: the largest margin (float)N / sd2 - limk decides (limk is shaved by 2^-20, see
-                // record()); a hit is re-tested below against the limk of that moment.
+                // one branch for the group: the largest margin decides - lean plan fl(x - T) against -2 D, stepped plan
+                // (float)N - limk sd2 against 0 (see record()); a hit is re-tested below against the state of that moment.
                 float mg[N];
 #pragma unroll
-                for (int q = 0; q < N; q++) mg[q] = RS ? __builtin_fmaf((float)num[q], rs[q], -limk) : __builtin_fmaf(-limk, rs[q], (float)num[q]);
+                for (int q = 0; q < N; q++) mg[q] = RS ? __builtin_fmaf((float)num[q], rs[q], -T) : __builtin_fmaf(-limk, rs[q], (float)num[q]);
                 float margin = mg[0];
 #pragma unroll
                 for (int q = 1; q < N; q++) margin = fmaxf(margin, mg[q]);
+                const float mlo = RS ? M : 0.0f;
                 if (COUNT) {
 #pragma unroll
                     for (int q = 0; q < N; q++)
                         if (mx && (uint32_t)(dyb + S0 + q - bl) < wv && (RS ? rs[q] > 0.0f : rs[q] < __builtin_inff())) evaluated++;
                 }
-                if (margin >= 0.0f && !(dbg & 64)) {
+                if (margin >= mlo && !(dbg & 64)) {
                     // (stepped lines: the lane's own first plane at this step, needed only here)
                     // (behind an opaque copy of dx: the compiler otherwise evaluates the six f64 operations ahead of the branch,
                     // in every step)
@@ -717,12 +754,14 @@
                                     }
                                 }
                                 const int dmaj = (TR ? (int)y : xi) + dx - (int)r0; // position along the line (stepped lanes: major_x != TR)
-                                if (stripe != 0xFFFFFFFFu) record((float)numj * (c1 * __builtin_amdgcn_rcpf(rsj)), (stripe << 11) | (uint32_t)dmaj);
+                                const float rr = __builtin_amdgcn_rcpf(rsj);
+                                if (stripe != 0xFFFFFFFFu)
+                                    record(__builtin_fmaf((float)numj, rr, -T) > 0.0f, __builtin_fmaf((float)numj, rr, D), (stripe << 11) | (uint32_t)dmaj);
                             }
                         }
                         return;
                     }
-                    // Planes from the middle of the group outwards: every record raises limk, and the stripe through
+                    // Planes from the middle of the group outwards: every record raises the bound, and the stripe through
                     // the predicted position is where the best match usually is - once it is in, its neighbours
                     // (typically 0.6 .. 0.9 against ~1) fail the re-test and their record bodies are skipped.  The
                     // order is free: the contender list is unordered and re-evaluated exactly.
@@ -730,16 +769,22 @@
                     for (int qi = 0; qi < N; qi++) {
                         const int q = (N - 1) / 2 + ((qi & 1) ? (qi + 1) / 2 : -(qi / 2)); // m, m+1, m-1, m+2, ...
                         const int dy = dyb + S0 + q; // displacement across the planes (y; x when TR)
-                        // (the plane's own pre-screen margin first - one compare; it was taken with a limk that has only
-                        // risen since, so nothing that passes the exact test below is missed)
-                        const float nr = (float)num[q] * rs[q]; // (lean plan)
-                        if (mg[q] >= 0.0f && mx && (uint32_t)(dy - bl) < wv &&
-                            (RS ? nr >= limk : (rs[q] < __builtin_inff() && (float)num[q] >= limk * rs[q]))) {
-                            // back to image axes: candidate (x + ddx, y + ddy), stripe origin (ox, oy)
-                            const int ddx = TR ? dy : dx, ddy = TR ? dx : dy, ox = TR ? bl : lox, oy = TR ? loy : bl;
-                            const uint32_t code = major_x ? ((uint32_t)(ddy - oy) << 11) | (uint32_t)(xi + ddx - (int)r0)
-                                                          : ((uint32_t)(ddx - ox) << 11) | (uint32_t)((int)y + ddy - (int)r0);
-                            record(RS ? nr * c1 : (float)num[q] * (c1 * __builtin_amdgcn_rcpf(rs[q])), code);
+                        // (the plane's own pre-screen margin first - one compare; it was taken with a T that has only risen
+                        // since, so nothing that passes the test below is missed.  Lean plan: the first plane's margin IS the
+                        // test - nothing was recorded since.)
+                        const float mgc = qi == 0 ? mg[q] : __builtin_fmaf((float)num[q], rs[q], -T); // (lean plan)
+                        if (mg[q] >= mlo && mx && (uint32_t)(dy - bl) < wv &&
+                            (RS ? mgc >= M : (rs[q] < __builtin_inff() && (float)num[q] >= limk * rs[q]))) {
+                            if (RS) {
+                                record(mgc > 0.0f, __builtin_fmaf((float)num[q], rs[q], D), ((uint32_t)(S0 + q) << 7) | (uint32_t)step);
+                            } else {
+                                // back to image axes: candidate (x + ddx, y + ddy), stripe origin (ox, oy)
+                                const int ddx = TR ? dy : dx, ddy = TR ? dx : dy, ox = TR ? bl : lox, oy = TR ? loy : bl;
+                                const uint32_t code = major_x ? ((uint32_t)(ddy - oy) << 11) | (uint32_t)(xi + ddx - (int)r0)
+                                                              : ((uint32_t)(ddx - ox) << 11) | (uint32_t)((int)y + ddy - (int)r0);
+                                const float rr = __builtin_amdgcn_rcpf(rs[q]);
+                                record(__builtin_fmaf((float)num[q], rr, -T) > 0.0f, __builtin_fmaf((float)num[q], rr, D), code);
+                            }
                         }
                     }
                 }
@@ -827,6 +872,22 @@
     // elsewhere, or - a pass whose scores nobody can read (CorrParams::need_scores) - if ONE contender is in the band: every
     // other candidate then has g < g* - 2 delta, i.e. f < f*, and g* >= threshold + delta means f* >= threshold; the match
     // is that contender, the 121-term chain could only add the score, and the cell keeps g*.
+    const uint32_t count = (uint32_t)(clist >> 60);
+    clist &= (1ull << 60) - 1ull;
+    if (!STEP) {
+        // the lean walk recorded (plane << 7 | step): the candidate at displacement (mnx + step, dy0 + plane) on the kernel's
+        // axes; its code (stripe << 11 | i - r0) on the image's, with the position along the lanes where the line runs along them
+        const bool pu = major_x != TR;
+        unsigned long long codes = 0ull;
+        for (uint32_t j = 0; j < min(count, (uint32_t)S2_K); j++) {
+            const uint32_t rel = (uint32_t)(clist >> (15u * j)) & 0x7FFFu;
+            const int du = mnx + (int)(rel & 127u), dv = dy0 + (int)(rel >> 7);
+            const uint32_t code = pu ? ((uint32_t)(dv - lov) << 11) | (uint32_t)(ui + du - (int)r0)
+                                     : ((uint32_t)(du - lou) << 11) | (uint32_t)((int)vv + dv - (int)r0);
+            codes |= (unsigned long long)code << (15u * j);
+        }
+        clist = codes;
+    }
     uint32_t ecount = 0;
     Line ex = e;
     if (has) {
@@ -835,7 +896,6 @@
             whole = 1;
             evaluated = 0; // the exact kernel walks (and counts) the whole corridor
         } else if (count > 0u && !(dbg & (16 | 512))) { // (512: the contenders come from unstaged LDS)
-            multi = count > 1 ? 1u : 0u;
             // Rectified instantiation: the epipolar line is not needed during the walk, so it is re-derived here (same
             // expressions, same bits) instead of living in 8 registers across it.
             if (!STEP) {
@@ -844,10 +904,14 @@
                 ex = epipolar_line(p, xo, yo);
             }
             ecount = count;
-            if (!p.need_scores && count == 1u && runmax >= p.threshold + S2_DELTA) {
+            // (the one contender is the last record and a restart or the only one: T = fl(x* + D) where T > T0, and then
+            // g* = x* / k1 >= threshold + DELTA follows from the test below with 2^-18 to spare for its roundings; the score
+            // the cell keeps is that g* to within them - a pass without scores never writes it)
+            const float T0 = start_of();
+            if (!p.need_scores && count == 1u && T > T0 && T - D >= (p.threshold + S2_DELTA + 3.814697265625e-6f) * k1) {
                 const uint32_t code = (uint32_t)clist & 0x7FFFu;
                 const CandXY c = candidate_xy(ex, r0 + (code & 0x7FFu), (int)(code >> 11) - cs);
-                cell = make_uint2(c.x | (c.y << 16), __float_as_uint(runmax));
+                cell = make_uint2(c.x | (c.y << 16), __float_as_uint((T - D) * __builtin_amdgcn_rcpf(k1)));
                 ecount = 0u;
             }
         }
@@ -916,7 +980,6 @@
             evaluated = 0;
             ecount = 0;
             extras = 0;
-            multi = 0;
         }
         q_incl = wave_prefix_sum(extras);
         q_total = (uint32_t)__builtin_amdgcn_readlane((int)q_incl, 63);
@@ -974,7 +1037,7 @@
     const size_t pix_e = (size_t)ys * p.w1 + xs;
     if (is_out && !whole) store_cell(p, out, out_score, pix_e, cell);
     if (counters) {
-        uint32_t v0 = evaluated, v1 = exact_evals, v2 = multi, v3 = whole;
+        uint32_t v0 = evaluated, v1 = exact_evals, v2 = ecount > 1u ? 1u : 0u, v3 = whole; // (v2: pixels with more than one contender)
         if (dbg & 32) { // diagnostics: displacements walked per wave, waves that walked
             v1 = lane == 0 && wave_has ? (uint32_t)((mxx - mnx + 1) * NPL) : 0u;
             v2 = lane == 0 && wave_has ? 1u : 0u;

@@ -1608,16 +1608,17 @@ __device__ __forceinline__ uint32_t load_dword_checked(const uint8_t *__restrict
 // of the displacement box is dx);  TR = true: the same kernel with the two image axes exchanged - lanes along y,
 // waves along x, the packed 11-byte vectors are image ROWS - for column-major lines.  Below, u is the lane axis
 // and v the other one; S12 is the same integer either way.
-// Launch bound of the lean instantiation: 6 waves/SIMD (76 VGPRs, no spill).  7 waves - what its 22.5 KB of LDS would
+// Launch bound of the lean instantiation, both line directions: 6 waves/SIMD (80 VGPRs, no spill; with a bound of 5 the
+// transposed one takes 95 and loses the sixth wave).  7 waves - what its 22.5 KB of LDS would
 // admit - was measured 1.8 % faster (5.89 vs 6.00 ms per 4096^2 pair) but only with 10 VGPRs spilled: 28 B of scratch
 // per lane x 54 M threads put +1.17 GB per step on the L2 write-back counter (whole step 3.0 -> 4.2 GB).  Not taken.
-// (the candidate-counting instantiations - profiling and tests only - need 85 registers (lean) and ~100 (stepped): five and
+// (the candidate-counting instantiations - profiling and tests only - need 80 registers (lean) and ~115 (stepped): five and
 // four waves rather than 28 B of scratch)
 #ifndef CVHIP_STEP_WAVES
 #define CVHIP_STEP_WAVES 5
 #endif
 template <bool COUNT, bool STEP, bool TR>
-__global__ __launch_bounds__(256, STEP ? (COUNT ? 4 : CVHIP_STEP_WAVES) : ((TR || COUNT) ? 5 : 6)) void search3_box_kernel(SearchJob ja, SearchJob jb)
+__global__ __launch_bounds__(256, STEP ? (COUNT ? 4 : CVHIP_STEP_WAVES) : (COUNT ? 5 : 6)) void search3_box_kernel(SearchJob ja, SearchJob jb)
 {
     const SearchJob &j = this_job(); // both directions of a level in one launch (see search_range_kernel)
     const CorrParams &p = j.p;
