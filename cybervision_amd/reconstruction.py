@@ -285,7 +285,8 @@ def reconstruct_perspective_surface(device, pyramids, pairs_result, cameras, bun
 def recover_camera_poses(device, tri, seed: int = 0, log=None):
     """recover_camera_poses (reconstruction.rs:627-666) over a PerspectiveTriangulation whose sparse pairs are in: calls
     recover_next_cameras until it places no more images; an image whose recover_pose fails is skipped (the reference prints
-    the error and goes on).  Then complete_sparse_triangulation.  -> (camera_order, per-call info)."""
+    the error and goes on).  Then complete_sparse_triangulation.  -> (camera_order, per-call info): "images" for a call
+    that placed some, "failure" (the message) for one that failed, next to what recover_next_cameras left in last_pose."""
     from . import _lib
 
     order, info = [], []
@@ -293,7 +294,8 @@ def recover_camera_poses(device, tri, seed: int = 0, log=None):
         try:
             images = tri.recover_next_cameras(device, seed=seed + len(info))
         except _lib.CvhipError as exc:  # "Failed to recover pose for next image"
-            info.append({"error": str(exc), **(tri.last_pose or {})})
+            # (last_pose has an "error" of its own, recover_pose's residual, so the message gets a key that it cannot overwrite)
+            info.append({**(tri.last_pose or {}), "failure": str(exc)})
             if log is not None:
                 log(f"Failed to recover pose for next image: {exc}")
             continue

@@ -6,6 +6,7 @@ Transcribes, citing zlogic/cybervision v0.20.3 src/triangulation.rs:
     tracks_reprojection_error, point_reprojection_error                       :1033-1210, 1296-1328
   - solve_quartic, polish_roots                                               :1595-1673
   - add_image_pair_sparse, recover_next_cameras, triangulate_tracks's bookkeeping (SparseTriangulation) :620-811
+  - recover_camera_poses' loop over a SparseTriangulation                     src/reconstruction.rs:627-666
 plus the device's sample generator (csrc/pose_kernels.hip draw_samples), so that the restatement can be fed the same
 index stream.  Unpinned: nalgebra's SVD signs (np.linalg.svd here) - they change find_projection_matrix's candidate
 order, which matters only on a tie of counts.  Nothing in cybervision_amd/ may import this module.
@@ -190,9 +191,10 @@ def tracks_reprojection_error(tracks, projections, include, threshold, per_track
     return (count, error, errs) if per_track else (count, error)
 
 
-def pose_candidates(linked_tracks, linked_points, projections, image, K, max_dimension, triple, per_track=False):
+def pose_candidates(linked_tracks, linked_points, projections, image, K, max_dimension, triple, per_track=False, score=True):
     """One hypothesis of recover_pose (:1091-1121) on a given sample triple
-    -> [(slot, R, t, r, P, passed, count, error, per-track errors or None)]."""
+    -> [(slot, R, t, r, P, passed, count, error, per-track errors or None)]; score=False stops after the 3-sample check
+    (count and error None for a pose that passed)."""
     k_inv = np.linalg.pinv(K, rcond=0.0)
     samples = [(linked_tracks[i][image], linked_points[i]) for i in triple]
     validate = [i for i, pr in enumerate(projections) if pr is not None or i == image]
@@ -207,6 +209,9 @@ def pose_candidates(linked_tracks, linked_points, projections, image, K, max_dim
         if cnt != RANSAC_N:
             out.append((slot, R, t, cam.r, P, False, 0, np.nan, None))
             continue
+        if not score:
+            out.append((slot, R, t, cam.r, P, True, None, None, None))
+            continue
         count, error, errs = tracks_reprojection_error(linked_tracks, prj, validate, RANSAC_T * max_dimension, per_track=True)
         with np.errstate(all="ignore"):
             out.append((slot, R, t, cam.r, P, True, count, np.float64(error) / count, errs if per_track else None))
@@ -219,24 +224,46 @@ def linked(tracks, points, ok, image):
     return np.asarray(tracks)[sel], np.asarray(points)[sel]
 
 
-def recover_pose(tracks, points, ok, projections, image, K, max_dimension, seed, samples=device_samples):
+def recover_pose_batch(lt, lp, projections, image, K, max_dimension, seed, batch, samples=device_samples, observe=None):
+    """The hypotheses of one batch (:1091-1121) scanned in (hypothesis, root) order from the empty result
+    -> (camera (r, t, P) or None, count, error, winner (batch, hyp, slot) or None).  observe(batch, hyp, slot, count, error,
+    per-track errors) is called for every scored pose."""
+    best = (None, 0, np.finfo(np.float64).max, None)
+    for h in range(RANSAC_CHECK_INTERVAL):
+        for slot, R, t, r, P, passed, count, error, errs in pose_candidates(
+                lt, lp, projections, image, K, max_dimension, samples(seed, batch, h, len(lt)), per_track=observe is not None):
+            if not passed:
+                continue
+            if observe is not None:
+                observe(batch, h, slot, count, error, errs)
+            if count > best[1] or (count == best[1] and error < best[2]):
+                best = ((r, t, P), count, error, (batch, h, slot))
+    return best
+
+
+def recover_pose(tracks, points, ok, projections, image, K, max_dimension, seed, samples=device_samples, observe=None,
+                 batch_results=None):
     """recover_pose (:1033-1144) fed with an index stream (the device's by default); reduce_best_result applied as a scan
-    in (batch, hypothesis, root) order after the carried result (the device's convention).
-    -> dict(camera (r, t, P) or None when not accepted, count, error, batches, winner (batch, hyp, slot) or None, linked)."""
+    in (batch, hypothesis, root) order after the carried result (the device's convention): a batch's own best replaces the
+    carried result when it is strictly better, which is the same scan.  batch_results: {batch: recover_pose_batch's result}
+    computed elsewhere (the fixture generator's workers).
+    -> dict(camera (r, t, P) or None when not accepted, best (the carried camera, accepted or not), count, error, batches,
+    winner (batch, hyp, slot) or None, linked, ransac_d, history [(count, error, winner) after every batch])."""
     lt, lp = linked(tracks, points, ok, image)
-    res = {"camera": None, "count": 0, "error": 0.0, "batches": 0, "winner": None, "linked": len(lt)}
+    d = RANSAC_D_PERCENT * len(lt) // 100
+    res = {"camera": None, "best": None, "count": 0, "error": 0.0, "batches": 0, "winner": None, "linked": len(lt),
+           "ransac_d": d, "history": []}
     if len(lt) < RANSAC_N:
         return res
     best = (None, 0, np.finfo(np.float64).max, None)
-    d = RANSAC_D_PERCENT * len(lt) // 100
     d_early = RANSAC_D_PERCENT_EARLY_EXIT * len(lt) // 100
     batches = 0
     for batch in range(RANSAC_K // RANSAC_CHECK_INTERVAL):
-        for h in range(RANSAC_CHECK_INTERVAL):
-            for slot, R, t, r, P, passed, count, error, _ in pose_candidates(
-                    lt, lp, projections, image, K, max_dimension, samples(seed, batch, h, len(lt))):
-                if passed and (count > best[1] or (count == best[1] and error < best[2])):
-                    best = ((r, t, P), count, error, (batch, h, slot))
+        b = batch_results[batch] if batch_results is not None else recover_pose_batch(
+            lt, lp, projections, image, K, max_dimension, seed, batch, samples, observe)
+        if b[1] > best[1] or (b[1] == best[1] and b[2] < best[2]):
+            best = b
+        res["history"].append((best[1], best[2], best[3]))
         batches = batch + 1
         if best[1] >= d_early:
             break
@@ -260,7 +287,7 @@ class SparseTriangulation:
         self.best = None  # (score, pair, p2)
         self.remaining = list(range(images_count))
         self.points, self.ok = np.zeros((0, 3)), np.zeros(0, dtype=bool)
-        self.last = None
+        self.last = self.last_image = self.last_counts = None
 
     def add_image_pair_sparse(self, i, j, F, inliers):
         w, h = self.shapes[i]
@@ -287,9 +314,10 @@ class SparseTriangulation:
         P = [pr if pr is not None else np.zeros((3, 4)) for pr in self.projections]
         self.points, self.ok, _ = rt.triangulate_tracks(masked, P)
 
-    def recover_next_cameras(self, seed=0):
-        """:710-811 -> the images placed ([] when none is left); raises TriangulationError when recover_pose fails."""
-        self.last = None
+    def recover_next_cameras(self, seed=0, recover=None):
+        """:710-811 -> the images placed ([] when none is left); raises TriangulationError when recover_pose fails.
+        recover: stands in for recover_pose (same arguments and result), for a run recorded in tests/golden/."""
+        self.last = self.last_image = self.last_counts = None
         if self.best is not None:
             _, (i1, i2), p2 = self.best
             self.projections[i1] = self.K[i1] @ np.eye(3, 4)
@@ -310,8 +338,9 @@ class SparseTriangulation:
             if counts[k] >= counts[best]:
                 best = k
         self.remaining = [k for k in self.remaining if k != best]
-        res = recover_pose(self.tracks, self.points, self.ok, self.projections, best, self.K[best], max(self.shapes[best]),
-                           seed)
+        self.last_image, self.last_counts = best, counts
+        res = (recover or recover_pose)(self.tracks, self.points, self.ok, self.projections, best, self.K[best],
+                                        max(self.shapes[best]), seed)
         self.last = res
         if res["camera"] is None:
             raise rt.TriangulationError("Unable to find projection matrix")
@@ -320,6 +349,28 @@ class SparseTriangulation:
         self.projections[best] = P
         self.triangulate_tracks()
         return [best]
+
+
+def recover_camera_poses(st, seed=0, recover=None):
+    """recover_camera_poses (reconstruction.rs:627-666) over a SparseTriangulation whose pairs are in: recover_next_cameras
+    with seed + the number of earlier calls until it places nothing; a failed image is skipped and the loop goes on.
+    -> (order, calls): per call that tried something {images | failure, image, counts, pose (recover_pose's result), and
+    the state after it: points, ok, projections, cameras}."""
+    order, calls = [], []
+    while True:
+        entry = {}
+        try:
+            placed = st.recover_next_cameras(seed=seed + len(calls), recover=recover)
+        except rt.TriangulationError as exc:
+            entry["failure"] = str(exc)
+            placed = None
+        if placed is not None and not placed:
+            break
+        entry.update(images=placed, image=st.last_image, counts=st.last_counts, pose=st.last, points=st.points.copy(),
+                     ok=st.ok.copy(), projections=list(st.projections), cameras=list(st.cameras))
+        calls.append(entry)
+        order.extend(placed or [])
+    return order, calls
 
 
 def find_projection_matrix(F, k1, k2, short_tracks):

@@ -2,6 +2,7 @@
 import numpy as np
 import pytest
 
+import pose_checks
 import pose_scenes
 import ref_pose as rp
 import ref_triangulation as rt
@@ -70,63 +71,10 @@ def test_pose_models_match_restatement_per_sample(gpu_device):
     P, has = _known(K, poses)
     pts, ok = device_triangulate(gpu_device, tracks, P, has)
     lt, lp = rp.linked(tracks, pts, ok, 2)
-    rng = np.random.default_rng(9)
-    B = 3000
-    samples = rng.integers(0, len(lt), size=(B, 3)).astype(np.uint32)
-    samples[:100, 1] = samples[:100, 0]              # duplicate indices
-    samples[100:150, 2] = samples[100:150, 0]
-    # near-collinear: the third point close to the line through the first two
-    d = np.linalg.norm(lp[:, None, :] - lp[None, :, :], axis=-1)
-    for b in range(150, 400):
-        i0, i1 = samples[b, 0], samples[b, 1]
-        mid = 0.5 * (lp[i0] + lp[i1])
-        dist = np.linalg.norm(lp - mid, axis=1)
-        dist[[i0, i1]] = np.inf
-        samples[b, 2] = np.argmin(dist)
-    del d
-    samples = np.ascontiguousarray(samples)
-    pose, status = np.zeros((B, 4, 27)), np.zeros((B, 4), dtype=np.int8)
-    count, err = np.zeros((B, 4), dtype=np.uint32), np.zeros((B, 4))
-    n = len(tracks)
-    okb = ok.astype(np.uint8)
-    _lib.check(_lib.lib().cvhip_recover_pose_models(gpu_device.handle, _p(tracks), n, 3, _p(pts), _p(okb), _p(P), _p(has), 2,
-                                                    _p(K), 512, _p(samples), B, _p(pose), _p(status), _p(count), _p(err)),
-               "models")
-    projections = [P[0], P[1], None]
-    thr = rp.RANSAC_T * 512
-    scored = exact = loose = poses_seen = 0
-    for b in range(B):
-        want = rp.pose_candidates(lt, lp, projections, 2, K, 512, [int(v) for v in samples[b]], per_track=True)
-        assert [k for k in range(4) if status[b, k] != 0] == [w[0] for w in want], b
-        # ill-conditioned triples (the near-collinear ones, and some random ones) amplify the last-bit differences of the
-        # device's pow / sqrt / atan2 through the closed form's cancellations: every pose must match to 1e-6, at least 99 %
-        # of them to 1e-9, and a pose's score is compared at the tolerance its pose met
-        for slot, R, t, r, Pw, passed, cnt, e, errs in want:
-            got = pose[b, slot]
-            want_vec = np.concatenate([R.ravel(), t, r, Pw.ravel()])
-            tight = np.allclose(got, want_vec, rtol=1e-9, atol=1e-9)
-            rtol = 1e-9 if tight else 1e-6
-            loose += 0 if tight else 1
-            poses_seen += 1
-            assert np.allclose(got[:9], R.ravel(), rtol=1e-6, atol=1e-12), b
-            assert np.allclose(got[9:12], t, rtol=1e-6, atol=1e-12), b
-            assert np.allclose(got[12:15], r, rtol=1e-6, atol=1e-12), b
-            assert np.allclose(got[15:], Pw.ravel(), rtol=1e-6, atol=1e-9), b
-            assert (status[b, slot] == 2) == passed, b
-            if not passed:
-                continue
-            scored += 1
-            near = int((np.abs(errs - thr) <= rtol * 512).sum())
-            assert abs(int(count[b, slot]) - cnt) <= near, b
-            if near == 0:
-                exact += 1
-                assert count[b, slot] == cnt
-                # the error is a reprojection residual, a difference of pixel coordinates up to 512: compared in pixels
-                # (the largest residual, error * count) at rtol times the image size
-                assert abs(err[b, slot] * cnt - e * cnt) <= rtol * 512 or (np.isnan(err[b, slot]) and np.isnan(e)), b
-    print(f"{B} triples, {poses_seen} poses ({loose} matched to 1e-6 only), {scored} scored, {exact} without a "
-          f"near-threshold track")
-    assert scored > 1000 and exact > 0.9 * scored and loose <= 0.01 * poses_seen
+    # (noise_triples: this test's samples stay as drawn, as they always were)
+    samples = pose_checks.sample_triples(lp, 3000, seed=9, noise_triples=True)
+    got = pose_checks.device_models(gpu_device, tracks, pts, ok, P, has, 2, K, 512, samples)
+    pose_checks.check_models(got, lt, lp, [P[0], P[1], None], 2, K, 512, samples)
 
 
 def test_extend_tracks_matches_is_bit_exact(gpu_device, oracle):

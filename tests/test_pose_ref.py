@@ -1,6 +1,7 @@
 """Pose recovery's restatement (tests/ref_pose.py) on the CPU: solve_quartic, P3P on exact triples, find_projection_matrix
 on the planted geometry, the device generator's index stream."""
 import numpy as np
+import pytest
 
 import ref_pose as rp
 import ref_triangulation as rt
@@ -104,3 +105,221 @@ def test_restated_recover_next_cameras_order_config5_512(oracle, oracle_fm):
     assert len(first) == 2 and len(second) == 1 and sorted(first + second) == [0, 1, 2]
     assert st.recover_next_cameras(seed=2) == []
     assert st.last is None
+
+
+# ---- the scenes of tests/test_pose_multiview_gpu.py: each one shown, from the restatement alone, to exercise what it is for
+def _near_threshold_margin(contenders, final_count):
+    return min(mg for c, mg in contenders if c >= final_count - 1)
+
+
+def test_multiview_scene_is_ragged_and_inside_the_image():
+    import pose_scenes
+
+    for m in range(2, 9):
+        tracks, K, poses, X = pose_scenes.multiview_scene(m, 500, seed=30 + m, miss=0.3)
+        again = pose_scenes.multiview_scene(m, 500, seed=30 + m, miss=0.3)[0]
+        seen = tracks[..., 0] >= 0
+        assert np.array_equal(tracks, again) and tracks[seen].min() >= 0 and tracks[seen].max() < 512
+        assert (tracks[~seen] == -1).all() and 0.6 < seen.mean() < 0.8 and len(poses) == m
+        for R, t in poses[1:]:
+            assert 0.01 < np.linalg.norm(t) < 0.07 and np.arcsin(np.linalg.norm(R - R.T) / np.sqrt(8.0)) < 0.002
+        # the planted matches fit the true F: x2^T F x1 = 0 up to the rounding to pixels
+        for (i, j), (rows, F) in pose_scenes.planted_matches(tracks, K, poses).items():
+            x1 = np.hstack([rows[:, :2], np.ones((len(rows), 1))])
+            x2 = np.hstack([rows[:, 2:], np.ones((len(rows), 1))])
+            line = x1 @ F.T
+            dist = np.abs((x2 * line).sum(axis=1)) / np.linalg.norm(line[:, :2], axis=1)
+            assert len(rows) == (seen[:, i] & seen[:, j]).sum() and dist.max() < 1.5, (m, i, j)
+
+
+def test_per_sample_configs_cover_the_slots():
+    """The configurations of the per-sample parity test: m in {3, 4, 6, 8}; the image first, in the middle and last; 2 to
+    m - 1 known views; at m = 8 view 7 known alone with one other."""
+    import pose_checks as pc
+
+    assert {m for m, _, _ in pc.MULTIVIEW_CONFIGS} == {3, 4, 6, 8}
+    assert (8, 7) in {(m, len(p)) for m, _, p in pc.MULTIVIEW_CONFIGS} and any(
+        m == 8 and 7 in p and len(p) == 2 for m, _, p in pc.MULTIVIEW_CONFIGS)
+    for m in (4, 6, 8):
+        images = {i for mm, i, _ in pc.MULTIVIEW_CONFIGS if mm == m}
+        assert 0 in images and m - 1 in images and images - {0, m - 1}
+        assert {len(p) for mm, _, p in pc.MULTIVIEW_CONFIGS if mm == m} >= {2, m - 1}
+
+
+def _per_sample_configs():
+    import pose_checks as pc
+
+    return pc.MULTIVIEW_CONFIGS
+
+
+@pytest.mark.parametrize("m,image,placed", _per_sample_configs())
+def test_per_sample_config_scores_enough_poses(m, image, placed):
+    """A configuration of the per-sample parity test: more than 1000 poses pass the 3-sample check (every one of them is
+    scored: the existing test's floor) and the linked tracks are seen in 2, in 3 and in more known views where that many
+    are known."""
+    import pose_checks as pc
+
+    assert image not in placed
+    tracks, K, P, has, projections = pc.multiview_config(m, image, placed)
+    pts, ok = pc.restated_points(tracks, P, has)
+    lt, lp = rp.linked(tracks, pts, ok, image)
+    known = (lt[:, list(placed), 0] >= 0).sum(axis=1)
+    assert (known == 2).any() and (len(placed) < 3 or (known == 3).any()) and (len(placed) < 4 or (known > 3).any())
+    samples = pc.sample_triples(lp, pc.MULTIVIEW_TRIPLES)
+    passed = sum(c[5] for s in samples for c in rp.pose_candidates(lt, lp, projections, image, K, 512, [int(v) for v in s],
+                                                                   score=False))
+    print(m, image, placed, len(lt), "linked,", passed, "poses pass the 3-sample check")
+    assert passed > 1000 and len(lt) > 200, (m, image, placed, passed)
+
+
+def test_middle_batch_scene_leaves_in_a_middle_batch():
+    """pose_scenes' middle_batch run: accepted after 2..20 batches with a winner from a later batch than the first; the
+    best after batch 0 is replaced, and a carried result survives at least one batch; no track of the winner or of a
+    hypothesis within 1 of its count lies within 1e-6 * max_dimension of the threshold."""
+    import pose_checks as pc
+
+    tracks, pts, ok, projections, image, K, md, seed = pc.run_inputs("middle_batch")
+    contenders = []
+
+    def observe(_b, _h, _s, count, _e, errs):
+        with np.errstate(all="ignore"):
+            contenders.append((count, float(np.nanmin(np.abs(errs - rp.RANSAC_T * md)))))
+
+    res = rp.recover_pose(tracks, pts, ok, projections, image, K, md, seed, observe=observe)
+    winners = [w for _, _, w in res["history"]]
+    print("middle batch:", res["count"], "of", res["linked"], "after", res["batches"], "batches, winners", winners)
+    assert res["camera"] is not None and 2 <= res["batches"] <= 20 and res["winner"][0] >= 1
+    assert winners[0] is not None and winners[0] != res["winner"]
+    assert any(winners[k] == winners[k - 1] for k in range(1, len(winners)))
+    assert res["count"] >= rp.RANSAC_D_PERCENT_EARLY_EXIT * res["linked"] // 100 > res["history"][-2][0]
+    assert _near_threshold_margin(contenders, res["count"]) > 1e-6 * md
+
+
+def test_pose_fixture_matches_restatement(oracle):
+    """tests/golden/pose_runs.json against the restatement: the inputs' digest and linked count, batch 0 and the winner's
+    batch re-derived from scratch; and what the recorded runs are for: 100 batches each, one accepted with a winner past
+    batch 50 that replaced earlier ones, two rejected; no near-threshold track among the contenders."""
+    import json
+    from pathlib import Path
+
+    import pose_checks as pc
+
+    runs = json.loads((Path(__file__).resolve().parent / "golden" / "pose_runs.json").read_text())["runs"]
+    assert set(runs) == {"accepted_late", "scrambled_rejected", "stage_scrambled"}
+    for name, fx in runs.items():
+        tracks, pts, ok, projections, image, K, md, seed = pc.run_inputs(name)
+        lt, lp = rp.linked(tracks, pts, ok, image)
+        assert pc.table_digest(tracks) == fx["table"] and len(lt) == fx["linked"] and (image, md, seed) == (
+            fx["image"], fx["max_dimension"], fx["seed"])
+        assert fx["ransac_d"] == rp.RANSAC_D_PERCENT * len(lt) // 100 and fx["batches"] == 100 == len(fx["history"])
+        assert fx["accepted"] == (fx["count"] > fx["ransac_d"]) and fx["count"] < rp.RANSAC_D_PERCENT_EARLY_EXIT * len(lt) // 100
+        assert fx["history"][-1] == [fx["count"], fx["error"], fx["winner"]] and fx["margin"] > 1e-6 * md
+        for batch in sorted({0, fx["winner"][0]}):
+            cam, count, error, winner = rp.recover_pose_batch(lt, lp, projections, image, K, md, seed, batch)
+            if batch == 0:
+                assert [count, list(winner)] == [fx["history"][0][0], fx["history"][0][2]]
+                assert np.isclose(error, fx["history"][0][1], rtol=1e-9, atol=0)
+            if batch == fx["winner"][0]:
+                assert count == fx["count"] and list(winner) == fx["winner"] and np.isclose(error, fx["error"], rtol=1e-9, atol=0)
+                for got, want in zip(cam, (fx["r"], fx["t"], fx["projection"])):
+                    assert np.allclose(got, want, rtol=1e-9, atol=1e-12)
+    late = runs["accepted_late"]
+    changes = [k for k in range(100) if k == 0 or late["history"][k][2] != late["history"][k - 1][2]]
+    assert late["accepted"] and late["winner"][0] >= 50 and len(changes) >= 3 and changes[-1] == late["winner"][0]
+    assert not runs["scrambled_rejected"]["accepted"] and not runs["stage_scrambled"]["accepted"]
+    assert runs["stage_scrambled"]["linked"] < 300  # (the failing image's table stays small: the generator's cost)
+
+
+def _restated_stage(oracle, scene, recover=None, seed=3):
+    import pose_scenes
+
+    tracks, K, poses, _, matches = scene
+    m = tracks.shape[1]
+    st = rp.SparseTriangulation(m, [(512, 512)] * m, [K] * m, oracle.extend_tracks)
+    pose_scenes.restated_pairs(st, matches)
+    initial = st.best[1]
+    order, calls = rp.recover_camera_poses(st, seed=seed, recover=recover)
+    return st, initial, order, calls
+
+
+def test_equal_counts_scene_ties_and_takes_the_later_image(oracle):
+    import pose_scenes
+
+    st, initial, order, calls = _restated_stage(oracle, pose_scenes.equal_counts_scene())
+    assert initial == (2, 3) and order == [2, 3, 1, 0]
+    assert calls[1]["counts"][0] == calls[1]["counts"][1] > 100 and calls[1]["image"] == 1
+    assert all(c["pose"]["camera"] is not None for c in calls[1:])
+
+
+def test_few_links_scene_fails_at_once_and_last(oracle):
+    """Image 3 has fewer than RANSAC_N linked tracks: the restated recover_next_cameras raises for it without a batch.
+    It is the last image tried (nothing can be placed after such a failure: see pose_scenes.few_links_scene), and the
+    call still counts."""
+    import pose_scenes
+
+    st, initial, order, calls = _restated_stage(oracle, pose_scenes.few_links_scene())
+    assert sorted(order) == [0, 1, 2, 4] and len(calls) == 4
+    failed = calls[-1]
+    assert "failure" in failed and failed["image"] == 3 and 0 < failed["pose"]["linked"] < rp.RANSAC_N
+    assert failed["pose"]["batches"] == 0 and st.projections[3] is None
+    assert all("failure" not in c for c in calls[:-1])
+
+
+def test_scrambled_scene_fails_first_and_the_others_follow(oracle):
+    """Image 3 (random points) has the most linked tracks after the initial pair, so it is tried first; its 100 batches
+    are the fixture's stage_scrambled run (re-derived in part by test_pose_fixture_matches_restatement); the restated
+    recover_next_cameras raises for it and the remaining images are placed after it."""
+    import json
+    from pathlib import Path
+
+    import pose_checks as pc
+    import pose_scenes
+
+    fx = json.loads((Path(__file__).resolve().parent / "golden" / "pose_runs.json").read_text())["runs"]["stage_scrambled"]
+    seeds = []
+
+    def recover(tracks, points, ok, projections, image, K, md, seed):
+        seeds.append((image, seed))
+        if image != fx["image"]:
+            return rp.recover_pose(tracks, points, ok, projections, image, K, md, seed)
+        assert pc.table_digest(tracks) == fx["table"] and seed == fx["seed"] and md == fx["max_dimension"]
+        return {"camera": None, "count": fx["count"], "batches": fx["batches"], "winner": tuple(fx["winner"]),
+                "linked": fx["linked"]}
+
+    st, initial, order, calls = _restated_stage(oracle, pose_scenes.scrambled_scene(), recover=recover)
+    assert 3 not in initial and order == list(initial) + [c["image"] for c in calls[2:]] and len(order) == 4
+    failed = calls[1]
+    assert "failure" in failed and failed["image"] == 3 and failed["counts"][3] == fx["linked"] == max(failed["counts"].values())
+    assert seeds == [(3, 4)] + [(c["image"], 3 + k) for k, c in enumerate(calls) if k >= 2]
+    assert all(c["pose"]["camera"] is not None for c in calls[2:]) and st.projections[3] is None
+
+
+def test_recover_camera_poses_keeps_the_failure_message_and_goes_on():
+    """reconstruction.recover_camera_poses around a stand-in triangulation: a failed call is listed with its message under
+    "failure" next to the call's own figures (whose "error" is recover_pose's residual, not the message), takes a seed
+    like any other, and the loop goes on to the next image."""
+    from cybervision_amd import _lib, reconstruction
+
+    class Stub:
+        def __init__(self):
+            self.script = [[0, 1], None, [3], []]
+            self.seeds, self.completed, self.last_pose = [], False, None
+
+        def recover_next_cameras(self, device, seed=0):
+            self.seeds.append(seed)
+            step = self.script.pop(0)
+            self.last_pose = None if step is None or len(step) != 1 else {"image": step[0], "error": 0.25, "count": 9}
+            if step is None:
+                self.last_pose = {"image": 2, "error": 0.5, "count": 4}
+                raise _lib.CvhipError(-6, "cvhip_recover_pose", "Unable to find projection matrix")
+            return step
+
+        def complete_sparse_triangulation(self):
+            self.completed = True
+
+    tri, log = Stub(), []
+    order, info = reconstruction.recover_camera_poses(None, tri, seed=7, log=log.append)
+    assert order == [0, 1, 3] and tri.seeds == [7, 8, 9, 10] and tri.completed and len(log) == 1
+    assert info[0] == {"images": [0, 1]} and info[2] == {"images": [3], "image": 3, "error": 0.25, "count": 9}
+    assert "images" not in info[1] and "Unable to find projection matrix" in info[1]["failure"]
+    assert info[1]["image"] == 2 and info[1]["error"] == 0.5 and info[1]["count"] == 4
