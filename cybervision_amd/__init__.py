@@ -7,6 +7,6 @@ used by tests and bench.py plus the host-side mirror of the reference interface
 (`PointCorrelations`, `orb.extract_points`, `FundamentalMatrix`).  There is NO CPU fallback:
 if the extension is missing or no GPU is present, calls raise.
 """
-from . import synth  # noqa: F401
+from . import mesh, synth  # noqa: F401
 
-__all__ = ["synth"]
+__all__ = ["mesh", "synth"]

@@ -112,6 +112,17 @@ SIGNATURES = {
     "cvhip_recover_pose_models": (C.c_int, [_vp, _vp, C.c_uint64, _u32, _vp, _vp, _vp, _vp, _u32, _vp, _u32, _vp, _u32, _vp,
                                             _vp, _vp, _vp]),
     "cvhip_merge_tracks": (C.c_int, [_vp, _vp, C.c_uint64, _u32, _u32, _u32, _u32, _vp, _vp, C.POINTER(C.c_uint64), _vp]),
+    # the mesh stage; the surface is (points, tracks, n, m, projection, r, t, image_dims) in every entry
+    "cvhip_mesh_set_wide_threshold": (C.c_int, [_vp, _u32]),
+    "cvhip_mesh_camera_points": (C.c_int, [_vp, _vp, _vp, C.c_uint64, _u32, _vp, _vp, _vp, _vp, _u32, _vp, _vp, C.c_uint64,
+                                           C.POINTER(C.c_uint64)]),
+    "cvhip_mesh_depth_buffer": (C.c_int, [_vp, _vp, _vp, C.c_uint64, _u32, _vp, _vp, _vp, _vp, _u32, _vp, C.c_uint64,
+                                          C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "cvhip_mesh_cull": (C.c_int, [_vp, _vp, _vp, C.c_uint64, _u32, _vp, _vp, _vp, _vp, _u32, _vp, C.c_uint64, _vp, _vp]),
+    "cvhip_mesh_merge": (C.c_int, [_vp, _vp, _vp, C.c_uint64, _vp, _vp, C.POINTER(C.c_uint64)]),
+    "cvhip_mesh_depth_image": (C.c_int, [_vp, _vp, _vp, C.c_uint64, _u32, _vp, _vp, _vp, _vp, _u32, C.c_double, _vp,
+                                         C.c_uint64, _vp, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), _vp, _vp,
+                                         C.POINTER(C.c_uint64)]),
 }
 
 

@@ -220,6 +220,7 @@ struct Device {
     int ransac_count_mfma = 0;   // cvhip_ransac_set_count_mfma: the counting screen's head as f32 matrix products (ransac_count_mfma_kernel) - exact, measured slower: off
     int ransac_lm_pipeline = 2;  // cvhip_ransac_set_lm_pipeline (test hook): validate_f's LM as 2 = two passes on refilled lanes (default), 1 = two passes, a root per thread, 0 = the scalar loop in one kernel
     int ransac_pencil = CVHIP_PENCIL_THIN_SVD; // cvhip_ransac_set_pencil: the 7-point pencil's basis (default: the reference's)
+    uint32_t mesh_wide_threshold = CVHIP_MESH_WIDE_THRESHOLD_DEFAULT; // cvhip_mesh_set_wide_threshold
     // complete() into HOST memory (GpuContext::complete_process, gpu/mod.rs:210-216): two device staging sets that the
     // full-resolution grid is expanded into, and a copy stream of its own, so that the 12 B/px transfer of one pair can
     // run under the search of the next (cvhip_ctx_set_async_readback) and no call allocates.  Grow-only, per handle.

@@ -10,6 +10,7 @@
 //   orb::extract_points, orb::optimal_scale_steps          src/orb.rs:50-84, 407-415
 //   KeypointMatching::new(...).matches                     src/pointmatching.rs:29-77
 //   FundamentalMatrix::{new, find_ransac}                  src/fundamentalmatrix.rs:72-147
+//   mesh::Mesh::create, mesh::depth_image                  src/output.rs:363-387, 1016-1143 (Delaunay: the caller's)
 //
 // Header-only, no dependencies beyond the C ABI and the C++17 standard library.  Nothing here does
 // arithmetic on the dense/ORB/matcher path: it only calls libcvhip.so.  RANSAC keeps the reference's
@@ -469,5 +470,111 @@ class FundamentalMatrix {
     size_t ransac_k_, ransac_n_, ransac_d_, ransac_d_early_exit_;
     double ransac_t_;
 };
+
+// ---- the mesh stage of output::output (src/output.rs:567-611) ------------------------------------------------
+namespace mesh {
+
+struct Surface { // triangulation::Surface (triangulation.rs:142-150) as the cvhip_mesh_* entries take it
+    std::vector<double> points;       // n x 3
+    std::vector<int32_t> tracks;      // n x m x 2, (-1, -1) = None
+    std::vector<double> projection;   // m x 12
+    std::vector<double> r, t;         // m x 3 each
+    std::vector<uint32_t> image_dims; // m x 2: width, height
+    uint64_t tracks_len() const { return points.size() / 3; }
+    uint32_t cameras_len() const { return (uint32_t)(projection.size() / 12); }
+};
+
+struct Polygon { // output.rs:49-53
+    uint32_t camera_i;
+    std::array<uint32_t, 3> vertices;
+};
+
+struct CameraPoints { // Mesh::process_camera's Delaunay input (:401-423), in track order
+    std::vector<uint32_t> track_i;
+    std::vector<double> xy; // 2 per point
+};
+
+inline CameraPoints camera_points(GpuDevice &dev, const Surface &s, uint32_t camera_i)
+{
+    uint64_t n = 0;
+    check(cvhip_mesh_camera_points(dev.handle(), s.points.data(), s.tracks.data(), s.tracks_len(), s.cameras_len(), s.projection.data(),
+                                   s.r.data(), s.t.data(), s.image_dims.data(), camera_i, nullptr, nullptr, 0, &n),
+          "cvhip_mesh_camera_points");
+    CameraPoints out;
+    out.track_i.resize(n);
+    out.xy.resize(2 * n);
+    if (n)
+        check(cvhip_mesh_camera_points(dev.handle(), s.points.data(), s.tracks.data(), s.tracks_len(), s.cameras_len(),
+                                       s.projection.data(), s.r.data(), s.t.data(), s.image_dims.data(), camera_i, out.track_i.data(),
+                                       out.xy.data(), n, &n),
+              "cvhip_mesh_camera_points");
+    return out;
+}
+
+// the culling loop of process_camera (:457-508): keep[p] = 0 iff polygon p obstructs in another camera
+inline std::vector<uint8_t> cull(GpuDevice &dev, const Surface &s, uint32_t camera_i, const std::vector<uint32_t> &polygons)
+{
+    std::vector<uint8_t> keep(polygons.size() / 3);
+    check(cvhip_mesh_cull(dev.handle(), s.points.data(), s.tracks.data(), s.tracks_len(), s.cameras_len(), s.projection.data(),
+                          s.r.data(), s.t.data(), s.image_dims.data(), camera_i, polygons.data(), keep.size(), keep.data(), nullptr),
+          "cvhip_mesh_cull");
+    return keep;
+}
+
+class Mesh { // output.rs:356-387
+  public:
+    std::vector<Polygon> polygons;
+
+    // Mesh::create: `triangulate(xy) -> faces` (3 indices into the camera's points each) is the caller's Delaunay
+    template <typename Triangulate> static Mesh create(GpuDevice &dev, const Surface &s, Triangulate triangulate)
+    {
+        std::vector<uint32_t> kept, cams;
+        for (uint32_t i = 0; i < s.cameras_len(); i++) {
+            const CameraPoints cp = camera_points(dev, s, i);
+            const std::vector<uint32_t> faces = triangulate(cp);
+            std::vector<uint32_t> polys(faces.size());
+            for (size_t k = 0; k < faces.size(); k++) polys[k] = cp.track_i.at(faces[k]);
+            const std::vector<uint8_t> keep = cull(dev, s, i, polys);
+            for (size_t p = 0; p < keep.size(); p++)
+                if (keep[p]) {
+                    kept.insert(kept.end(), polys.begin() + 3 * p, polys.begin() + 3 * p + 3);
+                    cams.push_back(i);
+                }
+        }
+        std::vector<uint32_t> out_p(kept.size()), out_c(cams.size());
+        uint64_t n = 0;
+        check(cvhip_mesh_merge(dev.handle(), kept.data(), cams.data(), cams.size(), out_p.data(), out_c.data(), &n), "cvhip_mesh_merge");
+        Mesh mesh;
+        for (uint64_t p = 0; p < n; p++) mesh.polygons.push_back(Polygon{out_c[p], {out_p[3 * p], out_p[3 * p + 1], out_p[3 * p + 2]}});
+        return mesh;
+    }
+};
+
+struct DepthImage { // ImageWriter's output_map (:1009-1013) with its origin and depth range
+    Grid<double> map; // NaN = None
+    double min_x = 0, min_y = 0, min_depth = 0, max_depth = 0;
+};
+
+inline DepthImage depth_image(GpuDevice &dev, const Surface &s, uint32_t project_to_image, double scale, const std::vector<Polygon> &polygons)
+{
+    std::vector<uint32_t> flat;
+    for (const Polygon &p : polygons) flat.insert(flat.end(), p.vertices.begin(), p.vertices.end());
+    uint64_t w = 0, h = 0;
+    double origin[2] = {0, 0}, minmax[2] = {0, 0};
+    check(cvhip_mesh_depth_image(dev.handle(), s.points.data(), s.tracks.data(), s.tracks_len(), s.cameras_len(), s.projection.data(),
+                                 s.r.data(), s.t.data(), s.image_dims.data(), project_to_image, scale, flat.data(), polygons.size(),
+                                 nullptr, 0, &w, &h, origin, nullptr, nullptr),
+          "cvhip_mesh_depth_image");
+    DepthImage out;
+    out.map = Grid<double>(w, h, 0.0);
+    check(cvhip_mesh_depth_image(dev.handle(), s.points.data(), s.tracks.data(), s.tracks_len(), s.cameras_len(), s.projection.data(),
+                                 s.r.data(), s.t.data(), s.image_dims.data(), project_to_image, scale, flat.data(), polygons.size(),
+                                 out.map.data(), w * h, &w, &h, origin, minmax, nullptr),
+          "cvhip_mesh_depth_image");
+    out.min_x = origin[0], out.min_y = origin[1], out.min_depth = minmax[0], out.max_depth = minmax[1];
+    return out;
+}
+
+} // namespace mesh
 
 } // namespace cvhip_host

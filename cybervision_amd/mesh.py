@@ -1,0 +1,155 @@
+"""The mesh stage of output::output (src/output.rs:567-611) over the C ABI: the Delaunay input of a
+camera, the occlusion culling of its polygons against the other cameras' depth buffers, the polygon list of Mesh::create
+and ImageWriter's depth map.  The Delaunay construction itself is the caller's (`triangulate`); `delaunay_scipy` is one.
+No compute in Python - array bookkeeping and the calls only.
+
+Defined where the reference's result depends on its thread order: a depth-buffer cell is the minimum of its depths (a
+depth-image cell the maximum), and a triple that two cameras produce stays with the lowest camera.
+"""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+
+from . import _lib
+
+GRID_LANES = 262144                # CVHIP_MESH_GRID_LANES: lanes of one grid-stride launch
+WIDE_THRESHOLD_DEFAULT = 2048      # CVHIP_MESH_WIDE_THRESHOLD_DEFAULT
+WIDE_ALL, WIDE_NONE = 0, 0xFFFFFFFF
+STATS = ("width", "height", "occupied", "dropped", "wide")
+
+
+def _p(a):
+    return C.c_void_p(a.ctypes.data) if a is not None and a.size else None
+
+
+def _surface_args(surface, image_shapes):
+    """(points, tracks, n, m, projection, r, t, image_dims) as every cvhip_mesh_* entry takes them, and the arrays kept
+    alive."""
+    pts = np.ascontiguousarray(surface.points, dtype=np.float64).reshape(-1, 3)
+    tracks = np.ascontiguousarray(surface.tracks, dtype=np.int32)
+    m = len(surface.cameras)
+    P = np.ascontiguousarray(np.stack([np.asarray(c.projection, dtype=np.float64).reshape(12) for c in surface.cameras])) \
+        if m else np.zeros((0, 12))
+    r = np.ascontiguousarray(np.stack([np.asarray(c.r, dtype=np.float64).reshape(3) for c in surface.cameras])) if m else np.zeros((0, 3))
+    t = np.ascontiguousarray(np.stack([np.asarray(c.t, dtype=np.float64).reshape(3) for c in surface.cameras])) if m else np.zeros((0, 3))
+    dims = np.ascontiguousarray(np.asarray(image_shapes, dtype=np.uint32).reshape(-1, 2))
+    if len(dims) != m:
+        raise ValueError("one (width, height) per camera")
+    keep = (pts, tracks, P, r, t, dims)
+    one = np.zeros(1)  # (the arrays of m = 0 still need an address: the library reports the error)
+    args = [_p(pts), _p(tracks), len(pts), m] + [C.c_void_p((a if a.size else one).ctypes.data) for a in (P, r, t)] + \
+           [C.c_void_p((dims if dims.size else one.view(np.uint32)).ctypes.data)]
+    return args, keep
+
+
+def set_wide_threshold(device, pixels: int):
+    """cvhip_mesh_set_wide_threshold: polygons whose bounding box in the buffer holds `pixels` or more take the wave path
+    (WIDE_ALL = 0: all, WIDE_NONE: none)."""
+    _lib.check(_lib.lib().cvhip_mesh_set_wide_threshold(device.handle, int(pixels)), "cvhip_mesh_set_wide_threshold")
+
+
+def camera_points(device, surface, image_shapes, camera_i: int):
+    """The Delaunay input of camera_i (process_camera, :401-423) in track order -> (track index [k] uint32, xy [k, 2])."""
+    args, _keep = _surface_args(surface, image_shapes)
+    n = C.c_uint64(0)
+    L = _lib.lib()
+    _lib.check(L.cvhip_mesh_camera_points(device.handle, *args, int(camera_i), None, None, 0, C.byref(n)), "cvhip_mesh_camera_points")
+    k = n.value
+    index, xy = np.zeros(k, dtype=np.uint32), np.zeros((k, 2))
+    if k:
+        _lib.check(L.cvhip_mesh_camera_points(device.handle, *args, int(camera_i), _p(index), _p(xy), k, C.byref(n)),
+                   "cvhip_mesh_camera_points")
+    return index, xy
+
+
+def depth_buffer(device, surface, image_shapes, camera_j: int):
+    """DepthBuffer::new (:262-318) of camera_j -> [height, width] f64, NaN = None ((0, 0) without points)."""
+    args, _keep = _surface_args(surface, image_shapes)
+    w, h = C.c_uint64(0), C.c_uint64(0)
+    L = _lib.lib()
+    _lib.check(L.cvhip_mesh_depth_buffer(device.handle, *args, int(camera_j), None, 0, C.byref(w), C.byref(h)), "cvhip_mesh_depth_buffer")
+    buf = np.zeros((h.value, w.value))
+    if buf.size:
+        _lib.check(L.cvhip_mesh_depth_buffer(device.handle, *args, int(camera_j), _p(buf), buf.size, C.byref(w), C.byref(h)),
+                   "cvhip_mesh_depth_buffer")
+    return buf
+
+
+def cull(device, surface, image_shapes, camera_i: int, polygons):
+    """The culling of camera_i's polygons ([k, 3] track indices) against every other camera (:457-508)
+    -> (keep [k] bool, stats: per camera a dict of STATS; camera_i's is all zero)."""
+    args, _keep = _surface_args(surface, image_shapes)
+    poly = np.ascontiguousarray(polygons, dtype=np.uint32).reshape(-1, 3)
+    keep = np.zeros(len(poly), dtype=np.uint8)
+    m = args[3]
+    stats = np.zeros((max(m, 1), 5), dtype=np.uint64)
+    _lib.check(_lib.lib().cvhip_mesh_cull(device.handle, *args, int(camera_i), _p(poly), len(poly), _p(keep), _p(stats)),
+               "cvhip_mesh_cull")
+    return keep.astype(bool), [dict(zip(STATS, (int(v) for v in stats[j]))) for j in range(m)]
+
+
+def merge(device, polygons, camera):
+    """Mesh::create's list (:50-105, 384, 510-516) from the kept polygons of every camera ([k, 3]) and their cameras ([k])
+    -> (polygons [k', 3] uint32, camera [k'] uint32): rotated, de-duplicated (the lowest camera wins), grouped by camera."""
+    poly = np.ascontiguousarray(polygons, dtype=np.uint32).reshape(-1, 3)
+    cam = np.ascontiguousarray(camera, dtype=np.uint32).reshape(-1)
+    if len(cam) != len(poly):
+        raise ValueError("one camera per polygon")
+    out_p, out_c = np.zeros_like(poly), np.zeros_like(cam)
+    n = C.c_uint64(0)
+    _lib.check(_lib.lib().cvhip_mesh_merge(device.handle, _p(poly), _p(cam), len(poly), _p(out_p), _p(out_c), C.byref(n)),
+               "cvhip_mesh_merge")
+    return out_p[:n.value].copy(), out_c[:n.value].copy()
+
+
+def create(device, surface, image_shapes, triangulate):
+    """Mesh::create (:363-387) for a perspective surface: per camera the camera points, the caller's Delaunay
+    `triangulate(xy [k, 2]) -> [f, 3]` (indices into xy), the culling, and the merged list.
+    -> dict: polygons [p, 3] (track indices), camera [p], per_camera (points, polygons, kept, stats per camera)."""
+    kept_p, kept_c, per_camera = [], [], []
+    for i in range(len(surface.cameras)):
+        index, xy = camera_points(device, surface, image_shapes, i)
+        faces = np.asarray(triangulate(xy), dtype=np.int64).reshape(-1, 3)
+        poly = index[faces].astype(np.uint32) if len(faces) else np.zeros((0, 3), dtype=np.uint32)
+        keep, stats = cull(device, surface, image_shapes, i, poly)
+        kept_p.append(poly[keep])
+        kept_c.append(np.full(int(keep.sum()), i, dtype=np.uint32))
+        per_camera.append({"points": len(index), "polygons": len(poly), "kept": int(keep.sum()), "stats": stats})
+    polygons, camera = merge(device, np.concatenate(kept_p) if kept_p else np.zeros((0, 3), dtype=np.uint32),
+                             np.concatenate(kept_c) if kept_c else np.zeros(0, dtype=np.uint32))
+    return {"polygons": polygons, "camera": camera, "per_camera": per_camera}
+
+
+def depth_image(device, surface, image_shapes, project_to_image: int, scale: float, polygons):
+    """ImageWriter (:1016-1143) without the colour table and the encoder -> dict: map [height, width] f64 (NaN = None),
+    origin (min_x, min_y), min_depth, max_depth, wide (polygons that took the wave path).  Raises CvhipError
+    (CVHIP_ERR_NO_SURFACE, "No point projections found") when no projection is in range."""
+    args, _keep = _surface_args(surface, image_shapes)
+    poly = np.ascontiguousarray(polygons, dtype=np.uint32).reshape(-1, 3)
+    w, h, wide = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+    origin, minmax = np.zeros(2), np.zeros(2)
+    L = _lib.lib()
+    _lib.check(L.cvhip_mesh_depth_image(device.handle, *args, int(project_to_image), float(scale), _p(poly), len(poly), None, 0,
+                                        C.byref(w), C.byref(h), _p(origin), None, None), "cvhip_mesh_depth_image")
+    out = np.zeros((h.value, w.value))
+    _lib.check(L.cvhip_mesh_depth_image(device.handle, *args, int(project_to_image), float(scale), _p(poly), len(poly), _p(out),
+                                        out.size, C.byref(w), C.byref(h), _p(origin), _p(minmax), C.byref(wide)),
+               "cvhip_mesh_depth_image")
+    return {"map": out, "origin": (float(origin[0]), float(origin[1])), "min_depth": float(minmax[0]),
+            "max_depth": float(minmax[1]), "wide": int(wide.value)}
+
+
+def delaunay_scipy(xy):
+    """A `triangulate` for `create`: scipy.spatial.Delaunay's simplices of the points ([k, 2] -> [f, 3]).  scipy is
+    optional: without it this raises (the package itself does not need it)."""
+    try:
+        from scipy.spatial import Delaunay
+    except ImportError as exc:
+        raise RuntimeError("delaunay_scipy needs scipy (scipy.spatial.Delaunay); pass another `triangulate` to "
+                           "mesh.create, or install scipy") from exc
+    xy = np.asarray(xy, dtype=np.float64).reshape(-1, 2)
+    if len(xy) < 3:
+        return np.zeros((0, 3), dtype=np.int64)
+    return np.asarray(Delaunay(xy).simplices, dtype=np.int64)

@@ -376,3 +376,32 @@ def reconstruct_perspective(device, pyramids, K, bundle_adjustment: bool = True,
     if merge_tracks:
         out["merges"] = merges
     return out
+
+
+def reconstruct_perspective_mesh(device, pyramids, K, triangulate=None, project_to_image=None, depth_scale: float = -1.0,
+                                 **kwargs):
+    """reconstruct_perspective, then the mesh stage of output::output (output.rs:567-611; DESIGN.md 4.11) on its surface:
+    mesh.create - per camera the Delaunay input, `triangulate(xy) -> [f, 3]` (the caller's Delaunay; default
+    mesh.delaunay_scipy), the occlusion culling and the merged polygon list - and, when project_to_image is not None,
+    ImageWriter's depth map of that camera (depth_scale = out_scale.2.signum()).  kwargs go to reconstruct_perspective.
+    -> its dict with mesh (mesh.create's dict), depth_image (mesh.depth_image's dict or None) and timings_ms mesh /
+    depth_image added."""
+    import time
+
+    from . import mesh
+
+    out = reconstruct_perspective(device, pyramids, K, **kwargs)
+    shapes = [(int(p[0].shape[1]), int(p[0].shape[0])) for p in pyramids]
+    # (the surface's cameras are the placed images, in image order: prune_projections keeps the order)
+    placed = [i for i in range(len(pyramids)) if out["projections"][i] is not None]
+    shapes = [shapes[i] for i in placed]
+    t0 = time.perf_counter()
+    out["mesh"] = mesh.create(device, out["surface"], shapes, triangulate or mesh.delaunay_scipy)
+    t1 = time.perf_counter()
+    out["depth_image"] = None
+    if project_to_image is not None:
+        out["depth_image"] = mesh.depth_image(device, out["surface"], shapes, project_to_image, depth_scale, out["mesh"]["polygons"])
+    out["mesh_image_shapes"] = shapes
+    out["timings_ms"]["mesh"] = (t1 - t0) * 1e3
+    out["timings_ms"]["depth_image"] = (time.perf_counter() - t1) * 1e3
+    return out

@@ -303,6 +303,89 @@ int cvhip_recover_pose_models(cvhip_device *dev, const int32_t *tracks, uint64_t
                               uint32_t image_index, const double *K, uint32_t max_dimension, const uint32_t *sample_idx,
                               uint32_t B, double *out_pose, int8_t *out_status, uint32_t *out_count, double *out_error);
 
+/* ------------------------------------------------------------------------------------------
+ * Mesh stage (output::output, src/output.rs:567-611; csrc/mesh_kernels.hip).  All f64 on the device, each
+ * operation one IEEE operation in the reference's order.
+ * The SURFACE is passed the same way to every entry: points (n x 3 f64), tracks (n x m x 2 int32, (-1, -1) = no point) -
+ * host or device pointers - and per camera projection (m x 12 row-major), r (m x 3, the Camera's axis-angle), t (m x 3) and
+ * image_dims (m x 2 uint32, width then height) in host memory: what triangulation's Surface holds.  m <=
+ * CVHIP_TRIANGULATE_MAX_CAMERAS (CVHIP_ERR_UNSUPPORTED above; m = 0, an affine surface, is CVHIP_ERR_INVALID: the reference
+ * skips culling for it).  Polygons (n_poly x 3 uint32 track indices) and the outputs named so are host or device
+ * pointers; counts and statistics are host memory.  CVHIP_ERR_UNSUPPORTED with 2^32 - 1 or more tracks, polygons or cells.
+ * A track projects to P (X, Y, Z, 1) divided by its third component unless that is below f64::EPSILON in magnitude
+ * (Surface::project_point, triangulation.rs:63-74); it is IN RANGE when the projection lies in [c - 4 size, c + 4 size) on
+ * both axes, c = size / 2 (img_range, output.rs:613-624); its depth is Camera::point_depth (triangulation.rs:492-495).
+ * Not here: the Delaunay construction (the caller supplies the triangles), the OBJ and PLY writers, the colour table and
+ * the PNG encoder.
+ * Two of the reference's results depend on its thread order, and are DEFINED here:
+ *  - DepthBuffer::new folds a cell's points in par_bridge's order, keeping a new depth iff cur - new > f64::EPSILON; here
+ *    the cell is the MINIMUM of its depths (one of the reference's outcomes unless two depths of a cell differ by a
+ *    non-zero amount <= EPSILON).  The depth image's cells are the MAXIMUM likewise.
+ *  - process_camera sorts with sort_unstable and de-duplicates by vertices alone, so the camera of a triple that two
+ *    cameras produce is not determined; here the LOWEST camera keeps it. */
+
+/* lanes of one grid-stride launch of the mesh kernels (1024 blocks of 256): more polygons or tracks than this take more
+ * than one trip of the loops */
+#define CVHIP_MESH_GRID_LANES 262144
+/* cvhip_mesh_set_wide_threshold's default (DESIGN.md 4.11 has the sweep behind it) */
+#define CVHIP_MESH_WIDE_THRESHOLD_DEFAULT 2048
+
+/* A polygon whose bounding box inside the buffer (rows x columns of the scanline walk's bounds) holds `pixels` or more is
+ * not walked by its lane but queued for a wave, whose lanes take consecutive x of a row.  0 sends every polygon through
+ * the wave path, UINT32_MAX none.  Both paths give the same flags and maps. */
+int cvhip_mesh_set_wide_threshold(cvhip_device *dev, uint32_t pixels);
+
+/* The Delaunay input of camera_i (Mesh::process_camera, output.rs:401-423): the tracks with a point in camera_i whose
+ * projection is in range, in TRACK ORDER (the reference collects them in par_bridge's order).  out_index (uint32 track
+ * index) and out_xy (2 f64) get the first `cap` of them, *out_n their number: cap = 0 sizes the buffers. */
+int cvhip_mesh_camera_points(cvhip_device *dev, const double *points, const int32_t *tracks, uint64_t n, uint32_t m,
+                             const double *projection, const double *r, const double *t, const uint32_t *image_dims,
+                             uint32_t camera_i, uint32_t *out_index, double *out_xy, uint64_t cap, uint64_t *out_n);
+
+/* DepthBuffer::new for camera_j (output.rs:262-318): over the tracks with a point in camera_j and a projection in range,
+ * the grid is (ceil(max x) + 1) x (ceil(max y) + 1) (0 x 0 without such a track); a track goes to cell (round(x) as usize,
+ * round(y) as usize) - half away from zero, saturating, so negative coordinates land in column or row 0 -; the cell is the
+ * minimum of its depths.  out_buffer (width x height f64, NaN = None) is written when cap_cells >= width x height;
+ * cap_cells = 0 sizes it.  (cvhip_mesh_cull builds the same buffers itself; this entry shows them.) */
+int cvhip_mesh_depth_buffer(cvhip_device *dev, const double *points, const int32_t *tracks, uint64_t n, uint32_t m,
+                            const double *projection, const double *r, const double *t, const uint32_t *image_dims,
+                            uint32_t camera_j, double *out_buffer, uint64_t cap_cells, uint64_t *out_width,
+                            uint64_t *out_height);
+
+/* The culling of camera_i's polygons (Mesh::process_camera, output.rs:457-508): out_keep[p] = 0 iff polygon p obstructs in
+ * some camera j != camera_i (polygon_obstructs, :320-353): its three vertices are projected into j with their depths,
+ * stably sorted by y (total_cmp) and walked by ProjectedPolygon's scanline iterator (:107-254, restated with its quirks:
+ * DESIGN.md 4.11) with max_x, max_y = the buffer's width and height; it obstructs iff some emitted pixel's cell is
+ * occupied and cell - depth > f64::EPSILON.  out_stats (m x 5 uint64, may be NULL; row camera_i is zero): the buffer's
+ * width, height and occupied cells, the polygons that obstruct in that camera, and the polygons sent to the wave path.
+ * A vertex >= n: CVHIP_ERR_INVALID with nothing written. */
+int cvhip_mesh_cull(cvhip_device *dev, const double *points, const int32_t *tracks, uint64_t n, uint32_t m,
+                    const double *projection, const double *r, const double *t, const uint32_t *image_dims,
+                    uint32_t camera_i, const uint32_t *polygons, uint64_t n_poly, uint8_t *out_keep, uint64_t *out_stats);
+
+/* The polygon list of Mesh::create (output.rs:50-105, 384, 510-516) from the cameras' kept polygons, concatenated, with
+ * the camera of each: Polygon::new's rotation (the smallest vertex first, orientation kept), sorted by vertices and
+ * de-duplicated by vertices alone - the lowest camera keeps a shared triple -, then grouped by camera (stable).  Host C++
+ * inside the library (not a hot path).  out_polygons (n_poly x 3), out_camera (n_poly): room for n_poly; *out_n written. */
+int cvhip_mesh_merge(cvhip_device *dev, const uint32_t *polygons, const uint32_t *camera, uint64_t n_poly,
+                     uint32_t *out_polygons, uint32_t *out_camera, uint64_t *out_n);
+
+/* ImageWriter (output.rs:1016-1143) without the colour table and the encoder: every track is projected to
+ * project_to_image (visibility is not required; out of range = None); with min / max x / y over the rest, width =
+ * (ceil(max_x) - floor(min_x)) as usize + 1, height likewise; each vertex is placed at (x - min_x, y - min_y, depth *
+ * scale) (scale = +-1: out_scale.2.signum()) and splatted at its rounded position clamped into the map; each polygon
+ * whose three vertices are Some is rasterised by the scanline iterator with max_x, max_y = width - 1, height - 1 (so the
+ * last row and column never receive face pixels); a cell keeps the MAXIMUM.  out_map (width x height f64, NaN = None) is
+ * written when cap_cells >= width x height; cap_cells = 0 sizes it (width, height and origin are returned either way).
+ * out_origin[2] = (min_x, min_y), out_minmax[2] = the map's smallest and largest depth, *out_wide = polygons sent to the
+ * wave path (each may be NULL).  Errors: CVHIP_ERR_NO_SURFACE "No point projections found" (:1046) when no projection is
+ * in range; CVHIP_ERR_INVALID for a vertex >= n (nothing written). */
+int cvhip_mesh_depth_image(cvhip_device *dev, const double *points, const int32_t *tracks, uint64_t n, uint32_t m,
+                           const double *projection, const double *r, const double *t, const uint32_t *image_dims,
+                           uint32_t project_to_image, double scale, const uint32_t *polygons, uint64_t n_poly,
+                           double *out_map, uint64_t cap_cells, uint64_t *out_width, uint64_t *out_height,
+                           double *out_origin, double *out_minmax, uint64_t *out_wide);
+
 /* Row sharding (multi-GPU): restrict the SEARCH passes of this context to shard `num` of `den`
  * equal row chunks of the searched level image: rows [num*rps, min((num+1)*rps, h_level)) with
  * rps = ceil(h_level / den).  Rows outside the band keep whatever the level grid holds until
