@@ -123,6 +123,10 @@ SIGNATURES = {
     "cvhip_mesh_depth_image": (C.c_int, [_vp, _vp, _vp, C.c_uint64, _u32, _vp, _vp, _vp, _vp, _u32, C.c_double, _vp,
                                          C.c_uint64, _vp, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), _vp, _vp,
                                          C.POINTER(C.c_uint64)]),
+    # the mesh output: (points, tracks, n, m, images, image_offsets, image_dims, vertex_mode, out_scale, polygons, n_poly, ...)
+    "cvhip_mesh_ply": (C.c_int, [_vp, _vp, _vp, C.c_uint64, _u32, _vp, _vp, _vp, _u32, _vp, _vp, C.c_uint64, _vp, C.c_uint64,
+                                 C.POINTER(C.c_uint64), _vp]),
+    "cvhip_mesh_colour_map": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint64, C.c_double, C.c_double, _vp, _vp]),
 }
 
 

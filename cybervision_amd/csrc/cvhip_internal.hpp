@@ -145,6 +145,43 @@ void launch_extend_tracks_new(const uint32_t *cells, uint32_t lw, uint32_t lh, u
                               const uint8_t *removed, uint32_t *block_counts, uint32_t *total, uint32_t *out_new_p1,
                               uint32_t *out_new_p2, unsigned long long cap, hipStream_t s);
 
+// ---- shared by the mesh entry points (mesh_kernels.hip, mesh_output_kernels.hip) ---------------
+bool mesh_on_device(const void *p); // device or managed memory (anything else is taken as host memory)
+// mesh_check_polygons_kernel: *bad |= 1 when a polygon names a track >= n (the callers run nothing else then)
+void launch_mesh_check_polygons(const uint32_t *polygons, unsigned long long n_poly, unsigned long long n, uint32_t *bad, hipStream_t s);
+// per-call device scratch, freed together (error paths included)
+struct MeshScratch {
+    std::vector<void *> owned;
+    MeshScratch() = default;
+    MeshScratch(const MeshScratch &) = delete;
+    MeshScratch &operator=(const MeshScratch &) = delete;
+    ~MeshScratch()
+    {
+        for (void *p : owned) (void)hipFree(p);
+    }
+    template <typename T> hipError_t alloc(T **out, size_t count)
+    {
+        void *p = nullptr;
+        const hipError_t e = hipMalloc(&p, std::max<size_t>(count, 1) * sizeof(T));
+        if (e == hipSuccess) owned.push_back(p);
+        *out = static_cast<T *>(p);
+        return e;
+    }
+    // the caller's array on the device: itself, or a copy of the host array
+    template <typename T> hipError_t input(const T *src, size_t count, const T **out, hipStream_t s)
+    {
+        if (!count || mesh_on_device(src)) {
+            *out = src;
+            return hipSuccess;
+        }
+        T *d = nullptr;
+        hipError_t e = alloc(&d, count);
+        if (e == hipSuccess) e = hipMemcpyAsync(d, src, count * sizeof(T), hipMemcpyHostToDevice, s);
+        *out = d;
+        return e;
+    }
+};
+
 #ifdef __HIPCC__
 // the match stored for full-resolution cell (gx, gy), if any: level cell (gx >> k, gy >> k) when both are multiples
 // of 2^k (the scatter of mod.rs:311-316), scaled back by 2^k (mod.rs:459-462)

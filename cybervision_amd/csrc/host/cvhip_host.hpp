@@ -575,6 +575,60 @@ inline DepthImage depth_image(GpuDevice &dev, const Surface &s, uint32_t project
     return out;
 }
 
+// ---- the mesh output: PlyWriter's file image (:648-772) and ImageWriter::complete's colours (:1117-1229) ------
+enum class VertexMode : uint32_t { Plain = CVHIP_VERTEX_PLAIN, Color = CVHIP_VERTEX_COLOR, Texture = CVHIP_VERTEX_TEXTURE };
+
+struct RgbImage { // image::RgbImage: row-major, 3 bytes per pixel
+    uint32_t width = 0, height = 0;
+    std::vector<uint8_t> pixels;
+};
+
+struct PlySections {
+    uint64_t header = 0, vertices = 0, faces = 0;
+};
+
+// Mesh::output with a PlyWriter -> the file's bytes.  images: one per image of a track, read in Color mode only; the surface
+// may be affine (no cameras): `m` is then the number of images.
+inline std::vector<uint8_t> ply(GpuDevice &dev, const Surface &s, const std::vector<Polygon> &polygons, const std::vector<RgbImage> &images,
+                                VertexMode mode, const std::array<double, 3> &out_scale, PlySections *sections = nullptr)
+{
+    std::vector<uint32_t> flat;
+    for (const Polygon &p : polygons) flat.insert(flat.end(), p.vertices.begin(), p.vertices.end());
+    const uint64_t n = s.tracks_len();
+    const uint32_t m = n ? (uint32_t)(s.tracks.size() / (2 * n)) : (uint32_t)images.size();
+    std::vector<uint8_t> pixels;
+    std::vector<uint64_t> offsets{0};
+    std::vector<uint32_t> dims;
+    for (const RgbImage &im : images) {
+        pixels.insert(pixels.end(), im.pixels.begin(), im.pixels.end());
+        offsets.push_back(pixels.size());
+        dims.push_back(im.width), dims.push_back(im.height);
+    }
+    const bool with_images = mode == VertexMode::Color && images.size() == m && m > 0;
+    uint64_t size = 0, sec[3] = {0, 0, 0};
+    auto call = [&](uint8_t *out, uint64_t cap) {
+        check(cvhip_mesh_ply(dev.handle(), s.points.data(), s.tracks.data(), n, m, with_images ? pixels.data() : nullptr,
+                             with_images ? offsets.data() : nullptr, with_images ? dims.data() : nullptr, (uint32_t)mode, out_scale.data(),
+                             flat.data(), polygons.size(), out, cap, &size, sec),
+              "cvhip_mesh_ply");
+    };
+    call(nullptr, 0);
+    std::vector<uint8_t> out(size);
+    call(out.data(), size);
+    if (sections) *sections = PlySections{sec[0], sec[1], sec[2]};
+    return out;
+}
+
+// ImageWriter::complete: the depth map through `table` (256 x R, G, B) -> width x height x RGBA
+inline std::vector<uint8_t> colour_map(GpuDevice &dev, const DepthImage &img, const std::array<uint8_t, 768> &table)
+{
+    std::vector<uint8_t> rgba(img.map.width() * img.map.height() * 4);
+    check(cvhip_mesh_colour_map(dev.handle(), img.map.data(), img.map.width(), img.map.height(), img.min_depth, img.max_depth, table.data(),
+                                rgba.data()),
+          "cvhip_mesh_colour_map");
+    return rgba;
+}
+
 } // namespace mesh
 
 } // namespace cvhip_host

@@ -3,8 +3,8 @@
 // polygon list's merge (:50-105, :384, :510-516) and ImageWriter's depth map (:1009-1143).  DESIGN.md 4.11.
 //
 // All f64, one IEEE operation per written operation in the written order (-ffp-contract=off).  The Delaunay construction
-// itself stays with the caller (spade's result on co-circular points cannot be pinned); so do the OBJ / PLY writers, the
-// colour table and the PNG encoder.
+// itself stays with the caller (spade's result on co-circular points cannot be pinned); the PLY writer and the colour
+// mapping are mesh_output_kernels.hip; the OBJ writer, the colour table and the PNG encoder stay out.
 //
 // Two results of the reference depend on its thread order; here they are defined:
 //   - DepthBuffer::new keeps a new depth iff the cell is empty or cur - new > f64::EPSILON, folding the points in
@@ -456,7 +456,9 @@ __global__ __launch_bounds__(BLOCK) void mesh_check_polygons_kernel(const uint32
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------------------------
-bool on_device(const void *p)
+} // namespace
+
+bool mesh_on_device(const void *p)
 {
     hipPointerAttribute_t attr;
     if (hipPointerGetAttributes(&attr, p) != hipSuccess) {
@@ -466,37 +468,17 @@ bool on_device(const void *p)
     return attr.type == hipMemoryTypeDevice || attr.type == hipMemoryTypeManaged;
 }
 
+void launch_mesh_check_polygons(const uint32_t *polygons, unsigned long long n_poly, unsigned long long n, uint32_t *bad, hipStream_t s)
+{
+    const uint32_t blocks = (uint32_t)std::min<unsigned long long>(MAX_GRID, std::max<unsigned long long>(1, (n_poly + BLOCK - 1) / BLOCK));
+    hipLaunchKernelGGL(mesh_check_polygons_kernel, dim3(blocks), dim3(BLOCK), 0, s, polygons, n_poly, n, bad);
+}
+
+namespace {
+
 uint32_t grid_for(unsigned long long n) { return (uint32_t)std::min<unsigned long long>(MAX_GRID, std::max<unsigned long long>(1, (n + BLOCK - 1) / BLOCK)); }
 
-// per-call device scratch, freed together (error paths included)
-struct Scratch {
-    std::vector<void *> owned;
-    ~Scratch()
-    {
-        for (void *p : owned) (void)hipFree(p);
-    }
-    template <typename T> hipError_t alloc(T **out, size_t count)
-    {
-        void *p = nullptr;
-        const hipError_t e = hipMalloc(&p, std::max<size_t>(count, 1) * sizeof(T));
-        if (e == hipSuccess) owned.push_back(p);
-        *out = static_cast<T *>(p);
-        return e;
-    }
-    // the caller's array on the device: itself, or a copy of the host array
-    template <typename T> hipError_t input(const T *src, size_t count, const T **out, hipStream_t s)
-    {
-        if (!count || on_device(src)) {
-            *out = src;
-            return hipSuccess;
-        }
-        T *d = nullptr;
-        hipError_t e = alloc(&d, count);
-        if (e == hipSuccess) e = hipMemcpyAsync(d, src, count * sizeof(T), hipMemcpyHostToDevice, s);
-        *out = d;
-        return e;
-    }
-};
+using Scratch = MeshScratch;
 
 // the surface as every entry point takes it, checked and staged on the device
 struct SurfaceArgs {
@@ -599,7 +581,7 @@ hipError_t decode(Scratch &sc, const DeviceSurface &d, const unsigned long long 
                   double *out, Extent *h_stats, hipStream_t s)
 {
     double *d_out = out;
-    const bool copy = out && !on_device(out);
+    const bool copy = out && !mesh_on_device(out);
     hipError_t e = hipSuccess;
     if (copy) e = sc.alloc(&d_out, (size_t)cells);
     if (e != hipSuccess) return e;
@@ -649,7 +631,7 @@ extern "C" int cvhip_mesh_camera_points(cvhip_device *dev, const double *points,
     const uint32_t blocks = (uint32_t)((n + BLOCK - 1) / BLOCK);
     uint32_t *counts = nullptr, *d_index = out_index;
     double *d_xy = out_xy;
-    const bool idx_copy = !on_device(out_index), xy_copy = !on_device(out_xy);
+    const bool idx_copy = !mesh_on_device(out_index), xy_copy = !mesh_on_device(out_xy);
     e = sc.alloc(&counts, (size_t)blocks + 1);
     if (e == hipSuccess && idx_copy) e = sc.alloc(&d_index, (size_t)k);
     if (e == hipSuccess && xy_copy) e = sc.alloc(&d_xy, (size_t)k * 2);
@@ -712,7 +694,7 @@ extern "C" int cvhip_mesh_cull(cvhip_device *dev, const double *points, const in
     const uint32_t *d_poly = nullptr;
     uint32_t *queue = nullptr, *counters = nullptr; // counters: per camera {obstructing, queued}, then the bad-vertex flag
     uint8_t *d_keep = out_keep;
-    const bool keep_copy = n_poly && !on_device(out_keep);
+    const bool keep_copy = n_poly && !mesh_on_device(out_keep);
     const uint32_t pblocks = grid_for(n_poly), threshold = dev->d.mesh_wide_threshold;
     uint32_t h_counters[2 * CVHIP_TRIANGULATE_MAX_CAMERAS + 1] = {};
     uint64_t stats[CVHIP_TRIANGULATE_MAX_CAMERAS][5] = {};

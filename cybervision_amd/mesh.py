@@ -1,6 +1,8 @@
 """The mesh stage of output::output (src/output.rs:567-611) over the C ABI: the Delaunay input of a
 camera, the occlusion culling of its polygons against the other cameras' depth buffers, the polygon list of Mesh::create
 and ImageWriter's depth map.  The Delaunay construction itself is the caller's (`triangulate`); `delaunay_scipy` is one.
+The mesh output: `ply` / `write_ply` - PlyWriter's binary file image - and `colour_map` /
+`depth_image_rgba` - ImageWriter::complete's colours; the colour table is the caller's.
 No compute in Python - array bookkeeping and the calls only.
 
 Defined where the reference's result depends on its thread order: a depth-buffer cell is the minimum of its depths (a
@@ -9,6 +11,7 @@ depth-image cell the maximum), and a triple that two cameras produce stays with 
 from __future__ import annotations
 
 import ctypes as C
+import enum
 
 import numpy as np
 
@@ -18,6 +21,13 @@ GRID_LANES = 262144                # CVHIP_MESH_GRID_LANES: lanes of one grid-st
 WIDE_THRESHOLD_DEFAULT = 2048      # CVHIP_MESH_WIDE_THRESHOLD_DEFAULT
 WIDE_ALL, WIDE_NONE = 0, 0xFFFFFFFF
 STATS = ("width", "height", "occupied", "dropped", "wide")
+
+
+class VertexMode(enum.IntEnum):
+    """VertexMode (output.rs) as cvhip_mesh_ply takes it (CVHIP_VERTEX_*).  Texture writes what Plain writes."""
+    Plain = 0
+    Color = 1
+    Texture = 2
 
 
 def _p(a):
@@ -139,6 +149,101 @@ def depth_image(device, surface, image_shapes, project_to_image: int, scale: flo
                "cvhip_mesh_depth_image")
     return {"map": out, "origin": (float(origin[0]), float(origin[1])), "min_depth": float(minmax[0]),
             "max_depth": float(minmax[1]), "wide": int(wide.value)}
+
+
+def _image_args(images):
+    """(images, image_offsets, image_dims) of cvhip_mesh_ply from a list of [h, w, 3] uint8 arrays, and the arrays kept alive."""
+    imgs = [np.ascontiguousarray(im, dtype=np.uint8) for im in images]
+    if any(im.ndim != 3 or im.shape[2] != 3 for im in imgs):
+        raise ValueError("images are [height, width, 3] uint8")
+    flat = np.concatenate([im.reshape(-1) for im in imgs]) if imgs else np.zeros(0, dtype=np.uint8)
+    offsets = np.zeros(len(imgs) + 1, dtype=np.uint64)
+    offsets[1:] = np.cumsum([im.size for im in imgs], dtype=np.uint64)
+    dims = np.array([[im.shape[1], im.shape[0]] for im in imgs], dtype=np.uint32).reshape(-1, 2)
+    one = np.zeros(1, dtype=np.uint8)  # (an address for an empty array: the library reports what is wrong)
+    return [C.c_void_p((flat if flat.size else one).ctypes.data), _p(offsets), _p(dims)], (flat, offsets, dims, one)
+
+
+def ply(device, surface, polygons, images=None, vertex_mode=VertexMode.Plain, out_scale=(1.0, 1.0, 1.0), sections=None):
+    """The binary PLY file image of Mesh::output with a PlyWriter (output.rs:521-559, 648-772; cvhip_mesh_ply) -> uint8 array.
+    images: one [h, w, 3] uint8 array per image of a track (Color mode only; a vertex takes the pixel of its track's first
+    point, and no colour bytes when that point lies past its image).  `sections`, a list, receives the header's, the
+    vertices' and the faces' byte counts.  Raises CvhipError ("Track has no images") for a track without a point in Color
+    mode."""
+    pts = np.ascontiguousarray(surface.points, dtype=np.float64).reshape(-1, 3)
+    tracks = np.ascontiguousarray(surface.tracks, dtype=np.int32)
+    if tracks.ndim != 3:
+        tracks = tracks.reshape(len(pts), -1, 2)
+    poly = np.ascontiguousarray(polygons, dtype=np.uint32).reshape(-1, 3)
+    scale = np.array([float(v) for v in out_scale], dtype=np.float64)
+    if scale.shape != (3,):
+        raise ValueError("out_scale is (x, y, z)")
+    m = tracks.shape[1]
+    img_args, _keep = _image_args(images) if images is not None else ([None, None, None], None)
+    if images is not None and len(images) != m:
+        raise ValueError("one image per image of a track")
+    size, sec = C.c_uint64(0), np.zeros(3, dtype=np.uint64)
+    L = _lib.lib()
+    args = [device.handle, _p(pts), _p(tracks), len(pts), m, *img_args, int(vertex_mode), _p(scale), _p(poly), len(poly)]
+    _lib.check(L.cvhip_mesh_ply(*args, None, 0, C.byref(size), _p(sec)), "cvhip_mesh_ply")
+    out = np.zeros(size.value, dtype=np.uint8)
+    _lib.check(L.cvhip_mesh_ply(*args, _p(out), out.size, C.byref(size), _p(sec)), "cvhip_mesh_ply")
+    if sections is not None:
+        sections[:] = [int(v) for v in sec]
+    return out
+
+
+def write_ply(path, device, surface, polygons, images=None, vertex_mode=VertexMode.Plain, out_scale=(1.0, 1.0, 1.0)):
+    """`ply` written to `path` -> (header, vertex, face) byte counts."""
+    sections = []
+    ply(device, surface, polygons, images, vertex_mode, out_scale, sections=sections).tofile(path)
+    return tuple(sections)
+
+
+def _table(table):
+    t = np.ascontiguousarray(table, dtype=np.uint8)
+    if t.shape != (256, 3):
+        raise ValueError("the colour table is [256, 3] uint8: R, G, B per entry")
+    return t
+
+
+def colour_map(device, depth_map, min_depth: float, max_depth: float, table):
+    """ImageWriter::complete's colour mapping (output.rs:1117-1229; cvhip_mesh_colour_map) of a depth map ([h, w] f64, NaN =
+    None) -> [h, w, 4] uint8 RGBA.  table: [256, 3] uint8 (none is shipped)."""
+    depth = np.ascontiguousarray(depth_map, dtype=np.float64)
+    if depth.ndim != 2:
+        raise ValueError("the depth map is [height, width]")
+    t = _table(table)
+    h, w = depth.shape
+    out = np.zeros((h, w, 4), dtype=np.uint8)
+    _lib.check(_lib.lib().cvhip_mesh_colour_map(device.handle, _p(depth), w, h, float(min_depth), float(max_depth), _p(t), _p(out)),
+               "cvhip_mesh_colour_map")
+    return out
+
+
+def depth_image_rgba(device, surface, image_shapes, project_to_image: int, scale: float, polygons, table):
+    """ImageWriter with its colour mapping (:1016-1229): cvhip_mesh_depth_image into device memory, cvhip_mesh_colour_map on
+    it; only the RGBA crosses to the host -> dict: rgba [h, w, 4] uint8, origin, min_depth, max_depth."""
+    import torch
+
+    args, _keep = _surface_args(surface, image_shapes)
+    poly = np.ascontiguousarray(polygons, dtype=np.uint32).reshape(-1, 3)
+    t = _table(table)
+    w, h = C.c_uint64(0), C.c_uint64(0)
+    origin, minmax = np.zeros(2), np.zeros(2)
+    L = _lib.lib()
+    _lib.check(L.cvhip_mesh_depth_image(device.handle, *args, int(project_to_image), float(scale), _p(poly), len(poly), None, 0,
+                                        C.byref(w), C.byref(h), _p(origin), None, None), "cvhip_mesh_depth_image")
+    ordinal = getattr(device, "ordinal", -1)
+    d_map = torch.empty((h.value, w.value), dtype=torch.float64, device=torch.device("cuda", ordinal) if ordinal >= 0 else "cuda")
+    _lib.check(L.cvhip_mesh_depth_image(device.handle, *args, int(project_to_image), float(scale), _p(poly), len(poly),
+                                        C.c_void_p(d_map.data_ptr()), d_map.numel(), C.byref(w), C.byref(h), _p(origin), _p(minmax),
+                                        None), "cvhip_mesh_depth_image")
+    rgba = np.zeros((h.value, w.value, 4), dtype=np.uint8)
+    _lib.check(L.cvhip_mesh_colour_map(device.handle, C.c_void_p(d_map.data_ptr()), w.value, h.value, float(minmax[0]),
+                                       float(minmax[1]), _p(t), _p(rgba)), "cvhip_mesh_colour_map")
+    return {"rgba": rgba, "origin": (float(origin[0]), float(origin[1])), "min_depth": float(minmax[0]),
+            "max_depth": float(minmax[1])}
 
 
 def delaunay_scipy(xy):

@@ -379,13 +379,19 @@ def reconstruct_perspective(device, pyramids, K, bundle_adjustment: bool = True,
 
 
 def reconstruct_perspective_mesh(device, pyramids, K, triangulate=None, project_to_image=None, depth_scale: float = -1.0,
+                                 ply_path=None, images=None, vertex_mode=0, out_scale=(1.0, 1.0, 1.0), colour_table=None,
                                  **kwargs):
     """reconstruct_perspective, then the mesh stage of output::output (output.rs:567-611; DESIGN.md 4.11) on its surface:
     mesh.create - per camera the Delaunay input, `triangulate(xy) -> [f, 3]` (the caller's Delaunay; default
     mesh.delaunay_scipy), the occlusion culling and the merged polygon list - and, when project_to_image is not None,
     ImageWriter's depth map of that camera (depth_scale = out_scale.2.signum()).  kwargs go to reconstruct_perspective.
     -> its dict with mesh (mesh.create's dict), depth_image (mesh.depth_image's dict or None) and timings_ms mesh /
-    depth_image added."""
+    depth_image added.
+    The output files' contents, each only when asked for: ply_path - the binary PLY of the surface and the
+    merged list is written there (mesh.write_ply with images - one [h, w, 3] uint8 array per placed image, Color mode only -,
+    vertex_mode, a mesh.VertexMode, and out_scale), its section sizes are out["ply_sections"], its time timings_ms["ply"];
+    colour_table ([256, 3] uint8, with project_to_image) - out["depth_image"]["rgba"] is the depth map through
+    mesh.colour_map."""
     import time
 
     from . import mesh
@@ -401,7 +407,15 @@ def reconstruct_perspective_mesh(device, pyramids, K, triangulate=None, project_
     out["depth_image"] = None
     if project_to_image is not None:
         out["depth_image"] = mesh.depth_image(device, out["surface"], shapes, project_to_image, depth_scale, out["mesh"]["polygons"])
+        if colour_table is not None:
+            img = out["depth_image"]
+            img["rgba"] = mesh.colour_map(device, img["map"], img["min_depth"], img["max_depth"], colour_table)
     out["mesh_image_shapes"] = shapes
     out["timings_ms"]["mesh"] = (t1 - t0) * 1e3
     out["timings_ms"]["depth_image"] = (time.perf_counter() - t1) * 1e3
+    if ply_path is not None:
+        t2 = time.perf_counter()
+        out["ply_sections"] = mesh.write_ply(ply_path, device, out["surface"], out["mesh"]["polygons"], images,
+                                             mesh.VertexMode(int(vertex_mode)), out_scale)
+        out["timings_ms"]["ply"] = (time.perf_counter() - t2) * 1e3
     return out

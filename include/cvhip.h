@@ -315,8 +315,8 @@ int cvhip_recover_pose_models(cvhip_device *dev, const int32_t *tracks, uint64_t
  * A track projects to P (X, Y, Z, 1) divided by its third component unless that is below f64::EPSILON in magnitude
  * (Surface::project_point, triangulation.rs:63-74); it is IN RANGE when the projection lies in [c - 4 size, c + 4 size) on
  * both axes, c = size / 2 (img_range, output.rs:613-624); its depth is Camera::point_depth (triangulation.rs:492-495).
- * Not here: the Delaunay construction (the caller supplies the triangles), the OBJ and PLY writers, the colour table and
- * the PNG encoder.
+ * Not here: the Delaunay construction (the caller supplies the triangles), the OBJ writer, the colour table (an argument of
+ * cvhip_mesh_colour_map) and the PNG encoder.  The PLY writer and the colour mapping are the mesh OUTPUT entries below.
  * Two of the reference's results depend on its thread order, and are DEFINED here:
  *  - DepthBuffer::new folds a cell's points in par_bridge's order, keeping a new depth iff cur - new > f64::EPSILON; here
  *    the cell is the MINIMUM of its depths (one of the reference's outcomes unless two depths of a cell differ by a
@@ -385,6 +385,53 @@ int cvhip_mesh_depth_image(cvhip_device *dev, const double *points, const int32_
                            uint32_t project_to_image, double scale, const uint32_t *polygons, uint64_t n_poly,
                            double *out_map, uint64_t cap_cells, uint64_t *out_width, uint64_t *out_height,
                            double *out_origin, double *out_minmax, uint64_t *out_wide);
+
+/* ------------------------------------------------------------------------------------------
+ * Mesh output (csrc/mesh_output_kernels.hip): what output::output writes once the polygon list exists -
+ * PlyWriter's binary file image (output.rs:648-772) and ImageWriter::complete's colour mapping (:1117-1229) -, pinned
+ * byte for byte.  Neither touches the cameras: an affine surface works the same, and m is the number of images per track.
+ * Not here: the OBJ writer and its vt / UV tables (Rust's shortest-round-trip decimal text), the PNG encoder. */
+
+/* VertexMode (output.rs): what a PLY vertex record carries.  Texture writes what Plain writes. */
+#define CVHIP_VERTEX_PLAIN 0
+#define CVHIP_VERTEX_COLOR 1
+#define CVHIP_VERTEX_TEXTURE 2
+
+/* The binary PLY file image of Mesh::output with a PlyWriter (:521-559, :648-772): the header (:687-710; 198 + digits(n) +
+ * digits(n_poly) bytes, 60 more in Color mode, composed on the host), one record per track in track order, one per polygon
+ * in list order.
+ *  - vertex (:712-750): x * sx, (-y) * sy, z * sz (out_scale[3]; the negation first, then one multiply: y = 0 gives -0.0)
+ *    as 8 big-endian bytes each; NaN coordinates are written as their bytes.  In Color mode the pixel of the track's first
+ *    present point - the lowest image c with tracks[i][c].x >= 0 - follows as 3 bytes IF get_pixel_checked finds it: a point
+ *    with x >= width or y >= height of its image gets none, and its record is 24 bytes, not 27 (the reference's file).  A
+ *    track without any point is the reference's error "Track has no images" in Color mode only.
+ *  - face (:752-763): 0x03, then big-endian uint32 of vertices[2], vertices[1], vertices[0].
+ * points (n x 3 f64), tracks (n x m x 2 int32; read in Color mode only), polygons (n_poly x 3 uint32), images and out are host
+ * or device pointers; image_offsets, image_dims, out_scale and the counts are host memory.  images: the m RGB8 images
+ * concatenated, row-major, 3 bytes per pixel; image_offsets: m + 1 byte offsets into it; image_dims: m x 2, width then height
+ * (an image shorter than width x height x 3 bytes is CVHIP_ERR_INVALID).  They are read in Color mode only, where images =
+ * NULL is CVHIP_ERR_INVALID.  vertex_mode: CVHIP_VERTEX_*; any other value is CVHIP_ERR_INVALID.
+ * *out_size = the size of the file image, out_sections[3] (may be NULL) = the header's, the vertices' and the faces' bytes.
+ * cap = 0 sizes the image and writes nothing (in Color mode it runs the counting pass, and reports a track without points);
+ * 0 < cap < size is CVHIP_ERR_INVALID.  n = 0 and n_poly = 0 give the header alone.
+ * Errors, each with nothing written: CVHIP_ERR_INVALID "Track has no images" (Color mode: a track without a point, or m = 0
+ * with n > 0), CVHIP_ERR_INVALID for a vertex >= n, CVHIP_ERR_UNSUPPORTED for 2^32 - 1 or more tracks or polygons. */
+int cvhip_mesh_ply(cvhip_device *dev, const double *points, const int32_t *tracks, uint64_t n, uint32_t m,
+                   const uint8_t *images, const uint64_t *image_offsets, const uint32_t *image_dims,
+                   uint32_t vertex_mode, const double *out_scale,
+                   const uint32_t *polygons, uint64_t n_poly,
+                   uint8_t *out, uint64_t cap, uint64_t *out_size, uint64_t *out_sections);
+
+/* ImageWriter::complete's colour mapping (:1117-1143, map_depth / map_color :1146-1229) of a depth map as
+ * cvhip_mesh_depth_image writes it (width x height f64, NaN = None) with its min_depth / max_depth: a None cell gives
+ * (0, 0, 0, 0); otherwise value = (depth - min) / (max - min) and per channel table[255] if value >= 1, else with step =
+ * 1 / 255: box = clamp(floor(value / step) as usize, 0, 254), ratio = (value - step * box) / step, round(c2 * ratio + c1 *
+ * (1 - ratio)) as u8 (c1, c2 = table[box], table[box + 1]; half away from zero; the casts saturate, NaN -> 0), alpha 255.
+ * All f64, one IEEE operation per written operation.  A constant map (max = min) gives (0, 0, 0, 255) in every Some cell.
+ * table (host memory): 256 x 3 bytes, R, G, B per entry - the library ships none.  map and out_rgba (width x height x 4
+ * bytes, 4-byte aligned) are host or device pointers; CVHIP_ERR_UNSUPPORTED with 2^32 - 1 or more cells. */
+int cvhip_mesh_colour_map(cvhip_device *dev, const double *map, uint64_t width, uint64_t height,
+                          double min_depth, double max_depth, const uint8_t *table, uint8_t *out_rgba);
 
 /* Row sharding (multi-GPU): restrict the SEARCH passes of this context to shard `num` of `den`
  * equal row chunks of the searched level image: rows [num*rps, min((num+1)*rps, h_level)) with
