@@ -127,6 +127,9 @@ SIGNATURES = {
     "cvhip_mesh_ply": (C.c_int, [_vp, _vp, _vp, C.c_uint64, _u32, _vp, _vp, _vp, _u32, _vp, _vp, C.c_uint64, _vp, C.c_uint64,
                                  C.POINTER(C.c_uint64), _vp]),
     "cvhip_mesh_colour_map": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint64, C.c_double, C.c_double, _vp, _vp]),
+    # the Delaunay triangulation of a camera's points: (xy, k, out_faces, cap_faces, out_n_faces, out_stats)
+    "cvhip_mesh_delaunay": (C.c_int, [_vp, _vp, C.c_uint64, _vp, C.c_uint64, C.POINTER(C.c_uint64), _vp]),
+    "cvhip_mesh_delaunay_set_lane_cells": (C.c_int, [_vp, _u32]),
 }
 
 

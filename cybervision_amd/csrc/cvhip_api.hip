@@ -1832,3 +1832,20 @@ int cvhip_ctx_set_search_version(cvhip_ctx *ctx, int version)
 }
 
 } // extern "C"
+
+// ---- the Delaunay triangulation of a camera's points (delaunay_kernels.hip) ----------------------------------
+extern "C" int cvhip_mesh_delaunay(cvhip_device *dev, const double *xy, uint64_t k, uint32_t *out_faces, uint64_t cap_faces,
+                                   uint64_t *out_n_faces, uint64_t *out_stats)
+{
+    if (!dev || !out_n_faces || (k && !xy) || (cap_faces && !out_faces)) return fail(CVHIP_ERR_INVALID, "mesh_delaunay: null argument");
+    if (k >= 0x80000000ull) return fail(CVHIP_ERR_UNSUPPORTED, "mesh_delaunay: 2^31 or more points");
+    CVHIP_TRY_HIP(hipSetDevice(dev->d.ordinal));
+    return mesh_delaunay_run(dev->d, xy, k, out_faces, cap_faces, out_n_faces, out_stats);
+}
+
+extern "C" int cvhip_mesh_delaunay_set_lane_cells(cvhip_device *dev, uint32_t cells)
+{
+    if (!dev) return fail(CVHIP_ERR_INVALID, "cvhip_mesh_delaunay_set_lane_cells: null device");
+    dev->d.mesh_delaunay_lane_cells = cells;
+    return CVHIP_OK;
+}

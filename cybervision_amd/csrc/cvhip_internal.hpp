@@ -258,6 +258,7 @@ struct Device {
     int ransac_lm_pipeline = 2;  // cvhip_ransac_set_lm_pipeline (test hook): validate_f's LM as 2 = two passes on refilled lanes (default), 1 = two passes, a root per thread, 0 = the scalar loop in one kernel
     int ransac_pencil = CVHIP_PENCIL_THIN_SVD; // cvhip_ransac_set_pencil: the 7-point pencil's basis (default: the reference's)
     uint32_t mesh_wide_threshold = CVHIP_MESH_WIDE_THRESHOLD_DEFAULT; // cvhip_mesh_set_wide_threshold
+    uint32_t mesh_delaunay_lane_cells = CVHIP_MESH_DELAUNAY_LANE_CELLS_DEFAULT; // cvhip_mesh_delaunay_set_lane_cells
     // complete() into HOST memory (GpuContext::complete_process, gpu/mod.rs:210-216): two device staging sets that the
     // full-resolution grid is expanded into, and a copy stream of its own, so that the 12 B/px transfer of one pair can
     // run under the search of the next (cvhip_ctx_set_async_readback) and no call allocates.  Grow-only, per handle.
@@ -430,6 +431,9 @@ struct cvhip_device {
 };
 
 namespace cvhip {
+// cvhip_mesh_delaunay behind its argument checks (delaunay_kernels.hip)
+int mesh_delaunay_run(Device &d, const double *xy, uint64_t k, uint32_t *out_faces, uint64_t cap_faces, uint64_t *out_n_faces,
+                      uint64_t *out_stats);
 void device_free(cvhip_device *dev); // cvhip_api.hip: what cvhip_device_destroy does once nothing references the handle
 }
 

@@ -511,6 +511,30 @@ inline CameraPoints camera_points(GpuDevice &dev, const Surface &s, uint32_t cam
     return out;
 }
 
+struct DelaunayStats { // CVHIP_DELAUNAY_STAT_*
+    uint64_t grid_width = 0, grid_height = 0, device_stars = 0, host_stars = 0, duplicates = 0, most_cells = 0;
+};
+
+// DelaunayTriangulation::bulk_load of a camera's points (:425) on the device -> the faces, 3 indices into the
+// points each, counter-clockwise, the smallest first (cvhip.h has the definition); a `triangulate` for Mesh::create:
+//   Mesh::create(dev, s, [&](const CameraPoints &cp) { return mesh::delaunay(dev, cp); })
+inline std::vector<uint32_t> delaunay(GpuDevice &dev, const std::vector<double> &xy, DelaunayStats *stats = nullptr)
+{
+    const uint64_t k = xy.size() / 2;
+    std::vector<uint32_t> faces(6 * k); // (2 k faces are always enough)
+    uint64_t n = 0, st[CVHIP_DELAUNAY_STATS] = {0};
+    check(cvhip_mesh_delaunay(dev.handle(), xy.data(), k, faces.data(), 2 * k, &n, st), "cvhip_mesh_delaunay");
+    faces.resize(3 * n);
+    if (stats) *stats = DelaunayStats{st[0], st[1], st[2], st[3], st[4], st[5]};
+    return faces;
+}
+inline std::vector<uint32_t> delaunay(GpuDevice &dev, const CameraPoints &cp, DelaunayStats *stats = nullptr) { return delaunay(dev, cp.xy, stats); }
+
+inline void set_delaunay_lane_cells(GpuDevice &dev, uint32_t cells)
+{
+    check(cvhip_mesh_delaunay_set_lane_cells(dev.handle(), cells), "cvhip_mesh_delaunay_set_lane_cells");
+}
+
 // the culling loop of process_camera (:457-508): keep[p] = 0 iff polygon p obstructs in another camera
 inline std::vector<uint8_t> cull(GpuDevice &dev, const Surface &s, uint32_t camera_i, const std::vector<uint32_t> &polygons)
 {
@@ -526,6 +550,7 @@ class Mesh { // output.rs:356-387
     std::vector<Polygon> polygons;
 
     // Mesh::create: `triangulate(xy) -> faces` (3 indices into the camera's points each) is the caller's Delaunay
+    // (mesh::delaunay is one, on the device)
     template <typename Triangulate> static Mesh create(GpuDevice &dev, const Surface &s, Triangulate triangulate)
     {
         std::vector<uint32_t> kept, cams;

@@ -3,7 +3,7 @@
 // polygon list's merge (:50-105, :384, :510-516) and ImageWriter's depth map (:1009-1143).  DESIGN.md 4.11.
 //
 // All f64, one IEEE operation per written operation in the written order (-ffp-contract=off).  The Delaunay construction
-// itself stays with the caller (spade's result on co-circular points cannot be pinned); the PLY writer and the colour
+// is delaunay_kernels.hip (a caller may supply triangles of its own just as well); the PLY writer and the colour
 // mapping are mesh_output_kernels.hip; the OBJ writer, the colour table and the PNG encoder stay out.
 //
 // Two results of the reference depend on its thread order; here they are defined:

@@ -1,6 +1,8 @@
 """The mesh stage of output::output (src/output.rs:567-611) over the C ABI: the Delaunay input of a
 camera, the occlusion culling of its polygons against the other cameras' depth buffers, the polygon list of Mesh::create
-and ImageWriter's depth map.  The Delaunay construction itself is the caller's (`triangulate`); `delaunay_scipy` is one.
+and ImageWriter's depth map.  The Delaunay construction is a callback (`triangulate`): `delaunay_scipy` (the default of
+reconstruct_perspective_mesh) is one, `delaunay_device(device)` - cvhip_mesh_delaunay, DESIGN.md 4.13 - runs on the device
+and needs no scipy.
 The mesh output: `ply` / `write_ply` - PlyWriter's binary file image - and `colour_map` /
 `depth_image_rgba` - ImageWriter::complete's colours; the colour table is the caller's.
 No compute in Python - array bookkeeping and the calls only.
@@ -21,6 +23,9 @@ GRID_LANES = 262144                # CVHIP_MESH_GRID_LANES: lanes of one grid-st
 WIDE_THRESHOLD_DEFAULT = 2048      # CVHIP_MESH_WIDE_THRESHOLD_DEFAULT
 WIDE_ALL, WIDE_NONE = 0, 0xFFFFFFFF
 STATS = ("width", "height", "occupied", "dropped", "wide")
+DELAUNAY_LANE_CELLS_DEFAULT = 1024  # CVHIP_MESH_DELAUNAY_LANE_CELLS_DEFAULT
+LANE_CELLS_HOST, LANE_CELLS_UNBOUNDED = 0, 0xFFFFFFFF
+DELAUNAY_STATS = ("grid_width", "grid_height", "device_stars", "host_stars", "duplicates", "most_cells")  # CVHIP_DELAUNAY_STAT_*
 
 
 class VertexMode(enum.IntEnum):
@@ -116,7 +121,8 @@ def merge(device, polygons, camera):
 
 def create(device, surface, image_shapes, triangulate):
     """Mesh::create (:363-387) for a perspective surface: per camera the camera points, the caller's Delaunay
-    `triangulate(xy [k, 2]) -> [f, 3]` (indices into xy), the culling, and the merged list.
+    `triangulate(xy [k, 2]) -> [f, 3]` (indices into xy; `delaunay_device(device)` needs no scipy), the culling, and the
+    merged list.
     -> dict: polygons [p, 3] (track indices), camera [p], per_camera (points, polygons, kept, stats per camera)."""
     kept_p, kept_c, per_camera = [], [], []
     for i in range(len(surface.cameras)):
@@ -246,9 +252,39 @@ def depth_image_rgba(device, surface, image_shapes, project_to_image: int, scale
             "max_depth": float(minmax[1])}
 
 
+def set_delaunay_lane_cells(device, cells: int):
+    """cvhip_mesh_delaunay_set_lane_cells: a device star that would visit more than `cells` grid cells is finished on the
+    exact host path (LANE_CELLS_HOST = 0: every star, LANE_CELLS_UNBOUNDED: none for its size).  The faces do not change."""
+    _lib.check(_lib.lib().cvhip_mesh_delaunay_set_lane_cells(device.handle, int(cells)), "cvhip_mesh_delaunay_set_lane_cells")
+
+
+def delaunay(device, xy, stats=None):
+    """cvhip_mesh_delaunay: the Delaunay triangulation of the distinct positions of xy ([k, 2] f64) -> [f, 3] uint32 faces,
+    counter-clockwise, the smallest index first, grouped by it; exact ties are fanned from their lowest index, of several
+    indices at one position the lowest is the vertex (include/cvhip.h has the definition).  `stats`, a dict, receives
+    DELAUNAY_STATS.  Raises CvhipError for a coordinate that is not finite."""
+    pts = np.ascontiguousarray(xy, dtype=np.float64).reshape(-1, 2)
+    k = len(pts)
+    faces = np.zeros((2 * k, 3), dtype=np.uint32)  # (2 k faces are always enough: one call, no sizing pass)
+    n, st = C.c_uint64(0), np.zeros(len(DELAUNAY_STATS), dtype=np.uint64)
+    _lib.check(_lib.lib().cvhip_mesh_delaunay(device.handle, _p(pts), k, _p(faces), len(faces), C.byref(n), _p(st)), "cvhip_mesh_delaunay")
+    if stats is not None:
+        stats.update(zip(DELAUNAY_STATS, (int(v) for v in st)))
+    return faces[:n.value].copy()
+
+
+def delaunay_device(device):
+    """A `triangulate` for `create` and reconstruct_perspective_mesh(triangulate=...) that runs on the device (`delaunay`):
+    the way to build a mesh without scipy."""
+    def triangulate(xy):
+        return delaunay(device, xy)
+
+    return triangulate
+
+
 def delaunay_scipy(xy):
     """A `triangulate` for `create`: scipy.spatial.Delaunay's simplices of the points ([k, 2] -> [f, 3]).  scipy is
-    optional: without it this raises (the package itself does not need it)."""
+    optional: without it this raises (the package itself does not need it; `delaunay_device` runs without it)."""
     try:
         from scipy.spatial import Delaunay
     except ImportError as exc:

@@ -383,8 +383,8 @@ def reconstruct_perspective_mesh(device, pyramids, K, triangulate=None, project_
                                  **kwargs):
     """reconstruct_perspective, then the mesh stage of output::output (output.rs:567-611; DESIGN.md 4.11) on its surface:
     mesh.create - per camera the Delaunay input, `triangulate(xy) -> [f, 3]` (the caller's Delaunay; default
-    mesh.delaunay_scipy), the occlusion culling and the merged polygon list - and, when project_to_image is not None,
-    ImageWriter's depth map of that camera (depth_scale = out_scale.2.signum()).  kwargs go to reconstruct_perspective.
+    mesh.delaunay_scipy; mesh.delaunay_device(device) runs on the device and needs no scipy), the occlusion culling and the
+    merged polygon list - and, when project_to_image is not None, ImageWriter's depth map of that camera (depth_scale = out_scale.2.signum()).  kwargs go to reconstruct_perspective.
     -> its dict with mesh (mesh.create's dict), depth_image (mesh.depth_image's dict or None) and timings_ms mesh /
     depth_image added.
     The output files' contents, each only when asked for: ply_path - the binary PLY of the surface and the

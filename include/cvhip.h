@@ -315,8 +315,9 @@ int cvhip_recover_pose_models(cvhip_device *dev, const int32_t *tracks, uint64_t
  * A track projects to P (X, Y, Z, 1) divided by its third component unless that is below f64::EPSILON in magnitude
  * (Surface::project_point, triangulation.rs:63-74); it is IN RANGE when the projection lies in [c - 4 size, c + 4 size) on
  * both axes, c = size / 2 (img_range, output.rs:613-624); its depth is Camera::point_depth (triangulation.rs:492-495).
- * Not here: the Delaunay construction (the caller supplies the triangles), the OBJ writer, the colour table (an argument of
- * cvhip_mesh_colour_map) and the PNG encoder.  The PLY writer and the colour mapping are the mesh OUTPUT entries below.
+ * The Delaunay construction is cvhip_mesh_delaunay below (a caller may still supply triangles of its own: the other entries
+ * take any).  Not here: the OBJ writer, the colour table (an argument of cvhip_mesh_colour_map) and the PNG encoder.  The PLY
+ * writer and the colour mapping are the mesh OUTPUT entries below.
  * Two of the reference's results depend on its thread order, and are DEFINED here:
  *  - DepthBuffer::new folds a cell's points in par_bridge's order, keeping a new depth iff cur - new > f64::EPSILON; here
  *    the cell is the MINIMUM of its depths (one of the reference's outcomes unless two depths of a cell differ by a
@@ -385,6 +386,50 @@ int cvhip_mesh_depth_image(cvhip_device *dev, const double *points, const int32_
                            uint32_t project_to_image, double scale, const uint32_t *polygons, uint64_t n_poly,
                            double *out_map, uint64_t cap_cells, uint64_t *out_width, uint64_t *out_height,
                            double *out_origin, double *out_minmax, uint64_t *out_wide);
+
+/* cvhip_mesh_delaunay_set_lane_cells' default: a GUESS until measured (tests/tools/bench_delaunay.py
+ * sweeps it; on a jittered lattice a star visits about 85 cells, and about 1 star in 2000 - hull points - more than this) */
+#define CVHIP_MESH_DELAUNAY_LANE_CELLS_DEFAULT 1024
+/* out_stats of cvhip_mesh_delaunay: uint64 values */
+#define CVHIP_DELAUNAY_STAT_GRID_WIDTH 0   /* cells of the uniform grid along x */
+#define CVHIP_DELAUNAY_STAT_GRID_HEIGHT 1  /* and along y */
+#define CVHIP_DELAUNAY_STAT_DEVICE_STARS 2 /* stars finished on the device */
+#define CVHIP_DELAUNAY_STAT_HOST_STARS 3   /* stars finished on the exact host path */
+#define CVHIP_DELAUNAY_STAT_DUPLICATES 4   /* points at the position of a lower index */
+#define CVHIP_DELAUNAY_STAT_MOST_CELLS 5   /* the largest number of grid cells one device star visited */
+#define CVHIP_DELAUNAY_STATS 6
+
+/* The Delaunay triangulation of a camera's points (DelaunayTriangulation::bulk_load in Mesh::process_camera, output.rs:425;
+ * DESIGN.md 4.13; csrc/delaunay_kernels.hip, csrc/delaunay_common.hpp).  xy: k points of 2 finite f64 - a camera's points
+ * in track order, as cvhip_mesh_camera_points writes them.  out_faces: the faces of the Delaunay triangulation of the
+ * DISTINCT positions, 3 uint32 positions in xy each, DEFINED as follows:
+ *  - every decision is the sign of the EXACT orientation or in-circle determinant of the doubles as given (the device
+ *    certifies a rounded determinant against its forward error bound; what it cannot certify is decided on the host with
+ *    floating-point expansions), so without exact ties this is THE Delaunay triangulation, the reference's (spade's) too;
+ *  - a face (a, b, c) is counter-clockwise, (xb - xa)(yc - ya) - (yb - ya)(xc - xa) > 0 (spade's vertices() order), and
+ *    starts with its smallest index (Polygon::new's rotation);
+ *  - exact ties: a maximal set of four or more points on one circle with no point strictly inside is a convex polygon; it
+ *    is fanned from its vertex with the LOWEST index (the reference leaves this to spade's insertion order);
+ *  - duplicates: of several indices at one position the lowest is the vertex, the others are in no face;
+ *  - k < 3, or all points collinear: 0 faces, CVHIP_OK.
+ * FACE ORDER: grouped by the face's first (lowest) index, ascending; within a group in the order of that point's star -
+ * counter-clockwise from the point's nearest point (of equally near ones the lowest index) and, at a point of the convex
+ * hull, then clockwise from it.  Deterministic: two calls on the same input give the same bytes.
+ * xy and out_faces are host or device pointers; the counts and out_stats (CVHIP_DELAUNAY_STATS uint64, may be NULL: the
+ * CVHIP_DELAUNAY_STAT_* values; which path finishes a star whose signs are near zero may depend on the order of the grid's
+ * atomics, the faces do not) are host memory.  *out_n_faces is always written on success; cap_faces = 0 sizes the output
+ * and writes no face; 0 < cap_faces < n_faces is CVHIP_ERR_INVALID with nothing written; 2 k is always enough.
+ * Errors: CVHIP_ERR_INVALID for a coordinate that is not finite (nothing written); CVHIP_ERR_UNSUPPORTED for k >= 2^31
+ * (the face count must stay below 2^32 - 1; so k >= 2^32 - 1 too).  The signs are exact while no product of coordinate
+ * differences over- or underflows (differences within 2^-240 .. 2^240 in magnitude).
+ * Affine surfaces (integer lattices) are not what this is for: every star is a tie and runs on the host. */
+int cvhip_mesh_delaunay(cvhip_device *dev, const double *xy, uint64_t k,
+                        uint32_t *out_faces, uint64_t cap_faces, uint64_t *out_n_faces, uint64_t *out_stats);
+
+/* A device star that would visit more than `cells` grid cells is left to the host path, so that one long star cannot hold
+ * its wave: 0 sends every star to the host path, UINT32_MAX never leaves the device for size.  Every setting gives the same
+ * faces. */
+int cvhip_mesh_delaunay_set_lane_cells(cvhip_device *dev, uint32_t cells);
 
 /* ------------------------------------------------------------------------------------------
  * Mesh output (csrc/mesh_output_kernels.hip): what output::output writes once the polygon list exists -
