@@ -22,7 +22,7 @@ int fail(int code, const std::string &msg)
 
 // Is `p` a device pointer usable on the current GPU?  Unregistered host memory makes
 // hipPointerGetAttributes fail, which is not an error for us.
-static bool is_device_ptr(const void *p)
+bool on_device(const void *p)
 {
     hipPointerAttribute_t attr;
     std::memset(&attr, 0, sizeof(attr));
@@ -36,7 +36,7 @@ static bool is_device_ptr(const void *p)
 
 static int copy_in(void *dst, const void *src, size_t bytes, hipStream_t s)
 {
-    const hipMemcpyKind kind = is_device_ptr(src) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+    const hipMemcpyKind kind = on_device(src) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
     CVHIP_TRY_HIP(hipMemcpyAsync(dst, src, bytes, kind, s));
     return CVHIP_OK;
 }
@@ -304,7 +304,7 @@ static int stage_images(cvhip_ctx *c, int k, const uint8_t *img1, size_t n1, con
     const size_t off = img_level_offset(c->max_px, k);
     bool waited_readers = false;
     for (int i = 0; i < 2; i++) {
-        if (is_device_ptr(src[i])) {
+        if (on_device(src[i])) {
             if (c->borrow_inputs) {
                 c->cur_img[i] = src[i];
             } else {
@@ -978,7 +978,7 @@ int level_begin(cvhip_ctx *ctx, const uint8_t *img1, uint32_t w1, uint32_t h1, c
     }
     uint2 *const st0 = ctx->istats[0] + stats_level_offset(ctx->max_px, k), *const st1 = ctx->istats[1] + stats_level_offset(ctx->max_px, k);
     bool stats_ahead = ctx->stats_ahead && ctx->time_kernels != 1 && !sharded && ctx->borrow_inputs &&
-                       is_device_ptr(img1) && is_device_ptr(img2) && k < 16;
+                       on_device(img1) && on_device(img2) && k < 16;
     if (stats_ahead && ctx->dev->d.sa.verdict == 0 && ctx->dev->d.sa.probe_recorded && first_pass) {
         // the previous run's probe, if it has completed (never waits)
         Device::StatsAhead &sa = ctx->dev->d.sa;
@@ -1190,7 +1190,7 @@ int level_cross(cvhip_ctx *ctx, int k, bool stats_ahead)
 // could not be had: then the pageable sources must not be reused by the caller before the copy has happened.
 int release_host_sources(cvhip_ctx *ctx, const uint8_t *img1, const uint8_t *img2)
 {
-    if (ctx->staged_from_pageable && (!is_device_ptr(img1) || !is_device_ptr(img2))) CVHIP_TRY_HIP(hipStreamSynchronize(ctx->dev->d.stream));
+    if (ctx->staged_from_pageable && (!on_device(img1) || !on_device(img2))) CVHIP_TRY_HIP(hipStreamSynchronize(ctx->dev->d.stream));
     return CVHIP_OK;
 }
 } // namespace
@@ -1402,8 +1402,8 @@ static int complete_grid(cvhip_ctx *ctx, int dir, int32_t *out_xy, float *out_co
     hipStream_t s = ctx->dev->d.stream;
     DirState &ds = ctx->dir[dir];
     const size_t n = (size_t)ds.gw * ds.gh;
-    const bool xy_dev = is_device_ptr(out_xy);
-    const bool corr_dev = out_corr ? is_device_ptr(out_corr) : true;
+    const bool xy_dev = on_device(out_xy);
+    const bool corr_dev = out_corr ? on_device(out_corr) : true;
     const bool to_host = !xy_dev || (out_corr && !corr_dev);
     int32_t *d_xy = out_xy;
     float *d_corr = out_corr;
@@ -1504,27 +1504,23 @@ int cvhip_triangulate_affine(cvhip_ctx *ctx, double *out_points3d, uint32_t *out
     // the search-interval buffer is free between levels: reuse it for the block counts (+ total)
     if ((size_t)nblocks + 1 > ctx->max_px) return fail(CVHIP_ERR_INVALID, "image too small for the scratch buffer");
     uint32_t *counts = ctx->range, *total = ctx->range + nblocks;
-    const bool p3_dev = out_points3d ? is_device_ptr(out_points3d) : true, p2_dev = out_p2 ? is_device_ptr(out_p2) : true;
-    double *d_p3 = out_points3d;
-    uint32_t *d_p2 = out_p2;
-    hipError_t e = hipSuccess;
-    if (cap && !p3_dev) e = hipMalloc(&d_p3, (size_t)cap * 3 * sizeof(double));
-    if (e == hipSuccess && cap && out_p2 && !p2_dev) e = hipMalloc(&d_p2, (size_t)cap * 2 * sizeof(uint32_t));
+    CallScratch sc;
+    double *d_p3 = nullptr;
+    uint32_t *d_p2 = nullptr;
     uint32_t h_total = 0;
+    hipError_t e = sc.output(out_points3d, (size_t)cap * 3, &d_p3);
+    if (e == hipSuccess) e = sc.output(out_p2, (size_t)cap * 2, &d_p2);
     if (e == hipSuccess) {
         launch_triangulate_affine(ds.cells[ds.cur], ds.lw, ds.lh, ds.k, ds.gw, ds.gh, counts, total, d_p3, d_p2, cap, s);
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipMemcpyAsync(&h_total, total, sizeof(uint32_t), hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
-    const uint64_t written = std::min<uint64_t>(h_total, cap);
-    if (e == hipSuccess && cap && !p3_dev && written)
-        e = hipMemcpy(out_points3d, d_p3, (size_t)written * 3 * sizeof(double), hipMemcpyDeviceToHost);
-    if (e == hipSuccess && cap && out_p2 && !p2_dev && written)
-        e = hipMemcpy(out_p2, d_p2, (size_t)written * 2 * sizeof(uint32_t), hipMemcpyDeviceToHost);
-    if (cap && !p3_dev && d_p3) (void)hipFree(d_p3);
-    if (cap && out_p2 && !p2_dev && d_p2) (void)hipFree(d_p2);
-    if (e != hipSuccess) return fail(CVHIP_ERR_DEVICE, std::string("triangulate_affine: ") + hipGetErrorString(e));
+    const size_t written = (size_t)std::min<uint64_t>(h_total, cap);
+    if (e == hipSuccess) e = sc.copy_out(out_points3d, d_p3, written * 3, s);
+    if (e == hipSuccess) e = sc.copy_out(out_p2, d_p2, written * 2, s);
+    if (e == hipSuccess) e = sc.drain(s);
+    if (e != hipSuccess) return device_error("triangulate_affine", e);
     *out_n = h_total;
     return CVHIP_OK;
 }

@@ -145,17 +145,33 @@ void launch_extend_tracks_new(const uint32_t *cells, uint32_t lw, uint32_t lh, u
                               const uint8_t *removed, uint32_t *block_counts, uint32_t *total, uint32_t *out_new_p1,
                               uint32_t *out_new_p2, unsigned long long cap, hipStream_t s);
 
-// ---- shared by the mesh entry points (mesh_kernels.hip, mesh_output_kernels.hip) ---------------
-bool mesh_on_device(const void *p); // device or managed memory (anything else is taken as host memory)
+// ---- shared by the multi-view entry points (tracks, triangulation, pose, mesh, mesh output, Delaunay) ------------------------
+bool on_device(const void *p); // device or managed memory (anything else is taken as host memory); cvhip_api.hip
+inline int device_error(const char *what, hipError_t e) { return fail(CVHIP_ERR_DEVICE, std::string(what) + ": " + hipGetErrorString(e)); }
+#define CVHIP_TRY_HIP_AT(what, expr)                              \
+    do {                                                          \
+        hipError_t _e = (expr);                                   \
+        if (_e != hipSuccess) return ::cvhip::device_error(what, _e); \
+    } while (0)
+// blocks of 256 lanes of a grid-stride launch over n elements: at least one, at most CVHIP_MESH_GRID_LANES lanes
+inline uint32_t grid_for(unsigned long long n)
+{
+    return (uint32_t)std::min<unsigned long long>(CVHIP_MESH_GRID_LANES / 256, std::max<unsigned long long>(1, (n + 255) / 256));
+}
 // mesh_check_polygons_kernel: *bad |= 1 when a polygon names a track >= n (the callers run nothing else then)
 void launch_mesh_check_polygons(const uint32_t *polygons, unsigned long long n_poly, unsigned long long n, uint32_t *bad, hipStream_t s);
-// per-call device scratch, freed together (error paths included)
-struct MeshScratch {
+// Per-call device scratch, freed together (error paths included), and the rule for the caller's arrays:
+// input() borrows what is on the device and only read, copy_in() copies what the call overwrites, output() / copy_out()
+// give a host destination a stand-in and copy back exactly the elements that were written.
+class CallScratch {
     std::vector<void *> owned;
-    MeshScratch() = default;
-    MeshScratch(const MeshScratch &) = delete;
-    MeshScratch &operator=(const MeshScratch &) = delete;
-    ~MeshScratch()
+    bool copying_out = false;
+
+  public:
+    CallScratch() = default;
+    CallScratch(const CallScratch &) = delete;
+    CallScratch &operator=(const CallScratch &) = delete;
+    ~CallScratch()
     {
         for (void *p : owned) (void)hipFree(p);
     }
@@ -167,10 +183,26 @@ struct MeshScratch {
         *out = static_cast<T *>(p);
         return e;
     }
+    // free one allocation before the call ends
+    void release(void *p)
+    {
+        const auto it = std::find(owned.begin(), owned.end(), p);
+        if (it == owned.end()) return;
+        (void)hipFree(p);
+        owned.erase(it);
+    }
+    // an owned copy of the caller's host or device array
+    template <typename T> hipError_t copy_in(const T *src, size_t count, T **out, hipStream_t s)
+    {
+        hipError_t e = alloc(out, count);
+        if (e == hipSuccess && count)
+            e = hipMemcpyAsync(*out, src, count * sizeof(T), on_device(src) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s);
+        return e;
+    }
     // the caller's array on the device: itself, or a copy of the host array
     template <typename T> hipError_t input(const T *src, size_t count, const T **out, hipStream_t s)
     {
-        if (!count || mesh_on_device(src)) {
+        if (!count || on_device(src)) {
             *out = src;
             return hipSuccess;
         }
@@ -179,6 +211,29 @@ struct MeshScratch {
         if (e == hipSuccess) e = hipMemcpyAsync(d, src, count * sizeof(T), hipMemcpyHostToDevice, s);
         *out = d;
         return e;
+    }
+    // where the kernels write the caller's output: the array itself (on the device, NULL or empty), or a stand-in
+    template <typename T> hipError_t output(T *dst, size_t count, T **out)
+    {
+        if (!dst || !count || on_device(dst)) {
+            *out = dst;
+            return hipSuccess;
+        }
+        return alloc(out, count);
+    }
+    // the first `count` elements of the stand-in into the caller's array, enqueued (nothing when there is no stand-in)
+    template <typename T> hipError_t copy_out(T *dst, const T *dev, size_t count, hipStream_t s)
+    {
+        if (dst == dev || !count) return hipSuccess;
+        copying_out = true;
+        return hipMemcpyAsync(dst, dev, count * sizeof(T), on_device(dst) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s);
+    }
+    // wait for the copies enqueued by copy_out(), if any (for a call that has synchronised already to learn `count`)
+    hipError_t drain(hipStream_t s)
+    {
+        if (!copying_out) return hipSuccess;
+        copying_out = false;
+        return hipStreamSynchronize(s);
     }
 };
 

@@ -198,10 +198,6 @@ __global__ __launch_bounds__(BLOCK) void dln_write_kernel(Grid g, unsigned long 
     }
 }
 
-uint32_t grid_for(unsigned long long n) { return (uint32_t)std::min<unsigned long long>(MAX_GRID, std::max<unsigned long long>(1, (n + BLOCK - 1) / BLOCK)); }
-
-int device_error(const char *what, hipError_t e) { return fail(CVHIP_ERR_DEVICE, std::string(what) + ": " + hipGetErrorString(e)); }
-
 struct CollectFaces {
     std::vector<uint32_t> *faces;
     uint32_t n = 0;
@@ -220,7 +216,7 @@ int mesh_delaunay_run(Device &d, const double *xy, uint64_t k, uint32_t *out_fac
                       uint64_t *out_stats)
 {
     hipStream_t s = d.stream;
-    MeshScratch sc;
+    CallScratch sc;
     uint64_t stats[6] = {0, 0, 0, 0, 0, 0};
     auto finish = [&](uint64_t n) {
         *out_n_faces = n;
@@ -294,7 +290,7 @@ int mesh_delaunay_run(Device &d, const double *xy, uint64_t k, uint32_t *out_fac
         std::vector<double> h_xy;
         e = hipMemcpyAsync(h_start.data(), cell_start, h_start.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, s);
         if (e == hipSuccess) e = hipMemcpyAsync(h_pts.data(), cell_pts, h_pts.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess && mesh_on_device(xy)) {
+        if (e == hipSuccess && on_device(xy)) {
             h_xy.resize((size_t)k * 2);
             e = hipMemcpyAsync(h_xy.data(), d_xy, h_xy.size() * sizeof(double), hipMemcpyDeviceToHost, s);
         }
@@ -337,14 +333,13 @@ int mesh_delaunay_run(Device &d, const double *xy, uint64_t k, uint32_t *out_fac
     if (e != hipSuccess) return device_error("mesh_delaunay", e);
     if (!cap_faces || !total) return finish(total);
     if (cap_faces < total) return fail(CVHIP_ERR_INVALID, "mesh_delaunay: the buffer is smaller than the face count");
-    uint32_t *d_out = out_faces;
-    const bool copy = !mesh_on_device(out_faces);
-    if (copy) e = sc.alloc(&d_out, (size_t)total * 3);
+    uint32_t *d_out = nullptr;
+    e = sc.output(out_faces, (size_t)total * 3, &d_out);
     if (e != hipSuccess) return device_error("mesh_delaunay", e);
     hipLaunchKernelGGL(dln_write_kernel, dim3(grid_for((unsigned long long)blocks * BLOCK)), dim3(BLOCK), 0, s, g, lane_cells, count, status, offset_of,
                        d_host_faces, (uint32_t)(host_faces.size() / 3), block_counts, blocks, (unsigned long long)total, d_out);
     e = hipGetLastError();
-    if (e == hipSuccess && copy) e = hipMemcpyAsync(out_faces, d_out, (size_t)total * 3 * sizeof(uint32_t), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = sc.copy_out(out_faces, d_out, (size_t)total * 3, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     if (e != hipSuccess) return device_error("mesh_delaunay", e);
     return finish(total);

@@ -458,27 +458,12 @@ __global__ __launch_bounds__(BLOCK) void mesh_check_polygons_kernel(const uint32
 // ---- host side ------------------------------------------------------------------------------------------------------------------
 } // namespace
 
-bool mesh_on_device(const void *p)
-{
-    hipPointerAttribute_t attr;
-    if (hipPointerGetAttributes(&attr, p) != hipSuccess) {
-        (void)hipGetLastError();
-        return false;
-    }
-    return attr.type == hipMemoryTypeDevice || attr.type == hipMemoryTypeManaged;
-}
-
 void launch_mesh_check_polygons(const uint32_t *polygons, unsigned long long n_poly, unsigned long long n, uint32_t *bad, hipStream_t s)
 {
-    const uint32_t blocks = (uint32_t)std::min<unsigned long long>(MAX_GRID, std::max<unsigned long long>(1, (n_poly + BLOCK - 1) / BLOCK));
-    hipLaunchKernelGGL(mesh_check_polygons_kernel, dim3(blocks), dim3(BLOCK), 0, s, polygons, n_poly, n, bad);
+    hipLaunchKernelGGL(mesh_check_polygons_kernel, dim3(grid_for(n_poly)), dim3(BLOCK), 0, s, polygons, n_poly, n, bad);
 }
 
 namespace {
-
-uint32_t grid_for(unsigned long long n) { return (uint32_t)std::min<unsigned long long>(MAX_GRID, std::max<unsigned long long>(1, (n + BLOCK - 1) / BLOCK)); }
-
-using Scratch = MeshScratch;
 
 // the surface as every entry point takes it, checked and staged on the device
 struct SurfaceArgs {
@@ -529,7 +514,7 @@ MeshCam make_cam(const SurfaceArgs &a, uint32_t j)
     return c;
 }
 
-hipError_t stage_surface(Scratch &sc, const SurfaceArgs &a, DeviceSurface &d, hipStream_t s)
+hipError_t stage_surface(CallScratch &sc, const SurfaceArgs &a, DeviceSurface &d, hipStream_t s)
 {
     const int32_t *tr = nullptr;
     hipError_t e = sc.input(a.points, (size_t)a.n * 3, &d.points, s);
@@ -564,7 +549,7 @@ void buffer_dims(const Extent &e, uint64_t *w, uint64_t *h)
 }
 
 // the minimum buffer of camera j from the projected plane
-hipError_t build_buffer(Scratch &sc, const SurfaceArgs &a, const DeviceSurface &d, uint32_t w, uint32_t h, unsigned long long **buf,
+hipError_t build_buffer(CallScratch &sc, const SurfaceArgs &a, const DeviceSurface &d, uint32_t w, uint32_t h, unsigned long long **buf,
                         hipStream_t s)
 {
     const unsigned long long cells = (unsigned long long)w * h;
@@ -577,25 +562,21 @@ hipError_t build_buffer(Scratch &sc, const SurfaceArgs &a, const DeviceSurface &
 }
 
 // decode a buffer into `out` (host or device, may be NULL) and fold (min, max, occupied) into *h_stats
-hipError_t decode(Scratch &sc, const DeviceSurface &d, const unsigned long long *buf, unsigned long long cells, unsigned long long none,
+hipError_t decode(CallScratch &sc, const DeviceSurface &d, const unsigned long long *buf, unsigned long long cells, unsigned long long none,
                   double *out, Extent *h_stats, hipStream_t s)
 {
-    double *d_out = out;
-    const bool copy = out && !mesh_on_device(out);
-    hipError_t e = hipSuccess;
-    if (copy) e = sc.alloc(&d_out, (size_t)cells);
+    double *d_out = nullptr;
+    hipError_t e = sc.output(out, (size_t)cells, &d_out);
     if (e != hipSuccess) return e;
     const uint32_t blocks = grid_for(cells);
     hipLaunchKernelGGL(mesh_decode_kernel, dim3(blocks), dim3(BLOCK), 0, s, buf, cells, none, d_out, d.partial);
     hipLaunchKernelGGL(extent_final_kernel, dim3(1), dim3(64), 0, s, d.partial, blocks, d.extent);
     e = hipGetLastError();
     if (e == hipSuccess) e = hipMemcpyAsync(h_stats, d.extent, sizeof(Extent), hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess && copy) e = hipMemcpyAsync(out, d_out, (size_t)cells * sizeof(double), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = sc.copy_out(out, d_out, (size_t)cells, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     return e;
 }
-
-int device_error(const char *what, hipError_t e) { return fail(CVHIP_ERR_DEVICE, std::string(what) + ": " + hipGetErrorString(e)); }
 
 } // namespace
 } // namespace cvhip
@@ -618,7 +599,7 @@ extern "C" int cvhip_mesh_camera_points(cvhip_device *dev, const double *points,
     if (!out_n || (cap && (!out_index || !out_xy))) return fail(CVHIP_ERR_INVALID, "mesh_camera_points: null output");
     CVHIP_TRY_HIP(hipSetDevice(dev->d.ordinal));
     hipStream_t s = dev->d.stream;
-    Scratch sc;
+    CallScratch sc;
     DeviceSurface d;
     Extent ext{};
     hipError_t e = stage_surface(sc, a, d, s);
@@ -629,12 +610,11 @@ extern "C" int cvhip_mesh_camera_points(cvhip_device *dev, const double *points,
     if (!k) return CVHIP_OK;
     // one block per 256 consecutive tracks (not a grid-stride loop: the blocks' counts are scanned into their offsets)
     const uint32_t blocks = (uint32_t)((n + BLOCK - 1) / BLOCK);
-    uint32_t *counts = nullptr, *d_index = out_index;
-    double *d_xy = out_xy;
-    const bool idx_copy = !mesh_on_device(out_index), xy_copy = !mesh_on_device(out_xy);
+    uint32_t *counts = nullptr, *d_index = nullptr;
+    double *d_xy = nullptr;
     e = sc.alloc(&counts, (size_t)blocks + 1);
-    if (e == hipSuccess && idx_copy) e = sc.alloc(&d_index, (size_t)k);
-    if (e == hipSuccess && xy_copy) e = sc.alloc(&d_xy, (size_t)k * 2);
+    if (e == hipSuccess) e = sc.output(out_index, (size_t)k, &d_index);
+    if (e == hipSuccess) e = sc.output(out_xy, (size_t)k * 2, &d_xy);
     if (e == hipSuccess) {
         hipLaunchKernelGGL(mesh_select_count_kernel, dim3(blocks), dim3(BLOCK), 0, s, d.plane, (unsigned long long)n, FLAG_RANGE | FLAG_SEEN, counts);
         launch_scan_u32(counts, blocks, counts + blocks, s);
@@ -642,8 +622,8 @@ extern "C" int cvhip_mesh_camera_points(cvhip_device *dev, const double *points,
                            counts, (unsigned long long)k, d_index, d_xy);
         e = hipGetLastError();
     }
-    if (e == hipSuccess && idx_copy) e = hipMemcpyAsync(out_index, d_index, (size_t)k * sizeof(uint32_t), hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess && xy_copy) e = hipMemcpyAsync(out_xy, d_xy, (size_t)k * 2 * sizeof(double), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = sc.copy_out(out_index, d_index, (size_t)k, s);
+    if (e == hipSuccess) e = sc.copy_out(out_xy, d_xy, (size_t)k * 2, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     if (e != hipSuccess) return device_error("mesh_camera_points", e);
     return CVHIP_OK;
@@ -659,7 +639,7 @@ extern "C" int cvhip_mesh_depth_buffer(cvhip_device *dev, const double *points, 
     if (!out_width || !out_height || (cap_cells && !out_buffer)) return fail(CVHIP_ERR_INVALID, "mesh_depth_buffer: null output");
     CVHIP_TRY_HIP(hipSetDevice(dev->d.ordinal));
     hipStream_t s = dev->d.stream;
-    Scratch sc;
+    CallScratch sc;
     DeviceSurface d;
     Extent ext{};
     hipError_t e = stage_surface(sc, a, d, s);
@@ -689,12 +669,11 @@ extern "C" int cvhip_mesh_cull(cvhip_device *dev, const double *points, const in
     if (n_poly >= 0xFFFFFFFFull) return fail(CVHIP_ERR_UNSUPPORTED, "mesh_cull: 2^32 - 1 or more polygons");
     CVHIP_TRY_HIP(hipSetDevice(dev->d.ordinal));
     hipStream_t s = dev->d.stream;
-    Scratch sc;
+    CallScratch sc;
     DeviceSurface d;
     const uint32_t *d_poly = nullptr;
     uint32_t *queue = nullptr, *counters = nullptr; // counters: per camera {obstructing, queued}, then the bad-vertex flag
-    uint8_t *d_keep = out_keep;
-    const bool keep_copy = n_poly && !mesh_on_device(out_keep);
+    uint8_t *d_keep = nullptr;
     const uint32_t pblocks = grid_for(n_poly), threshold = dev->d.mesh_wide_threshold;
     uint32_t h_counters[2 * CVHIP_TRIANGULATE_MAX_CAMERAS + 1] = {};
     uint64_t stats[CVHIP_TRIANGULATE_MAX_CAMERAS][5] = {};
@@ -702,7 +681,7 @@ extern "C" int cvhip_mesh_cull(cvhip_device *dev, const double *points, const in
     if (e == hipSuccess) e = sc.input(polygons, (size_t)n_poly * 3, &d_poly, s);
     if (e == hipSuccess) e = sc.alloc(&queue, (size_t)n_poly);
     if (e == hipSuccess) e = sc.alloc(&counters, 2 * (size_t)m + 1);
-    if (e == hipSuccess && keep_copy) e = sc.alloc(&d_keep, (size_t)n_poly);
+    if (e == hipSuccess) e = sc.output(out_keep, (size_t)n_poly, &d_keep);
     if (e == hipSuccess) e = hipMemsetAsync(counters, 0, (2 * (size_t)m + 1) * sizeof(uint32_t), s);
     if (e == hipSuccess && n_poly) {
         hipLaunchKernelGGL(mesh_check_polygons_kernel, dim3(pblocks), dim3(BLOCK), 0, s, d_poly, (unsigned long long)n_poly,
@@ -735,13 +714,10 @@ extern "C" int cvhip_mesh_cull(cvhip_device *dev, const double *points, const in
         }
         if (e == hipSuccess) e = decode(sc, d, buf, w * h, KEY_NONE_MIN, nullptr, &occ, s); // (synchronises: buf can go)
         stats[j][2] = occ.count;
-        if (buf) { // (the newest allocation)
-            (void)hipFree(buf);
-            sc.owned.pop_back();
-        }
+        sc.release(buf); // before the next camera's
     }
     if (e == hipSuccess) e = hipMemcpyAsync(h_counters, counters, 2 * (size_t)m * sizeof(uint32_t), hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess && keep_copy) e = hipMemcpyAsync(out_keep, d_keep, (size_t)n_poly, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = sc.copy_out(out_keep, d_keep, (size_t)n_poly, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     if (e != hipSuccess) return device_error("mesh_cull", e);
     if (out_stats)
@@ -765,7 +741,7 @@ extern "C" int cvhip_mesh_depth_image(cvhip_device *dev, const double *points, c
     if (n_poly >= 0xFFFFFFFFull) return fail(CVHIP_ERR_UNSUPPORTED, "mesh_depth_image: 2^32 - 1 or more polygons");
     CVHIP_TRY_HIP(hipSetDevice(dev->d.ordinal));
     hipStream_t s = dev->d.stream;
-    Scratch sc;
+    CallScratch sc;
     DeviceSurface d;
     Extent ext{};
     hipError_t e = stage_surface(sc, a, d, s);

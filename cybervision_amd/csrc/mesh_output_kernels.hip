@@ -20,7 +20,6 @@ namespace cvhip {
 namespace {
 
 constexpr int BLOCK = 256;
-constexpr int MAX_GRID = CVHIP_MESH_GRID_LANES / BLOCK; // blocks of a grid-stride launch
 constexpr uint32_t VERTEX_BYTES = 24, COLOUR_BYTES = 3, FACE_BYTES = 13;
 // a block's records (at most 256 x 27 = 6912 bytes) behind up to 3 bytes that stand for the rest of its first dword
 constexpr uint32_t STAGE_DWORDS = (BLOCK * (VERTEX_BYTES + COLOUR_BYTES) + 3 + 3) / 4;
@@ -207,10 +206,6 @@ __global__ __launch_bounds__(BLOCK) void mesh_colour_kernel(const double *__rest
     }
 }
 
-uint32_t grid_for(unsigned long long n) { return (uint32_t)std::min<unsigned long long>(MAX_GRID, std::max<unsigned long long>(1, n)); }
-
-int device_error(const char *what, hipError_t e) { return fail(CVHIP_ERR_DEVICE, std::string(what) + ": " + hipGetErrorString(e)); }
-
 // PlyWriter::output_header (:687-710)
 std::string ply_header(uint64_t n, uint64_t n_poly, bool color)
 {
@@ -249,7 +244,7 @@ extern "C" int cvhip_mesh_ply(cvhip_device *dev, const double *points, const int
     }
     CVHIP_TRY_HIP(hipSetDevice(dev->d.ordinal));
     hipStream_t s = dev->d.stream;
-    MeshScratch sc;
+    CallScratch sc;
     const std::string header = ply_header(n, n_poly, color);
     const unsigned long long v_blocks = (n + BLOCK - 1) / BLOCK, f_blocks = (n_poly + BLOCK - 1) / BLOCK;
     const int32_t *d_tracks = nullptr;
@@ -268,7 +263,7 @@ extern "C" int cvhip_mesh_ply(cvhip_device *dev, const double *points, const int
         if (e == hipSuccess) e = sc.alloc(&counts, (size_t)v_blocks + 2);
         if (e == hipSuccess) e = hipMemsetAsync(counts + v_blocks, 0, 2 * sizeof(uint32_t), s);
         if (e == hipSuccess) {
-            hipLaunchKernelGGL(mesh_ply_count_kernel, dim3(grid_for(v_blocks)), dim3(BLOCK), 0, s, reinterpret_cast<const int2 *>(d_tracks),
+            hipLaunchKernelGGL(mesh_ply_count_kernel, dim3(grid_for(n)), dim3(BLOCK), 0, s, reinterpret_cast<const int2 *>(d_tracks),
                                (unsigned long long)n, m, img.dims, v_blocks, counts, counts + v_blocks + 1);
             launch_scan_u32(counts, (uint32_t)v_blocks, counts + v_blocks, s);
             e = hipGetLastError();
@@ -287,8 +282,7 @@ extern "C" int cvhip_mesh_ply(cvhip_device *dev, const double *points, const int
     const double *d_points = nullptr;
     const uint32_t *d_poly = nullptr;
     uint32_t *bad = nullptr, h_bad = 0;
-    uint8_t *d_out = out;
-    const bool copy = !mesh_on_device(out);
+    uint8_t *d_out = nullptr;
     e = sc.input(points, (size_t)n * 3, &d_points, s);
     if (e == hipSuccess) e = sc.input(polygons, (size_t)n_poly * 3, &d_poly, s);
     if (e == hipSuccess && n_poly) {
@@ -303,26 +297,25 @@ extern "C" int cvhip_mesh_ply(cvhip_device *dev, const double *points, const int
     }
     if (e != hipSuccess) return device_error("mesh_ply", e);
     if (h_bad) return fail(CVHIP_ERR_INVALID, "mesh_ply: a polygon names a track >= n");
-    if (copy) e = sc.alloc(&d_out, (size_t)size); // (the same offsets as in `out`: the body starts behind the header's length)
+    e = sc.output(out, (size_t)size, &d_out); // (a stand-in has the same offsets as `out`: the body starts behind the header's length)
     if (e != hipSuccess) return device_error("mesh_ply", e);
     uint8_t *d_vertices = d_out + header.size(), *d_faces = d_vertices + vertex_bytes;
     if (n) {
         if (color)
-            hipLaunchKernelGGL((mesh_ply_vertex_kernel<true>), dim3(grid_for(v_blocks)), dim3(BLOCK), 0, s, d_points,
+            hipLaunchKernelGGL((mesh_ply_vertex_kernel<true>), dim3(grid_for(n)), dim3(BLOCK), 0, s, d_points,
                                reinterpret_cast<const int2 *>(d_tracks), (unsigned long long)n, m, img, out_scale[0], out_scale[1],
                                out_scale[2], counts, v_blocks, d_vertices, (unsigned long long)vertex_bytes);
         else
-            hipLaunchKernelGGL((mesh_ply_vertex_kernel<false>), dim3(grid_for(v_blocks)), dim3(BLOCK), 0, s, d_points,
+            hipLaunchKernelGGL((mesh_ply_vertex_kernel<false>), dim3(grid_for(n)), dim3(BLOCK), 0, s, d_points,
                                static_cast<const int2 *>(nullptr), (unsigned long long)n, m, img, out_scale[0], out_scale[1], out_scale[2],
                                static_cast<const uint32_t *>(nullptr), v_blocks, d_vertices, (unsigned long long)vertex_bytes);
     }
     if (n_poly)
-        hipLaunchKernelGGL(mesh_ply_face_kernel, dim3(grid_for(f_blocks)), dim3(BLOCK), 0, s, d_poly, (unsigned long long)n_poly, f_blocks,
+        hipLaunchKernelGGL(mesh_ply_face_kernel, dim3(grid_for(n_poly)), dim3(BLOCK), 0, s, d_poly, (unsigned long long)n_poly, f_blocks,
                            d_faces);
     e = hipGetLastError();
-    if (copy) {
-        if (e == hipSuccess && size > header.size())
-            e = hipMemcpyAsync(out + header.size(), d_vertices, (size_t)(size - header.size()), hipMemcpyDeviceToHost, s);
+    if (d_out != out) { // the body from the stand-in, the header from here
+        if (e == hipSuccess) e = sc.copy_out(out + header.size(), d_vertices, (size_t)(size - header.size()), s);
         if (e == hipSuccess) e = hipStreamSynchronize(s);
         if (e == hipSuccess) std::memcpy(out, header.data(), header.size());
     } else {
@@ -343,21 +336,20 @@ extern "C" int cvhip_mesh_colour_map(cvhip_device *dev, const double *map, uint6
     if (!map || !out_rgba) return fail(CVHIP_ERR_INVALID, "mesh_colour_map: null argument");
     CVHIP_TRY_HIP(hipSetDevice(dev->d.ordinal));
     hipStream_t s = dev->d.stream;
-    MeshScratch sc;
+    CallScratch sc;
     const double *d_map = nullptr;
-    uint8_t *d_table = nullptr, *d_out = out_rgba;
-    const bool copy = !mesh_on_device(out_rgba);
+    uint8_t *d_table = nullptr, *d_out = nullptr;
     hipError_t e = sc.input(map, (size_t)cells, &d_map, s);
     if (e == hipSuccess) e = sc.alloc(&d_table, 768);
     if (e == hipSuccess) e = hipMemcpyAsync(d_table, table, 768, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess && copy) e = sc.alloc(&d_out, (size_t)cells * 4);
+    if (e == hipSuccess) e = sc.output(out_rgba, (size_t)cells * 4, &d_out);
     if (e == hipSuccess && (reinterpret_cast<uintptr_t>(d_out) & 3u)) return fail(CVHIP_ERR_INVALID, "mesh_colour_map: out_rgba is not 4-byte aligned");
     if (e == hipSuccess) {
-        hipLaunchKernelGGL(mesh_colour_kernel, dim3(grid_for((cells + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, s, d_map, cells, min_depth,
+        hipLaunchKernelGGL(mesh_colour_kernel, dim3(grid_for(cells)), dim3(BLOCK), 0, s, d_map, cells, min_depth,
                            max_depth, d_table, reinterpret_cast<uchar4 *>(d_out));
         e = hipGetLastError();
     }
-    if (e == hipSuccess && copy) e = hipMemcpyAsync(out_rgba, d_out, (size_t)cells * 4, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = sc.copy_out(out_rgba, d_out, (size_t)cells * 4, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     if (e != hipSuccess) return device_error("mesh_colour_map", e);
     return CVHIP_OK;

@@ -941,16 +941,6 @@ static void gaussian_kernel_host(int width, double *kernel)
     }
 }
 
-static bool dev_ptr(const void *p)
-{
-    hipPointerAttribute_t attr;
-    if (hipPointerGetAttributes(&attr, p) != hipSuccess) {
-        (void)hipGetLastError();
-        return false;
-    }
-    return attr.type == hipMemoryTypeDevice || attr.type == hipMemoryTypeManaged;
-}
-
 } // namespace cvhip
 
 using namespace cvhip;
@@ -974,7 +964,7 @@ extern "C" int cvhip_downsample_box(cvhip_device *dev, const uint8_t *src, uint3
     CVHIP_TRY_HIP(hipSetDevice(dev->d.ordinal));
     hipStream_t s = dev->d.stream;
     DevAllocs mem(dev->d);
-    const bool s_dev = dev_ptr(src), d_dev = dev_ptr(dst);
+    const bool s_dev = on_device(src), d_dev = on_device(dst);
     const uint8_t *d_src = src;
     uint8_t *d_dst = dst, *tmp = nullptr;
     if (!s_dev) {
@@ -1117,7 +1107,7 @@ extern "C" int cvhip_orb_extract_batch(cvhip_device *dev, uint32_t n_images, con
                 CVHIP_TRY_HIP(mem.alloc(&j.d_mm, 2));
                 CVHIP_TRY_HIP(mem.alloc(&j.d_counts, j.nblocks));
                 j.d_total = d_totals + i;
-                CVHIP_TRY_HIP(hipMemcpyAsync(j.d_img, j.img, j.n, dev_ptr(j.img) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
+                CVHIP_TRY_HIP(hipMemcpyAsync(j.d_img, j.img, j.n, on_device(j.img) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
                 OrbJobDev &t = h_tbl[i];
                 std::memset(&t, 0, sizeof(t));
                 t.img = j.d_img;
@@ -1167,7 +1157,7 @@ extern "C" int cvhip_orb_extract_batch(cvhip_device *dev, uint32_t n_images, con
                 CVHIP_TRY_HIP(mem.alloc(&j.d_mm, 2));
                 CVHIP_TRY_HIP(mem.alloc(&j.d_counts, j.nblocks));
                 CVHIP_TRY_HIP(mem.alloc(&j.d_total, 1));
-                CVHIP_TRY_HIP(hipMemcpyAsync(j.d_img, j.img, j.n, dev_ptr(j.img) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
+                CVHIP_TRY_HIP(hipMemcpyAsync(j.d_img, j.img, j.n, on_device(j.img) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
                 CVHIP_TRY_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(j.d_mm), 255, 1, s)); // {min, max} = {255, 0}
                 CVHIP_TRY_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(j.d_mm + 1), 0, 1, s));
                 const unsigned rblocks = (unsigned)std::min<size_t>(2048, (j.n + 255) / 256);
@@ -1262,8 +1252,8 @@ extern "C" int cvhip_orb_extract_batch(cvhip_device *dev, uint32_t n_images, con
                 OrbJobDev &t = h_tbl[i];
                 std::memset(&t, 0, sizeof(t));
                 j.d_pack = d_packs + j.pack_off / sizeof(uint32_t);
-                j.xy_dev = dev_ptr(j.out_xy);
-                j.desc_dev = dev_ptr(j.out_desc);
+                j.xy_dev = on_device(j.out_xy);
+                j.desc_dev = on_device(j.out_desc);
                 j.d_idx_sorted = d_idx_plain + key_off[i];
                 double *d_blur_h = nullptr;
                 if (j.n_fast) {
@@ -1386,8 +1376,8 @@ extern "C" int cvhip_orb_extract_batch(cvhip_device *dev, uint32_t n_images, con
             CVHIP_TRY_HIP(mem.alloc(&j.d_desc, (size_t)j.count * 8));
             CVHIP_TRY_HIP(mem.alloc(&j.d_flags, j.count));
             CVHIP_TRY_HIP(mem.alloc(&j.d_pack, j.pack_bytes / sizeof(uint32_t)));
-            j.xy_dev = dev_ptr(j.out_xy);
-            j.desc_dev = dev_ptr(j.out_desc);
+            j.xy_dev = on_device(j.out_xy);
+            j.desc_dev = on_device(j.out_desc);
             hipLaunchKernelGGL(moments_kernel, dim3(j.count), dim3(64), 0, s, j.d_blur, j.w, j.h, j.d_kp, j.d_idx_sorted, j.count, j.n_fast, j.d_mom,
                                j.d_sc);
             if (i == 0) report(0.35f);
@@ -1536,7 +1526,7 @@ extern "C" int cvhip_match_points(cvhip_device *dev, const uint32_t *xy1, const 
     CVHIP_TRY_HIP(mem.alloc(&d_om, (size_t)n1 * 4));
     CVHIP_TRY_HIP(mem.alloc(&d_od, n1));
     CVHIP_TRY_HIP(mem.alloc(&d_n, 1));
-    auto kind = [](const void *p) { return dev_ptr(p) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice; };
+    auto kind = [](const void *p) { return on_device(p) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice; };
     CVHIP_TRY_HIP(hipMemcpyAsync(d_xy1, xy1, (size_t)n1 * 8, kind(xy1), s));
     CVHIP_TRY_HIP(hipMemcpyAsync(d_xy2, xy2, (size_t)n2 * 8, kind(xy2), s));
     CVHIP_TRY_HIP(hipMemcpyAsync(d_desc1, desc1, (size_t)n1 * 32, kind(desc1), s));
@@ -1586,10 +1576,10 @@ extern "C" int cvhip_match_points(cvhip_device *dev, const uint32_t *xy1, const 
     CVHIP_TRY_HIP(hipGetLastError());
     if (n) {
         CVHIP_TRY_HIP(hipMemcpy(out_matches, d_om, (size_t)n * 16,
-                                dev_ptr(out_matches) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost));
+                                on_device(out_matches) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost));
         if (out_dist)
             CVHIP_TRY_HIP(hipMemcpy(out_dist, d_od, (size_t)n * 4,
-                                    dev_ptr(out_dist) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost));
+                                    on_device(out_dist) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost));
     }
     *out_n = n;
     return CVHIP_OK;

@@ -462,38 +462,6 @@ __global__ __launch_bounds__(BLOCK) void pose_best_kernel(const PoseCand *__rest
 }
 
 // ---- host ----------------------------------------------------------------------------------------------------------------
-bool dev_ptr(const void *p)
-{
-    hipPointerAttribute_t attr;
-    if (hipPointerGetAttributes(&attr, p) != hipSuccess) {
-        (void)hipGetLastError();
-        return false;
-    }
-    return attr.type == hipMemoryTypeDevice || attr.type == hipMemoryTypeManaged;
-}
-
-struct DevMem {
-    std::vector<void *> ptrs;
-    ~DevMem()
-    {
-        for (void *p : ptrs) (void)hipFree(p);
-    }
-    template <class T>
-    hipError_t alloc(T **p, size_t bytes)
-    {
-        *p = nullptr;
-        hipError_t e = hipMalloc((void **)p, bytes ? bytes : 8);
-        if (e == hipSuccess) ptrs.push_back(*p);
-        return e;
-    }
-};
-
-#define POSE_TRY(what, expr)                                                                                       \
-    do {                                                                                                           \
-        hipError_t _e = (expr);                                                                                    \
-        if (_e != hipSuccess) return cvhip::fail(CVHIP_ERR_DEVICE, std::string(what) + ": " + #expr + ": " + hipGetErrorString(_e)); \
-    } while (0)
-
 // 3 x 3 SVD by one-sided Jacobi on the columns: A V = U S, singular values in decreasing order (as nalgebra's `svd`
 // returns them).  A column whose singular value is below 1e-300 gets U's column from the cross product of the other two.
 void svd3(const double A[9], double U[9], double S[3], double V[9])
@@ -629,24 +597,22 @@ extern "C" int cvhip_triangulate_tracks(cvhip_device *dev, const int32_t *tracks
     PoseViews pv;
     set_views(pv, m, projections, has_projection, 0, nullptr);
     hipStream_t s = dev->d.stream;
-    DevMem mem;
-    int2 *d_tr;
-    double *d_pts;
-    uint8_t *d_ok;
-    PoseViews *d_pv;
-    POSE_TRY("triangulate_tracks", mem.alloc(&d_pv, sizeof(PoseViews)));
-    POSE_TRY("triangulate_tracks", hipMemcpyAsync(d_pv, &pv, sizeof(pv), hipMemcpyHostToDevice, s));
-    POSE_TRY("triangulate_tracks", mem.alloc(&d_tr, (size_t)n * m * sizeof(int2)));
-    POSE_TRY("triangulate_tracks", mem.alloc(&d_pts, (size_t)n * 24));
-    POSE_TRY("triangulate_tracks", mem.alloc(&d_ok, (size_t)n));
-    POSE_TRY("triangulate_tracks", hipMemcpyAsync(d_tr, tracks, (size_t)n * m * sizeof(int2),
-                                                  dev_ptr(tracks) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
+    cvhip::CallScratch sc;
+    const int2 *d_tr = nullptr;
+    double *d_pts = nullptr;
+    uint8_t *d_ok = nullptr;
+    PoseViews *d_pv = nullptr;
+    const char *const what = "triangulate_tracks";
+    CVHIP_TRY_HIP_AT(what, sc.alloc(&d_pv, 1));
+    CVHIP_TRY_HIP_AT(what, hipMemcpyAsync(d_pv, &pv, sizeof(pv), hipMemcpyHostToDevice, s));
+    CVHIP_TRY_HIP_AT(what, sc.input(reinterpret_cast<const int2 *>(tracks), (size_t)n * m, &d_tr, s));
+    CVHIP_TRY_HIP_AT(what, sc.output(out_points, (size_t)n * 3, &d_pts));
+    CVHIP_TRY_HIP_AT(what, sc.output(out_ok, (size_t)n, &d_ok));
     hipLaunchKernelGGL(pose_triangulate_kernel, dim3((unsigned)((n + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, s, d_tr, n, d_pv, d_pts, d_ok);
-    POSE_TRY("triangulate_tracks", hipGetLastError());
-    POSE_TRY("triangulate_tracks", hipMemcpyAsync(out_points, d_pts, (size_t)n * 24,
-                                                  dev_ptr(out_points) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s));
-    POSE_TRY("triangulate_tracks", hipMemcpyAsync(out_ok, d_ok, (size_t)n, dev_ptr(out_ok) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s));
-    POSE_TRY("triangulate_tracks", hipStreamSynchronize(s));
+    CVHIP_TRY_HIP_AT(what, hipGetLastError());
+    CVHIP_TRY_HIP_AT(what, sc.copy_out(out_points, d_pts, (size_t)n * 3, s));
+    CVHIP_TRY_HIP_AT(what, sc.copy_out(out_ok, d_ok, (size_t)n, s));
+    CVHIP_TRY_HIP_AT(what, hipStreamSynchronize(s));
     return CVHIP_OK;
 }
 
@@ -699,19 +665,17 @@ extern "C" int cvhip_find_projection_matrix(cvhip_device *dev, const double *F, 
     uint64_t counts[4] = {0, 0, 0, 0};
     if (n) {
         hipStream_t s = dev->d.stream;
-        DevMem mem;
+        cvhip::CallScratch sc;
         const uint32_t nb = (uint32_t)((n + BLOCK - 1) / BLOCK);
-        int2 *d_tr;
-        uint32_t *d_cnt;
-        POSE_TRY("find_projection_matrix", mem.alloc(&d_tr, (size_t)n * 2 * sizeof(int2)));
-        POSE_TRY("find_projection_matrix", mem.alloc(&d_cnt, (size_t)nb * 4 * 4));
-        POSE_TRY("find_projection_matrix", hipMemcpyAsync(d_tr, short_tracks, (size_t)n * 2 * sizeof(int2),
-                                                          dev_ptr(short_tracks) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
+        const int2 *d_tr = nullptr;
+        uint32_t *d_cnt = nullptr;
+        CVHIP_TRY_HIP_AT("find_projection_matrix", sc.input(reinterpret_cast<const int2 *>(short_tracks), (size_t)n * 2, &d_tr, s));
+        CVHIP_TRY_HIP_AT("find_projection_matrix", sc.alloc(&d_cnt, (size_t)nb * 4));
         hipLaunchKernelGGL(pose_cheirality_kernel, dim3(nb), dim3(BLOCK), 0, s, d_tr, n, ch, d_cnt);
-        POSE_TRY("find_projection_matrix", hipGetLastError());
+        CVHIP_TRY_HIP_AT("find_projection_matrix", hipGetLastError());
         std::vector<uint32_t> h((size_t)nb * 4);
-        POSE_TRY("find_projection_matrix", hipMemcpyAsync(h.data(), d_cnt, h.size() * 4, hipMemcpyDeviceToHost, s));
-        POSE_TRY("find_projection_matrix", hipStreamSynchronize(s));
+        CVHIP_TRY_HIP_AT("find_projection_matrix", hipMemcpyAsync(h.data(), d_cnt, h.size() * 4, hipMemcpyDeviceToHost, s));
+        CVHIP_TRY_HIP_AT("find_projection_matrix", hipStreamSynchronize(s));
         for (int c = 0; c < 4; c++)
             for (uint32_t b = 0; b < nb; b++) counts[c] += h[(size_t)c * nb + b];
     }
@@ -731,7 +695,7 @@ extern "C" int cvhip_find_projection_matrix(cvhip_device *dev, const double *F, 
 namespace {
 
 struct PoseRun {
-    DevMem mem;
+    cvhip::CallScratch mem;
     int2 *tr = nullptr;
     double *pts = nullptr;
     uint32_t len = 0;
@@ -755,15 +719,15 @@ int pose_setup(PoseRun &r, cvhip_device *dev, const int32_t *tracks, uint64_t n,
     set_views(r.pv, m, projections, has_projection, image_index, K);
     r.pv.has &= ~(1u << image_index); // the image's own slot is the candidate's
     hipStream_t s = dev->d.stream;
-    POSE_TRY(what, r.mem.alloc(&r.d_pv, sizeof(PoseViews)));
-    POSE_TRY(what, hipMemcpyAsync(r.d_pv, &r.pv, sizeof(PoseViews), hipMemcpyHostToDevice, s));
-    POSE_TRY(what, r.mem.alloc(&r.tr, lt.size() * sizeof(int2)));
-    POSE_TRY(what, r.mem.alloc(&r.pts, lp.size() * 8));
+    CVHIP_TRY_HIP_AT(what, r.mem.alloc(&r.d_pv, 1));
+    CVHIP_TRY_HIP_AT(what, hipMemcpyAsync(r.d_pv, &r.pv, sizeof(PoseViews), hipMemcpyHostToDevice, s));
+    CVHIP_TRY_HIP_AT(what, r.mem.alloc(&r.tr, lt.size()));
+    CVHIP_TRY_HIP_AT(what, r.mem.alloc(&r.pts, lp.size()));
     if (r.len) {
-        POSE_TRY(what, hipMemcpyAsync(r.tr, lt.data(), lt.size() * sizeof(int2), hipMemcpyHostToDevice, s));
-        POSE_TRY(what, hipMemcpyAsync(r.pts, lp.data(), lp.size() * 8, hipMemcpyHostToDevice, s));
+        CVHIP_TRY_HIP_AT(what, hipMemcpyAsync(r.tr, lt.data(), lt.size() * sizeof(int2), hipMemcpyHostToDevice, s));
+        CVHIP_TRY_HIP_AT(what, hipMemcpyAsync(r.pts, lp.data(), lp.size() * 8, hipMemcpyHostToDevice, s));
     }
-    POSE_TRY(what, hipStreamSynchronize(s)); // (the host vectors and r.pv's copy are read before they go)
+    CVHIP_TRY_HIP_AT(what, hipStreamSynchronize(s)); // (the host vectors and r.pv's copy are read before they go)
     return CVHIP_OK;
 }
 
@@ -789,9 +753,9 @@ extern "C" int cvhip_recover_pose(cvhip_device *dev, const int32_t *tracks, uint
     PoseCand *cands;
     PoseScore *scores;
     PoseBest *best;
-    POSE_TRY("recover_pose", r.mem.alloc(&cands, sizeof(PoseCand) * NC));
-    POSE_TRY("recover_pose", r.mem.alloc(&scores, sizeof(PoseScore) * NC));
-    POSE_TRY("recover_pose", r.mem.alloc(&best, sizeof(PoseBest)));
+    CVHIP_TRY_HIP_AT("recover_pose", r.mem.alloc(&cands, NC));
+    CVHIP_TRY_HIP_AT("recover_pose", r.mem.alloc(&scores, NC));
+    CVHIP_TRY_HIP_AT("recover_pose", r.mem.alloc(&best, 1));
     // best_result = (Camera::from_matrix(k, I, 0), 0, f64::MAX) (:1072-1076)
     PoseBest hb;
     std::memset(&hb, 0, sizeof(hb));
@@ -801,7 +765,7 @@ extern "C" int cvhip_recover_pose(cvhip_device *dev, const int32_t *tracks, uint
     const double Id[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, z3[3] = {0, 0, 0};
     std::memcpy(hb.R, Id, 72);
     given_projection(K, Id, z3, hb.P);
-    POSE_TRY("recover_pose", hipMemcpyAsync(best, &hb, sizeof(hb), hipMemcpyHostToDevice, s));
+    CVHIP_TRY_HIP_AT("recover_pose", hipMemcpyAsync(best, &hb, sizeof(hb), hipMemcpyHostToDevice, s));
     const uint32_t max_dim = max_dimension;
     const double inl_t = RANSAC_INLIERS_T * (double)max_dim, pts_t = RANSAC_T * (double)max_dim;
     uint32_t batches = 0;
@@ -810,9 +774,9 @@ extern "C" int cvhip_recover_pose(cvhip_device *dev, const int32_t *tracks, uint
                            (unsigned long long)seed, batch, H, (const uint32_t *)nullptr, inl_t, cands);
         hipLaunchKernelGGL(pose_score_kernel, dim3(NC), dim3(BLOCK), 0, s, r.tr, r.len, r.d_pv, cands, pts_t, scores);
         hipLaunchKernelGGL(pose_best_kernel, dim3(1), dim3(BLOCK), 0, s, cands, scores, NC, batch, best);
-        POSE_TRY("recover_pose", hipGetLastError());
-        POSE_TRY("recover_pose", hipMemcpyAsync(&hb, best, sizeof(hb), hipMemcpyDeviceToHost, s));
-        POSE_TRY("recover_pose", hipStreamSynchronize(s));
+        CVHIP_TRY_HIP_AT("recover_pose", hipGetLastError());
+        CVHIP_TRY_HIP_AT("recover_pose", hipMemcpyAsync(&hb, best, sizeof(hb), hipMemcpyDeviceToHost, s));
+        CVHIP_TRY_HIP_AT("recover_pose", hipStreamSynchronize(s));
         batches = batch + 1;
         if (progress) progress(user, 0.02f + 0.98f * ((float)(batches * H) / (float)RANSAC_K));
         if (hb.count >= ransac_d_early_exit) break; // :1126-1129
@@ -846,20 +810,20 @@ extern "C" int cvhip_recover_pose_models(cvhip_device *dev, const int32_t *track
     PoseCand *cands;
     PoseScore *scores;
     uint32_t *d_idx;
-    POSE_TRY("recover_pose_models", r.mem.alloc(&cands, sizeof(PoseCand) * NC));
-    POSE_TRY("recover_pose_models", r.mem.alloc(&scores, sizeof(PoseScore) * NC));
-    POSE_TRY("recover_pose_models", r.mem.alloc(&d_idx, 12ull * B));
-    POSE_TRY("recover_pose_models", hipMemcpyAsync(d_idx, sample_idx, 12ull * B, hipMemcpyHostToDevice, s));
+    CVHIP_TRY_HIP_AT("recover_pose_models", r.mem.alloc(&cands, NC));
+    CVHIP_TRY_HIP_AT("recover_pose_models", r.mem.alloc(&scores, NC));
+    CVHIP_TRY_HIP_AT("recover_pose_models", r.mem.alloc(&d_idx, 3 * (size_t)B));
+    CVHIP_TRY_HIP_AT("recover_pose_models", hipMemcpyAsync(d_idx, sample_idx, 12ull * B, hipMemcpyHostToDevice, s));
     const double inl_t = RANSAC_INLIERS_T * (double)max_dimension, pts_t = RANSAC_T * (double)max_dimension;
     hipLaunchKernelGGL(pose_hypothesis_kernel, dim3((B + 63) / 64), dim3(64), 0, s, r.tr, r.pts, r.len, r.d_pv, 0ull, 0u, B,
                        (const uint32_t *)d_idx, inl_t, cands);
     hipLaunchKernelGGL(pose_score_kernel, dim3(NC), dim3(BLOCK), 0, s, r.tr, r.len, r.d_pv, cands, pts_t, scores);
-    POSE_TRY("recover_pose_models", hipGetLastError());
+    CVHIP_TRY_HIP_AT("recover_pose_models", hipGetLastError());
     std::vector<PoseCand> hc(NC);
     std::vector<PoseScore> hs(NC);
-    POSE_TRY("recover_pose_models", hipMemcpyAsync(hc.data(), cands, sizeof(PoseCand) * NC, hipMemcpyDeviceToHost, s));
-    POSE_TRY("recover_pose_models", hipMemcpyAsync(hs.data(), scores, sizeof(PoseScore) * NC, hipMemcpyDeviceToHost, s));
-    POSE_TRY("recover_pose_models", hipStreamSynchronize(s));
+    CVHIP_TRY_HIP_AT("recover_pose_models", hipMemcpyAsync(hc.data(), cands, sizeof(PoseCand) * NC, hipMemcpyDeviceToHost, s));
+    CVHIP_TRY_HIP_AT("recover_pose_models", hipMemcpyAsync(hs.data(), scores, sizeof(PoseScore) * NC, hipMemcpyDeviceToHost, s));
+    CVHIP_TRY_HIP_AT("recover_pose_models", hipStreamSynchronize(s));
     for (uint32_t c = 0; c < NC; c++) {
         double *o = out_pose + 27ull * c;
         const bool any = hc[c].status != 0;

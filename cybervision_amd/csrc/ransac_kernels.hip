@@ -2991,18 +2991,6 @@ __global__ void ransac_refit_mask_kernel(const double *__restrict__ F, const uin
 
 using namespace cvhip;
 
-namespace {
-bool dev_ptr(const void *p)
-{
-    hipPointerAttribute_t attr;
-    if (hipPointerGetAttributes(&attr, p) != hipSuccess) {
-        (void)hipGetLastError();
-        return false;
-    }
-    return attr.type == hipMemoryTypeDevice || attr.type == hipMemoryTypeManaged;
-}
-} // namespace
-
 extern "C" int cvhip_ransac_score(cvhip_device *dev, const double *F, uint32_t H, const uint32_t *matches,
                                   uint32_t N, double t, uint32_t *out_count, double *out_err_sum)
 {
@@ -3012,10 +3000,10 @@ extern "C" int cvhip_ransac_score(cvhip_device *dev, const double *F, uint32_t H
     CVHIP_TRY_HIP(hipSetDevice(dev->d.ordinal));
     hipStream_t s = dev->d.stream;
     // the kernel reads matches as 16-byte vectors: a device pointer that is not 16-byte aligned is copied too
-    const bool f_dev = dev_ptr(F),
-               m_dev = N ? (dev_ptr(matches) && (reinterpret_cast<uintptr_t>(matches) & 15u) == 0) : true,
-               c_dev = dev_ptr(out_count),
-               e_dev = dev_ptr(out_err_sum);
+    const bool f_dev = on_device(F),
+               m_dev = N ? (on_device(matches) && (reinterpret_cast<uintptr_t>(matches) & 15u) == 0) : true,
+               c_dev = on_device(out_count),
+               e_dev = on_device(out_err_sum);
     double *d_F = const_cast<double *>(F), *d_err = out_err_sum;
     uint32_t *d_m = const_cast<uint32_t *>(matches), *d_cnt = out_count;
     hipError_t e = hipSuccess;
@@ -3027,7 +3015,7 @@ extern "C" int cvhip_ransac_score(cvhip_device *dev, const double *F, uint32_t H
         e = hipMalloc(&d_m, (size_t)N * 4 * sizeof(uint32_t));
         if (e == hipSuccess)
             e = hipMemcpyAsync(d_m, matches, (size_t)N * 4 * sizeof(uint32_t),
-                               dev_ptr(matches) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s);
+                               on_device(matches) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s);
     }
     if (e == hipSuccess && !c_dev) e = hipMalloc(&d_cnt, (size_t)H * sizeof(uint32_t));
     if (e == hipSuccess && !e_dev) e = hipMalloc(&d_err, (size_t)H * sizeof(double));
@@ -3068,8 +3056,8 @@ extern "C" int cvhip_ransac_round_score(cvhip_device *dev, const double *F, uint
     CVHIP_TRY_HIP(mem.alloc(&d_cnt, H));
     CVHIP_TRY_HIP(mem.alloc(&d_live, (size_t)H + 4 + TIED_CAP));
     CVHIP_TRY_HIP(mem.alloc(&d_best, 1));
-    CVHIP_TRY_HIP(hipMemcpyAsync(d_F, F, (size_t)H * 9 * sizeof(double), dev_ptr(F) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
-    if (N) CVHIP_TRY_HIP(hipMemcpyAsync(d_m, matches, (size_t)N * 16, dev_ptr(matches) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
+    CVHIP_TRY_HIP(hipMemcpyAsync(d_F, F, (size_t)H * 9 * sizeof(double), on_device(F) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
+    if (N) CVHIP_TRY_HIP(hipMemcpyAsync(d_m, matches, (size_t)N * 16, on_device(matches) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
     CVHIP_TRY_HIP(hipMemsetAsync(d_best, 0, sizeof(RansacBest), s));
     CVHIP_TRY_HIP(hipMemsetAsync(d_err, 0, std::max<size_t>(H, 64) * sizeof(double), s));
     float4 *d_mf = nullptr;
@@ -3081,8 +3069,8 @@ extern "C" int cvhip_ransac_round_score(cvhip_device *dev, const double *F, uint
     launch_ransac_score_round(d_F, H, d_m, d_m, d_mf, N, t, d_live, d_live + H, d_live + H + 1, d_live + H + 3 + TIED_CAP, false, false, 0u, d_best,
                               d_cnt, d_err, s, nullptr, 0u, 0xFFFFFFFFu, dev->d.ransac_count_mfma ? &ws : nullptr);
     CVHIP_TRY_HIP(hipGetLastError());
-    CVHIP_TRY_HIP(hipMemcpyAsync(out_count, d_cnt, (size_t)H * sizeof(uint32_t), dev_ptr(out_count) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s));
-    CVHIP_TRY_HIP(hipMemcpyAsync(out_err_sum, d_err, (size_t)H * sizeof(double), dev_ptr(out_err_sum) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s));
+    CVHIP_TRY_HIP(hipMemcpyAsync(out_count, d_cnt, (size_t)H * sizeof(uint32_t), on_device(out_count) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s));
+    CVHIP_TRY_HIP(hipMemcpyAsync(out_err_sum, d_err, (size_t)H * sizeof(double), on_device(out_err_sum) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s));
     CVHIP_TRY_HIP(hipStreamSynchronize(s));
     return CVHIP_OK;
 }
@@ -3121,8 +3109,8 @@ extern "C" int cvhip_ransac_rounds_pick(cvhip_device *dev, const double *F, uint
     CountMfmaWs ws;
     if (dev->d.ransac_count_mfma) CVHIP_TRY_HIP(alloc_count_mfma(mem, N, per, ws));
     uint32_t *const d_tied = d_live + live_words, *const d_coord_max = d_tied + 2 + TIED_CAP;
-    CVHIP_TRY_HIP(hipMemcpyAsync(d_F, F, (size_t)H * 9 * sizeof(double), dev_ptr(F) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
-    CVHIP_TRY_HIP(hipMemcpyAsync(d_m, matches, (size_t)N * 16, dev_ptr(matches) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
+    CVHIP_TRY_HIP(hipMemcpyAsync(d_F, F, (size_t)H * 9 * sizeof(double), on_device(F) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
+    CVHIP_TRY_HIP(hipMemcpyAsync(d_m, matches, (size_t)N * 16, on_device(matches) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
     CVHIP_TRY_HIP(hipMemcpyAsync(d_mo, d_m, (size_t)N * 16, hipMemcpyDeviceToDevice, s));
     CVHIP_TRY_HIP(hipMemsetAsync(d_best, 0, sizeof(RansacBest), s));
     CVHIP_TRY_HIP(hipMemsetAsync(d_cand, 0, 2 * sizeof(uint32_t), s));
@@ -3150,7 +3138,7 @@ extern "C" int cvhip_ransac_rounds_pick(cvhip_device *dev, const double *F, uint
     std::memcpy(out_F, h_best.f, sizeof(h_best.f));
     *out_count = h_best.matches_count;
     if (h_best.err_known) *out_mean_error = h_best.best_error;
-    if (!dev_ptr(F)) // (the index: the first hypothesis with exactly these nine doubles)
+    if (!on_device(F)) // (the index: the first hypothesis with exactly these nine doubles)
         for (uint32_t h = 0; h < H && *out_index < 0; h++)
             if (std::memcmp(F + (size_t)h * 9, h_best.f, sizeof(h_best.f)) == 0) *out_index = (int64_t)h;
     return CVHIP_OK;
@@ -3206,7 +3194,7 @@ extern "C" int cvhip_ransac_affine(cvhip_device *dev, const uint32_t *matches, u
     if (e == hipSuccess) e = hipMalloc(&d_mask, N);
     uint32_t *d_live = nullptr;
     if (e == hipSuccess) e = hipMalloc(&d_live, ((size_t)CHECK_INTERVAL + 4 + TIED_CAP) * sizeof(uint32_t));
-    if (e == hipSuccess) e = hipMemcpyAsync(d_m, matches, (size_t)N * 16, dev_ptr(matches) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_m, matches, (size_t)N * 16, on_device(matches) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s);
     if (e == hipSuccess) e = hipMemsetAsync(d_best, 0, sizeof(RansacBest), s);
     float4 *d_mf = nullptr;
     if (e == hipSuccess) e = hipMalloc(&d_mf, (size_t)ransac_padded(N) * sizeof(float4));
@@ -3335,7 +3323,7 @@ int ransac_rounds(cvhip_device *dev, DevAllocs &mem, const uint32_t *matches, ui
     if (e == hipSuccess && ws) e = alloc_count_mfma(mem, N, std::max<uint32_t>(GEN_BATCH * H, late ? late->cap : 0u), mfma_ws);
     if (e == hipSuccess) e = hipMemsetAsync(d_cand, 0, 2 * sizeof(uint32_t), s);
     if (e == hipSuccess)
-        e = hipMemcpyAsync(d_m, matches, (size_t)N * 16, dev_ptr(matches) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s);
+        e = hipMemcpyAsync(d_m, matches, (size_t)N * 16, on_device(matches) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s);
     if (e == hipSuccess && late) e = hipMemsetAsync(late->list, 0, sizeof(uint32_t), s);
     if (e == hipSuccess && late) e = hipMemsetAsync(late->F, 0xFF, (size_t)late->cap * 9 * sizeof(double), s); // (all ones: NaN)
     // (the generators need the list and nothing else of what follows: their event goes right behind the upload)
@@ -4188,8 +4176,8 @@ extern "C" int cvhip_optimize_perspective_f_device(cvhip_device *dev, const doub
     CVHIP_TRY_HIP(mem.alloc(&d_J, (size_t)n * 7));
     CVHIP_TRY_HIP(mem.alloc(&d_F, 18));
     CVHIP_TRY_HIP(mem.alloc(&d_ref, 1));
-    if (n) CVHIP_TRY_HIP(hipMemcpyAsync(d_inl, matches, (size_t)n * 16, dev_ptr(matches) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
-    CVHIP_TRY_HIP(hipMemcpyAsync(d_F, F, 9 * sizeof(double), dev_ptr(F) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
+    if (n) CVHIP_TRY_HIP(hipMemcpyAsync(d_inl, matches, (size_t)n * 16, on_device(matches) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
+    CVHIP_TRY_HIP(hipMemcpyAsync(d_F, F, 9 * sizeof(double), on_device(F) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
     hipLaunchKernelGGL(ransac_refit_kernel, dim3(1), dim3(refit::THREADS), 0, s, reinterpret_cast<const uint4 *>(d_inl), n,
                        (const uint32_t *)nullptr, d_r, d_rn, d_J, (const double *)d_F, d_F + 9, d_ref);
     CVHIP_TRY_HIP(hipGetLastError());
@@ -4242,14 +4230,14 @@ extern "C" int cvhip_fits_model(cvhip_device *dev, const double *F, const uint32
     hipError_t e = hipMalloc(&d_m, (size_t)N * 16);
     if (e == hipSuccess) e = hipMalloc(&d_best, sizeof(RansacBest));
     if (e == hipSuccess) e = hipMalloc(&d_mask, N);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_m, matches, (size_t)N * 16, dev_ptr(matches) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_m, matches, (size_t)N * 16, on_device(matches) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s);
     if (e == hipSuccess) e = hipMemcpyAsync(d_best, &h_best, sizeof(RansacBest), hipMemcpyHostToDevice, s);
     if (e == hipSuccess) {
         hipLaunchKernelGGL(ransac_inlier_mask_kernel, dim3((N + 255) / 256), dim3(256), 0, s, d_best,
                            reinterpret_cast<const uint4 *>(d_m), N, t, d_mask);
         e = hipGetLastError();
     }
-    if (e == hipSuccess) e = hipMemcpyAsync(out_mask, d_mask, N, dev_ptr(out_mask) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(out_mask, d_mask, N, on_device(out_mask) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     (void)hipFree(d_m);
     (void)hipFree(d_best);

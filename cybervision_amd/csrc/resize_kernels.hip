@@ -107,18 +107,6 @@ __global__ __launch_bounds__(256) void lanczos_horizontal_kernel(const float *__
 
 using namespace cvhip;
 
-namespace {
-bool resident(const void *p)
-{
-    hipPointerAttribute_t attr;
-    if (hipPointerGetAttributes(&attr, p) != hipSuccess) {
-        (void)hipGetLastError();
-        return false;
-    }
-    return attr.type == hipMemoryTypeDevice || attr.type == hipMemoryTypeManaged;
-}
-} // namespace
-
 extern "C" int cvhip_resize_lanczos3(cvhip_device *dev, const uint8_t *src, uint32_t w, uint32_t h, uint8_t *dst,
                                      uint32_t nw, uint32_t nh)
 {
@@ -127,7 +115,7 @@ extern "C" int cvhip_resize_lanczos3(cvhip_device *dev, const uint8_t *src, uint
     if (w > 65535 || h > 65535 || nw > 65535 || nh > 65535) return fail(CVHIP_ERR_UNSUPPORTED, "image dimension above 65535");
     CVHIP_TRY_HIP(hipSetDevice(dev->d.ordinal));
     hipStream_t s = dev->d.stream;
-    const bool src_dev = resident(src), dst_dev = resident(dst);
+    const bool src_dev = on_device(src), dst_dev = on_device(dst);
     try {
         if (nw == w && nh == h) { // "if the new dimensions are the same as the old, make a copy instead of resampling"
             const hipMemcpyKind kind = src_dev ? (dst_dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost)

@@ -359,18 +359,6 @@ void launch_merge_tracks(const int2 *tracks, unsigned long long n, uint32_t m, u
 
 using namespace cvhip;
 
-namespace {
-bool on_device(const void *p)
-{
-    hipPointerAttribute_t attr;
-    if (hipPointerGetAttributes(&attr, p) != hipSuccess) {
-        (void)hipGetLastError();
-        return false;
-    }
-    return attr.type == hipMemoryTypeDevice || attr.type == hipMemoryTypeManaged;
-}
-} // namespace
-
 extern "C" int cvhip_extend_tracks(cvhip_ctx *ctx, const int32_t *track_p1, uint64_t n_tracks, uint32_t max_dimension2,
                                    int32_t *out_track_p2, uint32_t *out_new_p1, uint32_t *out_new_p2, uint64_t cap,
                                    uint64_t *out_n_new)
@@ -400,25 +388,18 @@ extern "C" int cvhip_extend_tracks(cvhip_ctx *ctx, const int32_t *track_p1, uint
     uint32_t *counts = ctx->range, *total = ctx->range + nblocks, *oob = ctx->range + nblocks + 1;
     // EXTEND_TRACKS_SEARCH_RADIUS = 3, TRACKS_RADIUS_DENOMINATOR = 1000 (triangulation.rs:16, 19, 1346-1350)
     const uint32_t radius = max_dimension2 > 1000 ? (uint32_t)((uint64_t)3 * max_dimension2 / 1000) : 3u;
-    const bool tp1_dev = n_tracks ? on_device(track_p1) : true, tp2_dev = n_tracks ? on_device(out_track_p2) : true;
-    const bool n1_dev = cap ? on_device(out_new_p1) : true, n2_dev = cap ? on_device(out_new_p2) : true;
-    // scratch copies of host arrays (only these are freed; the caller's pointers are chosen at launch)
-    int2 *s_tp1 = nullptr, *s_tp2 = nullptr;
-    uint32_t *s_n1 = nullptr, *s_n2 = nullptr;
+    CallScratch sc;
+    const int2 *d_tp1 = nullptr;
+    int2 *const tp2 = reinterpret_cast<int2 *>(out_track_p2), *d_tp2 = nullptr;
+    uint32_t *d_n1 = nullptr, *d_n2 = nullptr;
+    uint32_t h_total = 0, h_oob = 0;
     hipError_t e = hipMemsetAsync(removed, 0, n, s);
     if (e == hipSuccess) e = hipMemsetAsync(oob, 0, sizeof(uint32_t), s);
-    if (e == hipSuccess && !tp1_dev) {
-        e = hipMalloc(&s_tp1, n_tracks * sizeof(int2));
-        if (e == hipSuccess) e = hipMemcpyAsync(s_tp1, track_p1, n_tracks * sizeof(int2), hipMemcpyHostToDevice, s);
-    }
-    if (e == hipSuccess && !tp2_dev) e = hipMalloc(&s_tp2, n_tracks * sizeof(int2));
-    if (e == hipSuccess && cap && !n1_dev) e = hipMalloc(&s_n1, (size_t)cap * 2 * sizeof(uint32_t));
-    if (e == hipSuccess && cap && !n2_dev) e = hipMalloc(&s_n2, (size_t)cap * 2 * sizeof(uint32_t));
-    uint32_t h_total = 0, h_oob = 0;
+    if (e == hipSuccess) e = sc.input(reinterpret_cast<const int2 *>(track_p1), (size_t)n_tracks, &d_tp1, s);
+    if (e == hipSuccess) e = sc.output(tp2, (size_t)n_tracks, &d_tp2);
+    if (e == hipSuccess) e = sc.output(out_new_p1, (size_t)cap * 2, &d_n1);
+    if (e == hipSuccess) e = sc.output(out_new_p2, (size_t)cap * 2, &d_n2);
     if (e == hipSuccess) {
-        const int2 *d_tp1 = tp1_dev ? reinterpret_cast<const int2 *>(track_p1) : s_tp1;
-        int2 *d_tp2 = tp2_dev ? reinterpret_cast<int2 *>(out_track_p2) : s_tp2;
-        uint32_t *d_n1 = n1_dev ? out_new_p1 : s_n1, *d_n2 = n2_dev ? out_new_p2 : s_n2;
         launch_extend_tracks_match(ds.cells[ds.cur], ds.lw, ds.lh, ds.k, ds.gw, ds.gh, d_tp1, n_tracks, radius, d_tp2, removed,
                                    oob, s);
         launch_extend_tracks_new(ds.cells[ds.cur], ds.lw, ds.lh, ds.k, ds.gw, ds.gh, removed, counts, total, d_n1, d_n2, cap, s);
@@ -426,17 +407,13 @@ extern "C" int cvhip_extend_tracks(cvhip_ctx *ctx, const int32_t *track_p1, uint
     }
     if (e == hipSuccess) e = hipMemcpyAsync(&h_total, total, sizeof(uint32_t), hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipMemcpyAsync(&h_oob, oob, sizeof(uint32_t), hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess && n_tracks && s_tp2)
-        e = hipMemcpyAsync(out_track_p2, s_tp2, n_tracks * sizeof(int2), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = sc.copy_out(tp2, d_tp2, (size_t)n_tracks, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
-    const uint64_t written = h_total < cap ? h_total : cap;
-    if (e == hipSuccess && written && s_n1)
-        e = hipMemcpy(out_new_p1, s_n1, (size_t)written * 2 * sizeof(uint32_t), hipMemcpyDeviceToHost);
-    if (e == hipSuccess && written && s_n2)
-        e = hipMemcpy(out_new_p2, s_n2, (size_t)written * 2 * sizeof(uint32_t), hipMemcpyDeviceToHost);
-    for (void *p : {(void *)s_tp1, (void *)s_tp2, (void *)s_n1, (void *)s_n2})
-        if (p) (void)hipFree(p);
-    if (e != hipSuccess) return fail(CVHIP_ERR_DEVICE, std::string("extend_tracks: ") + hipGetErrorString(e));
+    const size_t written = (size_t)std::min<uint64_t>(h_total, cap);
+    if (e == hipSuccess) e = sc.copy_out(out_new_p1, d_n1, written * 2, s);
+    if (e == hipSuccess) e = sc.copy_out(out_new_p2, d_n2, written * 2, s);
+    if (e == hipSuccess) e = sc.drain(s);
+    if (e != hipSuccess) return device_error("extend_tracks", e);
     if (h_oob) return fail(CVHIP_ERR_INVALID, "Index out of bounds (a merged match lies outside the image-1 grid; the reference panics here, data.rs:61-64)");
     *out_n_new = h_total;
     return CVHIP_OK;
@@ -466,22 +443,21 @@ extern "C" int cvhip_extend_tracks_matches(cvhip_device *dev, const uint32_t *in
     hipStream_t s = dev->d.stream;
     const size_t n = (size_t)w1 * h1;
     const uint32_t nblocks = (uint32_t)((n + 255) / 256);
+    CallScratch sc;
     uint32_t *d_cells = nullptr, *d_counts = nullptr, *d_n1 = nullptr, *d_n2 = nullptr;
     uint8_t *d_removed = nullptr;
-    int2 *d_tp1 = nullptr, *d_tp2 = nullptr;
-    const size_t capw = (size_t)std::max<uint64_t>(cap, 1);
-    hipError_t e = hipMalloc(&d_cells, n * 4);
-    if (e == hipSuccess) e = hipMalloc(&d_removed, n);
-    if (e == hipSuccess) e = hipMalloc(&d_counts, ((size_t)nblocks + 2) * 4);
-    if (e == hipSuccess) e = hipMalloc(&d_tp1, std::max<uint64_t>(n_tracks, 1) * sizeof(int2));
-    if (e == hipSuccess) e = hipMalloc(&d_tp2, std::max<uint64_t>(n_tracks, 1) * sizeof(int2));
-    if (e == hipSuccess) e = hipMalloc(&d_n1, capw * 8);
-    if (e == hipSuccess) e = hipMalloc(&d_n2, capw * 8);
+    const int2 *d_tp1 = nullptr;
+    int2 *const tp2 = reinterpret_cast<int2 *>(out_track_p2), *d_tp2 = nullptr;
+    hipError_t e = sc.copy_in(cells.data(), n, &d_cells, s);
+    if (e == hipSuccess) e = sc.alloc(&d_removed, n);
+    if (e == hipSuccess) e = sc.alloc(&d_counts, (size_t)nblocks + 2);
+    if (e == hipSuccess) e = sc.input(reinterpret_cast<const int2 *>(track_p1), (size_t)n_tracks, &d_tp1, s);
+    if (e == hipSuccess) e = sc.output(tp2, (size_t)n_tracks, &d_tp2);
+    if (e == hipSuccess) e = sc.output(out_new_p1, (size_t)cap * 2, &d_n1);
+    if (e == hipSuccess) e = sc.output(out_new_p2, (size_t)cap * 2, &d_n2);
     uint32_t *total = d_counts + nblocks, *oob = d_counts + nblocks + 1;
-    if (e == hipSuccess) e = hipMemcpyAsync(d_cells, cells.data(), n * 4, hipMemcpyHostToDevice, s);
     if (e == hipSuccess) e = hipMemsetAsync(d_removed, 0, n, s);
     if (e == hipSuccess) e = hipMemsetAsync(oob, 0, 4, s);
-    if (e == hipSuccess && n_tracks) e = hipMemcpyAsync(d_tp1, track_p1, n_tracks * sizeof(int2), hipMemcpyHostToDevice, s);
     // EXTEND_TRACKS_SEARCH_RADIUS = 3, TRACKS_RADIUS_DENOMINATOR = 1000 (triangulation.rs:16, 19, 1346-1350)
     const uint32_t radius = max_dimension2 > 1000 ? (uint32_t)((uint64_t)3 * max_dimension2 / 1000) : 3u;
     uint32_t h_total = 0, h_oob = 0;
@@ -492,21 +468,20 @@ extern "C" int cvhip_extend_tracks_matches(cvhip_device *dev, const uint32_t *in
     }
     if (e == hipSuccess) e = hipMemcpyAsync(&h_total, total, 4, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipMemcpyAsync(&h_oob, oob, 4, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess && n_tracks) e = hipMemcpyAsync(out_track_p2, d_tp2, n_tracks * sizeof(int2), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = sc.copy_out(tp2, d_tp2, (size_t)n_tracks, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
-    const uint64_t written = h_total < cap ? h_total : cap;
-    if (e == hipSuccess && written) e = hipMemcpy(out_new_p1, d_n1, (size_t)written * 8, hipMemcpyDeviceToHost);
-    if (e == hipSuccess && written) e = hipMemcpy(out_new_p2, d_n2, (size_t)written * 8, hipMemcpyDeviceToHost);
-    for (void *p : {(void *)d_cells, (void *)d_removed, (void *)d_counts, (void *)d_tp1, (void *)d_tp2, (void *)d_n1, (void *)d_n2})
-        if (p) (void)hipFree(p);
-    if (e != hipSuccess) return fail(CVHIP_ERR_DEVICE, std::string("extend_tracks_matches: ") + hipGetErrorString(e));
+    const size_t written = (size_t)std::min<uint64_t>(h_total, cap);
+    if (e == hipSuccess) e = sc.copy_out(out_new_p1, d_n1, written * 2, s);
+    if (e == hipSuccess) e = sc.copy_out(out_new_p2, d_n2, written * 2, s);
+    if (e == hipSuccess) e = sc.drain(s);
+    if (e != hipSuccess) return device_error("extend_tracks_matches", e);
     if (h_oob) return fail(CVHIP_ERR_INVALID, "Index out of bounds (a merged match lies outside the image-1 grid; the reference panics here, data.rs:61-64)");
     *out_n_new = h_total;
     return CVHIP_OK;
 }
 
 // merge_tracks (triangulation.rs:1421-1540) for image `image_index` of shape width x height over the n x m x 2 table;
-// kernels above.  Scratch is taken per call, as cvhip_extend_tracks_matches does.
+// kernels above.
 extern "C" int cvhip_merge_tracks(cvhip_device *dev, const int32_t *tracks, uint64_t n, uint32_t m, uint32_t image_index,
                                   uint32_t width, uint32_t height, uint64_t *out_rows, int32_t *out_tracks, uint64_t *out_n,
                                   uint64_t *out_stats)
@@ -524,36 +499,30 @@ extern "C" int cvhip_merge_tracks(cvhip_device *dev, const int32_t *tracks, uint
     const uint64_t md = std::max(width, height);
     const uint32_t r = md > 1000 ? (uint32_t)(2 * md / 1000) : 2u;
     const unsigned long long d2 = md > 1000 ? 10ull * 10ull * md / 1000 : 100ull;
-    const size_t cells = (size_t)width * height, row_bytes = (size_t)m * 2 * sizeof(int32_t);
+    const size_t cells = (size_t)width * height;
     const uint32_t cblocks = (uint32_t)((cells + 255) / 256);
-    const bool tr_dev = n ? on_device(tracks) : true;
-    const bool rows_dev = out_rows ? on_device(out_rows) : true, otr_dev = out_tracks ? on_device(out_tracks) : true;
+    const size_t tblocks = (size_t)((n + 255) / 256);
+    CallScratch sc;
     uint32_t *d_last = nullptr, *d_area = nullptr, *d_counts = nullptr, *d_parts = nullptr;
     uint8_t *d_occ = nullptr, *d_keep = nullptr;
-    MergeCounters *d_cnt = nullptr;
-    // scratch copies of host tables and outputs (only these are freed; the caller's pointers are chosen at launch)
-    int2 *s_tr = nullptr, *s_otr = nullptr;
-    unsigned long long *s_rows = nullptr;
-    const size_t nw = (size_t)std::max<uint64_t>(n, 1);
-    hipError_t e = hipMalloc(&d_last, cells * 4);
-    if (e == hipSuccess) e = hipMalloc(&d_area, cells * 4);
-    if (e == hipSuccess) e = hipMalloc(&d_occ, cells);
-    if (e == hipSuccess) e = hipMalloc(&d_keep, cells);
-    const size_t tblocks = (size_t)((n + 255) / 256);
-    if (e == hipSuccess) e = hipMalloc(&d_counts, (size_t)cblocks * 4);
-    if (e == hipSuccess) e = hipMalloc(&d_parts, (tblocks + 2 * (size_t)cblocks) * 4);
-    if (e == hipSuccess) e = hipMalloc(&d_cnt, sizeof(MergeCounters));
-    if (e == hipSuccess && !tr_dev) e = hipMalloc(&s_tr, nw * row_bytes);
-    if (e == hipSuccess && out_rows && !rows_dev) e = hipMalloc(&s_rows, nw * sizeof(unsigned long long));
-    if (e == hipSuccess && out_tracks && !otr_dev) e = hipMalloc(&s_otr, nw * row_bytes);
+    MergeCounters *d_cnt = nullptr, h_cnt{};
+    // the table and the outputs as rows of m points (out_rows: one index per kept row)
+    const int2 *d_tr = nullptr;
+    int2 *const otr = reinterpret_cast<int2 *>(out_tracks), *d_otr = nullptr;
+    unsigned long long *const rows = reinterpret_cast<unsigned long long *>(out_rows), *d_rows = nullptr;
+    hipError_t e = sc.alloc(&d_last, cells);
+    if (e == hipSuccess) e = sc.alloc(&d_area, cells);
+    if (e == hipSuccess) e = sc.alloc(&d_occ, cells);
+    if (e == hipSuccess) e = sc.alloc(&d_keep, cells);
+    if (e == hipSuccess) e = sc.alloc(&d_counts, (size_t)cblocks);
+    if (e == hipSuccess) e = sc.alloc(&d_parts, tblocks + 2 * (size_t)cblocks);
+    if (e == hipSuccess) e = sc.alloc(&d_cnt, 1);
+    if (e == hipSuccess) e = sc.input(reinterpret_cast<const int2 *>(tracks), (size_t)n * m, &d_tr, s);
+    if (e == hipSuccess) e = sc.output(rows, (size_t)n, &d_rows);
+    if (e == hipSuccess) e = sc.output(otr, (size_t)n * m, &d_otr);
     if (e == hipSuccess) e = hipMemsetAsync(d_last, 0, cells * 4, s);
     if (e == hipSuccess) e = hipMemsetAsync(d_cnt, 0, sizeof(MergeCounters), s);
-    if (e == hipSuccess && n && !tr_dev) e = hipMemcpyAsync(s_tr, tracks, (size_t)n * row_bytes, hipMemcpyHostToDevice, s);
-    MergeCounters h_cnt{};
     if (e == hipSuccess) {
-        const int2 *d_tr = tr_dev ? reinterpret_cast<const int2 *>(tracks) : s_tr;
-        unsigned long long *d_rows = !out_rows ? nullptr : rows_dev ? reinterpret_cast<unsigned long long *>(out_rows) : s_rows;
-        int2 *d_otr = !out_tracks ? nullptr : otr_dev ? reinterpret_cast<int2 *>(out_tracks) : s_otr;
         launch_merge_tracks(d_tr, n, m, image_index, width, height, r, d2, d_last, d_occ, d_area, d_keep, d_counts, d_parts + 2 * cblocks,
                             d_parts, d_parts + cblocks, d_cnt, d_rows, d_otr, s);
         e = hipGetLastError();
@@ -561,13 +530,10 @@ extern "C" int cvhip_merge_tracks(cvhip_device *dev, const int32_t *tracks, uint
     if (e == hipSuccess) e = hipMemcpyAsync(&h_cnt, d_cnt, sizeof(MergeCounters), hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     const uint64_t k = h_cnt.total;
-    if (e == hipSuccess && !h_cnt.bad && k && s_rows)
-        e = hipMemcpy(out_rows, s_rows, (size_t)k * sizeof(unsigned long long), hipMemcpyDeviceToHost);
-    if (e == hipSuccess && !h_cnt.bad && k && s_otr) e = hipMemcpy(out_tracks, s_otr, (size_t)k * row_bytes, hipMemcpyDeviceToHost);
-    for (void *p : {(void *)d_last, (void *)d_area, (void *)d_occ, (void *)d_keep, (void *)d_counts, (void *)d_parts, (void *)d_cnt,
-                    (void *)s_tr, (void *)s_rows, (void *)s_otr})
-        if (p) (void)hipFree(p);
-    if (e != hipSuccess) return fail(CVHIP_ERR_DEVICE, std::string("merge_tracks: ") + hipGetErrorString(e));
+    if (e == hipSuccess && !h_cnt.bad) e = sc.copy_out(rows, d_rows, (size_t)k, s);
+    if (e == hipSuccess && !h_cnt.bad) e = sc.copy_out(otr, d_otr, (size_t)k * m, s);
+    if (e == hipSuccess) e = sc.drain(s);
+    if (e != hipSuccess) return device_error("merge_tracks", e);
     if (h_cnt.bad)
         return fail(CVHIP_ERR_INVALID, "merge_tracks: a point has exactly one negative coordinate, or an image-i point lies "
                                        "outside the image (the reference panics here, data.rs:61-64)");

@@ -669,31 +669,6 @@ __global__ void ba_finish_kernel(const double *__restrict__ sums, const double *
     if (sqrt(st->residual_ns) <= BA_RESIDUAL_EPSILON) st->status = BA_FOUND;
 }
 
-bool tri_dev_ptr(const void *p)
-{
-    hipPointerAttribute_t attr;
-    if (hipPointerGetAttributes(&attr, p) != hipSuccess) {
-        (void)hipGetLastError();
-        return false;
-    }
-    return attr.type == hipMemoryTypeDevice || attr.type == hipMemoryTypeManaged;
-}
-
-struct Bufs {
-    int2 *tracks = nullptr;
-    double *pts = nullptr, *Xn = nullptr, *gb = nullptr, *kept = nullptr, *part = nullptr, *part_max = nullptr, *sums = nullptr;
-    uint8_t *keep = nullptr;
-    uint32_t *counts = nullptr;
-    uint64_t *idx = nullptr, *total = nullptr;
-    TriCam *cams = nullptr, *cand = nullptr;
-    BaState *st = nullptr;
-    ~Bufs()
-    {
-        void *all[] = {tracks, pts, Xn, gb, kept, part, part_max, sums, keep, counts, idx, total, cams, cand, st};
-        for (void *p : all) (void)hipFree(p);
-    }
-};
-
 struct Args {
     cvhip_device *dev;
     const int32_t *tracks;
@@ -713,19 +688,22 @@ struct Args {
     void *user;
 };
 
-#define TRY_E(expr)                                                                                        \
-    do {                                                                                                   \
-        hipError_t _e = (expr);                                                                            \
-        if (_e != hipSuccess) return cvhip::fail(CVHIP_ERR_DEVICE, std::string("triangulate_perspective: ") + #expr + ": " + hipGetErrorString(_e)); \
-    } while (0)
+const char what[] = "triangulate_perspective";
 
 template <int M>
 int run(const Args &a)
 {
-    using cvhip::fail;
+    using namespace cvhip;
     hipStream_t s = a.dev->d.stream;
     const uint64_t n = a.n;
-    Bufs b;
+    CallScratch sc;
+    int2 *d_tracks = nullptr;
+    double *d_pts = nullptr, *d_Xn = nullptr, *d_gb = nullptr, *d_kept = nullptr, *d_part = nullptr, *d_part_max = nullptr, *d_sums = nullptr;
+    uint8_t *d_keep = nullptr;
+    uint32_t *d_counts = nullptr;
+    uint64_t *d_idx = nullptr, *d_total = nullptr;
+    TriCam *d_cams = nullptr, *d_cand = nullptr;
+    BaState *d_st = nullptr;
     const uint32_t nb = (uint32_t)((n + BLOCK - 1) / BLOCK);
     TriCam hc[M];
     for (int j = 0; j < M; j++) {
@@ -740,29 +718,29 @@ int run(const Args &a)
         given_projection(a.K + 9 * j, a.R + 9 * j, a.t + 3 * j, hc[j].Pg);
     }
     const size_t tb = (size_t)n * M * sizeof(int2);
-    TRY_E(hipMalloc(&b.tracks, tb));
-    TRY_E(hipMalloc(&b.pts, (size_t)n * 24));
-    TRY_E(hipMalloc(&b.kept, (size_t)n * 24));
-    TRY_E(hipMalloc(&b.idx, (size_t)n * 8));
-    TRY_E(hipMalloc(&b.keep, n));
-    TRY_E(hipMalloc(&b.counts, (size_t)nb * 4));
-    TRY_E(hipMalloc(&b.total, 8));
-    TRY_E(hipMalloc(&b.cams, sizeof(TriCam) * M));
-    TRY_E(hipMalloc(&b.cand, sizeof(TriCam) * M));
-    TRY_E(hipMemcpyAsync(b.tracks, a.tracks, tb, tri_dev_ptr(a.tracks) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
-    TRY_E(hipMemcpyAsync(b.cams, hc, sizeof(TriCam) * M, hipMemcpyHostToDevice, s));
+    // an owned copy of the table, whoever holds it: the bundle adjustment compacts it in place
+    CVHIP_TRY_HIP_AT(what, sc.copy_in(reinterpret_cast<const int2 *>(a.tracks), (size_t)n * M, &d_tracks, s));
+    CVHIP_TRY_HIP_AT(what, sc.alloc(&d_pts, (size_t)n * 3));
+    CVHIP_TRY_HIP_AT(what, sc.alloc(&d_kept, (size_t)n * 3));
+    CVHIP_TRY_HIP_AT(what, sc.alloc(&d_idx, (size_t)n));
+    CVHIP_TRY_HIP_AT(what, sc.alloc(&d_keep, (size_t)n));
+    CVHIP_TRY_HIP_AT(what, sc.alloc(&d_counts, (size_t)nb));
+    CVHIP_TRY_HIP_AT(what, sc.alloc(&d_total, 1));
+    CVHIP_TRY_HIP_AT(what, sc.alloc(&d_cams, M));
+    CVHIP_TRY_HIP_AT(what, sc.alloc(&d_cand, M));
+    CVHIP_TRY_HIP_AT(what, hipMemcpyAsync(d_cams, hc, sizeof(TriCam) * M, hipMemcpyHostToDevice, s));
     // triangulate_tracks + filter_outliers (:821, :832)
     const double cos_threshold = std::cos(0.5 * M_PI / 180.0); // MIN_ANGLE_BETWEEN_RAYS.cos()
-    hipLaunchKernelGGL(tri_dlt_filter_kernel<M>, dim3(nb), dim3(BLOCK), 0, s, b.tracks, n, b.cams, cos_threshold, b.pts,
-                       b.keep, b.counts);
-    TRY_E(hipGetLastError());
-    hipLaunchKernelGGL(tri_scan_kernel, dim3(1), dim3(BLOCK), 0, s, b.counts, nb, b.total);
-    TRY_E(hipGetLastError());
-    hipLaunchKernelGGL(tri_compact_kernel, dim3(nb), dim3(BLOCK), 0, s, b.keep, b.pts, n, b.counts, b.kept, b.idx);
-    TRY_E(hipGetLastError());
+    hipLaunchKernelGGL(tri_dlt_filter_kernel<M>, dim3(nb), dim3(BLOCK), 0, s, d_tracks, n, d_cams, cos_threshold, d_pts,
+                       d_keep, d_counts);
+    CVHIP_TRY_HIP_AT(what, hipGetLastError());
+    hipLaunchKernelGGL(tri_scan_kernel, dim3(1), dim3(BLOCK), 0, s, d_counts, nb, d_total);
+    CVHIP_TRY_HIP_AT(what, hipGetLastError());
+    hipLaunchKernelGGL(tri_compact_kernel, dim3(nb), dim3(BLOCK), 0, s, d_keep, d_pts, n, d_counts, d_kept, d_idx);
+    CVHIP_TRY_HIP_AT(what, hipGetLastError());
     uint64_t kept = 0;
-    TRY_E(hipMemcpyAsync(&kept, b.total, 8, hipMemcpyDeviceToHost, s));
-    TRY_E(hipStreamSynchronize(s));
+    CVHIP_TRY_HIP_AT(what, hipMemcpyAsync(&kept, d_total, 8, hipMemcpyDeviceToHost, s));
+    CVHIP_TRY_HIP_AT(what, hipStreamSynchronize(s));
 
     BaState hs;
     std::memset(&hs, 0, sizeof(hs));
@@ -775,52 +753,52 @@ int run(const Args &a)
         {
             std::vector<uint64_t> hidx(nk);
             std::vector<int2> htr(n * M), hk(nk * M);
-            TRY_E(hipMemcpyAsync(hidx.data(), b.idx, nk * 8, hipMemcpyDeviceToHost, s));
-            TRY_E(hipMemcpyAsync(htr.data(), b.tracks, tb, hipMemcpyDeviceToHost, s));
-            TRY_E(hipStreamSynchronize(s));
+            CVHIP_TRY_HIP_AT(what, hipMemcpyAsync(hidx.data(), d_idx, nk * 8, hipMemcpyDeviceToHost, s));
+            CVHIP_TRY_HIP_AT(what, hipMemcpyAsync(htr.data(), d_tracks, tb, hipMemcpyDeviceToHost, s));
+            CVHIP_TRY_HIP_AT(what, hipStreamSynchronize(s));
             for (uint64_t i = 0; i < nk; i++)
                 for (int j = 0; j < M; j++) hk[i * M + j] = htr[hidx[i] * M + j];
-            TRY_E(hipMemcpyAsync(b.tracks, hk.data(), nk * M * sizeof(int2), hipMemcpyHostToDevice, s));
-            TRY_E(hipStreamSynchronize(s));
-            ktracks = b.tracks;
+            CVHIP_TRY_HIP_AT(what, hipMemcpyAsync(d_tracks, hk.data(), nk * M * sizeof(int2), hipMemcpyHostToDevice, s));
+            CVHIP_TRY_HIP_AT(what, hipStreamSynchronize(s));
+            ktracks = d_tracks;
         }
         const uint32_t G = (uint32_t)std::min<uint64_t>((nk + BLOCK - 1) / BLOCK, MAX_GRID);
         const uint32_t nq_s = 36 * M * M + 6 * M, nq_j = 6 * M + 1;
-        TRY_E(hipMalloc(&b.Xn, nk * 24));
-        TRY_E(hipMalloc(&b.gb, nk * 24));
-        TRY_E(hipMalloc(&b.part, (size_t)std::max(nq_s, nq_j) * G * 8));
-        TRY_E(hipMalloc(&b.part_max, (size_t)G * 8));
-        TRY_E(hipMalloc(&b.sums, (size_t)nq_s * 8));
-        TRY_E(hipMalloc(&b.st, sizeof(BaState)));
-        TRY_E(hipMemcpyAsync(b.st, &hs, sizeof(hs), hipMemcpyHostToDevice, s));
-        double *X = b.kept;
+        CVHIP_TRY_HIP_AT(what, sc.alloc(&d_Xn, (size_t)nk * 3));
+        CVHIP_TRY_HIP_AT(what, sc.alloc(&d_gb, (size_t)nk * 3));
+        CVHIP_TRY_HIP_AT(what, sc.alloc(&d_part, (size_t)std::max(nq_s, nq_j) * G));
+        CVHIP_TRY_HIP_AT(what, sc.alloc(&d_part_max, (size_t)G));
+        CVHIP_TRY_HIP_AT(what, sc.alloc(&d_sums, (size_t)nq_s));
+        CVHIP_TRY_HIP_AT(what, sc.alloc(&d_st, 1));
+        CVHIP_TRY_HIP_AT(what, hipMemcpyAsync(d_st, &hs, sizeof(hs), hipMemcpyHostToDevice, s));
+        double *X = d_kept;
         // initial residual and J^T r (:2045-2052)
-        hipLaunchKernelGGL(ba_jtr_kernel<M>, dim3(G, (M + JTR_GROUP - 1) / JTR_GROUP), dim3(BLOCK), 0, s, ktracks, X, b.Xn, b.gb, nk, b.cams, b.st, 1, b.part, b.part_max);
-        hipLaunchKernelGGL(ba_reduce_kernel, dim3((nq_j + 63) / 64), dim3(64), 0, s, b.part, nq_j, G, b.sums);
-        hipLaunchKernelGGL(ba_finish_kernel<M>, dim3(1), dim3(1), 0, s, b.sums, b.part_max, G, b.st, 1);
-        TRY_E(hipGetLastError());
-        TRY_E(hipMemcpyAsync(&hs, b.st, sizeof(hs), hipMemcpyDeviceToHost, s));
-        TRY_E(hipStreamSynchronize(s));
+        hipLaunchKernelGGL(ba_jtr_kernel<M>, dim3(G, (M + JTR_GROUP - 1) / JTR_GROUP), dim3(BLOCK), 0, s, ktracks, X, d_Xn, d_gb, nk, d_cams, d_st, 1, d_part, d_part_max);
+        hipLaunchKernelGGL(ba_reduce_kernel, dim3((nq_j + 63) / 64), dim3(64), 0, s, d_part, nq_j, G, d_sums);
+        hipLaunchKernelGGL(ba_finish_kernel<M>, dim3(1), dim3(1), 0, s, d_sums, d_part_max, G, d_st, 1);
+        CVHIP_TRY_HIP_AT(what, hipGetLastError());
+        CVHIP_TRY_HIP_AT(what, hipMemcpyAsync(&hs, d_st, sizeof(hs), hipMemcpyDeviceToHost, s));
+        CVHIP_TRY_HIP_AT(what, hipStreamSynchronize(s));
         norms[0] = std::sqrt(hs.residual_ns);
         int it = 0;
         for (; hs.status == BA_RUNNING && it < BA_MAX_ITERATIONS; it++) {
             if (a.progress) a.progress(a.user, (float)it / (float)BA_MAX_ITERATIONS); // :2054-2056
-            hipLaunchKernelGGL(ba_schur_kernel<M>, dim3(G, 2 * M * M + M), dim3(BLOCK), 0, s, ktracks, X, nk, b.cams, b.st, b.part);
-            hipLaunchKernelGGL(ba_reduce_kernel, dim3((nq_s + 63) / 64), dim3(64), 0, s, b.part, nq_s, G, b.sums);
-            hipLaunchKernelGGL(ba_solve_kernel<M>, dim3(1), dim3(1), 0, s, b.sums, b.st, b.cams, b.cand);
-            hipLaunchKernelGGL(ba_step_kernel<M>, dim3(G), dim3(BLOCK), 0, s, ktracks, X, b.Xn, b.gb, nk, b.cams, b.cand, b.st, b.part);
-            hipLaunchKernelGGL(ba_decide_kernel<M>, dim3(1), dim3(1), 0, s, b.part, G, b.st, b.cams, b.cand);
-            hipLaunchKernelGGL(ba_jtr_kernel<M>, dim3(G, (M + JTR_GROUP - 1) / JTR_GROUP), dim3(BLOCK), 0, s, ktracks, X, b.Xn, b.gb, nk, b.cams, b.st, 0, b.part, b.part_max);
-            hipLaunchKernelGGL(ba_reduce_kernel, dim3((nq_j + 63) / 64), dim3(64), 0, s, b.part, nq_j, G, b.sums);
-            hipLaunchKernelGGL(ba_finish_kernel<M>, dim3(1), dim3(1), 0, s, b.sums, b.part_max, G, b.st, 0);
-            TRY_E(hipGetLastError());
+            hipLaunchKernelGGL(ba_schur_kernel<M>, dim3(G, 2 * M * M + M), dim3(BLOCK), 0, s, ktracks, X, nk, d_cams, d_st, d_part);
+            hipLaunchKernelGGL(ba_reduce_kernel, dim3((nq_s + 63) / 64), dim3(64), 0, s, d_part, nq_s, G, d_sums);
+            hipLaunchKernelGGL(ba_solve_kernel<M>, dim3(1), dim3(1), 0, s, d_sums, d_st, d_cams, d_cand);
+            hipLaunchKernelGGL(ba_step_kernel<M>, dim3(G), dim3(BLOCK), 0, s, ktracks, X, d_Xn, d_gb, nk, d_cams, d_cand, d_st, d_part);
+            hipLaunchKernelGGL(ba_decide_kernel<M>, dim3(1), dim3(1), 0, s, d_part, G, d_st, d_cams, d_cand);
+            hipLaunchKernelGGL(ba_jtr_kernel<M>, dim3(G, (M + JTR_GROUP - 1) / JTR_GROUP), dim3(BLOCK), 0, s, ktracks, X, d_Xn, d_gb, nk, d_cams, d_st, 0, d_part, d_part_max);
+            hipLaunchKernelGGL(ba_reduce_kernel, dim3((nq_j + 63) / 64), dim3(64), 0, s, d_part, nq_j, G, d_sums);
+            hipLaunchKernelGGL(ba_finish_kernel<M>, dim3(1), dim3(1), 0, s, d_sums, d_part_max, G, d_st, 0);
+            CVHIP_TRY_HIP_AT(what, hipGetLastError());
             // one small readback per iteration: the loop's state word
-            TRY_E(hipMemcpyAsync(&hs.status, (const char *)b.st + offsetof(BaState, status), sizeof(int), hipMemcpyDeviceToHost, s));
-            TRY_E(hipStreamSynchronize(s));
+            CVHIP_TRY_HIP_AT(what, hipMemcpyAsync(&hs.status, (const char *)d_st + offsetof(BaState, status), sizeof(int), hipMemcpyDeviceToHost, s));
+            CVHIP_TRY_HIP_AT(what, hipStreamSynchronize(s));
         }
-        TRY_E(hipMemcpyAsync(&hs, b.st, sizeof(hs), hipMemcpyDeviceToHost, s));
-        TRY_E(hipMemcpyAsync(hc, b.cams, sizeof(TriCam) * M, hipMemcpyDeviceToHost, s));
-        TRY_E(hipStreamSynchronize(s));
+        CVHIP_TRY_HIP_AT(what, hipMemcpyAsync(&hs, d_st, sizeof(hs), hipMemcpyDeviceToHost, s));
+        CVHIP_TRY_HIP_AT(what, hipMemcpyAsync(hc, d_cams, sizeof(TriCam) * M, hipMemcpyDeviceToHost, s));
+        CVHIP_TRY_HIP_AT(what, hipStreamSynchronize(s));
         norms[1] = std::sqrt(hs.residual_ns);
         if (a.out_iterations) *a.out_iterations = (uint32_t)hs.iterations;
         if (a.out_history) std::memcpy(a.out_history, hs.history, BA_MAX_ITERATIONS);
@@ -833,10 +811,10 @@ int run(const Args &a)
         if (a.out_residual_norms) std::memcpy(a.out_residual_norms, norms, sizeof(norms));
     }
     if (kept) {
-        TRY_E(hipMemcpyAsync(a.out_points, b.kept, kept * 24, tri_dev_ptr(a.out_points) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s));
-        TRY_E(hipMemcpyAsync(a.out_index, b.idx, kept * 8, tri_dev_ptr(a.out_index) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s));
+        CVHIP_TRY_HIP_AT(what, sc.copy_out(a.out_points, d_kept, (size_t)kept * 3, s));
+        CVHIP_TRY_HIP_AT(what, sc.copy_out(a.out_index, d_idx, (size_t)kept, s));
     }
-    TRY_E(hipStreamSynchronize(s));
+    CVHIP_TRY_HIP_AT(what, hipStreamSynchronize(s));
     for (int j = 0; j < M; j++) {
         if (a.out_r) std::memcpy(a.out_r + 3 * j, hc[j].r, 24);
         if (a.out_t) std::memcpy(a.out_t + 3 * j, hc[j].t, 24);

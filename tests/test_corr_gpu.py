@@ -9,7 +9,7 @@ import pytest
 
 import box_scenes
 import cases
-from cybervision_amd import correlation, synth
+from cybervision_amd import _lib, correlation, synth
 
 pytestmark = pytest.mark.gpu
 GOLDEN = Path(__file__).resolve().parent / "golden"
@@ -1120,6 +1120,128 @@ def test_extend_tracks_matches_oracle(gpu_device, oracle, name, max_dim2):
     if name != "flat":
         assert (tp2[:, 0] >= 0).sum() > 1000 and len(n1) < valid.sum()
         assert (tp2[tracks[:, 0] < 0] == -1).all()
+
+
+def _correlated(dev, name):
+    """An open context with the whole pyramid of case `name` correlated (the caller closes it)."""
+    c = cases.make_case(name)
+    p1, p2 = cases.pyramids(c)
+    h1, w1 = c["img1"].shape
+    h2, w2 = c["img2"].shape
+    pc = correlation.PointCorrelations(dev, (w1, h1), (w2, h2), c["F"], correlation.ProjectionMode(c["projection"]))
+    try:
+        for i in range(c["steps"] + 1):
+            k = c["steps"] - i
+            pc.correlate_images(p1[k], p2[k], 1.0 / float(1 << k))
+    except Exception:
+        pc.close()
+        raise
+    return pc
+
+
+_FILL = 0x5A5A5A5A  # what the caller's output arrays hold before a call (as int32 / uint32 bits)
+
+
+def _filled(shape, on_device, dtype=np.int32, value=_FILL):
+    """An output array holding `value` everywhere: numpy, or a CUDA tensor with the same bits."""
+    a = np.full(shape, value, dtype=dtype)
+    if not on_device:
+        return a
+    import torch
+    return torch.from_numpy(a).cuda()
+
+
+def _host(a):
+    return a.cpu().numpy() if hasattr(a, "cpu") else a
+
+
+def _ptr(a):
+    import ctypes as C
+    return None if a is None else C.c_void_p(a.data_ptr() if hasattr(a, "data_ptr") else a.ctypes.data)
+
+
+def _extend_tracks(pc, tp1, max_dim2, tp2, n1, n2, cap):
+    import ctypes as C
+    total = C.c_uint64(0)
+    _lib.check(_lib.lib().cvhip_extend_tracks(pc._h, _ptr(tp1), len(tp1), max_dim2, _ptr(tp2), _ptr(n1), _ptr(n2), cap,
+                                              C.byref(total)), "cvhip_extend_tracks")
+    return total.value
+
+
+# which of track_p1, out_track_p2, out_new_p1, out_new_p2 are in device memory
+@pytest.mark.parametrize("where", [(True, True, True, True), (False, True, False, True), (True, False, True, False)],
+                         ids=["device", "mixed", "mixed-swapped"])
+def test_extend_tracks_device_pointers(gpu_device, where):
+    """cvhip_extend_tracks with its arrays in device memory, all or some of them: the host call's bytes with cap = total;
+    with cap = total // 2 the total is still reported, exactly cap rows are written - the host result's first - and
+    the rows behind them keep what they held."""
+    import torch
+
+    pc = _correlated(gpu_device, "tilt3_200x150")
+    try:
+        xy, _ = pc.complete()
+        tracks = _tracks_for(xy, seed=13)
+        want_tp2, want_n1, want_n2 = pc.extend_tracks(tracks, 2300)
+        total, n = len(want_n1), len(tracks)
+        assert total > 1000 and (want_tp2[:, 0] >= 0).sum() > 1000
+        for cap in (total, total // 2):
+            tp1 = torch.from_numpy(tracks).cuda() if where[0] else tracks
+            tp2, n1, n2 = _filled((n, 2), where[1]), _filled((total + 8, 2), where[2]), _filled((total + 8, 2), where[3])
+            torch.cuda.synchronize()
+            assert _extend_tracks(pc, tp1, 2300, tp2, n1, n2, cap) == total
+            assert _host(tp2).tobytes() == want_tp2.tobytes()
+            for got, want in ((n1, want_n1), (n2, want_n2)):
+                got = _host(got).view(np.uint32)
+                assert got[:cap].tobytes() == want[:cap].tobytes() and (got[cap:] == _FILL).all()
+            assert _host(tp1).tobytes() == tracks.tobytes()
+    finally:
+        pc.close()
+
+
+def test_extend_tracks_nothing_correlated_fills_device_destination(gpu_device):
+    """Before anything is correlated there is no match and no new track: a device out_track_p2 comes back all -1 (as a
+    host one does), nothing else is written."""
+    c = cases.make_case("tilt3_200x150")
+    h1, w1 = c["img1"].shape
+    h2, w2 = c["img2"].shape
+    pc = correlation.PointCorrelations(gpu_device, (w1, h1), (w2, h2), c["F"])
+    try:
+        tracks = _tracks_for(np.zeros((h1, w1, 2)), seed=13, n=600)
+        for on_device in (True, False):
+            tp2, n1, n2 = _filled((600, 2), on_device), _filled((8, 2), on_device), _filled((8, 2), on_device)
+            assert _extend_tracks(pc, tracks, 2300, tp2, n1, n2, 8) == 0
+            gpu_device.synchronize()  # (a device destination is filled in stream order)
+            assert (_host(tp2) == -1).all()
+            assert (_host(n1) == _FILL).all() and (_host(n2) == _FILL).all()
+    finally:
+        pc.close()
+
+
+@pytest.mark.parametrize("with_p2", [True, False])
+def test_triangulate_affine_device_pointers(gpu_device, with_p2):
+    """cvhip_triangulate_affine into device memory, with and without out_p2: the host call's bytes with cap = total; with
+    cap = total // 2 the total is still reported, exactly cap rows are written and the rows behind them keep theirs."""
+    import ctypes as C
+
+    pc = _correlated(gpu_device, "tilt3_200x150")
+    try:
+        want_pts, want_p2 = pc.triangulate_affine()
+        total = len(want_pts)
+        assert total > 1000
+        for cap in (total, total // 2):
+            pts = _filled((total + 8, 3), True, dtype=np.float64, value=-7.25)
+            p2 = _filled((total + 8, 2), True) if with_p2 else None
+            out_n = C.c_uint64(0)
+            _lib.check(_lib.lib().cvhip_triangulate_affine(pc._h, _ptr(pts), _ptr(p2), cap, C.byref(out_n)),
+                       "cvhip_triangulate_affine")
+            assert out_n.value == total
+            got = _host(pts)
+            assert got[:cap].tobytes() == want_pts[:cap].tobytes() and (got[cap:] == -7.25).all()
+            if with_p2:
+                got = _host(p2).view(np.uint32)
+                assert got[:cap].tobytes() == want_p2[:cap].tobytes() and (got[cap:] == _FILL).all()
+    finally:
+        pc.close()
 
 
 def test_device_box_pyramid_equals_host(gpu_device):

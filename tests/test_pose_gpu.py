@@ -45,6 +45,36 @@ def test_triangulate_tracks_matches_restatement(gpu_device):
         assert np.allclose(pts[ok], wpts[ok], rtol=1e-9, atol=1e-12)
 
 
+def test_triangulate_tracks_device_resident_table(gpu_device):
+    """cvhip_triangulate_tracks with the table in device memory (600 tracks, 3 views: past two blocks, no multiple of
+    256) reads it in place: the host call's bytes, into host and into device outputs, and the table is unchanged."""
+    import ctypes as C
+
+    import torch
+
+    tracks, K, poses, _ = pose_scenes.scene(n=600)
+    tracks[::7, 0] = -1
+    tracks = np.ascontiguousarray(tracks)
+    has = np.array([1, 1, 1], dtype=np.uint8)
+    P = np.ascontiguousarray(np.stack([pose_scenes.projection(K, R, t) for R, t in poses]))
+    n, m = tracks.shape[:2]
+    assert (n, m) == (600, 3)
+    want_pts, want_ok = np.zeros((n, 3)), np.zeros(n, dtype=np.uint8)
+    call = _lib.lib().cvhip_triangulate_tracks
+    _lib.check(call(gpu_device.handle, _p(tracks), n, m, _p(P), _p(has), _p(want_pts), _p(want_ok)), "tt")
+    assert 0 < want_ok.sum()
+    d_tracks = torch.from_numpy(tracks).cuda()
+    dp = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
+    pts, ok = np.zeros((n, 3)), np.zeros(n, dtype=np.uint8)
+    _lib.check(call(gpu_device.handle, dp(d_tracks), n, m, _p(P), _p(has), _p(pts), _p(ok)), "tt")
+    assert pts.tobytes() == want_pts.tobytes() and ok.tobytes() == want_ok.tobytes()
+    d_pts = torch.zeros((n, 3), dtype=torch.float64, device="cuda")
+    d_ok = torch.zeros(n, dtype=torch.uint8, device="cuda")
+    _lib.check(call(gpu_device.handle, dp(d_tracks), n, m, _p(P), _p(has), dp(d_pts), dp(d_ok)), "tt")
+    assert d_pts.cpu().numpy().tobytes() == want_pts.tobytes() and d_ok.cpu().numpy().tobytes() == want_ok.tobytes()
+    assert d_tracks.cpu().numpy().tobytes() == tracks.tobytes()
+
+
 def test_find_projection_matrix_matches_restatement(gpu_device):
     tracks, K, poses, _ = pose_scenes.scene(n=3000)
     for i, j in [(0, 1), (0, 2), (1, 2)]:

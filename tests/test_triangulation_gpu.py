@@ -108,6 +108,72 @@ def test_errors(gpu_device):
     assert seen == [np.float32(i / 100.0) for i in range(surf.ba_iterations + 1)]
 
 
+def _call_perspective(dev, tracks, cams, bundle_adjustment, pts, idx):
+    """cvhip_triangulate_perspective with the table and the two per-track outputs wherever the caller keeps them (numpy
+    arrays or CUDA tensors) -> (out_n, the small host outputs' bytes)."""
+    import ctypes as C
+
+    def ptr(a):
+        return C.c_void_p(a.data_ptr() if hasattr(a, "data_ptr") else a.ctypes.data)
+
+    n, m = tracks.shape[:2]
+    K = np.ascontiguousarray(np.stack([np.asarray(c[0], dtype=np.float64).reshape(9) for c in cams]))
+    R = np.ascontiguousarray(np.stack([np.asarray(c[1], dtype=np.float64).reshape(9) for c in cams]))
+    t = np.ascontiguousarray(np.stack([np.asarray(c[2], dtype=np.float64).reshape(3) for c in cams]))
+    out_r, out_t, out_p = np.zeros((m, 3)), np.zeros((m, 3)), np.zeros((m, 3, 4))
+    out_n, iters = C.c_uint64(0), C.c_uint32(0)
+    history, norms = np.zeros(triangulation.BUNDLE_ADJUSTMENT_MAX_ITERATIONS, dtype=np.uint8), np.zeros(2)
+    _lib.check(_lib.lib().cvhip_triangulate_perspective(
+        dev.handle, ptr(tracks), n, m, ptr(K), ptr(R), ptr(t), int(bundle_adjustment), ptr(pts), ptr(idx), ptr(out_r),
+        ptr(out_t), ptr(out_p), C.byref(out_n), C.byref(iters), ptr(history), ptr(norms), _lib.NULL_PROGRESS, None),
+        "cvhip_triangulate_perspective")
+    return out_n.value, (out_r.tobytes(), out_t.tobytes(), out_p.tobytes(), iters.value, history.tobytes(), norms.tobytes())
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("bundle_adjustment", [False, True])
+def test_device_resident_table_and_outputs(gpu_device, bundle_adjustment):
+    """The table, out_points and out_index in device memory, all of them or some: out_n, the points, the index and the
+    cameras are the host call's bytes, rows from out_n on keep what they held, and the caller's table is not written -
+    the bundle adjustment compacts a copy of it.  600 tracks without the bundle adjustment (past two blocks, no multiple
+    of 256), the 2000-track scene of test_errors with it."""
+    import torch
+
+    if bundle_adjustment:
+        _, cams, tracks = tri_scenes.ba_scene(2000)
+    else:
+        cams = tri_scenes.rig(3)
+        tracks = tri_scenes.track_table(cams, 600, seed=5)
+    tracks = np.ascontiguousarray(tracks, dtype=np.int32)
+    n = len(tracks)
+    POINT, INDEX = -7.25, 0x5A5A5A5A5A5A5A5A
+
+    def host_outputs():
+        return np.full((n, 3), POINT), np.full(n, INDEX, dtype=np.uint64)
+
+    def device_outputs():
+        return (torch.full((n, 3), POINT, dtype=torch.float64, device="cuda"),
+                torch.full((n,), INDEX, dtype=torch.int64, device="cuda"))
+
+    def host(a):
+        return a.cpu().numpy() if hasattr(a, "cpu") else a
+
+    d_tracks = torch.from_numpy(tracks).cuda()
+    torch.cuda.synchronize()
+    want_pts, want_idx = host_outputs()
+    k, want_small = _call_perspective(gpu_device, tracks, cams, bundle_adjustment, want_pts, want_idx)
+    assert 0 < k and (bundle_adjustment or k < n)
+    assert (want_pts[k:] == POINT).all() and (want_idx[k:] == INDEX).all()
+    for tracks_dev, pts_dev, idx_dev in ((True, True, True), (True, False, True), (False, True, False)):
+        pts, idx = (device_outputs() if pts_dev else host_outputs())[0], (device_outputs() if idx_dev else host_outputs())[1]
+        torch.cuda.synchronize()
+        got_k, small = _call_perspective(gpu_device, d_tracks if tracks_dev else tracks, cams, bundle_adjustment, pts, idx)
+        assert got_k == k and small == want_small
+        assert host(pts).tobytes() == want_pts.tobytes()  # (the rows from k on: the fill value, as in want_pts)
+        assert host(idx).view(np.uint64).tobytes() == want_idx.tobytes()
+    assert d_tracks.cpu().numpy().tobytes() == tracks.tobytes()
+
+
 def _compare_ba(surf, idx, pts, cams, ba, tol, tol_res):
     """The device's bundle adjustment against the restatement's: the kept set, the iteration count, the exact accept /
     reject sequence, both residual norms to tol_res, points, and each camera's r, t and projection to tol (relative to
