@@ -71,6 +71,7 @@ SIGNATURES = {
     "cvhip_ctx_set_async_readback": (C.c_int, [_vp, C.c_int]),
     "cvhip_ctx_set_result_bands": (C.c_int, [_vp, C.c_uint32]),
     "cvhip_ctx_get_result_bands": (C.c_int, [_vp, C.POINTER(C.c_uint32)]),
+    "cvhip_ctx_set_fused_finish": (C.c_int, [_vp, C.c_int]),
     "cvhip_ctx_set_search_version": (C.c_int, [_vp, C.c_int]),
     "cvhip_ctx_set_borrow_inputs": (C.c_int, [_vp, C.c_int]),
     "cvhip_ctx_set_fuse_level_calls": (C.c_int, [_vp, C.c_int]),

@@ -286,6 +286,11 @@ class PointCorrelations:
         _lib.check(_lib.lib().cvhip_ctx_get_result_bands(self._h, C.byref(n)), "cvhip_ctx_get_result_bands")
         return int(n.value)
 
+    def set_fused_finish(self, on: bool):
+        """cvhip_ctx_set_fused_finish: the last level's forward cross-check runs inside complete()'s expansion (default
+        on; same result; include/cvhip.h)."""
+        _lib.check(_lib.lib().cvhip_ctx_set_fused_finish(self._h, int(on)), "cvhip_ctx_set_fused_finish")
+
     def set_exact_scores(self, all_passes: bool):
         """Scores of EVERY pass are the reference's bits (default: only the observable ones - the forward pass at
         scale 1; include/cvhip.h).  Positions are exact either way."""

@@ -3025,43 +3025,33 @@ struct CrossJob { // one direction's cross-check: `own` is filtered against `oth
     uint32_t ow, oh, rw, rh, row0; // oh = end of the row range handled, row0 its start
 };
 
-// One or both directions of a level in one launch (blockIdx.z).  The two filters may run side by side: a
-// match's supporters are exactly the matches it supports, so neither ever removes a cell the other one needs and
-// each decision depends on the UNFILTERED other grid only (DESIGN.md section 5).
-// zero_words (optional): eight u32 cleared by the first threads - the work-list counts of the NEXT level's search passes
-// (cvhip_ctx_set_stats_ahead: the statistics kernel that otherwise clears them runs on another stream)
-__global__ __launch_bounds__(256) void cross_check_kernel(CrossJob ja, CrossJob jb, uint32_t *__restrict__ zero_words)
+// does reverse match rm lie within +-CROSS_CHECK_SEARCH_AREA of own cell (cx, cy)?
+__device__ __forceinline__ bool cc_points_back(uint32_t rm, uint32_t cx, uint32_t cy)
 {
-    if (zero_words && blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0 && threadIdx.x < 8) zero_words[threadIdx.x] = 0u;
-    const CrossJob &job = blockIdx.z == 0 ? ja : jb;
-    uint32_t *__restrict__ own = job.own;
-    const uint32_t *__restrict__ other = job.other;
-    const uint32_t ow = job.ow, oh = job.oh, rw = job.rw, rh = job.rh, row0 = job.row0;
-    // oh = end of the row range handled by this launch, row0 its start
-    const TileId tid = xcd_tile();
-    static_assert(CC_ROWS == 1, "one cell per thread");
-    const uint32_t lane = threadIdx.x & 63;
-    const uint32_t x = tid.x * 64 + lane;
-    const uint32_t y = row0 + tid.y * 4 + (threadIdx.x >> 6); // (uniform in the wave)
     const uint32_t sa = CROSS_CHECK_SEARCH_AREA;
-    const bool in = x < ow && y < oh;
-    const uint32_t cell = in ? own[(size_t)y * ow + x] : CELL_NONE;
-    // The result is an existence test (mod.rs:613-623 returns true at the first hit), so the scan
-    // order is free: probe the window centre first — a consistent pair of matches points straight
-    // back — and fall back to the full scan only when that fails.
+    const uint32_t rx = rm & 0xFFFFu, ry = rm >> 16;
+    return rm != CELL_NONE && rx >= sat_sub_u32(cx, sa) && rx < cx + sa + 1 && ry >= sat_sub_u32(cy, sa) && ry < cy + sa + 1;
+}
+
+// The result is an existence test (mod.rs:613-623 returns true at the first hit), so the scan order is free: the window's
+// centre - the cell of the other grid that `cell` matches - is probed first, since a consistent pair of matches points
+// straight back, and the full scan (cc_scan_failed) runs only where that fails.
+__device__ __forceinline__ uint32_t cc_probe(const uint32_t *__restrict__ other, uint32_t rw, uint32_t rh, uint32_t cell)
+{
     const uint32_t pmx = cell & 0xFFFFu, pmy = cell >> 16;
-    const uint32_t probe = (cell != CELL_NONE && pmx < rw && pmy < rh) ? other[(size_t)pmy * rw + pmx] : CELL_NONE;
-    // does reverse match rm lie within +-sa of own cell (cx, cy)?
-    auto points_back = [&](uint32_t rm, uint32_t cx, uint32_t cy) {
-        const uint32_t rx = rm & 0xFFFFu, ry = rm >> 16;
-        return rm != CELL_NONE && rx >= sat_sub_u32(cx, sa) && rx < cx + sa + 1 && ry >= sat_sub_u32(cy, sa) && ry < cy + sa + 1;
-    };
-    bool found = cell != CELL_NONE && points_back(probe, x, y);
-    // The cells whose probe failed: their (2 sa + 1)^2 windows of the other grid are scanned by the WHOLE wave, one cell
-    // of the window per lane (81 cells: two loads per lane), instead of by the failing lane alone while the others wait -
-    // a wave with a single failing lane used to issue 81 load instructions for it, and nearly every wave has one; the
-    // kernel's time was those instructions (it sat at the texture addresser's rate, VALU busy 0.18).  Two failing cells
-    // per round, so that four loads are in flight.
+    return (cell != CELL_NONE && pmx < rw && pmy < rh) ? other[(size_t)pmy * rw + pmx] : CELL_NONE;
+}
+
+// The cells of one wave's 64-cell row segment (cell x0 + lane of row y; wave-uniform x0, y) whose probe failed: their
+// (2 sa + 1)^2 windows of the other grid are scanned by the WHOLE wave, one cell of the window per lane (81 cells: two loads
+// per lane), instead of by the failing lane alone while the others wait - a wave with a single failing lane used to issue
+// 81 load instructions for it, and nearly every wave has one; the kernel's time was those instructions (it sat at the
+// texture addresser's rate, VALU busy 0.18).  Two failing cells per round, so that four loads are in flight.
+// -> found, with the scanned cells' verdicts filled in.
+__device__ __forceinline__ bool cc_scan_failed(const uint32_t *__restrict__ other, uint32_t rw, uint32_t rh, uint32_t cell, bool found,
+                                               uint32_t x0, uint32_t y, uint32_t lane)
+{
+    const uint32_t sa = CROSS_CHECK_SEARCH_AREA;
     constexpr uint32_t CCW = 2 * CROSS_CHECK_SEARCH_AREA + 1, CCN = CCW * CCW;
     static_assert(CCN > 64 && CCN <= 128, "two window cells per lane");
     const uint32_t wy0 = lane / CCW, wx0 = lane - wy0 * CCW, t1 = lane + 64u, wy1 = t1 / CCW, wx1 = t1 - wy1 * CCW;
@@ -3080,17 +3070,43 @@ __global__ __launch_bounds__(256) void cross_check_kernel(CrossJob ja, CrossJob 
             const uint32_t mx = c & 0xFFFFu, my = c >> 16;
             const uint32_t min_x = min(sat_sub_u32(mx, sa), rw), max_x = min(mx + sa + 1, rw);
             const uint32_t min_y = min(sat_sub_u32(my, sa), rh), max_y = min(my + sa + 1, rh);
-            cxs[q] = tid.x * 64 + (uint32_t)src;
+            cxs[q] = x0 + (uint32_t)src;
             const uint32_t ax = min_x + wx0, ay = min_y + wy0, bx = min_x + wx1, by = min_y + wy1;
             rm[q][0] = (ax < max_x && ay < max_y) ? other[(size_t)ay * rw + ax] : CELL_NONE;
             rm[q][1] = (t1 < CCN && bx < max_x && by < max_y) ? other[(size_t)by * rw + bx] : CELL_NONE;
         }
 #pragma unroll
         for (int q = 0; q < 2; q++) {
-            const bool any = __ballot(points_back(rm[q][0], cxs[q], y) || points_back(rm[q][1], cxs[q], y)) != 0ull;
+            const bool any = __ballot(cc_points_back(rm[q][0], cxs[q], y) || cc_points_back(rm[q][1], cxs[q], y)) != 0ull;
             if ((int)lane == (q ? s1 : s0)) found = any;
         }
     }
+    return found;
+}
+
+// One or both directions of a level in one launch (blockIdx.z).  The two filters may run side by side: a
+// match's supporters are exactly the matches it supports, so neither ever removes a cell the other one needs and
+// each decision depends on the UNFILTERED other grid only (DESIGN.md section 5).
+// zero_words (optional): eight u32 cleared by the first threads - the work-list counts of the NEXT level's search passes
+// (cvhip_ctx_set_stats_ahead: the statistics kernel that otherwise clears them runs on another stream)
+__global__ __launch_bounds__(256) void cross_check_kernel(CrossJob ja, CrossJob jb, uint32_t *__restrict__ zero_words)
+{
+    if (zero_words && blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0 && threadIdx.x < 8) zero_words[threadIdx.x] = 0u;
+    const CrossJob &job = blockIdx.z == 0 ? ja : jb;
+    uint32_t *__restrict__ own = job.own;
+    const uint32_t *__restrict__ other = job.other;
+    const uint32_t ow = job.ow, oh = job.oh, rw = job.rw, rh = job.rh, row0 = job.row0;
+    // oh = end of the row range handled by this launch, row0 its start
+    const TileId tid = xcd_tile();
+    static_assert(CC_ROWS == 1, "one cell per thread");
+    const uint32_t lane = threadIdx.x & 63;
+    const uint32_t x = tid.x * 64 + lane;
+    const uint32_t y = row0 + tid.y * 4 + (threadIdx.x >> 6); // (uniform in the wave)
+    const bool in = x < ow && y < oh;
+    const uint32_t cell = in ? own[(size_t)y * ow + x] : CELL_NONE;
+    const uint32_t probe = cc_probe(other, rw, rh, cell);
+    bool found = cell != CELL_NONE && cc_points_back(probe, x, y);
+    found = cc_scan_failed(other, rw, rh, cell, found, tid.x * 64, y, lane); // (the full scan only where the probe fails)
     if (cell != CELL_NONE && !found) own[(size_t)y * ow + x] = CELL_NONE; // (the score of a None cell is never looked at)
 }
 
@@ -3170,6 +3186,81 @@ void launch_expand_grid(const uint32_t *cells, const float *scores, uint32_t lw,
         hipLaunchKernelGGL(expand_grid_kernel<true>, grid, dim3(256), 0, s, cells, scores, lw, lh, k, gw, gy0, gy1, out_xy, out_corr);
     else
         hipLaunchKernelGGL(expand_grid_kernel<false>, grid, dim3(256), 0, s, cells, scores, lw, lh, k, gw, gy0, gy1, out_xy, out_corr);
+}
+
+// ---------------------------------------------------------------------------------------------
+// finish_grid: the forward cross-check of the full-resolution level and complete()'s expansion in one pass (k == 0: level
+// cell == full-resolution cell).  The decision is cross_check_kernel's (cc_probe / cc_points_back / cc_scan_failed: the rule
+// exists once), a removed cell is stored as CELL_NONE in `own` as there, and every cell is written out as
+// expand_grid_kernel<PACKED> writes it at k == 0.  Run one behind the other the two kernels add the filter's dependent
+// round trips (own cell -> probe -> scan) to the expansion's streaming stores; here the stores of one wave go out under
+// the gathers of the others, and the match plane is read once.
+// FINISH_ROWS cells per lane (rows y, y + 4, ... of a 64 x 4 FINISH_ROWS tile): every own-cell load is issued before the
+// first probe, every probe before the first scan, so a lane has that many independent chains in flight (in the ISA: the
+// own-cell and score loads of both rows before the first s_waitcnt, both probes before the second).  4096^2, per call:
+// 105 us with one cell per lane, 84 us with two, 87 us with four - against 92 + 69 us for the two kernels it replaces
+// (profiles/r10_fused_finish.txt).
+// ---------------------------------------------------------------------------------------------
+constexpr int FINISH_ROWS = 2;
+
+template <bool PACKED>
+__global__ __launch_bounds__(256) void finish_grid_kernel(uint32_t *__restrict__ own, const uint32_t *__restrict__ other,
+                                                           const float *__restrict__ scores, uint32_t ow, uint32_t row0, uint32_t row1,
+                                                           uint32_t rw, uint32_t rh, int32_t *__restrict__ out_xy,
+                                                           float *__restrict__ out_corr, uint32_t *__restrict__ zero_words)
+{
+    if (zero_words && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x < 8) zero_words[threadIdx.x] = 0u;
+    const TileId tid = xcd_tile();
+    const uint32_t lane = threadIdx.x & 63;
+    const uint32_t x = tid.x * 64 + lane;
+    const uint32_t y0 = row0 + tid.y * (4 * FINISH_ROWS) + (threadIdx.x >> 6); // (uniform in the wave)
+    uint32_t cell[FINISH_ROWS], probe[FINISH_ROWS];
+    float score[FINISH_ROWS];
+    bool found[FINISH_ROWS];
+#pragma unroll
+    for (int r = 0; r < FINISH_ROWS; r++) {
+        const uint32_t y = y0 + 4u * r;
+        const bool in = x < ow && y < row1;
+        cell[r] = in ? own[(size_t)y * ow + x] : CELL_NONE;
+        // (the score's address does not depend on the cell: loaded beside it instead of behind the verdict; a None cell's is dropped)
+        score[r] = (in && scores && out_corr) ? scores[(size_t)y * ow + x] : __builtin_nanf("");
+    }
+#pragma unroll
+    for (int r = 0; r < FINISH_ROWS; r++) probe[r] = cc_probe(other, rw, rh, cell[r]);
+#pragma unroll
+    for (int r = 0; r < FINISH_ROWS; r++) found[r] = cell[r] != CELL_NONE && cc_points_back(probe[r], x, y0 + 4u * r);
+#pragma unroll
+    for (int r = 0; r < FINISH_ROWS; r++) {
+        const uint32_t y = y0 + 4u * r;
+        if (y >= row1) break; // (uniform in the wave)
+        found[r] = cc_scan_failed(other, rw, rh, cell[r], found[r], tid.x * 64, y, lane);
+        if (x >= ow) continue;
+        const size_t o = (size_t)y * ow + x;
+        const bool some = cell[r] != CELL_NONE && found[r];
+        if (cell[r] != CELL_NONE && !found[r]) own[o] = CELL_NONE;
+        if (PACKED) // one word per cell: y << 16 | x, all ones = None
+            reinterpret_cast<uint32_t *>(out_xy)[o] = some ? cell[r] : CELL_NONE;
+        else
+            reinterpret_cast<int2 *>(out_xy)[o] = some ? make_int2((int32_t)(cell[r] & 0xFFFFu), (int32_t)(cell[r] >> 16)) : make_int2(-1, -1);
+        if (out_corr) out_corr[o] = some ? score[r] : __builtin_nanf("");
+    }
+}
+
+// rows [row0, min(row1, oh)) of the forward grid at k == 0 (ow x oh cells = the full-resolution grid), filtered against the
+// rw x rh reverse plane `other` and written to out_xy / out_corr (may be null); scores may be null (every score NaN)
+void launch_finish_grid(uint32_t *own, const uint32_t *other, const float *scores, uint32_t ow, uint32_t oh, uint32_t rw, uint32_t rh,
+                        int32_t *out_xy, float *out_corr, hipStream_t s, uint32_t row0, uint32_t row1, bool packed, uint32_t *zero_words)
+{
+    row1 = std::min(row1, oh);
+    if (row1 <= row0) {
+        if (zero_words) (void)hipMemsetAsync(zero_words, 0, 8 * sizeof(uint32_t), s);
+        return;
+    }
+    dim3 grid((ow + 63) / 64, (row1 - row0 + 4 * FINISH_ROWS - 1) / (4 * FINISH_ROWS));
+    if (packed)
+        hipLaunchKernelGGL(finish_grid_kernel<true>, grid, dim3(256), 0, s, own, other, scores, ow, row0, row1, rw, rh, out_xy, out_corr, zero_words);
+    else
+        hipLaunchKernelGGL(finish_grid_kernel<false>, grid, dim3(256), 0, s, own, other, scores, ow, row0, row1, rw, rh, out_xy, out_corr, zero_words);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -363,6 +363,22 @@ struct PassPlan {
     bool stepped = false, transposed = false, mfma = false, pair = false;
 };
 
+// The forward filter of the last level may wait for complete() (cvhip_ctx::fwd_cross_check_pending) on a plain context only.
+static bool may_defer_forward_cross_check(const cvhip_ctx *c)
+{
+    return c->fused_finish && !c->band_mode && c->shard_den <= 1 && !c->gather;
+}
+
+// A deferred forward filter whose grid is about to be replaced: only the clearing it owed (fwd_zero_work_pending) is done.
+static int drop_forward_cross_check(cvhip_ctx *c)
+{
+    const bool zero = c->fwd_cross_check_pending && c->fwd_zero_work_pending;
+    c->fwd_cross_check_pending = false;
+    c->fwd_zero_work_pending = false;
+    if (zero) CVHIP_TRY_HIP(hipMemsetAsync(c->work, 0, 8 * sizeof(uint32_t), c->dev->d.stream));
+    return CVHIP_OK;
+}
+
 static int plan_pass(cvhip_ctx *c, int a, int b, uint32_t lw1, uint32_t lh1, uint32_t lw2, uint32_t lh2, float scale,
                      int k, int first_pass, int dir, PassPlan &plan, const uint32_t *rows = nullptr)
 {
@@ -375,6 +391,8 @@ static int plan_pass(cvhip_ctx *c, int a, int b, uint32_t lw1, uint32_t lh1, uin
             return fail(CVHIP_ERR_UNSUPPORTED, "scale must shrink by powers of two from level to level");
     }
     if (dir == 1) c->rev_cross_check_pending = false; // the reverse grid is being replaced
+    if (dir == 0) CVHIP_TRY(drop_forward_cross_check(c)); // the forward grid is being replaced: nobody reads the filtered one
+    else CVHIP_TRY(cvhip::flush_forward_cross_check(c)); // (it reads the reverse grid that is about to go)
     CorrParams &p = plan.job.p;
     std::memset(&p, 0, sizeof(p));
     for (int i = 0; i < 3; i++)
@@ -629,6 +647,10 @@ static int cross_check_pass(cvhip_ctx *c, int k, int dir)
     } else if (dir == 1 && k == 0) { // nothing reads the filtered reverse grid of the last level: deferred
         c->rev_cross_check_pending = true;
         return CVHIP_OK;
+    } else if (dir == 0 && k == 0 && may_defer_forward_cross_check(c)) { // complete() filters while it expands
+        c->fwd_cross_check_pending = true;
+        c->fwd_zero_work_pending = false;
+        return CVHIP_OK;
     }
     CVHIP_TRY(timed(c, cvhip_ctx::K_CROSS, [&] {
         launch_cross_check(own.cells[own.cur], other.cells[other.cur], own.lw, own.lh, other.lw, other.lh, r0, r1,
@@ -647,6 +669,26 @@ static int flush_reverse_cross_check(cvhip_ctx *c)
     if (!own.valid || !other.valid || own.k != 0 || other.k != 0) return CVHIP_OK;
     CVHIP_TRY(timed(c, cvhip_ctx::K_CROSS, [&] {
         launch_cross_check(own.cells[own.cur], other.cells[other.cur], own.lw, own.lh, other.lw, other.lh, 0, own.lh, c->dev->d.stream);
+    }));
+    CVHIP_TRY_HIP(hipGetLastError());
+    return CVHIP_OK;
+}
+
+// the deferred forward cross-check of the full-resolution level (cvhip_ctx::fwd_cross_check_pending): the plain filter,
+// as the level would have launched it.  Before or after the reverse one - each decision depends on the unfiltered other
+// grid only, and neither filter removes a cell the other needs.
+extern "C++" int cvhip::flush_forward_cross_check(cvhip_ctx *c)
+{
+    if (!c->fwd_cross_check_pending) return CVHIP_OK;
+    const bool zero = c->fwd_zero_work_pending;
+    c->fwd_cross_check_pending = false;
+    c->fwd_zero_work_pending = false;
+    DirState &own = c->dir[0], &other = c->dir[1];
+    if (!own.valid || !other.valid || own.k != 0 || other.k != 0) return CVHIP_OK;
+    CVHIP_TRY(set_device(c->dev));
+    CVHIP_TRY(timed(c, cvhip_ctx::K_CROSS, [&] {
+        launch_cross_check_pair(own.cells[own.cur], other.cells[other.cur], own.lw, own.lh, other.lw, other.lh, 0, own.lh, 0, 0,
+                                c->dev->d.stream, zero ? c->work : nullptr);
     }));
     CVHIP_TRY_HIP(hipGetLastError());
     return CVHIP_OK;
@@ -1176,6 +1218,11 @@ int level_cross(cvhip_ctx *ctx, int k, bool stats_ahead)
     } else if (k == 0) { // the reverse filter of the last level is deferred (cvhip_ctx::rev_cross_check_pending)
         r0 = r1 = 0;
         ctx->rev_cross_check_pending = true;
+        if (may_defer_forward_cross_check(ctx)) { // ... and so is the forward one: complete() filters while it expands
+            ctx->fwd_cross_check_pending = true;
+            ctx->fwd_zero_work_pending = stats_ahead; // (whoever runs the filter clears the work-list counts in its place)
+            return CVHIP_OK;
+        }
     }
     CVHIP_TRY(timed(ctx, cvhip_ctx::K_CROSS, [&] {
         // (stats ahead: the next level's statistics kernel runs on another stream and cannot clear the work-list counts)
@@ -1401,6 +1448,11 @@ static int complete_grid(cvhip_ctx *ctx, int dir, int32_t *out_xy, float *out_co
     if (dir == 1) CVHIP_TRY(flush_reverse_cross_check(ctx));
     hipStream_t s = ctx->dev->d.stream;
     DirState &ds = ctx->dir[dir];
+    // the deferred forward filter runs inside the expansion where the level grid is the full-resolution grid
+    DirState &rev = ctx->dir[1];
+    const bool finish = dir == 0 && ctx->fwd_cross_check_pending && ds.valid && ds.k == 0 && ds.gh == ds.lh && ds.gw == ds.lw &&
+                        rev.valid && rev.k == 0 && !(ctx->live_bands > 1);
+    if (dir == 0 && !finish) CVHIP_TRY(flush_forward_cross_check(ctx));
     const size_t n = (size_t)ds.gw * ds.gh;
     const bool xy_dev = on_device(out_xy);
     const bool corr_dev = out_corr ? on_device(out_corr) : true;
@@ -1447,7 +1499,15 @@ static int complete_grid(cvhip_ctx *ctx, int dir, int32_t *out_xy, float *out_co
         if (!ctx->async_readback) CVHIP_TRY_HIP(hipStreamSynchronize(rb.stream));
         return CVHIP_OK;
     }
-    if (ds.valid) {
+    if (finish) {
+        const bool zero = ctx->fwd_zero_work_pending;
+        ctx->fwd_cross_check_pending = false;
+        ctx->fwd_zero_work_pending = false;
+        (void)timed(ctx, cvhip_ctx::K_EXPAND, [&] {
+            launch_finish_grid(ds.cells[ds.cur], rev.cells[rev.cur], ds.scores_valid ? ds.scores : nullptr, ds.lw, ds.lh, rev.lw, rev.lh,
+                               d_xy, d_corr, s, 0, ds.lh, packed, zero ? ctx->work : nullptr);
+        });
+    } else if (ds.valid) {
         (void)timed(ctx, cvhip_ctx::K_EXPAND,
                     [&] {
                         launch_expand_grid(ds.cells[ds.cur], ds.scores_valid ? ds.scores : nullptr, ds.lw, ds.lh, ds.k, ds.gw, ds.gh, d_xy,
@@ -1495,6 +1555,7 @@ int cvhip_triangulate_affine(cvhip_ctx *ctx, double *out_points3d, uint32_t *out
     CVHIP_TRY(flush_level_calls(ctx));
     if (cap && !out_points3d) return fail(CVHIP_ERR_INVALID, "out_points3d is null");
     CVHIP_TRY(set_device(ctx->dev));
+    CVHIP_TRY(flush_forward_cross_check(ctx));
     hipStream_t s = ctx->dev->d.stream;
     DirState &ds = ctx->dir[0];
     *out_n = 0;
@@ -1658,10 +1719,9 @@ int cvhip_ctx_level_grid(cvhip_ctx *ctx, int dir, void **cells, void **scores, u
     if (dir != 0 && dir != 1) return fail(CVHIP_ERR_INVALID, "dir must be 0 or 1");
     DirState &ds = ctx->dir[dir];
     if (!ds.valid) return fail(CVHIP_ERR_INVALID, "no level computed yet");
-    if (dir == 1) {
-        CVHIP_TRY(set_device(ctx->dev));
-        CVHIP_TRY(flush_reverse_cross_check(ctx));
-    }
+    CVHIP_TRY(set_device(ctx->dev));
+    if (dir == 1) CVHIP_TRY(flush_reverse_cross_check(ctx));
+    else CVHIP_TRY(flush_forward_cross_check(ctx));
     if (cells) *cells = ds.cells[ds.cur];
     if (scores) *scores = ds.scores;
     if (lw) *lw = ds.lw;
@@ -1781,6 +1841,15 @@ int cvhip_ctx_set_result_bands(cvhip_ctx *ctx, uint32_t bands)
     if (bands > 16) return fail(CVHIP_ERR_INVALID, "result bands: 0 (the library's choice), 1 .. 16");
     CVHIP_TRY(flush_level_calls(ctx));
     ctx->result_bands = bands;
+    return CVHIP_OK;
+}
+
+int cvhip_ctx_set_fused_finish(cvhip_ctx *ctx, int on)
+{
+    if (!ctx) return fail(CVHIP_ERR_INVALID, "ctx is null");
+    CVHIP_TRY(flush_level_calls(ctx));
+    if (!on) CVHIP_TRY(flush_forward_cross_check(ctx));
+    ctx->fused_finish = on != 0;
     return CVHIP_OK;
 }
 

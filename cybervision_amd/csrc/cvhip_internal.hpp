@@ -129,6 +129,9 @@ void launch_cross_check_pair(uint32_t *fwd, uint32_t *rev, uint32_t fw, uint32_t
 // scores == nullptr: the level's scores were not computed (CorrParams::need_scores): NaN everywhere
 void launch_expand_grid(const uint32_t *cells, const float *scores, uint32_t lw, uint32_t lh, uint32_t k, uint32_t gw, uint32_t gh,
                         int32_t *out_xy, float *out_corr, hipStream_t s, uint32_t gy0 = 0, uint32_t gy1 = 0xFFFFFFFFu, bool packed = false);
+// the forward cross-check of the full-resolution level and its expansion in one kernel (finish_grid_kernel; k == 0 only)
+void launch_finish_grid(uint32_t *own, const uint32_t *other, const float *scores, uint32_t ow, uint32_t oh, uint32_t rw, uint32_t rh,
+                        int32_t *out_xy, float *out_corr, hipStream_t s, uint32_t row0, uint32_t row1, bool packed, uint32_t *zero_words);
 void launch_fill_u32(uint32_t *p, uint32_t v, size_t n, hipStream_t s);
 // tracks of the affine dense consumer; block_counts must hold ceil(gw*gh/256) u32, total is one u32
 void launch_triangulate_affine(const uint32_t *cells, uint32_t lw, uint32_t lh, uint32_t k, uint32_t gw, uint32_t gh,
@@ -391,6 +394,7 @@ struct Device {
 struct cvhip_ctx;
 namespace cvhip {
 int flush_level_calls(cvhip_ctx *ctx); // cvhip_api.hip: run what cvhip_ctx_set_fuse_level_calls has deferred
+int flush_forward_cross_check(cvhip_ctx *ctx); // cvhip_api.hip: run the deferred forward filter (cvhip_ctx::fwd_cross_check_pending)
 inline hipError_t aux_stream(Device &d, int i, hipStream_t *out)
 {
     hipError_t e = hipSuccess;
@@ -516,6 +520,14 @@ struct cvhip_ctx {
     // level follows scale 1 and complete() returns the forward grid (mod.rs:208-215).  It is therefore deferred and
     // only runs if somebody does ask for the reverse grid (cvhip_complete_dir(.., 1, ..), cvhip_ctx_level_grid(.., 1, ..)).
     bool rev_cross_check_pending = false;
+    // The FORWARD cross-check of the full-resolution level is deferred too (cvhip_ctx_set_fused_finish, default on):
+    // complete() runs it inside its expansion (finish_grid_kernel) - one pass over the grid instead of two.  Everything else
+    // that reads or hands out the forward match plane runs the plain filter first (cvhip::flush_forward_cross_check); a search
+    // pass that replaces the forward grid drops it.  Never set in band mode, on a row-sharded context or for a level that
+    // went out in result bands.
+    bool fused_finish = true;
+    bool fwd_cross_check_pending = false;
+    bool fwd_zero_work_pending = false; // ... and that filter was to clear the work-list counts (level_cross, statistics ahead)
     // cvhip_ctx_set_fuse_level_calls: the caller issues the four backend calls of a level in
     // PointCorrelations::correlate_images' order (mod.rs:217-245) - forward, reverse with the SAME two images exchanged,
     // cross-check forward, cross-check reverse - and the library executes them as cvhip_correlate_level would: the

@@ -368,6 +368,7 @@ extern "C" int cvhip_extend_tracks(cvhip_ctx *ctx, const int32_t *track_p1, uint
     if (n_tracks && (!track_p1 || !out_track_p2)) return fail(CVHIP_ERR_INVALID, "track arrays are null");
     if (cap && (!out_new_p1 || !out_new_p2)) return fail(CVHIP_ERR_INVALID, "new-track arrays are null");
     CVHIP_TRY_HIP(hipSetDevice(ctx->dev->d.ordinal));
+    CVHIP_TRY(cvhip::flush_forward_cross_check(ctx));
     hipStream_t s = ctx->dev->d.stream;
     DirState &ds = ctx->dir[0];
     *out_n_new = 0;

@@ -122,6 +122,14 @@ int cvhip_ctx_set_result_bands(cvhip_ctx *ctx, uint32_t bands);
 /* How many bands the grid now held went out in (1: not banded - the geometry, the size or the call order ruled it out). */
 int cvhip_ctx_get_result_bands(cvhip_ctx *ctx, uint32_t *live);
 
+/* The forward cross-check of the last level (scale 1) inside complete()'s expansion.  On (the default): that filter is
+ * deferred, and cvhip_complete / cvhip_complete_dir(dir 0) / cvhip_complete_packed filter each cell while they write it out
+ * - one pass over the grid and one launch instead of two.  Every other entry point that reads or hands out the forward
+ * grid (cvhip_ctx_level_grid, cvhip_triangulate_affine, cvhip_extend_tracks) runs the plain filter first, so no result
+ * changes, bit for bit (tests/test_fused_finish_gpu.py).  Row-sharded and band-mode contexts and levels that went out in
+ * result bands never defer.  Off: the filter runs where the level's calls ask for it (a pending one is run at once). */
+int cvhip_ctx_set_fused_finish(cvhip_ctx *ctx, int on);
+
 /* GpuContext::complete_process (gpu/mod.rs:210-216; called mod.rs:208-215): write the forward
  * full-resolution grid.  out_xy: 2*w1*h1 int32, out_corr: w1*h1 float (may be NULL).
  * Host destinations are complete on return (synchronises); DEVICE destinations are written in
