@@ -397,8 +397,8 @@ def box_pyramid_device(device: GpuDevice, img, steps: int):
 
 def resize_lanczos3(device: GpuDevice, img, scale: float):
     """SourceImage::resize (reconstruction.rs:146-162): the level image at `scale` with the `image` crate's Lanczos3
-    (cvhip_resize_lanczos3; tolerance parity, see include/cvhip.h).  img: numpy uint8 array or torch CUDA uint8 tensor;
-    the result lives where the input does.  A device result is written in the order of the DEVICE HANDLE's stream (no host
+    (cvhip_resize_lanczos3; byte for byte the oracle's restatement with libm's sinf, see include/cvhip.h).  img: numpy
+    uint8 array or torch CUDA uint8 tensor; the result lives where the input does. A device result is written in the order of the DEVICE HANDLE's stream (no host
     synchronisation): with a handle on a stream of its own, `device.synchronize()` before another stream reads it."""
     p, w, h, keep = _ptr_shape(img)
     s = np.float32(scale)
