@@ -128,6 +128,11 @@ SIGNATURES = {
     "cvhip_mesh_ply": (C.c_int, [_vp, _vp, _vp, C.c_uint64, _u32, _vp, _vp, _vp, _u32, _vp, _vp, C.c_uint64, _vp, C.c_uint64,
                                  C.POINTER(C.c_uint64), _vp]),
     "cvhip_mesh_colour_map": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint64, C.c_double, C.c_double, _vp, _vp]),
+    # the OBJ file image: cvhip_mesh_ply's arguments with polygon_cameras behind polygons and stem behind n_poly
+    "cvhip_mesh_obj": (C.c_int, [_vp, _vp, _vp, C.c_uint64, _u32, _vp, _vp, _vp, _u32, _vp, _vp, _vp, C.c_uint64, C.c_char_p, _vp,
+                                 C.c_uint64, C.POINTER(C.c_uint64), _vp]),
+    "cvhip_mesh_obj_mtl": (C.c_int, [C.c_char_p, _u32, _vp, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "cvhip_f64_display": (C.c_int, [_vp, _vp, C.c_uint64, _vp, C.c_uint64, C.POINTER(C.c_uint64), _vp]),
     # the Delaunay triangulation of a camera's points: (xy, k, out_faces, cap_faces, out_n_faces, out_stats)
     "cvhip_mesh_delaunay": (C.c_int, [_vp, _vp, C.c_uint64, _vp, C.c_uint64, C.POINTER(C.c_uint64), _vp]),
     "cvhip_mesh_delaunay_set_lane_cells": (C.c_int, [_vp, _u32]),

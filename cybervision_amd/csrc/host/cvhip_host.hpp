@@ -644,6 +644,55 @@ inline std::vector<uint8_t> ply(GpuDevice &dev, const Surface &s, const std::vec
     return out;
 }
 
+// ---- the OBJ writer: ObjWriter's file image (:774-1007) and its .mtl text ------------------------------------------
+struct ObjSections {
+    uint64_t header = 0, v = 0, vt = 0, f = 0;
+};
+
+// Mesh::output with an ObjWriter -> the file's bytes.  images: one per image of a track - their pixels are read in Color mode,
+// only their sizes in Texture mode (pixels may be empty there); each polygon's camera_i is read in Texture mode; stem: the
+// output path's file stem.  Saving the {stem}-{i}.png images is the caller's.
+inline std::vector<uint8_t> mesh_obj(GpuDevice &dev, const Surface &s, const std::vector<Polygon> &polygons, const std::vector<RgbImage> &images,
+                                     VertexMode mode, const std::array<double, 3> &out_scale, const std::string &stem,
+                                     ObjSections *sections = nullptr)
+{
+    std::vector<uint32_t> flat, cameras;
+    for (const Polygon &p : polygons) flat.insert(flat.end(), p.vertices.begin(), p.vertices.end()), cameras.push_back(p.camera_i);
+    const uint64_t n = s.tracks_len();
+    const uint32_t m = n ? (uint32_t)(s.tracks.size() / (2 * n)) : (uint32_t)images.size();
+    std::vector<uint8_t> pixels;
+    std::vector<uint64_t> offsets{0};
+    std::vector<uint32_t> dims;
+    for (const RgbImage &im : images) {
+        if (mode == VertexMode::Color) pixels.insert(pixels.end(), im.pixels.begin(), im.pixels.end());
+        offsets.push_back(pixels.size());
+        dims.push_back(im.width), dims.push_back(im.height);
+    }
+    const bool with_dims = mode != VertexMode::Plain && images.size() == m && m > 0, with_images = with_dims && mode == VertexMode::Color;
+    uint64_t size = 0, sec[4] = {0, 0, 0, 0};
+    auto call = [&](uint8_t *out, uint64_t cap) {
+        check(cvhip_mesh_obj(dev.handle(), s.points.data(), s.tracks.data(), n, m, with_images ? pixels.data() : nullptr,
+                             with_images ? offsets.data() : nullptr, with_dims ? dims.data() : nullptr, (uint32_t)mode, out_scale.data(),
+                             flat.data(), cameras.data(), polygons.size(), stem.c_str(), out, cap, &size, sec),
+              "cvhip_mesh_obj");
+    };
+    call(nullptr, 0);
+    std::vector<uint8_t> out(size);
+    call(out.data(), size);
+    if (sections) *sections = ObjSections{sec[0], sec[1], sec[2], sec[3]};
+    return out;
+}
+
+// ObjWriter::write_materials' text (:856-868) for m images
+inline std::string mesh_obj_mtl(const std::string &stem, uint32_t m)
+{
+    uint64_t size = 0;
+    check(cvhip_mesh_obj_mtl(stem.c_str(), m, nullptr, 0, &size), "cvhip_mesh_obj_mtl");
+    std::string out(size, '\0');
+    check(cvhip_mesh_obj_mtl(stem.c_str(), m, out.data(), size, &size), "cvhip_mesh_obj_mtl");
+    return out;
+}
+
 // ImageWriter::complete: the depth map through `table` (256 x R, G, B) -> width x height x RGBA
 inline std::vector<uint8_t> colour_map(GpuDevice &dev, const DepthImage &img, const std::array<uint8_t, 768> &table)
 {

@@ -4,7 +4,7 @@
 //
 // All f64, one IEEE operation per written operation in the written order (-ffp-contract=off).  The Delaunay construction
 // is delaunay_kernels.hip (a caller may supply triangles of its own just as well); the PLY writer and the colour
-// mapping are mesh_output_kernels.hip; the OBJ writer, the colour table and the PNG encoder stay out.
+// mapping are mesh_output_kernels.hip, the OBJ writer is mesh_obj_kernels.hip; the colour table and the PNG encoder stay out.
 //
 // Two results of the reference depend on its thread order; here they are defined:
 //   - DepthBuffer::new keeps a new depth iff the cell is empty or cur - new > f64::EPSILON, folding the points in

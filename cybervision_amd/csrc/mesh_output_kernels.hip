@@ -8,8 +8,7 @@
 //           image's right or lower edge gets none, so records are 24 or 27 bytes and their offsets a prefix sum;
 //   face:   0x03, then big-endian u32 of vertices[2], vertices[1], vertices[0].
 // The colour map is f64, one IEEE operation per written operation in the written order (-ffp-contract=off).
-// Not here: the OBJ writer (it needs Rust's shortest-round-trip decimal text), the colour table (an argument) and the PNG
-// encoder.
+// The OBJ writer is mesh_obj_kernels.hip.  Not here: the colour table (an argument) and the PNG encoder.
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -65,22 +64,6 @@ __global__ __launch_bounds__(BLOCK) void mesh_ply_count_kernel(const int2 *__res
             block_counts[blk] = coloured;
             if (none) atomicOr(no_point, 1u);
         }
-    }
-}
-
-// The block's `len` staged bytes, which begin `pad` bytes into `stage`, go to dst + pad .. dst + pad + len (dst is 4-byte
-// aligned): lanes take consecutive dwords; a dword whose four bytes are all the block's is one store, the others - the
-// block's unaligned head and tail, whose remaining bytes belong to the neighbouring blocks or the header - go byte by byte.
-__device__ __forceinline__ void stage_out(const uint32_t *stage, uint32_t pad, uint32_t len, uint8_t *__restrict__ dst)
-{
-    const uint8_t *bytes = reinterpret_cast<const uint8_t *>(stage);
-    const uint32_t end = pad + len;
-    for (uint32_t k = threadIdx.x; 4 * k < end; k += BLOCK) {
-        const uint32_t lo = 4 * k < pad ? pad : 4 * k, hi = 4 * k + 4 > end ? end : 4 * k + 4;
-        if (hi - lo == 4)
-            reinterpret_cast<uint32_t *>(dst)[k] = stage[k];
-        else
-            for (uint32_t b = lo; b < hi; b++) dst[b] = bytes[b];
     }
 }
 
@@ -143,7 +126,7 @@ __global__ __launch_bounds__(BLOCK) void mesh_ply_vertex_kernel(const double *__
             if (coloured) r[24] = rgb[0], r[25] = rgb[1], r[26] = rgb[2];
         }
         __syncthreads();
-        stage_out(s_rec, pad, len, dst - pad);
+        stage_out<BLOCK>(s_rec, pad, len, dst - pad);
         __syncthreads();
     }
 }
@@ -169,7 +152,7 @@ __global__ __launch_bounds__(BLOCK) void mesh_ply_face_kernel(const uint32_t *__
             }
         }
         __syncthreads();
-        stage_out(s_rec, pad, len, dst - pad);
+        stage_out<BLOCK>(s_rec, pad, len, dst - pad);
         __syncthreads();
     }
 }

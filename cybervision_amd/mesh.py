@@ -4,7 +4,8 @@ and ImageWriter's depth map.  The Delaunay construction is a callback (`triangul
 reconstruct_perspective_mesh) is one, `delaunay_device(device)` - cvhip_mesh_delaunay, DESIGN.md 4.13 - runs on the device
 and needs no scipy.
 The mesh output: `ply` / `write_ply` - PlyWriter's binary file image - and `colour_map` /
-`depth_image_rgba` - ImageWriter::complete's colours; the colour table is the caller's.
+`depth_image_rgba` - ImageWriter::complete's colours; the colour table is the caller's.  `obj` / `write_obj` / `obj_mtl` - ObjWriter's
+Wavefront OBJ text and its .mtl, `f64_display` - the decimal text of doubles that it rests on.
 No compute in Python - array bookkeeping and the calls only.
 
 Defined where the reference's result depends on its thread order: a depth-buffer cell is the minimum of its depths (a
@@ -29,7 +30,8 @@ DELAUNAY_STATS = ("grid_width", "grid_height", "device_stars", "host_stars", "du
 
 
 class VertexMode(enum.IntEnum):
-    """VertexMode (output.rs) as cvhip_mesh_ply takes it (CVHIP_VERTEX_*).  Texture writes what Plain writes."""
+    """VertexMode (output.rs) as cvhip_mesh_ply and cvhip_mesh_obj take it (CVHIP_VERTEX_*).  In a PLY, Texture writes what Plain
+    writes; in an OBJ it adds the vt table, the usemtl groups and the .mtl file."""
     Plain = 0
     Color = 1
     Texture = 2
@@ -204,6 +206,91 @@ def write_ply(path, device, surface, polygons, images=None, vertex_mode=VertexMo
     sections = []
     ply(device, surface, polygons, images, vertex_mode, out_scale, sections=sections).tofile(path)
     return tuple(sections)
+
+
+def _dims_args(dims):
+    """(NULL, NULL, image_dims) of cvhip_mesh_obj from (width, height) pairs: Texture mode reads no pixels."""
+    d = np.ascontiguousarray(np.asarray(dims, dtype=np.uint32).reshape(-1, 2))
+    return [None, None, _p(d)], (d,)
+
+
+def obj(device, surface, polygons, camera, images=None, vertex_mode=VertexMode.Plain, out_scale=(1.0, 1.0, 1.0), stem="mesh", sections=None):
+    """The Wavefront OBJ file image of Mesh::output with an ObjWriter (output.rs:521-559, 774-1007; cvhip_mesh_obj) -> uint8 array.
+    Every number is Rust's `{}`: the shortest decimal text that reads back as the same double, without an exponent.
+    camera: the camera of each polygon ([p], mesh.create's "camera"; read in Texture mode: a usemtl line where it changes, and
+    the uv index of a vertex counts the track's points in the images below it).  images: one [h, w, 3] uint8 array per image of
+    a track (Color: a vertex takes the pixel of its track's first point / 255, and none when that point lies past its image;
+    Texture: only the sizes are read, so a list of (width, height) does as well).  stem: the output's file stem (Texture:
+    "mtllib {stem}.mtl").  `sections`, a list, receives the header's, the v, the vt and the f bytes.  Raises CvhipError ("Track
+    has no images") for a track without a point in Color and Texture mode."""
+    pts = np.ascontiguousarray(surface.points, dtype=np.float64).reshape(-1, 3)
+    tracks = np.ascontiguousarray(surface.tracks, dtype=np.int32)
+    if tracks.ndim != 3:
+        tracks = tracks.reshape(len(pts), -1, 2)
+    poly = np.ascontiguousarray(polygons, dtype=np.uint32).reshape(-1, 3)
+    cam = np.ascontiguousarray(camera if camera is not None else np.zeros(len(poly)), dtype=np.uint32).reshape(-1)
+    if len(cam) != len(poly):
+        raise ValueError("one camera per polygon")
+    scale = np.array([float(v) for v in out_scale], dtype=np.float64)
+    if scale.shape != (3,):
+        raise ValueError("out_scale is (x, y, z)")
+    m = tracks.shape[1]
+    if images is not None and len(images) != m:
+        raise ValueError("one image per image of a track")
+    if images is None:
+        img_args, _keep = [None, None, None], None
+    elif all(hasattr(im, "shape") and len(im.shape) == 3 for im in images) and int(vertex_mode) != VertexMode.Texture:
+        img_args, _keep = _image_args(images)
+    else:
+        img_args, _keep = _dims_args([(im.shape[1], im.shape[0]) if hasattr(im, "shape") else im for im in images])
+    size, sec = C.c_uint64(0), np.zeros(4, dtype=np.uint64)
+    L = _lib.lib()
+    args = [device.handle, _p(pts), _p(tracks), len(pts), m, *img_args, int(vertex_mode), _p(scale), _p(poly), _p(cam), len(poly),
+            str(stem).encode("utf-8")]
+    _lib.check(L.cvhip_mesh_obj(*args, None, 0, C.byref(size), _p(sec)), "cvhip_mesh_obj")
+    out = np.zeros(size.value, dtype=np.uint8)
+    _lib.check(L.cvhip_mesh_obj(*args, _p(out), out.size, C.byref(size), _p(sec)), "cvhip_mesh_obj")
+    if sections is not None:
+        sections[:] = [int(v) for v in sec]
+    return out
+
+
+def obj_mtl(stem, m: int):
+    """The {stem}.mtl text of ObjWriter::write_materials (output.rs:856-868; cvhip_mesh_obj_mtl) for m images -> bytes."""
+    name = str(stem).encode("utf-8")
+    size = C.c_uint64(0)
+    L = _lib.lib()
+    _lib.check(L.cvhip_mesh_obj_mtl(name, int(m), None, 0, C.byref(size)), "cvhip_mesh_obj_mtl")
+    out = np.zeros(size.value, dtype=np.uint8)
+    _lib.check(L.cvhip_mesh_obj_mtl(name, int(m), _p(out), out.size, C.byref(size)), "cvhip_mesh_obj_mtl")
+    return out.tobytes()
+
+
+def write_obj(path, device, surface, polygons, camera, images=None, vertex_mode=VertexMode.Plain, out_scale=(1.0, 1.0, 1.0)):
+    """`obj` written to `path` with the path's file stem and, in Texture mode, `obj_mtl` to {stem}.mtl next to it
+    -> (header, v, vt, f) byte counts.  The .mtl names {stem}-{i}.png for image i: saving those images is the caller's (there is
+    no PNG encoder here)."""
+    import pathlib
+
+    path = pathlib.Path(path)
+    sections = []
+    obj(device, surface, polygons, camera, images, vertex_mode, out_scale, stem=path.stem, sections=sections).tofile(path)
+    if int(vertex_mode) == VertexMode.Texture:
+        m = np.asarray(surface.tracks).reshape(len(surface.points), -1, 2).shape[1] if len(surface.points) else len(images or [])
+        (path.parent / (path.stem + ".mtl")).write_bytes(obj_mtl(path.stem, m))
+    return tuple(sections)
+
+
+def f64_display(device, values):
+    """Rust's `{}` of each double, formatted on the device (cvhip_f64_display) -> list of str."""
+    v = np.ascontiguousarray(values, dtype=np.float64).reshape(-1)
+    size = C.c_uint64(0)
+    L = _lib.lib()
+    _lib.check(L.cvhip_f64_display(device.handle, _p(v), len(v), None, 0, C.byref(size), None), "cvhip_f64_display")
+    out, offsets = np.zeros(size.value, dtype=np.uint8), np.zeros(len(v) + 1, dtype=np.uint64)
+    _lib.check(L.cvhip_f64_display(device.handle, _p(v), len(v), _p(out), out.size, C.byref(size), _p(offsets)), "cvhip_f64_display")
+    text = out.tobytes().decode("ascii")
+    return [text[int(a):int(b)] for a, b in zip(offsets[:-1], offsets[1:])]
 
 
 def _table(table):

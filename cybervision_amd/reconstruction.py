@@ -380,7 +380,7 @@ def reconstruct_perspective(device, pyramids, K, bundle_adjustment: bool = True,
 
 def reconstruct_perspective_mesh(device, pyramids, K, triangulate=None, project_to_image=None, depth_scale: float = -1.0,
                                  ply_path=None, images=None, vertex_mode=0, out_scale=(1.0, 1.0, 1.0), colour_table=None,
-                                 **kwargs):
+                                 obj_path=None, **kwargs):
     """reconstruct_perspective, then the mesh stage of output::output (output.rs:567-611; DESIGN.md 4.11) on its surface:
     mesh.create - per camera the Delaunay input, `triangulate(xy) -> [f, 3]` (the caller's Delaunay; default
     mesh.delaunay_scipy; mesh.delaunay_device(device) runs on the device and needs no scipy), the occlusion culling and the
@@ -391,7 +391,9 @@ def reconstruct_perspective_mesh(device, pyramids, K, triangulate=None, project_
     merged list is written there (mesh.write_ply with images - one [h, w, 3] uint8 array per placed image, Color mode only -,
     vertex_mode, a mesh.VertexMode, and out_scale), its section sizes are out["ply_sections"], its time timings_ms["ply"];
     colour_table ([256, 3] uint8, with project_to_image) - out["depth_image"]["rgba"] is the depth map through
-    mesh.colour_map."""
+    mesh.colour_map; obj_path - the Wavefront OBJ of the surface and the merged list with its cameras is
+    written there (mesh.write_obj with the same images, vertex_mode and out_scale; in Texture mode the .mtl goes next to it and
+    the caller saves the {stem}-{i}.png images), its section sizes are out["obj_sections"], its time timings_ms["obj"]."""
     import time
 
     from . import mesh
@@ -418,4 +420,10 @@ def reconstruct_perspective_mesh(device, pyramids, K, triangulate=None, project_
         out["ply_sections"] = mesh.write_ply(ply_path, device, out["surface"], out["mesh"]["polygons"], images,
                                              mesh.VertexMode(int(vertex_mode)), out_scale)
         out["timings_ms"]["ply"] = (time.perf_counter() - t2) * 1e3
+    if obj_path is not None:
+        t3 = time.perf_counter()
+        out["obj_sections"] = mesh.write_obj(obj_path, device, out["surface"], out["mesh"]["polygons"], out["mesh"]["camera"],
+                                             shapes if images is None and int(vertex_mode) == mesh.VertexMode.Texture else images,
+                                             mesh.VertexMode(int(vertex_mode)), out_scale)
+        out["timings_ms"]["obj"] = (time.perf_counter() - t3) * 1e3
     return out

@@ -324,8 +324,8 @@ int cvhip_recover_pose_models(cvhip_device *dev, const int32_t *tracks, uint64_t
  * (Surface::project_point, triangulation.rs:63-74); it is IN RANGE when the projection lies in [c - 4 size, c + 4 size) on
  * both axes, c = size / 2 (img_range, output.rs:613-624); its depth is Camera::point_depth (triangulation.rs:492-495).
  * The Delaunay construction is cvhip_mesh_delaunay below (a caller may still supply triangles of its own: the other entries
- * take any).  Not here: the OBJ writer, the colour table (an argument of cvhip_mesh_colour_map) and the PNG encoder.  The PLY
- * writer and the colour mapping are the mesh OUTPUT entries below.
+ * take any).  Not here: the colour table (an argument of cvhip_mesh_colour_map) and the PNG encoder.  The PLY and OBJ
+ * writers and the colour mapping are the mesh OUTPUT entries below.
  * Two of the reference's results depend on its thread order, and are DEFINED here:
  *  - DepthBuffer::new folds a cell's points in par_bridge's order, keeping a new depth iff cur - new > f64::EPSILON; here
  *    the cell is the MINIMUM of its depths (one of the reference's outcomes unless two depths of a cell differ by a
@@ -443,9 +443,9 @@ int cvhip_mesh_delaunay_set_lane_cells(cvhip_device *dev, uint32_t cells);
  * Mesh output (csrc/mesh_output_kernels.hip): what output::output writes once the polygon list exists -
  * PlyWriter's binary file image (output.rs:648-772) and ImageWriter::complete's colour mapping (:1117-1229) -, pinned
  * byte for byte.  Neither touches the cameras: an affine surface works the same, and m is the number of images per track.
- * Not here: the OBJ writer and its vt / UV tables (Rust's shortest-round-trip decimal text), the PNG encoder. */
+ * The OBJ writer, with its vt / UV tables, is cvhip_mesh_obj further below.  Not here: the PNG encoder. */
 
-/* VertexMode (output.rs): what a PLY vertex record carries.  Texture writes what Plain writes. */
+/* VertexMode (output.rs): what a vertex carries.  In a PLY, Texture writes what Plain writes; in an OBJ it adds the vt table. */
 #define CVHIP_VERTEX_PLAIN 0
 #define CVHIP_VERTEX_COLOR 1
 #define CVHIP_VERTEX_TEXTURE 2
@@ -485,6 +485,48 @@ int cvhip_mesh_ply(cvhip_device *dev, const double *points, const int32_t *track
  * bytes, 4-byte aligned) are host or device pointers; CVHIP_ERR_UNSUPPORTED with 2^32 - 1 or more cells. */
 int cvhip_mesh_colour_map(cvhip_device *dev, const double *map, uint64_t width, uint64_t height,
                           double min_depth, double max_depth, const uint8_t *table, uint8_t *out_rgba);
+
+/* ------------------------------------------------------------------------------------------
+ * The Wavefront OBJ file image (csrc/mesh_obj_kernels.hip, csrc/f64_display.hpp): Mesh::output with an
+ * ObjWriter (output.rs:521-559, 774-1007), byte for byte.  Every number is Rust's `{}`: an f64 as the shortest decimal digits
+ * that read back as the same double, laid out without an exponent ("NaN", "inf", "-inf", "0", "-0"; 1e23 is 1 and 23 zeros,
+ * 5e-324 is 326 characters).  Every line ends with '\n'; in this order:
+ *  - header (:877-889): "mtllib {stem}.mtl" in Texture mode, nothing otherwise (composed on the host);
+ *  - v (:891-936), one per track in track order: "v {x * sx} {(-y) * sy} {z * sz}" (the PLY's arithmetic: y = 0 prints -0); in
+ *    Color mode " {r / 255} {g / 255} {b / 255}" of the track's first present point follows iff get_pixel_checked finds it;
+ *  - vt (:938-969), Texture mode only: per track, and per present point in image order, "vt {x / width} {1 - y / height}" with x,
+ *    y, width, height as u32 turned into f64.  No bounds test: a point past its image prints u above 1, a zero width inf or NaN;
+ *  - f (:971-997), one per polygon in list order: "f" and for i in 2, 1, 0 " {vertices[i] + 1}", in Texture mode
+ *    " {vertices[i] + 1}/{uv + 1}" with uv = (the present points of the tracks before vertices[i]) + (that track's present
+ *    points among the images below the polygon's camera; a camera >= m counts all of them).  In Texture mode
+ *    "usemtl Textured{camera}" goes before polygon 0 and before every polygon whose camera differs from its predecessor's.
+ * Arguments as cvhip_mesh_ply's, plus polygon_cameras (n_poly x uint32, host or device; read in Texture mode, where NULL with
+ * n_poly > 0 is CVHIP_ERR_INVALID) and stem (the output path's file stem; read in Texture mode, where NULL is
+ * CVHIP_ERR_INVALID).  tracks are read in Color and Texture mode, images and image_offsets in Color mode only, image_dims in
+ * both (Texture mode takes images = NULL).  out_sections[4] (may be NULL) = the header's, v, vt and f bytes.
+ * cap = 0 sizes the image - it runs the length pass, whose per-block byte counts go through a 64-bit scan - and writes nothing;
+ * 0 < cap < size is CVHIP_ERR_INVALID with nothing written.  n = 0 and n_poly = 0 give the header alone (an empty image
+ * outside Texture mode).
+ * Errors, each with nothing written: CVHIP_ERR_INVALID "Track has no images" (Color and Texture mode: a track without a point,
+ * or m = 0 with n > 0; Plain mode accepts such a track), CVHIP_ERR_INVALID for a vertex >= n, CVHIP_ERR_UNSUPPORTED for 2^32 - 1
+ * or more tracks or polygons, or n * m >= 2^32 - 1 in Color and Texture mode.  Saving the {stem}-{i}.png images is the caller's. */
+int cvhip_mesh_obj(cvhip_device *dev, const double *points, const int32_t *tracks, uint64_t n, uint32_t m,
+                   const uint8_t *images, const uint64_t *image_offsets, const uint32_t *image_dims,
+                   uint32_t vertex_mode, const double *out_scale,
+                   const uint32_t *polygons, const uint32_t *polygon_cameras, uint64_t n_poly, const char *stem,
+                   uint8_t *out, uint64_t cap, uint64_t *out_size, uint64_t *out_sections);
+
+/* The {stem}.mtl text of ObjWriter::write_materials (:856-868) for m images: per image "newmtl Textured{i}", the five fixed
+ * lines, "map_Ka {stem}-{i}.png", "map_Kd {stem}-{i}.png" and an empty line.  Host memory only, no device.  cap = 0 sizes;
+ * 0 < cap < size is CVHIP_ERR_INVALID. */
+int cvhip_mesh_obj_mtl(const char *stem, uint32_t m, char *out, uint64_t cap, uint64_t *out_size);
+
+/* Rust's `{}` of each of n doubles, concatenated without separators, formatted on the device (the formatter of
+ * cvhip_mesh_obj): value i's text is out[offsets[i] .. offsets[i + 1]).  values, out and offsets (n + 1 x uint64, may be NULL)
+ * are host or device pointers.  cap = 0 sizes (*out_size) and writes nothing; 0 < cap < size is CVHIP_ERR_INVALID;
+ * CVHIP_ERR_UNSUPPORTED with 2^32 - 1 or more values. */
+int cvhip_f64_display(cvhip_device *dev, const double *values, uint64_t n, uint8_t *out, uint64_t cap, uint64_t *out_size,
+                      uint64_t *offsets);
 
 /* Row sharding (multi-GPU): restrict the SEARCH passes of this context to shard `num` of `den`
  * equal row chunks of the searched level image: rows [num*rps, min((num+1)*rps, h_level)) with
