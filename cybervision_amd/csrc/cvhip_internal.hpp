@@ -140,6 +140,8 @@ void launch_triangulate_affine(const uint32_t *cells, uint32_t lw, uint32_t lh, 
 
 // single-block exclusive scan of n u32 in place, total to *total
 void launch_scan_u32(uint32_t *data, uint32_t n, uint32_t *total, hipStream_t s);
+// the same of n u64 (mesh_obj_kernels.hip): sums of bytes, which pass 2^32
+void launch_scan_u64(unsigned long long *data, unsigned long long n, unsigned long long *total, hipStream_t s);
 // Triangulation::extend_tracks on the forward grid (track_kernels.hip)
 void launch_extend_tracks_match(const uint32_t *cells, uint32_t lw, uint32_t lh, uint32_t k, uint32_t gw, uint32_t gh,
                                 const int2 *track_p1, unsigned long long n_tracks, uint32_t radius, int2 *out_p2,
@@ -241,23 +243,6 @@ class CallScratch {
 };
 
 #ifdef __HIPCC__
-// (shared by the mesh writers: mesh_output_kernels.hip, mesh_obj_kernels.hip; BLOCK = the lanes of the block)
-// The block's `len` staged bytes, which begin `pad` bytes into `stage`, go to dst + pad .. dst + pad + len (dst is 4-byte
-// aligned): lanes take consecutive dwords; a dword whose four bytes are all the block's is one store, the others - the
-// block's unaligned head and tail, whose remaining bytes belong to the neighbouring blocks or the header - go byte by byte.
-template <int BLOCK>
-__device__ __forceinline__ void stage_out(const uint32_t *stage, uint32_t pad, uint32_t len, uint8_t *__restrict__ dst)
-{
-    const uint8_t *bytes = reinterpret_cast<const uint8_t *>(stage);
-    const uint32_t end = pad + len;
-    for (uint32_t k = threadIdx.x; 4 * k < end; k += BLOCK) {
-        const uint32_t lo = 4 * k < pad ? pad : 4 * k, hi = 4 * k + 4 > end ? end : 4 * k + 4;
-        if (hi - lo == 4)
-            reinterpret_cast<uint32_t *>(dst)[k] = stage[k];
-        else
-            for (uint32_t b = lo; b < hi; b++) dst[b] = bytes[b];
-    }
-}
 // the match stored for full-resolution cell (gx, gy), if any: level cell (gx >> k, gy >> k) when both are multiples
 // of 2^k (the scatter of mod.rs:311-316), scaled back by 2^k (mod.rs:459-462)
 __device__ __forceinline__ bool full_res_match(const uint32_t *__restrict__ cells, uint32_t lw, uint32_t lh, uint32_t k,

@@ -612,34 +612,55 @@ struct PlySections {
     uint64_t header = 0, vertices = 0, faces = 0;
 };
 
+namespace detail {
+// the arrays of cvhip_mesh_ply and cvhip_mesh_obj: the polygons and their cameras, flattened, and the images, concatenated
+struct WriterArrays {
+    std::vector<uint32_t> polygons, cameras, dims;
+    std::vector<uint8_t> pixels;
+    std::vector<uint64_t> offsets{0};
+    uint64_t n = 0;
+    uint32_t m = 0;    // images per track (an affine surface has no cameras: the number of images then)
+    bool with_dims = false; // one image per image of a track
+};
+inline WriterArrays writer_arrays(const Surface &s, const std::vector<Polygon> &polygons, const std::vector<RgbImage> &images, bool with_pixels)
+{
+    WriterArrays a;
+    for (const Polygon &p : polygons) a.polygons.insert(a.polygons.end(), p.vertices.begin(), p.vertices.end()), a.cameras.push_back(p.camera_i);
+    a.n = s.tracks_len();
+    a.m = a.n ? (uint32_t)(s.tracks.size() / (2 * a.n)) : (uint32_t)images.size();
+    for (const RgbImage &im : images) {
+        if (with_pixels) a.pixels.insert(a.pixels.end(), im.pixels.begin(), im.pixels.end());
+        a.offsets.push_back(a.pixels.size());
+        a.dims.push_back(im.width), a.dims.push_back(im.height);
+    }
+    a.with_dims = images.size() == a.m && a.m > 0;
+    return a;
+}
+// call(out, cap, &size) twice: for the size, then into a vector of that size
+template <typename Call> inline std::vector<uint8_t> size_then_fill(Call &&call)
+{
+    uint64_t size = 0;
+    call(nullptr, 0, &size);
+    std::vector<uint8_t> out(size);
+    call(out.data(), size, &size);
+    return out;
+}
+} // namespace detail
+
 // Mesh::output with a PlyWriter -> the file's bytes.  images: one per image of a track, read in Color mode only; the surface
 // may be affine (no cameras): `m` is then the number of images.
 inline std::vector<uint8_t> ply(GpuDevice &dev, const Surface &s, const std::vector<Polygon> &polygons, const std::vector<RgbImage> &images,
                                 VertexMode mode, const std::array<double, 3> &out_scale, PlySections *sections = nullptr)
 {
-    std::vector<uint32_t> flat;
-    for (const Polygon &p : polygons) flat.insert(flat.end(), p.vertices.begin(), p.vertices.end());
-    const uint64_t n = s.tracks_len();
-    const uint32_t m = n ? (uint32_t)(s.tracks.size() / (2 * n)) : (uint32_t)images.size();
-    std::vector<uint8_t> pixels;
-    std::vector<uint64_t> offsets{0};
-    std::vector<uint32_t> dims;
-    for (const RgbImage &im : images) {
-        pixels.insert(pixels.end(), im.pixels.begin(), im.pixels.end());
-        offsets.push_back(pixels.size());
-        dims.push_back(im.width), dims.push_back(im.height);
-    }
-    const bool with_images = mode == VertexMode::Color && images.size() == m && m > 0;
-    uint64_t size = 0, sec[3] = {0, 0, 0};
-    auto call = [&](uint8_t *out, uint64_t cap) {
-        check(cvhip_mesh_ply(dev.handle(), s.points.data(), s.tracks.data(), n, m, with_images ? pixels.data() : nullptr,
-                             with_images ? offsets.data() : nullptr, with_images ? dims.data() : nullptr, (uint32_t)mode, out_scale.data(),
-                             flat.data(), polygons.size(), out, cap, &size, sec),
+    const detail::WriterArrays a = detail::writer_arrays(s, polygons, images, true);
+    const bool with_images = mode == VertexMode::Color && a.with_dims;
+    uint64_t sec[3] = {0, 0, 0};
+    std::vector<uint8_t> out = detail::size_then_fill([&](uint8_t *dst, uint64_t cap, uint64_t *size) {
+        check(cvhip_mesh_ply(dev.handle(), s.points.data(), s.tracks.data(), a.n, a.m, with_images ? a.pixels.data() : nullptr,
+                             with_images ? a.offsets.data() : nullptr, with_images ? a.dims.data() : nullptr, (uint32_t)mode, out_scale.data(),
+                             a.polygons.data(), polygons.size(), dst, cap, size, sec),
               "cvhip_mesh_ply");
-    };
-    call(nullptr, 0);
-    std::vector<uint8_t> out(size);
-    call(out.data(), size);
+    });
     if (sections) *sections = PlySections{sec[0], sec[1], sec[2]};
     return out;
 }
@@ -656,29 +677,15 @@ inline std::vector<uint8_t> mesh_obj(GpuDevice &dev, const Surface &s, const std
                                      VertexMode mode, const std::array<double, 3> &out_scale, const std::string &stem,
                                      ObjSections *sections = nullptr)
 {
-    std::vector<uint32_t> flat, cameras;
-    for (const Polygon &p : polygons) flat.insert(flat.end(), p.vertices.begin(), p.vertices.end()), cameras.push_back(p.camera_i);
-    const uint64_t n = s.tracks_len();
-    const uint32_t m = n ? (uint32_t)(s.tracks.size() / (2 * n)) : (uint32_t)images.size();
-    std::vector<uint8_t> pixels;
-    std::vector<uint64_t> offsets{0};
-    std::vector<uint32_t> dims;
-    for (const RgbImage &im : images) {
-        if (mode == VertexMode::Color) pixels.insert(pixels.end(), im.pixels.begin(), im.pixels.end());
-        offsets.push_back(pixels.size());
-        dims.push_back(im.width), dims.push_back(im.height);
-    }
-    const bool with_dims = mode != VertexMode::Plain && images.size() == m && m > 0, with_images = with_dims && mode == VertexMode::Color;
-    uint64_t size = 0, sec[4] = {0, 0, 0, 0};
-    auto call = [&](uint8_t *out, uint64_t cap) {
-        check(cvhip_mesh_obj(dev.handle(), s.points.data(), s.tracks.data(), n, m, with_images ? pixels.data() : nullptr,
-                             with_images ? offsets.data() : nullptr, with_dims ? dims.data() : nullptr, (uint32_t)mode, out_scale.data(),
-                             flat.data(), cameras.data(), polygons.size(), stem.c_str(), out, cap, &size, sec),
+    const detail::WriterArrays a = detail::writer_arrays(s, polygons, images, mode == VertexMode::Color);
+    const bool with_dims = mode != VertexMode::Plain && a.with_dims, with_images = with_dims && mode == VertexMode::Color;
+    uint64_t sec[4] = {0, 0, 0, 0};
+    std::vector<uint8_t> out = detail::size_then_fill([&](uint8_t *dst, uint64_t cap, uint64_t *size) {
+        check(cvhip_mesh_obj(dev.handle(), s.points.data(), s.tracks.data(), a.n, a.m, with_images ? a.pixels.data() : nullptr,
+                             with_images ? a.offsets.data() : nullptr, with_dims ? a.dims.data() : nullptr, (uint32_t)mode, out_scale.data(),
+                             a.polygons.data(), a.cameras.data(), polygons.size(), stem.c_str(), dst, cap, size, sec),
               "cvhip_mesh_obj");
-    };
-    call(nullptr, 0);
-    std::vector<uint8_t> out(size);
-    call(out.data(), size);
+    });
     if (sections) *sections = ObjSections{sec[0], sec[1], sec[2], sec[3]};
     return out;
 }

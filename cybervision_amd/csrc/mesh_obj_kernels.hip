@@ -13,14 +13,16 @@
 // Records have data-dependent lengths (a v line is 8 to ~990 bytes), so the file is made in two passes over the same kernels
 // (WRITE = false / true): the length pass leaves per block of 256 records the bytes of its records, a 64-bit exclusive scan
 // places the blocks, the host learns the section sizes; the write pass runs the formatter again (nothing is kept between the
-// passes but 8 bytes per block), places its records by an in-block scan, assembles them in LDS and copies them out as aligned
-// dwords.  A block with more bytes than the staging buffer (a block of subnormals is ~250 KB) stores its records directly.
+// passes but 8 bytes per block) and hands its records to the writer the PLY shares (mesh_records.hpp): placed by an in-block
+// scan, assembled in LDS and copied out as aligned dwords.  A block with more bytes than the staging buffer (a block of
+// subnormals is ~250 KB) stores its records directly.
 // Not here: saving the {stem}-{i}.png images (there is no PNG encoder).
 #include <cstdio>
 #include <cstring>
 #include <string>
 
-#include "cvhip_internal.hpp"
+#include "mesh_records.hpp"
+
 #include "f64_display.hpp"
 
 namespace cvhip {
@@ -28,37 +30,7 @@ namespace {
 
 namespace fd = f64_display;
 
-constexpr int BLOCK = 256;
 constexpr uint32_t STAGE_BYTES = 40 * 1024; // a block of 256 v lines of the usual kind is ~15 KB, ~29 KB with colours
-enum { MODE_PLAIN = 0, MODE_COLOR = 1, MODE_TEXTURE = 2 };
-
-struct ObjImages {
-    const uint8_t *pixels;
-    const unsigned long long *offsets;
-    const uint2 *dims;
-};
-
-// exclusive scan of v over the block's 256 lanes; total = the block's sum.  s_wave: BLOCK / 64 words of LDS.
-__device__ __forceinline__ uint32_t block_scan(uint32_t v, uint32_t *s_wave, uint32_t &total)
-{
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    uint32_t incl = v;
-#pragma unroll
-    for (int s = 1; s < 64; s <<= 1) {
-        const uint32_t t = __shfl_up(incl, s, 64);
-        if ((int)lane >= s) incl += t;
-    }
-    __syncthreads(); // (the previous round's readers are done with s_wave)
-    if (lane == 63) s_wave[wave] = incl;
-    __syncthreads();
-    uint32_t before = 0;
-    total = 0;
-    for (uint32_t k = 0; k < BLOCK / 64; k++) {
-        if (k < wave) before += s_wave[k];
-        total += s_wave[k];
-    }
-    return before + incl - v;
-}
 
 // single-block exclusive scan of n u64 in place, total to *total (launch_scan_u32 would wrap at 4 GB of text)
 __global__ __launch_bounds__(1024) void obj_scan_u64_kernel(unsigned long long *__restrict__ data, unsigned long long n,
@@ -91,9 +63,8 @@ __global__ __launch_bounds__(1024) void obj_scan_u64_kernel(unsigned long long *
 }
 
 // What every kernel does with its lane's record of `len` bytes (0: none), which `write(dst)` writes.
-// WRITE = false: sums[blk] = the block's bytes.  WRITE = true: the record goes to section + sums[blk] + (the bytes of the
-// lanes before it) - through the staging buffer, or directly when the block's bytes do not fit in it; a block that would
-// end past the section (the inputs changed since they were measured) writes nothing.
+// WRITE = false: sums[blk] = the block's bytes.  WRITE = true: write_records puts it at section + sums[blk] + (the bytes of
+// the lanes before it); *record_offset = that offset.
 template <bool WRITE, typename Writer>
 __device__ __forceinline__ void emit(uint32_t len, Writer &&write, unsigned long long blk, unsigned long long *__restrict__ sums,
                                      uint8_t *__restrict__ section, unsigned long long section_bytes, uint32_t *s_stage, uint32_t *s_wave,
@@ -107,16 +78,7 @@ __device__ __forceinline__ void emit(uint32_t len, Writer &&write, unsigned long
     }
     const unsigned long long start = sums[blk];
     if (record_offset) *record_offset = start + before;
-    if (start + total > section_bytes || total == 0) return;
-    uint8_t *dst = section + start;
-    if (total + 3 <= STAGE_BYTES) {
-        const uint32_t pad = (uint32_t)(reinterpret_cast<uintptr_t>(dst) & 3u);
-        if (len) write(reinterpret_cast<uint8_t *>(s_stage) + pad + before);
-        __syncthreads();
-        stage_out<BLOCK>(s_stage, pad, total, dst - pad);
-        __syncthreads();
-    } else if (len)
-        write(dst + before);
+    write_records<STAGE_BYTES>(len, before, total, write, start, section, section_bytes, s_stage);
 }
 
 // ---- tracks: present points ---------------------------------------------------------------------------------------------------------
@@ -156,7 +118,7 @@ __global__ __launch_bounds__(BLOCK) void mesh_obj_uv_index_kernel(uint32_t *__re
 // ---- v lines (:891-936) -------------------------------------------------------------------------------------------------------------
 template <bool COLOR, bool WRITE>
 __global__ __launch_bounds__(BLOCK) void mesh_obj_vertex_kernel(const double *__restrict__ points, const int2 *__restrict__ tracks,
-                                                                unsigned long long n, uint32_t m, ObjImages img, double sx, double sy,
+                                                                unsigned long long n, uint32_t m, TrackImages img, double sx, double sy,
                                                                 double sz, unsigned long long n_blocks, unsigned long long *__restrict__ sums,
                                                                 uint8_t *__restrict__ section, unsigned long long section_bytes)
 {
@@ -172,16 +134,12 @@ __global__ __launch_bounds__(BLOCK) void mesh_obj_vertex_kernel(const double *__
             d[2] = fd::shortest(points[3 * i + 2] * sz);
             values = 3;
             if (COLOR) {
-                for (uint32_t c = 0; c < m; c++) { // the first present point, and get_pixel_checked on it (:898-906)
-                    const int2 p = tracks[i * m + c];
-                    if (p.x < 0) continue;
-                    const uint2 dim = img.dims[c];
-                    if ((uint32_t)p.x < dim.x && (uint32_t)p.y < dim.y) {
-                        const uint8_t *px = img.pixels + img.offsets[c] + ((unsigned long long)(uint32_t)p.y * dim.x + (uint32_t)p.x) * 3ull;
-                        for (int k = 0; k < 3; k++) d[(COLOR ? 3 : 0) + k] = fd::shortest((double)px[k] / 255.0);
-                        values = 6;
-                    }
-                    break;
+                unsigned long long pixel = 0;
+                const int kind = first_point(tracks, i, m, img.dims, pixel); // (:898-906)
+                if ((kind & 3) == POINT_PIXEL) {
+                    const uint8_t *px = img.pixels + img.offsets[(uint32_t)kind >> 2] + pixel;
+                    for (int k = 0; k < 3; k++) d[(COLOR ? 3 : 0) + k] = fd::shortest((double)px[k] / 255.0);
+                    values = 6;
                 }
             }
             len = 2; // 'v' and '\n'
@@ -317,12 +275,13 @@ __global__ __launch_bounds__(BLOCK) void f64_display_kernel(const double *__rest
     }
 }
 
-void scan_u64(unsigned long long *data, unsigned long long n, unsigned long long *total, hipStream_t s)
+} // namespace
+
+void launch_scan_u64(unsigned long long *data, unsigned long long n, unsigned long long *total, hipStream_t s)
 {
     hipLaunchKernelGGL(obj_scan_u64_kernel, dim3(1), dim3(1024), 0, s, data, n, total);
 }
 
-} // namespace
 } // namespace cvhip
 
 using namespace cvhip;
@@ -332,28 +291,18 @@ extern "C" int cvhip_mesh_obj(cvhip_device *dev, const double *points, const int
                               const uint32_t *polygons, const uint32_t *polygon_cameras, uint64_t n_poly, const char *stem, uint8_t *out,
                               uint64_t cap, uint64_t *out_size, uint64_t *out_sections)
 {
-    if (vertex_mode > MODE_TEXTURE) return fail(CVHIP_ERR_INVALID, "mesh_obj: vertex_mode is not 0 (Plain), 1 (Color) or 2 (Texture)");
     const bool color = vertex_mode == MODE_COLOR, texture = vertex_mode == MODE_TEXTURE;
-    if (!dev || !out_size || !out_scale || (n && !points) || (n_poly && !polygons) || (cap && !out))
-        return fail(CVHIP_ERR_INVALID, "mesh_obj: null argument");
-    if (texture && !stem) return fail(CVHIP_ERR_INVALID, "mesh_obj: Texture mode without a stem");
-    if (texture && n_poly && !polygon_cameras) return fail(CVHIP_ERR_INVALID, "mesh_obj: Texture mode without polygon_cameras");
-    if (n >= 0xFFFFFFFFull) return fail(CVHIP_ERR_UNSUPPORTED, "mesh_obj: 2^32 - 1 or more tracks");
-    if (n_poly >= 0xFFFFFFFFull) return fail(CVHIP_ERR_UNSUPPORTED, "mesh_obj: 2^32 - 1 or more polygons");
+    int rc = check_writer_args("mesh_obj", dev, points, n, vertex_mode, out_scale, polygons, n_poly, out, cap, out_size,
+                               texture && !stem                         ? "mesh_obj: Texture mode without a stem"
+                               : texture && n_poly && !polygon_cameras ? "mesh_obj: Texture mode without polygon_cameras"
+                                                                       : nullptr);
+    if (rc != CVHIP_OK) return rc;
     const bool with_tracks = (color || texture) && n;
     if (with_tracks) {
         if (m == 0) return fail(CVHIP_ERR_INVALID, "Track has no images"); // :908, :961
         if (n > 0xFFFFFFFEull / m) return fail(CVHIP_ERR_UNSUPPORTED, "mesh_obj: 2^32 - 1 or more points of tracks");
-        if (!tracks || !image_dims) return fail(CVHIP_ERR_INVALID, color ? "mesh_obj: Color mode without images" : "mesh_obj: Texture mode without image_dims");
-    }
-    if (color && n) {
-        if (!images || !image_offsets) return fail(CVHIP_ERR_INVALID, "mesh_obj: Color mode without images");
-        for (uint32_t c = 0; c < m; c++) { // every pixel the kernels may read lies inside `images`
-            if (image_offsets[c + 1] < image_offsets[c]) return fail(CVHIP_ERR_INVALID, "mesh_obj: image_offsets decrease");
-            const uint64_t pixels = (uint64_t)image_dims[2 * c] * image_dims[2 * c + 1];
-            if (pixels > (image_offsets[c + 1] - image_offsets[c]) / 3)
-                return fail(CVHIP_ERR_INVALID, "mesh_obj: an image is smaller than width x height x 3 bytes");
-        }
+        if (texture && (!tracks || !image_dims)) return fail(CVHIP_ERR_INVALID, "mesh_obj: Texture mode without image_dims");
+        if (color && (rc = check_track_images("mesh_obj", tracks, m, images, image_offsets, image_dims)) != CVHIP_OK) return rc;
     }
     CVHIP_TRY_HIP(hipSetDevice(dev->d.ordinal));
     hipStream_t s = dev->d.stream;
@@ -362,9 +311,9 @@ extern "C" int cvhip_mesh_obj(cvhip_device *dev, const double *points, const int
     const unsigned long long cells = with_tracks && texture ? n * m : 0;
     const unsigned long long v_blocks = (n + BLOCK - 1) / BLOCK, uv_blocks = (cells + BLOCK - 1) / BLOCK, f_blocks = (n_poly + BLOCK - 1) / BLOCK;
     const double *d_points = nullptr;
-    const int32_t *d_tracks = nullptr;
-    const uint32_t *d_poly = nullptr, *d_cameras = nullptr, *d_dims = nullptr;
-    ObjImages img{nullptr, nullptr, nullptr};
+    const int2 *t2 = nullptr;
+    const uint32_t *d_poly = nullptr, *d_cameras = nullptr;
+    TrackImages img{nullptr, nullptr, nullptr};
     // per-block bytes of the v, vt and f records and present points of the tracks, then the four totals
     unsigned long long *sums = nullptr, h_totals[4] = {0, 0, 0, 0};
     uint32_t *flags = nullptr, h_flags[2] = {0, 0}; // a vertex >= n; a track without a point
@@ -373,15 +322,8 @@ extern "C" int cvhip_mesh_obj(cvhip_device *dev, const double *points, const int
     hipError_t e = sc.input(points, (size_t)n * 3, &d_points, s);
     if (e == hipSuccess) e = sc.input(polygons, (size_t)n_poly * 3, &d_poly, s);
     if (e == hipSuccess && texture) e = sc.input(polygon_cameras, (size_t)n_poly, &d_cameras, s);
-    if (e == hipSuccess && with_tracks) {
-        const unsigned long long *d_offsets = nullptr;
-        e = sc.input(tracks, (size_t)n * m * 2, &d_tracks, s);
-        if (e == hipSuccess) e = sc.input(image_dims, (size_t)m * 2, &d_dims, s);
-        if (e == hipSuccess && color) e = sc.input(images, (size_t)image_offsets[m], &img.pixels, s);
-        if (e == hipSuccess && color) e = sc.input(reinterpret_cast<const unsigned long long *>(image_offsets), (size_t)m + 1, &d_offsets, s);
-        img.offsets = d_offsets, img.dims = reinterpret_cast<const uint2 *>(d_dims);
-        if (e == hipSuccess && texture) e = sc.alloc(&uv_index, (size_t)n);
-    }
+    if (e == hipSuccess && with_tracks) e = upload_track_images(sc, tracks, n, m, images, image_offsets, image_dims, color, &t2, &img, s);
+    if (e == hipSuccess && with_tracks && texture) e = sc.alloc(&uv_index, (size_t)n);
     if (e == hipSuccess) e = sc.alloc(&sums, n_sums + 4);
     if (e == hipSuccess) e = sc.alloc(&flags, 2);
     if (e == hipSuccess) e = hipMemsetAsync(flags, 0, 2 * sizeof(uint32_t), s);
@@ -389,7 +331,6 @@ extern "C" int cvhip_mesh_obj(cvhip_device *dev, const double *points, const int
     if (e != hipSuccess) return device_error("mesh_obj", e);
     unsigned long long *v_sums = sums, *count_sums = sums + v_blocks, *uv_sums = count_sums + v_blocks, *f_sums = uv_sums + uv_blocks;
     unsigned long long *totals = sums + n_sums; // v, vt, f bytes; present points
-    const int2 *t2 = reinterpret_cast<const int2 *>(d_tracks);
     // ---- what must hold before a face is measured: vertices < n, and in Color and Texture mode a point in every track
     if (n_poly) launch_mesh_check_polygons(d_poly, n_poly, n, flags, s);
     if (with_tracks)
@@ -435,15 +376,15 @@ extern "C" int cvhip_mesh_obj(cvhip_device *dev, const double *points, const int
 #undef CVHIP_OBJ_FACE
     };
     if (cells) { // uv_index before the faces
-        scan_u64(count_sums, v_blocks, totals + 3, s);
+        launch_scan_u64(count_sums, v_blocks, totals + 3, s);
         hipLaunchKernelGGL(mesh_obj_uv_index_kernel, dim3(grid_for(n)), dim3(BLOCK), 0, s, uv_index, (unsigned long long)n, v_blocks, count_sums);
     }
     vertex_pass(false, nullptr, 0);
     uv_pass(false, nullptr, 0);
     face_pass(false, nullptr, 0);
-    if (n) scan_u64(v_sums, v_blocks, totals, s);
-    if (cells) scan_u64(uv_sums, uv_blocks, totals + 1, s);
-    if (n_poly) scan_u64(f_sums, f_blocks, totals + 2, s);
+    if (n) launch_scan_u64(v_sums, v_blocks, totals, s);
+    if (cells) launch_scan_u64(uv_sums, uv_blocks, totals + 1, s);
+    if (n_poly) launch_scan_u64(f_sums, f_blocks, totals + 2, s);
     e = hipGetLastError();
     if (e == hipSuccess) e = hipMemcpyAsync(h_totals, totals, sizeof(h_totals), hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
@@ -463,17 +404,7 @@ extern "C" int cvhip_mesh_obj(cvhip_device *dev, const double *points, const int
     vertex_pass(true, d_v, v_bytes);
     uv_pass(true, d_uv, uv_bytes);
     face_pass(true, d_f, f_bytes);
-    e = hipGetLastError();
-    if (d_out != out) { // the body from the stand-in, the header from here
-        if (e == hipSuccess) e = sc.copy_out(out + header.size(), d_v, (size_t)(size - header.size()), s);
-        if (e == hipSuccess) e = hipStreamSynchronize(s);
-        if (e == hipSuccess) std::memcpy(out, header.data(), header.size());
-    } else {
-        if (e == hipSuccess && !header.empty()) e = hipMemcpyAsync(out, header.data(), header.size(), hipMemcpyHostToDevice, s);
-        if (e == hipSuccess) e = hipStreamSynchronize(s);
-    }
-    if (e != hipSuccess) return device_error("mesh_obj", e);
-    return CVHIP_OK;
+    return finish_file_image("mesh_obj", sc, header, out, d_out, size, hipGetLastError(), s);
 }
 
 extern "C" int cvhip_mesh_obj_mtl(const char *stem, uint32_t m, char *out, uint64_t cap, uint64_t *out_size)
@@ -510,7 +441,7 @@ extern "C" int cvhip_f64_display(cvhip_device *dev, const double *values, uint64
     if (e == hipSuccess && n) {
         hipLaunchKernelGGL((f64_display_kernel<false>), dim3(grid_for(n)), dim3(BLOCK), 0, s, d_values, (unsigned long long)n, blocks, sums,
                            static_cast<uint8_t *>(nullptr), 0ull, static_cast<unsigned long long *>(nullptr));
-        scan_u64(sums, blocks, sums + blocks, s);
+        launch_scan_u64(sums, blocks, sums + blocks, s);
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipMemcpyAsync(&h_total, sums + blocks, sizeof(h_total), hipMemcpyDeviceToHost, s);

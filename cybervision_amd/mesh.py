@@ -172,12 +172,8 @@ def _image_args(images):
     return [C.c_void_p((flat if flat.size else one).ctypes.data), _p(offsets), _p(dims)], (flat, offsets, dims, one)
 
 
-def ply(device, surface, polygons, images=None, vertex_mode=VertexMode.Plain, out_scale=(1.0, 1.0, 1.0), sections=None):
-    """The binary PLY file image of Mesh::output with a PlyWriter (output.rs:521-559, 648-772; cvhip_mesh_ply) -> uint8 array.
-    images: one [h, w, 3] uint8 array per image of a track (Color mode only; a vertex takes the pixel of its track's first
-    point, and no colour bytes when that point lies past its image).  `sections`, a list, receives the header's, the
-    vertices' and the faces' byte counts.  Raises CvhipError ("Track has no images") for a track without a point in Color
-    mode."""
+def _writer_args(surface, polygons, out_scale, images):
+    """(points, tracks [n, m, 2], polygons [p, 3], out_scale, m) as cvhip_mesh_ply and cvhip_mesh_obj take them."""
     pts = np.ascontiguousarray(surface.points, dtype=np.float64).reshape(-1, 3)
     tracks = np.ascontiguousarray(surface.tracks, dtype=np.int32)
     if tracks.ndim != 3:
@@ -187,18 +183,39 @@ def ply(device, surface, polygons, images=None, vertex_mode=VertexMode.Plain, ou
     if scale.shape != (3,):
         raise ValueError("out_scale is (x, y, z)")
     m = tracks.shape[1]
-    img_args, _keep = _image_args(images) if images is not None else ([None, None, None], None)
     if images is not None and len(images) != m:
         raise ValueError("one image per image of a track")
-    size, sec = C.c_uint64(0), np.zeros(3, dtype=np.uint64)
-    L = _lib.lib()
-    args = [device.handle, _p(pts), _p(tracks), len(pts), m, *img_args, int(vertex_mode), _p(scale), _p(poly), len(poly)]
-    _lib.check(L.cvhip_mesh_ply(*args, None, 0, C.byref(size), _p(sec)), "cvhip_mesh_ply")
+    return pts, tracks, poly, scale, m
+
+
+def _size_then_fill(name, args, *tail):
+    """The entry `name` twice: `(*args, NULL, 0, &size, *tail)` for the size, then into an array of that size -> the array."""
+    fn, size = getattr(_lib.lib(), name), C.c_uint64(0)
+    _lib.check(fn(*args, None, 0, C.byref(size), *tail), name)
     out = np.zeros(size.value, dtype=np.uint8)
-    _lib.check(L.cvhip_mesh_ply(*args, _p(out), out.size, C.byref(size), _p(sec)), "cvhip_mesh_ply")
+    _lib.check(fn(*args, _p(out), out.size, C.byref(size), *tail), name)
+    return out
+
+
+def _file_image(name, args, n_sections, sections):
+    """_size_then_fill for a file image; `sections`, a list or None, receives its n_sections byte counts."""
+    sec = np.zeros(n_sections, dtype=np.uint64)
+    out = _size_then_fill(name, args, _p(sec))
     if sections is not None:
         sections[:] = [int(v) for v in sec]
     return out
+
+
+def ply(device, surface, polygons, images=None, vertex_mode=VertexMode.Plain, out_scale=(1.0, 1.0, 1.0), sections=None):
+    """The binary PLY file image of Mesh::output with a PlyWriter (output.rs:521-559, 648-772; cvhip_mesh_ply) -> uint8 array.
+    images: one [h, w, 3] uint8 array per image of a track (Color mode only; a vertex takes the pixel of its track's first
+    point, and no colour bytes when that point lies past its image).  `sections`, a list, receives the header's, the
+    vertices' and the faces' byte counts.  Raises CvhipError ("Track has no images") for a track without a point in Color
+    mode."""
+    pts, tracks, poly, scale, m = _writer_args(surface, polygons, out_scale, images)
+    img_args, _keep = _image_args(images) if images is not None else ([None, None, None], None)
+    args = [device.handle, _p(pts), _p(tracks), len(pts), m, *img_args, int(vertex_mode), _p(scale), _p(poly), len(poly)]
+    return _file_image("cvhip_mesh_ply", args, 3, sections)
 
 
 def write_ply(path, device, surface, polygons, images=None, vertex_mode=VertexMode.Plain, out_scale=(1.0, 1.0, 1.0)):
@@ -223,47 +240,24 @@ def obj(device, surface, polygons, camera, images=None, vertex_mode=VertexMode.P
     Texture: only the sizes are read, so a list of (width, height) does as well).  stem: the output's file stem (Texture:
     "mtllib {stem}.mtl").  `sections`, a list, receives the header's, the v, the vt and the f bytes.  Raises CvhipError ("Track
     has no images") for a track without a point in Color and Texture mode."""
-    pts = np.ascontiguousarray(surface.points, dtype=np.float64).reshape(-1, 3)
-    tracks = np.ascontiguousarray(surface.tracks, dtype=np.int32)
-    if tracks.ndim != 3:
-        tracks = tracks.reshape(len(pts), -1, 2)
-    poly = np.ascontiguousarray(polygons, dtype=np.uint32).reshape(-1, 3)
+    pts, tracks, poly, scale, m = _writer_args(surface, polygons, out_scale, images)
     cam = np.ascontiguousarray(camera if camera is not None else np.zeros(len(poly)), dtype=np.uint32).reshape(-1)
     if len(cam) != len(poly):
         raise ValueError("one camera per polygon")
-    scale = np.array([float(v) for v in out_scale], dtype=np.float64)
-    if scale.shape != (3,):
-        raise ValueError("out_scale is (x, y, z)")
-    m = tracks.shape[1]
-    if images is not None and len(images) != m:
-        raise ValueError("one image per image of a track")
     if images is None:
         img_args, _keep = [None, None, None], None
     elif all(hasattr(im, "shape") and len(im.shape) == 3 for im in images) and int(vertex_mode) != VertexMode.Texture:
         img_args, _keep = _image_args(images)
     else:
         img_args, _keep = _dims_args([(im.shape[1], im.shape[0]) if hasattr(im, "shape") else im for im in images])
-    size, sec = C.c_uint64(0), np.zeros(4, dtype=np.uint64)
-    L = _lib.lib()
     args = [device.handle, _p(pts), _p(tracks), len(pts), m, *img_args, int(vertex_mode), _p(scale), _p(poly), _p(cam), len(poly),
             str(stem).encode("utf-8")]
-    _lib.check(L.cvhip_mesh_obj(*args, None, 0, C.byref(size), _p(sec)), "cvhip_mesh_obj")
-    out = np.zeros(size.value, dtype=np.uint8)
-    _lib.check(L.cvhip_mesh_obj(*args, _p(out), out.size, C.byref(size), _p(sec)), "cvhip_mesh_obj")
-    if sections is not None:
-        sections[:] = [int(v) for v in sec]
-    return out
+    return _file_image("cvhip_mesh_obj", args, 4, sections)
 
 
 def obj_mtl(stem, m: int):
     """The {stem}.mtl text of ObjWriter::write_materials (output.rs:856-868; cvhip_mesh_obj_mtl) for m images -> bytes."""
-    name = str(stem).encode("utf-8")
-    size = C.c_uint64(0)
-    L = _lib.lib()
-    _lib.check(L.cvhip_mesh_obj_mtl(name, int(m), None, 0, C.byref(size)), "cvhip_mesh_obj_mtl")
-    out = np.zeros(size.value, dtype=np.uint8)
-    _lib.check(L.cvhip_mesh_obj_mtl(name, int(m), _p(out), out.size, C.byref(size)), "cvhip_mesh_obj_mtl")
-    return out.tobytes()
+    return _size_then_fill("cvhip_mesh_obj_mtl", [str(stem).encode("utf-8"), int(m)]).tobytes()
 
 
 def write_obj(path, device, surface, polygons, camera, images=None, vertex_mode=VertexMode.Plain, out_scale=(1.0, 1.0, 1.0)):
@@ -284,12 +278,8 @@ def write_obj(path, device, surface, polygons, camera, images=None, vertex_mode=
 def f64_display(device, values):
     """Rust's `{}` of each double, formatted on the device (cvhip_f64_display) -> list of str."""
     v = np.ascontiguousarray(values, dtype=np.float64).reshape(-1)
-    size = C.c_uint64(0)
-    L = _lib.lib()
-    _lib.check(L.cvhip_f64_display(device.handle, _p(v), len(v), None, 0, C.byref(size), None), "cvhip_f64_display")
-    out, offsets = np.zeros(size.value, dtype=np.uint8), np.zeros(len(v) + 1, dtype=np.uint64)
-    _lib.check(L.cvhip_f64_display(device.handle, _p(v), len(v), _p(out), out.size, C.byref(size), _p(offsets)), "cvhip_f64_display")
-    text = out.tobytes().decode("ascii")
+    offsets = np.zeros(len(v) + 1, dtype=np.uint64)  # (the sizing call of values with text leaves it alone)
+    text = _size_then_fill("cvhip_f64_display", [device.handle, _p(v), len(v)], _p(offsets)).tobytes().decode("ascii")
     return [text[int(a):int(b)] for a, b in zip(offsets[:-1], offsets[1:])]
 
 

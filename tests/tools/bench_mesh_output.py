@@ -35,8 +35,8 @@ sys.path.insert(0, str(Path(__file__).resolve().parent))
 import bench_mesh  # noqa: E402
 from cybervision_amd import _lib, correlation, mesh  # noqa: E402
 
-KERNELS = ("mesh_ply_count_kernel", "mesh_ply_vertex_kernel<false>", "mesh_ply_vertex_kernel<true>", "mesh_ply_face_kernel",
-           "mesh_colour_kernel")
+KERNELS = ("mesh_ply_vertex_kernel<true, false>", "mesh_ply_vertex_kernel<false, true>", "mesh_ply_vertex_kernel<true, true>",
+           "mesh_ply_face_kernel", "mesh_colour_kernel")
 
 
 def kernel_medians(trace_dir):
