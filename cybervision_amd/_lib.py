@@ -136,6 +136,9 @@ SIGNATURES = {
     # the Delaunay triangulation of a camera's points: (xy, k, out_faces, cap_faces, out_n_faces, out_stats)
     "cvhip_mesh_delaunay": (C.c_int, [_vp, _vp, C.c_uint64, _vp, C.c_uint64, C.POINTER(C.c_uint64), _vp]),
     "cvhip_mesh_delaunay_set_lane_cells": (C.c_int, [_vp, _u32]),
+    "cvhip_mesh_delaunay_set_lattice": (C.c_int, [_vp, C.c_int]),
+    "cvhip_mesh_delaunay_get_lattice": (C.c_int, [_vp, C.POINTER(C.c_int)]),
+    "cvhip_mesh_delaunay_get_lattice_stars": (C.c_int, [_vp, C.POINTER(C.c_uint64)]),
 }
 
 

@@ -1914,3 +1914,24 @@ extern "C" int cvhip_mesh_delaunay_set_lane_cells(cvhip_device *dev, uint32_t ce
     dev->d.mesh_delaunay_lane_cells = cells;
     return CVHIP_OK;
 }
+
+extern "C" int cvhip_mesh_delaunay_set_lattice(cvhip_device *dev, int on)
+{
+    if (!dev) return fail(CVHIP_ERR_INVALID, "cvhip_mesh_delaunay_set_lattice: null device");
+    dev->d.mesh_delaunay_lattice = on ? 1 : 0;
+    return CVHIP_OK;
+}
+
+extern "C" int cvhip_mesh_delaunay_get_lattice(cvhip_device *dev, int *out_on)
+{
+    if (!dev || !out_on) return fail(CVHIP_ERR_INVALID, "cvhip_mesh_delaunay_get_lattice: null argument");
+    *out_on = dev->d.mesh_delaunay_lattice;
+    return CVHIP_OK;
+}
+
+extern "C" int cvhip_mesh_delaunay_get_lattice_stars(cvhip_device *dev, uint64_t *out_stars)
+{
+    if (!dev || !out_stars) return fail(CVHIP_ERR_INVALID, "cvhip_mesh_delaunay_get_lattice_stars: null argument");
+    *out_stars = dev->d.mesh_delaunay_lattice_stars;
+    return CVHIP_OK;
+}

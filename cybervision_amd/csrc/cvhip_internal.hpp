@@ -319,6 +319,8 @@ struct Device {
     int ransac_pencil = CVHIP_PENCIL_THIN_SVD; // cvhip_ransac_set_pencil: the 7-point pencil's basis (default: the reference's)
     uint32_t mesh_wide_threshold = CVHIP_MESH_WIDE_THRESHOLD_DEFAULT; // cvhip_mesh_set_wide_threshold
     uint32_t mesh_delaunay_lane_cells = CVHIP_MESH_DELAUNAY_LANE_CELLS_DEFAULT; // cvhip_mesh_delaunay_set_lane_cells
+    int mesh_delaunay_lattice = CVHIP_MESH_DELAUNAY_LATTICE_DEFAULT; // cvhip_mesh_delaunay_set_lattice: integer coordinates take the lattice kernels
+    uint64_t mesh_delaunay_lattice_stars = 0;                        // cvhip_mesh_delaunay_get_lattice_stars: of the last call
     // complete() into HOST memory (GpuContext::complete_process, gpu/mod.rs:210-216): two device staging sets that the
     // full-resolution grid is expanded into, and a copy stream of its own, so that the 12 B/px transfer of one pair can
     // run under the search of the next (cvhip_ctx_set_async_readback) and no call allocates.  Grow-only, per handle.

@@ -1,7 +1,8 @@
 // delaunay_common.hpp — the Delaunay triangulation of a camera's points, one star at a time.
 //
-// Written once for both paths of cvhip_mesh_delaunay: the device lanes (delaunay_kernels.hip, FilterPolicy) and the exact
-// host path inside the library (ExactPolicy).  Compiles without HIP (tests/cpp/delaunay_host_exact.cpp).
+// Written once for every path of cvhip_mesh_delaunay: the device lanes (delaunay_kernels.hip; FilterPolicy, and LatticePolicy
+// when every coordinate is an integer within 2^24) and the exact host path inside the library (ExactPolicy).  Compiles
+// without HIP (tests/cpp/delaunay_host_exact.cpp, tests/cpp/delaunay_lattice_exact.cpp).
 //
 // The star of point a is built by WRAPPING over a uniform grid of the points:
 //   - the start is a's nearest point (a nearest point is a Delaunay neighbour whatever else is co-circular: the disc on
@@ -16,7 +17,11 @@
 // The cells searched are computed in CELL SPACE ((x - min_x) / s) in rounded arithmetic and inflated by more than their
 // error (DESIGN.md 4.13 has the bounds); a circle too flat to bound (|det| 2^20 < L^2) counts as the half-plane.
 //
-// Exact ties (ExactPolicy only): the points left of a->j on the empty circle through a and j form, with a and j, a convex
+// LatticePolicy is exact as well and runs on the device: for integer-valued coordinates the determinants are plain integer
+// arithmetic (its bound is stated at the policy).  It skips no duplicates: a candidate at the position of j, of the current k
+// or of the tie polygon's first or last vertex flags the star instead, and the host path applies the duplicate rule.
+//
+// Exact ties (ExactPolicy and LatticePolicy): the points left of a->j on the empty circle through a and j form, with a and j, a convex
 // polygon that is fanned from its lowest index m: the next neighbour is the polygon's first vertex after j when m = a, its
 // last when m = j, and m otherwise.  Of several indices at one position the lowest is the vertex.
 // The exactness holds while no product of coordinate differences over- or underflows (|differences| within 2^+-240).
@@ -126,6 +131,65 @@ struct FilterPolicy {
     }
     CVHIP_DLN_HD int dist(double ax, double ay, double px, double py, double qx, double qy) const { return dist_filter(ax, ay, px, py, qx, qy); }
     CVHIP_DLN_HD bool skip(uint32_t) const { return false; } // a duplicate is never skipped: its zero determinant flags the star
+    CVHIP_DLN_HD bool same_position(double, double, double, double) const { return false; } // (that zero comes first)
+};
+
+// ---- the lattice policy: exact signs of integer-valued coordinates, on the device as on the host -----------------------------
+// Valid when every coordinate is an integer with |v| <= LATTICE_MAX = 2^24 (the caller checks all of them before it picks this
+// policy).  Then every coordinate difference is an integer below 2^25 in magnitude, and
+//   orient: the two products are below 2^50, their difference below 2^51                                  - 64-bit integers;
+//   dist:   the four squares are below 2^50, each sum below 2^51, their difference below 2^52             - 64-bit integers;
+//   circle: the lifts (sums of two squares) and the 2 x 2 minors (differences of two products) are below 2^51, a lift times
+//           a minor below 2^102, the sum of the three below 2^104                                         - 128-bit signed.
+// The f64 filter runs first, as in ExactPolicy, and the integers only where it is UNSURE; the policy never answers UNSURE.
+constexpr double LATTICE_MAX = 16777216.0; // 2^24
+
+CVHIP_DLN_HD inline bool on_lattice(double v) { return fabs(v) <= LATTICE_MAX && v == rint(v); } // (false for NaN and infinity)
+
+CVHIP_DLN_HD inline int orient_lattice(double ax, double ay, double bx, double by, double cx, double cy)
+{
+    const int64_t iax = (int64_t)ax, iay = (int64_t)ay;
+    const int64_t l = ((int64_t)bx - iax) * ((int64_t)cy - iay), r = ((int64_t)by - iay) * ((int64_t)cx - iax);
+    return (l > r) - (l < r);
+}
+
+CVHIP_DLN_HD inline int circle_lattice(double ax, double ay, double bx, double by, double cx, double cy, double dx, double dy)
+{
+    const int64_t idx = (int64_t)dx, idy = (int64_t)dy;
+    const int64_t adx = (int64_t)ax - idx, ady = (int64_t)ay - idy, bdx = (int64_t)bx - idx, bdy = (int64_t)by - idy,
+                  cdx = (int64_t)cx - idx, cdy = (int64_t)cy - idy;
+    const int64_t alift = adx * adx + ady * ady, blift = bdx * bdx + bdy * bdy, clift = cdx * cdx + cdy * cdy;
+    const __int128 det = (__int128)alift * (bdx * cdy - cdx * bdy) + (__int128)blift * (cdx * ady - adx * cdy) +
+                         (__int128)clift * (adx * bdy - bdx * ady);
+    return (det > 0) - (det < 0);
+}
+
+CVHIP_DLN_HD inline int dist_lattice(double ax, double ay, double px, double py, double qx, double qy)
+{
+    const int64_t iax = (int64_t)ax, iay = (int64_t)ay;
+    const int64_t pdx = (int64_t)px - iax, pdy = (int64_t)py - iay, qdx = (int64_t)qx - iax, qdy = (int64_t)qy - iay;
+    const int64_t dp = pdx * pdx + pdy * pdy, dq = qdx * qdx + qdy * qdy;
+    return (dp > dq) - (dp < dq);
+}
+
+struct LatticePolicy {
+    CVHIP_DLN_HD int orient(double ax, double ay, double bx, double by, double cx, double cy) const
+    {
+        const int s = orient_filter(ax, ay, bx, by, cx, cy);
+        return s != UNSURE ? s : orient_lattice(ax, ay, bx, by, cx, cy);
+    }
+    CVHIP_DLN_HD int circle(double ax, double ay, double bx, double by, double cx, double cy, double dx, double dy) const
+    {
+        const int s = circle_filter(ax, ay, bx, by, cx, cy, dx, dy);
+        return s != UNSURE ? s : circle_lattice(ax, ay, bx, by, cx, cy, dx, dy);
+    }
+    CVHIP_DLN_HD int dist(double ax, double ay, double px, double py, double qx, double qy) const
+    {
+        const int s = dist_filter(ax, ay, px, py, qx, qy);
+        return s != UNSURE ? s : dist_lattice(ax, ay, px, py, qx, qy);
+    }
+    CVHIP_DLN_HD bool skip(uint32_t) const { return false; } // duplicates stay with the host: same_position flags the star
+    CVHIP_DLN_HD bool same_position(double px, double py, double qx, double qy) const { return px == qx && py == qy; }
 };
 
 // ---- one star ---------------------------------------------------------------------------------------------------------------
@@ -207,6 +271,7 @@ template <class Pol> CVHIP_DLN_HD uint32_t wrap_step(const Grid &g, const Pol &p
             const uint32_t p = g.cell_pts[q];
             if (p == a || p == j || p == k || p >= g.k || pol.skip(p)) continue;
             const double px = g.xy[2 * p], py = g.xy[2 * p + 1];
+            if (pol.same_position(px, py, jx, jy) || (k != NONE && pol.same_position(px, py, kx, ky))) return false; // (a duplicate)
             const int o = pol.orient(ax, ay, jx, jy, px, py);
             if (o == UNSURE) return false;
             if (o * dir <= 0) continue;
@@ -219,7 +284,10 @@ template <class Pol> CVHIP_DLN_HD uint32_t wrap_step(const Grid &g, const Pol &p
             if (s > 0) {
                 k = kmin = kfirst = klast = p, kx = px, ky = py;
                 circle_of();
-            } else if (s == 0) { // (exact policy only) p lies on the circle: one more vertex of the polygon
+            } else if (s == 0) { // (exact policies only) p lies on the circle: one more vertex of the polygon
+                if ((p != kfirst && pol.same_position(px, py, g.xy[2 * kfirst], g.xy[2 * kfirst + 1])) ||
+                    (p != klast && pol.same_position(px, py, g.xy[2 * klast], g.xy[2 * klast + 1])))
+                    return false; // (a duplicate of a vertex that may be returned; a cell can be scanned twice, so p may be that vertex)
                 if (p < kmin) kmin = p;
                 const int of = pol.orient(ax, ay, g.xy[2 * kfirst], g.xy[2 * kfirst + 1], px, py);
                 const int ol = pol.orient(ax, ay, g.xy[2 * klast], g.xy[2 * klast + 1], px, py);
@@ -505,6 +573,7 @@ struct ExactPolicy {
         return s != UNSURE ? s : dist_exact(ax, ay, px, py, qx, qy);
     }
     bool skip(uint32_t p) const { return dups->is_duplicate(p); }
+    bool same_position(double, double, double, double) const { return false; } // (a duplicate never gets that far)
 };
 
 // the grid built on the host (the library downloads the device's instead): cell_start and cell_pts are filled

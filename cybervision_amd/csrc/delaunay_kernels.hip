@@ -7,6 +7,9 @@
 // its point instead, and the library finishes the flagged stars on the host with exact predicates - the same routine, so
 // the faces fit together as they are.  Count / scan / write: the faces come out grouped by their lowest index, ascending,
 // in the order of the wrap - the same bytes on every call.  No lane keeps its star: the write pass wraps again.
+// When every coordinate is an integer within 2^24 (counted with the extent) and cvhip_mesh_delaunay_set_lattice is on, the
+// count and write kernels run as their LatticePolicy instantiations: exact integer signs, ties included, on the device; what
+// still flags (duplicates, lane_cells, more than MAX_NEIGHBOURS neighbours) goes to the host as before.
 #include <cmath>
 #include <cstring>
 #include <vector>
@@ -24,7 +27,8 @@ constexpr uint32_t MAX_NEIGHBOURS = 64; // a device star with more leaves for th
 
 struct Extent {
     double min_x, max_x, min_y, max_y;
-    unsigned long long bad; // non-finite coordinates
+    unsigned long long bad;         // non-finite coordinates
+    unsigned long long off_lattice; // finite coordinates that are no integer within 2^24 (LatticePolicy needs 0)
 };
 
 struct DeviceStats {
@@ -36,40 +40,41 @@ struct DeviceStats {
 __global__ __launch_bounds__(BLOCK) void dln_extent_kernel(const double2 *__restrict__ xy, unsigned long long k, Extent *__restrict__ partial)
 {
     __shared__ double s_v[4][BLOCK];
-    __shared__ unsigned long long s_n[BLOCK];
+    __shared__ unsigned long long s_n[BLOCK], s_off[BLOCK];
     double mnx = INFINITY, mxx = -INFINITY, mny = INFINITY, mxy = -INFINITY;
-    unsigned long long bad = 0;
+    unsigned long long bad = 0, off = 0;
     for (unsigned long long i = (unsigned long long)blockIdx.x * BLOCK + threadIdx.x; i < k; i += (unsigned long long)gridDim.x * BLOCK) {
         const double2 p = xy[i];
         if (!(fabs(p.x) < INFINITY) || !(fabs(p.y) < INFINITY)) {
             bad++;
             continue;
         }
+        off += (on_lattice(p.x) ? 0u : 1u) + (on_lattice(p.y) ? 0u : 1u);
         mnx = fmin(mnx, p.x), mxx = fmax(mxx, p.x), mny = fmin(mny, p.y), mxy = fmax(mxy, p.y);
     }
     const int t = threadIdx.x;
-    s_v[0][t] = mnx, s_v[1][t] = mxx, s_v[2][t] = mny, s_v[3][t] = mxy, s_n[t] = bad;
+    s_v[0][t] = mnx, s_v[1][t] = mxx, s_v[2][t] = mny, s_v[3][t] = mxy, s_n[t] = bad, s_off[t] = off;
     __syncthreads();
     for (int w = BLOCK / 2; w > 0; w >>= 1) {
         if (t < w) {
             s_v[0][t] = fmin(s_v[0][t], s_v[0][t + w]), s_v[1][t] = fmax(s_v[1][t], s_v[1][t + w]);
             s_v[2][t] = fmin(s_v[2][t], s_v[2][t + w]), s_v[3][t] = fmax(s_v[3][t], s_v[3][t + w]);
-            s_n[t] += s_n[t + w];
+            s_n[t] += s_n[t + w], s_off[t] += s_off[t + w];
         }
         __syncthreads();
     }
-    if (t == 0) partial[blockIdx.x] = Extent{s_v[0][0], s_v[1][0], s_v[2][0], s_v[3][0], s_n[0]};
+    if (t == 0) partial[blockIdx.x] = Extent{s_v[0][0], s_v[1][0], s_v[2][0], s_v[3][0], s_n[0], s_off[0]};
 }
 
 __global__ void dln_extent_final_kernel(const Extent *__restrict__ partial, uint32_t blocks, Extent *__restrict__ out)
 {
     if (threadIdx.x || blockIdx.x) return;
-    Extent e{INFINITY, -INFINITY, INFINITY, -INFINITY, 0};
+    Extent e{INFINITY, -INFINITY, INFINITY, -INFINITY, 0, 0};
     for (uint32_t b = 0; b < blocks; b++) {
         const Extent p = partial[b];
         e.min_x = fmin(e.min_x, p.min_x), e.max_x = fmax(e.max_x, p.max_x);
         e.min_y = fmin(e.min_y, p.min_y), e.max_y = fmax(e.max_y, p.max_y);
-        e.bad += p.bad;
+        e.bad += p.bad, e.off_lattice += p.off_lattice;
     }
     *out = e;
 }
@@ -111,10 +116,12 @@ struct WriteFaces {
 };
 
 // one lane per point: count[a] = the faces of which a is the lowest index, status[a] = 0; or status[a] = 1: the host path
+// (Pol: FilterPolicy, or LatticePolicy on integer coordinates - an instantiation each, so neither pays for the other)
+template <class Pol>
 __global__ __launch_bounds__(BLOCK) void dln_count_kernel(Grid g, unsigned long long lane_cells, uint32_t *__restrict__ count,
                                                           uint8_t *__restrict__ status, DeviceStats *__restrict__ stats)
 {
-    const FilterPolicy pol;
+    const Pol pol;
     unsigned long long done = 0, most = 0;
     for (unsigned long long i = (unsigned long long)blockIdx.x * BLOCK + threadIdx.x; i < g.k; i += (unsigned long long)gridDim.x * BLOCK) {
         CountFaces emit;
@@ -162,7 +169,8 @@ __global__ __launch_bounds__(BLOCK) void dln_block_sum_kernel(const uint32_t *__
 }
 
 // the faces of point a start at block_offsets[a / 256] + the counts of the block's earlier points; a device star is wrapped
-// again, a host star's faces are copied from host_faces
+// again (with the policy that counted it), a host star's faces are copied from host_faces
+template <class Pol>
 __global__ __launch_bounds__(BLOCK) void dln_write_kernel(Grid g, unsigned long long lane_cells, const uint32_t *__restrict__ count,
                                                           const uint8_t *__restrict__ status, const uint32_t *__restrict__ offset_of,
                                                           const uint32_t *__restrict__ host_faces, uint32_t n_host_faces,
@@ -170,7 +178,7 @@ __global__ __launch_bounds__(BLOCK) void dln_write_kernel(Grid g, unsigned long 
                                                           unsigned long long n_faces, uint32_t *__restrict__ out)
 {
     __shared__ uint32_t s_n[BLOCK];
-    const FilterPolicy pol;
+    const Pol pol;
     for (uint32_t b = blockIdx.x; b < blocks; b += gridDim.x) {
         const unsigned long long i = (unsigned long long)b * BLOCK + threadIdx.x;
         const uint32_t mine = i < g.k ? count[i] : 0u;
@@ -217,6 +225,7 @@ int mesh_delaunay_run(Device &d, const double *xy, uint64_t k, uint32_t *out_fac
 {
     hipStream_t s = d.stream;
     CallScratch sc;
+    d.mesh_delaunay_lattice_stars = 0; // (of this call, once its lattice kernels have run)
     uint64_t stats[6] = {0, 0, 0, 0, 0, 0};
     auto finish = [&](uint64_t n) {
         *out_n_faces = n;
@@ -240,6 +249,7 @@ int mesh_delaunay_run(Device &d, const double *xy, uint64_t k, uint32_t *out_fac
     if (e != hipSuccess) return device_error("mesh_delaunay", e);
     if (ext.bad) return fail(CVHIP_ERR_INVALID, "mesh_delaunay: a coordinate is not finite");
     if (k < 3) return finish(0);
+    const bool lattice = d.mesh_delaunay_lattice && ext.off_lattice == 0; // integer coordinates: the exact signs on the device
 
     Grid g{d_xy, (uint32_t)k, ext.min_x, ext.min_y, 1.0, 0.0, 1, 1, nullptr, nullptr};
     grid_dims(ext.min_x, ext.max_x, ext.min_y, ext.max_y, k, &g.s, &g.inv_s, &g.gw, &g.gh);
@@ -270,7 +280,10 @@ int mesh_delaunay_run(Device &d, const double *xy, uint64_t k, uint32_t *out_fac
     if (e != hipSuccess) return device_error("mesh_delaunay", e);
     hipLaunchKernelGGL(dln_cell_fill_kernel, dim3(lanes), dim3(BLOCK), 0, s, g, cursor, cell_pts);
     g.cell_start = cell_start, g.cell_pts = cell_pts;
-    hipLaunchKernelGGL(dln_count_kernel, dim3(lanes), dim3(BLOCK), 0, s, g, lane_cells, count, status, d_stats);
+    if (lattice)
+        hipLaunchKernelGGL(dln_count_kernel<LatticePolicy>, dim3(lanes), dim3(BLOCK), 0, s, g, lane_cells, count, status, d_stats);
+    else
+        hipLaunchKernelGGL(dln_count_kernel<FilterPolicy>, dim3(lanes), dim3(BLOCK), 0, s, g, lane_cells, count, status, d_stats);
     e = hipGetLastError();
     std::vector<uint8_t> h_status((size_t)k);
     if (e == hipSuccess) e = hipMemcpyAsync(h_status.data(), status, (size_t)k, hipMemcpyDeviceToHost, s);
@@ -278,6 +291,7 @@ int mesh_delaunay_run(Device &d, const double *xy, uint64_t k, uint32_t *out_fac
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     if (e != hipSuccess) return device_error("mesh_delaunay", e);
     stats[2] = h_stats.device_stars, stats[5] = h_stats.most_cells;
+    if (lattice) d.mesh_delaunay_lattice_stars = h_stats.device_stars;
 
     // the flagged stars, on the host: the same routine with the exact predicates, on the device's grid
     std::vector<uint32_t> host_point, host_count, host_offset, host_faces;
@@ -336,8 +350,13 @@ int mesh_delaunay_run(Device &d, const double *xy, uint64_t k, uint32_t *out_fac
     uint32_t *d_out = nullptr;
     e = sc.output(out_faces, (size_t)total * 3, &d_out);
     if (e != hipSuccess) return device_error("mesh_delaunay", e);
-    hipLaunchKernelGGL(dln_write_kernel, dim3(grid_for((unsigned long long)blocks * BLOCK)), dim3(BLOCK), 0, s, g, lane_cells, count, status, offset_of,
-                       d_host_faces, (uint32_t)(host_faces.size() / 3), block_counts, blocks, (unsigned long long)total, d_out);
+    const dim3 write_grid(grid_for((unsigned long long)blocks * BLOCK));
+    if (lattice)
+        hipLaunchKernelGGL(dln_write_kernel<LatticePolicy>, write_grid, dim3(BLOCK), 0, s, g, lane_cells, count, status, offset_of, d_host_faces,
+                           (uint32_t)(host_faces.size() / 3), block_counts, blocks, (unsigned long long)total, d_out);
+    else
+        hipLaunchKernelGGL(dln_write_kernel<FilterPolicy>, write_grid, dim3(BLOCK), 0, s, g, lane_cells, count, status, offset_of, d_host_faces,
+                           (uint32_t)(host_faces.size() / 3), block_counts, blocks, (unsigned long long)total, d_out);
     e = hipGetLastError();
     if (e == hipSuccess) e = sc.copy_out(out_faces, d_out, (size_t)total * 3, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);

@@ -535,6 +535,25 @@ inline void set_delaunay_lane_cells(GpuDevice &dev, uint32_t cells)
     check(cvhip_mesh_delaunay_set_lane_cells(dev.handle(), cells), "cvhip_mesh_delaunay_set_lane_cells");
 }
 
+// integer coordinates within 2^24 (an affine surface's camera points): exact integer predicates on the device (off by default)
+inline void set_delaunay_lattice(GpuDevice &dev, bool on)
+{
+    check(cvhip_mesh_delaunay_set_lattice(dev.handle(), on ? 1 : 0), "cvhip_mesh_delaunay_set_lattice");
+}
+inline bool delaunay_lattice(GpuDevice &dev)
+{
+    int on = 0;
+    check(cvhip_mesh_delaunay_get_lattice(dev.handle(), &on), "cvhip_mesh_delaunay_get_lattice");
+    return on != 0;
+}
+// the stars of the last mesh::delaunay call that the lattice kernels finished (0: the call did not qualify)
+inline uint64_t delaunay_lattice_stars(GpuDevice &dev)
+{
+    uint64_t n = 0;
+    check(cvhip_mesh_delaunay_get_lattice_stars(dev.handle(), &n), "cvhip_mesh_delaunay_get_lattice_stars");
+    return n;
+}
+
 // the culling loop of process_camera (:457-508): keep[p] = 0 iff polygon p obstructs in another camera
 inline std::vector<uint8_t> cull(GpuDevice &dev, const Surface &s, uint32_t camera_i, const std::vector<uint32_t> &polygons)
 {

@@ -26,6 +26,7 @@ WIDE_ALL, WIDE_NONE = 0, 0xFFFFFFFF
 STATS = ("width", "height", "occupied", "dropped", "wide")
 DELAUNAY_LANE_CELLS_DEFAULT = 1024  # CVHIP_MESH_DELAUNAY_LANE_CELLS_DEFAULT
 LANE_CELLS_HOST, LANE_CELLS_UNBOUNDED = 0, 0xFFFFFFFF
+DELAUNAY_LATTICE_DEFAULT = False    # CVHIP_MESH_DELAUNAY_LATTICE_DEFAULT
 DELAUNAY_STATS = ("grid_width", "grid_height", "device_stars", "host_stars", "duplicates", "most_cells")  # CVHIP_DELAUNAY_STAT_*
 
 
@@ -335,6 +336,28 @@ def set_delaunay_lane_cells(device, cells: int):
     _lib.check(_lib.lib().cvhip_mesh_delaunay_set_lane_cells(device.handle, int(cells)), "cvhip_mesh_delaunay_set_lane_cells")
 
 
+def set_delaunay_lattice(device, on: bool):
+    """cvhip_mesh_delaunay_set_lattice: with it on, a call whose coordinates are all integers within 2^24 (the camera points
+    of an affine surface) builds its stars - exact ties included - on the device with exact integer predicates; any other
+    call is not affected.  The faces do not change.  Off by default."""
+    _lib.check(_lib.lib().cvhip_mesh_delaunay_set_lattice(device.handle, int(bool(on))), "cvhip_mesh_delaunay_set_lattice")
+
+
+def delaunay_lattice(device) -> bool:
+    """cvhip_mesh_delaunay_get_lattice: whether set_delaunay_lattice is on."""
+    on = C.c_int(0)
+    _lib.check(_lib.lib().cvhip_mesh_delaunay_get_lattice(device.handle, C.byref(on)), "cvhip_mesh_delaunay_get_lattice")
+    return bool(on.value)
+
+
+def delaunay_lattice_stars(device) -> int:
+    """cvhip_mesh_delaunay_get_lattice_stars: the stars of the last `delaunay` call on this device that the lattice kernels
+    finished; 0 when that call did not qualify."""
+    n = C.c_uint64(0)
+    _lib.check(_lib.lib().cvhip_mesh_delaunay_get_lattice_stars(device.handle, C.byref(n)), "cvhip_mesh_delaunay_get_lattice_stars")
+    return int(n.value)
+
+
 def delaunay(device, xy, stats=None):
     """cvhip_mesh_delaunay: the Delaunay triangulation of the distinct positions of xy ([k, 2] f64) -> [f, 3] uint32 faces,
     counter-clockwise, the smallest index first, grouped by it; exact ties are fanned from their lowest index, of several
@@ -350,11 +373,19 @@ def delaunay(device, xy, stats=None):
     return faces[:n.value].copy()
 
 
-def delaunay_device(device):
+def delaunay_device(device, lattice=None):
     """A `triangulate` for `create` and reconstruct_perspective_mesh(triangulate=...) that runs on the device (`delaunay`):
-    the way to build a mesh without scipy."""
+    the way to build a mesh without scipy.  lattice: True / False - set_delaunay_lattice for the length of each call (the
+    device's setting is put back after it); None - the device's setting as it is."""
     def triangulate(xy):
-        return delaunay(device, xy)
+        if lattice is None:
+            return delaunay(device, xy)
+        before = delaunay_lattice(device)
+        set_delaunay_lattice(device, lattice)
+        try:
+            return delaunay(device, xy)
+        finally:
+            set_delaunay_lattice(device, before)
 
     return triangulate
 

@@ -427,3 +427,57 @@ def reconstruct_perspective_mesh(device, pyramids, K, triangulate=None, project_
                                              mesh.VertexMode(int(vertex_mode)), out_scale)
         out["timings_ms"]["obj"] = (time.perf_counter() - t3) * 1e3
     return out
+
+
+def reconstruct_affine_mesh(device, pyramid1, pyramid2, f, triangulate=None, project_to_image=None, depth_scale: float = -1.0,
+                            ply_path=None, obj_path=None, images=None, vertex_mode=0, out_scale=(1.0, 1.0, 1.0), colour_table=None):
+    """The affine `reconstruct` of one pair, through to the mesh and its outputs: the dense correlation of the two pyramids
+    with the affine F, AffineTriangulation::triangulate straight from the device grid (PointCorrelations.triangulate_affine),
+    its Surface (triangulation.affine_surface: two cameras with K = diag(1, 1, 0)), mesh.create - both cameras are
+    triangulated and culled as the reference does; the second camera's triangles are the first's, and the merge leaves them
+    with camera 0 - and the outputs of reconstruct_perspective_mesh, each only when asked for: project_to_image (with
+    depth_scale, colour_table), ply_path, obj_path (with images - one per image of the pair -, vertex_mode, out_scale).
+    triangulate: the Delaunay of a camera's points; the default is mesh.delaunay_device(device, lattice=True) - the camera
+    points are integer pixels, every star is an exact tie, and cvhip_mesh_delaunay decides those as defined, on the device
+    (scipy's tie choices are not the defined ones).
+    -> dict: surface, mesh, depth_image (or None), timings_ms (dense, triangulate, mesh, depth_image, ply, obj), and
+    ply_sections / obj_sections when those files were written."""
+    from . import mesh, triangulation
+
+    rec = ImageReconstruction(device, ProjectionMode.Affine)
+    shapes = [(int(p[0].shape[1]), int(p[0].shape[0])) for p in (pyramid1, pyramid2)]
+    pc = correlation.PointCorrelations(device, shapes[0], shapes[1], f, correlation.ProjectionMode(int(ProjectionMode.Affine)))
+    try:
+        def run():
+            steps = correlation.optimal_scale_steps(*shapes[0])
+            for s in range(steps + 1):
+                k = steps - s
+                pc.correlate_images(pyramid1[k], pyramid2[k], 1.0 / float(1 << k))
+
+        rec._timed("dense", run)
+        points3d, p2 = rec._timed("triangulate", pc.triangulate_affine)
+    finally:
+        pc.close()
+    out = {"surface": triangulation.affine_surface(points3d, p2), "depth_image": None}
+    out["mesh"] = rec._timed("mesh", lambda: mesh.create(device, out["surface"], shapes,
+                                                         triangulate or mesh.delaunay_device(device, lattice=True)))
+    polygons = out["mesh"]["polygons"]
+
+    def image():
+        img = mesh.depth_image(device, out["surface"], shapes, project_to_image, depth_scale, polygons)
+        if colour_table is not None:
+            img["rgba"] = mesh.colour_map(device, img["map"], img["min_depth"], img["max_depth"], colour_table)
+        return img
+
+    if project_to_image is not None:
+        out["depth_image"] = rec._timed("depth_image", image)
+    out["mesh_image_shapes"] = shapes
+    if ply_path is not None:
+        out["ply_sections"] = rec._timed("ply", lambda: mesh.write_ply(ply_path, device, out["surface"], polygons, images,
+                                                                      mesh.VertexMode(int(vertex_mode)), out_scale))
+    if obj_path is not None:
+        dims = shapes if images is None and int(vertex_mode) == mesh.VertexMode.Texture else images
+        out["obj_sections"] = rec._timed("obj", lambda: mesh.write_obj(obj_path, device, out["surface"], polygons, out["mesh"]["camera"],
+                                                                      dims, mesh.VertexMode(int(vertex_mode)), out_scale))
+    out["timings_ms"] = dict(rec.timings_ms)
+    return out

@@ -4,6 +4,7 @@ adjustment - in one call of cvhip_triangulate_perspective - and the sparse half 
 (add_image_pair_sparse, recover_next_cameras, :620-811): find_projection_matrix, triangulate_tracks and the P3P RANSAC of
 recover_pose run on the device - and merge_tracks (:1421-1540, cvhip_merge_tracks), which reconstruct_dense runs after
 each linked image's pairs.
+`affine_surface` is the Surface of AffineTriangulation::triangulate (:268-330) around cvhip_triangulate_affine's points.
 No compute in Python - the track table's bookkeeping and the calls only.
 """
 from __future__ import annotations
@@ -39,6 +40,26 @@ class Surface:
     ba_iterations: int = 0
     ba_history: list = field(default_factory=list)
     ba_residual_norms: tuple = (float("nan"), float("nan"))
+
+
+def affine_surface(points3d, p2) -> Surface:
+    """The Surface that AffineTriangulation::triangulate returns (triangulation.rs:268-330) around the rows of
+    PointCorrelations.triangulate_affine: `points` are the rows as given ((x, y, depth), x and y the pixel of image 1),
+    track_index = arange, tracks [n, 2, 2] hold (x, y) of image 1 and the match `p2` in image 2, and both images get the
+    reference's affine camera (:287-292): K = diag(1, 1, 0), R = I, t = 0, so r = t = 0 and the projection is
+    [[1, 0, 0, 0], [0, 1, 0, 0], [0, 0, 0, 0]] - a point projects to (x, y) exactly and its depth is z.  The mesh stage
+    (mesh.create, mesh.depth_image, mesh.ply, mesh.obj) takes it like any other surface."""
+    pts = np.ascontiguousarray(points3d, dtype=np.float64).reshape(-1, 3)
+    m2 = np.asarray(p2).reshape(-1, 2)
+    if len(m2) != len(pts):
+        raise ValueError("one image-2 point per 3D point")
+    tracks = np.empty((len(pts), 2, 2), dtype=np.int32)
+    tracks[:, 0] = pts[:, :2]  # (integer pixels: the conversion is exact)
+    tracks[:, 1] = m2
+    projection = np.zeros((3, 4))
+    projection[0, 0] = projection[1, 1] = 1.0
+    return Surface(points=pts, track_index=np.arange(len(pts), dtype=np.int64), tracks=tracks,
+                   cameras=[Camera(np.zeros(3), np.zeros(3), projection.copy()) for _ in range(2)])
 
 
 class PerspectiveTriangulation:

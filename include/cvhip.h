@@ -430,7 +430,8 @@ int cvhip_mesh_depth_image(cvhip_device *dev, const double *points, const int32_
  * Errors: CVHIP_ERR_INVALID for a coordinate that is not finite (nothing written); CVHIP_ERR_UNSUPPORTED for k >= 2^31
  * (the face count must stay below 2^32 - 1; so k >= 2^32 - 1 too).  The signs are exact while no product of coordinate
  * differences over- or underflows (differences within 2^-240 .. 2^240 in magnitude).
- * Affine surfaces (integer lattices) are not what this is for: every star is a tie and runs on the host. */
+ * Integer lattices (the camera points of an affine surface): every star meets an exact tie, so with
+ * cvhip_mesh_delaunay_set_lattice off every star runs on the host; with it on the device decides them in integers. */
 int cvhip_mesh_delaunay(cvhip_device *dev, const double *xy, uint64_t k,
                         uint32_t *out_faces, uint64_t cap_faces, uint64_t *out_n_faces, uint64_t *out_stats);
 
@@ -438,6 +439,22 @@ int cvhip_mesh_delaunay(cvhip_device *dev, const double *xy, uint64_t k,
  * its wave: 0 sends every star to the host path, UINT32_MAX never leaves the device for size.  Every setting gives the same
  * faces. */
 int cvhip_mesh_delaunay_set_lane_cells(cvhip_device *dev, uint32_t cells);
+
+/* The lattice kernels: when `on` is not 0 and EVERY coordinate of a call is an integer with |v| <= 2^24
+ * (decided per call, on the device, with the extent), the stars are built by kernels whose predicates go on, below the f64
+ * filter, with the exact integer determinant (64-bit for orientation and distance, 128-bit for in-circle): ties are decided
+ * on the device by the tie rule above, and only duplicates, stars past lane_cells and stars with more than 64 neighbours
+ * still go to the host.  Any other input, and every input when off, runs the filtered kernels.  The faces are the same bytes
+ * either way; only CVHIP_DELAUNAY_STAT_DEVICE_STARS / _HOST_STARS / _MOST_CELLS move (lattice stars count as device stars).
+ * The default is CVHIP_MESH_DELAUNAY_LATTICE_DEFAULT: off, so that a call computes and reports what it did before this
+ * switch existed; reconstruct_affine_mesh's triangulator switches it on. */
+#define CVHIP_MESH_DELAUNAY_LATTICE_DEFAULT 0
+int cvhip_mesh_delaunay_set_lattice(cvhip_device *dev, int on);
+/* *out_on = 1 when the switch is on, 0 when off */
+int cvhip_mesh_delaunay_get_lattice(cvhip_device *dev, int *out_on);
+/* *out_stars = the stars of this device's last cvhip_mesh_delaunay call that its lattice kernels finished; 0 when that
+ * call did not qualify (or failed before its stars were built) */
+int cvhip_mesh_delaunay_get_lattice_stars(cvhip_device *dev, uint64_t *out_stars);
 
 /* ------------------------------------------------------------------------------------------
  * Mesh output (csrc/mesh_output_kernels.hip): what output::output writes once the polygon list exists -
