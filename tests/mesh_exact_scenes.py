@@ -51,8 +51,8 @@ def cameras():
     return [rt.Camera(np.eye(3), np.zeros(3), T[j]) for j in range(3)]
 
 
-def surface(points, tracks):
-    return ref_mesh.Surface(points, tracks, cameras(), PROJECTIONS, [SIZE] * 3)
+def surface(points, tracks, dims=None):
+    return ref_mesh.Surface(points, tracks, cameras(), PROJECTIONS, [SIZE] * 3 if dims is None else dims)
 
 
 def lattice_points(rng, n):
@@ -154,6 +154,63 @@ def polygons(camera_i, seed=7):
 
 def device(s):
     return mesh_scenes.device_surface(s)
+
+
+# ---- img_range per camera and per axis ------------------------------------------------------------------------------------
+# Landscape, portrait, and a third shape: img_range is [-1120, 1440) x [-700, 900), [-700, 900) x [-1120, 1440) and
+# [-840, 1080) x [-1120, 1440).  With x held against the height's range or y against the width's - or with another
+# camera's dims - tracks on these edges change sides.
+EDGE_DIMS = [(320, 200), (200, 320), (240, 320)]
+N_EDGE_RANDOM, N_EDGE_POLYGONS = 600, 24
+
+
+def edge_values(size):
+    """Per axis the coordinates (on lo: in, a quarter below lo: out, a quarter below hi: in, on hi: out) of img_range(size)."""
+    lo, hi = ref_mesh.img_range(size)
+    return [(lo[a], lo[a] - 0.25, hi[a] - 0.25, hi[a]) for a in range(2)]
+
+
+@functools.lru_cache(maxsize=None)
+def edge_scene(seed=13):
+    """-> Scene over the exact cameras with EDGE_DIMS: N_EDGE_RANDOM lattice points, and for every camera and axis four
+    hand-placed tracks on both sides of both ends of its img_range (edge_values), the other coordinate at 10, depth 1.25,
+    seen everywhere.  edge[camera] = {"x": {x: track}, "y": {y: track}}."""
+    rng = np.random.default_rng(seed)
+    pts = [lattice_points(rng, N_EDGE_RANDOM)]
+    n = N_EDGE_RANDOM
+    s = Scene()
+    s.edge = []
+    for (dx, dy), size in zip(OFFSET, EDGE_DIMS):
+        xs, ys = edge_values(size)
+        pts.append(np.array([(x - dx, 10.0 - dy, 1.25) for x in xs] + [(10.0 - dx, y - dy, 1.25) for y in ys]))
+        s.edge.append({"x": dict(zip(xs, range(n, n + 4))), "y": dict(zip(ys, range(n + 4, n + 8)))})
+        n += 8
+    mask = rng.random((n, 3)) < SEEN
+    mask[N_EDGE_RANDOM:] = True
+    s.surface = surface(np.concatenate(pts), seen_tracks(mask), EDGE_DIMS)
+    s.image_dims = list(EDGE_DIMS)
+    return s
+
+
+@functools.lru_cache(maxsize=None)
+def edge_polygons(camera_i, seed=13):
+    """N_EDGE_POLYGONS triples for camera_i of edge_scene: half local ones among its lattice camera points (at most 3
+    pixels from the first, as polygons()), half with one or two of the edge tracks that are in range (polygons that cross
+    most of a buffer 1441 or 901 cells wide)."""
+    s = edge_scene(seed)
+    rng = np.random.default_rng(100 * seed + camera_i)
+    idx, xy = ref_mesh.camera_points(s.surface, camera_i)
+    small, far = idx[idx < N_EDGE_RANDOM], idx[idx >= N_EDGE_RANDOM]
+    polys = small[rng.integers(0, len(small), (N_EDGE_POLYGONS, 3))]
+    for k in range(N_EDGE_POLYGONS):
+        away = np.abs(xy[:len(small)] - xy[np.nonzero(small == polys[k, 0])[0][0]]).max(axis=1)
+        around = np.nonzero((away <= 3.0) & (away >= MIN_AWAY))[0]
+        if len(around):
+            polys[k, 1:] = small[rng.choice(around, 2)]
+    half = N_EDGE_POLYGONS // 2
+    polys[:half, 0] = far[rng.integers(0, len(far), half)]
+    polys[:half // 2, 1] = far[rng.integers(0, len(far), half // 2)]
+    return polys.astype(np.uint32)
 
 
 @functools.lru_cache(maxsize=None)

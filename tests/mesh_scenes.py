@@ -5,6 +5,7 @@ from __future__ import annotations
 
 import numpy as np
 
+import mixed_scenes
 import ref_mesh
 import tri_scenes
 
@@ -12,6 +13,8 @@ SIZE = 320          # image size of the rig: buffers of ~350^2 cells, lattice ce
 LATTICE = (96, 64)  # points per plane
 # seeds per camera count for which ref_mesh.near_threshold is empty for every camera_i (checked by test_mesh_ref.py)
 SEEDS = {2: 1, 3: 1, 4: 1, 8: 1}
+# the same for scene(m, mixed=True)
+MIXED_SEEDS = {3: 2, 8: 3}
 
 
 class Scene:
@@ -62,12 +65,23 @@ def facing_rig(m, size=SIZE):
     return cams
 
 
-def scene(m, seed=None, size=SIZE):
+def mixed_dims(m):
+    """mixed_scenes.DIMS at SIZE pixels on the longest side: (320, 200), (200, 320), (300, 225), (160, 240), (320, 320),
+    (250, 141), (141, 250), (200, 160)."""
+    return mixed_scenes.dims(m, 2048 / SIZE)
+
+
+def scene(m, seed=None, size=SIZE, mixed=False):
     """-> Scene: cams (rig(m)), surface (ref_mesh.Surface over the true points), image_dims, triangles (all lattice
-    triangles of both planes), n_background."""
-    seed = SEEDS.get(m, 1) if seed is None else seed
+    triangles of both planes), n_background.  mixed: camera j has mixed_scenes' K for its own image size mixed_dims(m)[j]
+    (no two alike, landscape and portrait), and a track is seen inside that image."""
+    seed = (MIXED_SEEDS if mixed else SEEDS).get(m, 1) if seed is None else seed
     rng = np.random.default_rng(1000 * m + seed)
     cams = facing_rig(m, size)
+    dims = [(size, size)] * m
+    if mixed:
+        dims = mixed_dims(m)
+        cams = [(mixed_scenes.calibration(j, dims[j]), R, t) for j, (_, R, t) in enumerate(cams)]
     # the background reaches past the image on every side (projections left of and above 0, and past the buffers' edges:
     # a track is seen only inside an image); the foreground hides its middle
     back = _plane(rng, 5.9, 5.8, 5.5, 0.02)
@@ -80,10 +94,10 @@ def scene(m, seed=None, size=SIZE):
     mask = np.zeros((n, m), dtype=bool)
     np.put_along_axis(mask, order, np.arange(m)[None, :] < k[:, None], axis=1)
     tracks = tri_scenes.observe(cams, X, mask)
-    tracks[(tracks >= size).any(axis=2)] = -1  # (and what falls past the right or lower edge of an image)
+    tracks[(tracks >= np.array(dims)[None]).any(axis=2)] = -1  # (and what falls past the right or lower edge of an image)
     s = Scene()
     s.m, s.seed, s.size, s.cams = m, seed, size, cams
-    s.image_dims = [(size, size)] * m
+    s.image_dims = dims
     # (not Camera::from_matrix: as written it turns a camera by more than its R - ref_triangulation notes the factor 2 -,
     # and the scene's tracks were observed through R itself)
     s.surface = ref_mesh.Surface.from_poses(X, tracks, [(K, axis_angle(R), t) for K, R, t in cams], s.image_dims)

@@ -34,6 +34,32 @@ def multiview_config(m, image, placed, size=512):
     return tracks, K, P, has, [P[j] if has[j] else None for j in range(m)]
 
 
+# one configuration of MULTIVIEW_CONFIGS per view count whose image is not square (mixed_scenes.dims(m, 4)): image 1 is
+# 320 x 512, image 3 256 x 384, image 7 320 x 256
+MIXED_CONFIGS = [(3, 1, (0, 2)), (6, 3, (0, 1, 5)), (8, 7, (0, 4))]
+
+
+def multiview_config_mixed(m, image, placed):
+    """multiview_config with a K and a size per image (pose_scenes.mixed_multiview_scene, the same seed, tracks and miss)
+    -> (tracks, Ks [m], P, has, projections as the restatement takes them, sizes [m] (width, height)): the projections
+    of `placed` use their own K; the recovered image's K is Ks[image] and its max_dimension max(sizes[image])."""
+    tracks, Ks, poses, _, sizes = pose_scenes.mixed_multiview_scene(m, MULTIVIEW_TRACKS, seed=20 + m, miss=0.3)
+    P, has = pose_scenes.known_views(Ks, poses, placed)
+    return tracks, Ks, P, has, [P[j] if has[j] else None for j in range(m)], sizes
+
+
+MIXED_RUN = {"config": (6, 3, (0, 1, 5)), "sample_seed": 5}
+
+
+def mixed_run_inputs():
+    """The inputs of the whole cvhip_recover_pose call on mixed cameras: MIXED_RUN's configuration, points from the
+    restatement -> (tracks, K of the image, P, has, image, points, ok, max_dimension, seed, projections (None = unknown))."""
+    m, image, placed = MIXED_RUN["config"]
+    tracks, Ks, P, has, projections, sizes = multiview_config_mixed(m, image, placed)
+    pts, ok = restated_points(tracks, P, has)
+    return tracks, Ks[image], P, has, image, pts, ok, max(sizes[image]), MIXED_RUN["sample_seed"], projections
+
+
 def restated_points(tracks, P, has):
     masked = np.array(tracks)
     masked[:, np.asarray(has) == 0] = -1

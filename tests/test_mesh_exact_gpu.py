@@ -163,3 +163,36 @@ def test_no_tracks(gpu_device):
         with pytest.raises(_lib.CvhipError) as exc:
             mesh.cull(gpu_device, dev, s.image_dims, j, np.zeros((1, 3), dtype=np.uint32))
         assert exc.value.code == -1  # CVHIP_ERR_INVALID: the polygon names a track >= n
+
+
+@pytest.mark.parametrize("i", range(3))
+def test_edge_scene_with_its_own_dims_per_camera_bit_for_bit(gpu_device, i):
+    """mesh_exact_scenes.edge_scene: exact cameras with images of 320 x 200, 200 x 320 and 240 x 320 and tracks exactly on
+    and a quarter below both ends of every camera's img_range on each axis.  Camera points, the other cameras' buffers
+    (each as wide and high as its own range), flags, statistics and the depth image, bit for bit, under every threshold of
+    the wave path.  Width for height in img_range, or another camera's dims, selects other tracks in every camera
+    (tests/test_mesh_exact_ref.py)."""
+    s = mx.edge_scene()
+    dev = mx.device(s)
+    polys = mx.edge_polygons(i)
+    want_idx, want_xy = ref_mesh.camera_points(s.surface, i)
+    want_keep, want_stats = ref_mesh.cull(s.surface, i, polys)
+    want_images = {scale: ref_mesh.depth_image(s.surface, i, scale, polys) for scale in SCALES}
+    try:
+        for name, thr in THRESHOLDS:
+            mesh.set_wide_threshold(gpu_device, thr)
+            idx, xy = mesh.camera_points(gpu_device, dev, s.image_dims, i)
+            assert np.array_equal(idx, want_idx) and xy.shape == want_xy.shape and xy.tobytes() == want_xy.tobytes(), name
+            for j in range(3):
+                if j != i:
+                    assert same_bits(mesh.depth_buffer(gpu_device, dev, s.image_dims, j), ref_mesh.depth_buffer(s.surface, j)), (name, j)
+            keep, stats = mesh.cull(gpu_device, dev, s.image_dims, i, polys)
+            assert np.array_equal(keep, want_keep), (name, np.nonzero(keep != want_keep)[0])
+            for j in range(3):
+                got = (stats[j]["width"], stats[j]["height"], stats[j]["occupied"], stats[j]["dropped"])
+                assert got == want_stats[j], (name, j, got, want_stats[j])
+            for scale in SCALES:
+                img = mesh.depth_image(gpu_device, dev, s.image_dims, i, scale, polys)
+                assert same_image(img, want_images[scale]), (name, scale)
+    finally:
+        mesh.set_wide_threshold(gpu_device, mesh.WIDE_THRESHOLD_DEFAULT)

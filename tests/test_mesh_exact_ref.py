@@ -247,3 +247,60 @@ def test_polygon_with_an_infinite_vertex_by_hand():
     want = [(x, y, 1.0) for y in (3, 4, 5, 6) for x in range(10, w)]
     assert got == sorted(want)
     assert flag == any(buf[y, x] - v > EPS for x, y, v in want) and flag
+
+
+# ---- img_range per camera and per axis: mesh_exact_scenes.edge_scene -------------------------------------------------------
+def _in_range_set(surface, j):
+    return ref_mesh.selected(surface, j, need_seen=False)[0]
+
+
+def test_edge_scene_tracks_sit_on_both_sides_of_every_range_end():
+    """Every camera of edge_scene has w != h and its own dims; its hand-placed tracks project exactly onto lo (in), a
+    quarter below lo (out), a quarter below hi (in) and hi (out) of its own img_range, on each axis."""
+    s = mx.edge_scene()
+    assert len(set(s.image_dims)) == 3 and all(w != h for w, h in s.image_dims)
+    assert any(w > h for w, h in s.image_dims) and any(w < h for w, h in s.image_dims)
+    for j, size in enumerate(s.image_dims):
+        lo, hi = ref_mesh.img_range(size)
+        mask, x, y, _ = ref_mesh.selected(s.surface, j)
+        for axis, name, got in ((0, "x", x), (1, "y", y)):
+            values = list(s.edge[j][name])
+            assert values == [lo[axis], lo[axis] - 0.25, hi[axis] - 0.25, hi[axis]]
+            for want, tr in s.edge[j][name].items():
+                assert got[tr] == want and mask[tr] == (want in (lo[axis], hi[axis] - 0.25)), (j, name, want)
+
+
+def test_edge_scene_tells_width_from_height_and_camera_from_camera():
+    """The restatement with every camera's dims transposed selects another set of tracks in every camera, and in each
+    camera one hand-placed track of the x axis AND one of the y axis changes sides: x held against the height's range,
+    or y against the width's, is visible there.  So do camera 0's dims used for every camera (cameras 1 and 2), and the
+    restatement with img_range's lo and hi exchanged between the axes."""
+    s = mx.edge_scene()
+    sf = s.surface
+    transposed = mx.surface(sf.points, sf.tracks, [(h, w) for w, h in s.image_dims])
+    first = mx.surface(sf.points, sf.tracks, [s.image_dims[0]] * 3)
+    for j in range(3):
+        real, other = _in_range_set(sf, j), _in_range_set(transposed, j)
+        assert not np.array_equal(real, other), j
+        for name in ("x", "y"):
+            tr = list(s.edge[j][name].values())
+            assert (real[tr] != other[tr]).any(), (j, name)
+        assert not np.array_equal(ref_mesh.camera_points(sf, j)[0], ref_mesh.camera_points(transposed, j)[0])
+        if j:
+            assert not np.array_equal(real, _in_range_set(first, j)), j
+
+
+def test_edge_scene_buffers_reach_the_range_ends():
+    """The in-range edge tracks stretch every camera's buffer to its own range: ceil(hi - 0.25) + 1 cells per axis, which
+    differ between the axes and between the cameras; the polygons of edge_polygons both obstruct and do not."""
+    s = mx.edge_scene()
+    shapes = []
+    for j, size in enumerate(s.image_dims):
+        lo, hi = ref_mesh.img_range(size)
+        buf = ref_mesh.depth_buffer(s.surface, j)
+        assert buf.shape == (int(hi[1]) + 1, int(hi[0]) + 1)
+        shapes.append(buf.shape)
+    assert len(set(shapes)) == 3 and all(h != w for h, w in shapes)
+    for i in range(3):
+        keep, _ = ref_mesh.cull(s.surface, i, mx.edge_polygons(i))
+        assert 0 < keep.sum() < len(keep), (i, keep)

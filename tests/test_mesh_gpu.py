@@ -353,3 +353,55 @@ def test_reconstruct_perspective_mesh_512(gpu_device):
     got, want = np.where(skip, np.nan, img["map"]), np.where(skip, np.nan, want_map)
     assert close(got, want) and skip.mean() <= 0.001
     assert abs(img["min_depth"] - want_min) <= RTOL * abs(want_min) and abs(img["max_depth"] - want_max) <= RTOL * abs(want_max)
+
+
+# ---- a K and an image size per camera (mesh_scenes.scene(m, mixed=True)) ---------------------------------------------------
+MIXED_CASES = [(3, 0), (3, 1), (3, 2), (8, 5), (8, 6)]  # every camera of the 3-camera scene; 250 x 141 and 141 x 250 of the 8
+
+
+@functools.lru_cache(maxsize=None)
+def mixed_scene(m):
+    s = mesh_scenes.scene(m, mixed=True)
+    s.device = mesh_scenes.device_surface(s)
+    return s
+
+
+@pytest.mark.parametrize("m,i", MIXED_CASES)
+def test_mixed_dims_match_restatement_on_both_paths(gpu_device, m, i):
+    """test_cull_and_depth_image_match_restatement's comparisons - camera points, depth buffers, flags, statistics and the
+    depth image: flags, masks and pixels equal, depths to 1e-9 - on scenes whose cameras each have their own K and their
+    own (width, height), landscape and portrait, no two alike; with every polygon through the wave path, none, and the
+    default threshold, as test_both_paths_give_the_same_flags_and_maps runs them.  near_threshold is empty for these
+    cameras (tests/test_mesh_ref.py)."""
+    s = mixed_scene(m)
+    assert len(set(s.image_dims)) == m
+    polys = mesh_scenes.polygons(s, i)
+    near = ref_mesh.Near()
+    want_idx, want_xy = ref_mesh.camera_points(s.surface, i, near=near)
+    want_keep, want_stats = ref_mesh.cull(s.surface, i, polys, near=near)
+    want_map, want_origin, want_min, want_max = ref_mesh.depth_image(s.surface, i, -1.0, polys, near=near)
+    assert near.empty(), (near.polygons, near.cells, near.tracks)
+    idx, xy = mesh.camera_points(gpu_device, s.device, s.image_dims, i)
+    assert np.array_equal(idx, want_idx) and same_bytes(xy, want_xy) and len(idx) > 1000
+    for j in ((i + 1) % m, (i + 2) % m):
+        assert close(mesh.depth_buffer(gpu_device, s.device, s.image_dims, j), ref_mesh.depth_buffer(s.surface, j)), j
+    try:
+        for name, thr in (("all", mesh.WIDE_ALL), ("none", mesh.WIDE_NONE), ("default", mesh.WIDE_THRESHOLD_DEFAULT)):
+            mesh.set_wide_threshold(gpu_device, thr)
+            keep, stats = mesh.cull(gpu_device, s.device, s.image_dims, i, polys)
+            assert np.array_equal(keep, want_keep), name
+            for k in range(m):
+                got = (stats[k]["width"], stats[k]["height"], stats[k]["occupied"], stats[k]["dropped"])
+                assert got == want_stats[k], (name, k, got, want_stats[k])
+                if k != i:
+                    assert 0.05 * len(polys) <= stats[k]["dropped"] <= 0.95 * len(polys)
+                    assert stats[k]["wide"] == {"all": len(polys), "none": 0}.get(name, stats[k]["wide"])
+                    assert name != "default" or 0 < stats[k]["wide"] < len(polys)
+            assert stats[i] == dict.fromkeys(mesh.STATS, 0)
+            img = mesh.depth_image(gpu_device, s.device, s.image_dims, i, -1.0, polys)
+            assert img["origin"] == want_origin and close(img["map"], want_map), name
+            assert abs(img["min_depth"] - want_min) <= RTOL * abs(want_min) and abs(img["max_depth"] - want_max) <= RTOL * abs(want_max)
+            assert img["wide"] == {"all": len(polys), "none": 0}.get(name, img["wide"])
+            assert name != "default" or 0 < img["wide"] < len(polys)
+    finally:
+        mesh.set_wide_threshold(gpu_device, mesh.WIDE_THRESHOLD_DEFAULT)

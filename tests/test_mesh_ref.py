@@ -241,3 +241,36 @@ def test_delaunay_scipy_reports_a_missing_scipy(monkeypatch):
     monkeypatch.setattr(builtins, "__import__", no_scipy)
     with pytest.raises(RuntimeError, match="scipy"):
         mesh.delaunay_scipy(np.zeros((4, 2)))
+
+
+MIXED_CASES = [(3, 0), (3, 1), (3, 2), (8, 5), (8, 6)]  # (tests/test_mesh_gpu.py's)
+
+
+@pytest.mark.parametrize("m,i", MIXED_CASES)
+def test_mixed_scene_seeds_meet_the_gpu_tests_conditions(m, i):
+    """What test_mixed_dims_match_restatement_on_both_paths assumes of mesh_scenes.scene(m, mixed=True): no two image
+    sizes alike, landscape and portrait, a K per camera with fx != fy and skew; every track seen in a camera lies inside
+    that camera's own image, and some only because the test is per axis (a pixel past the OTHER side's length); near_threshold is empty for camera_i; more than
+    1000 camera points; every other camera drops between 5 % and 95 % of the polygons.  The plain scene is what it was."""
+    s = mesh_scenes.scene(m, mixed=True)
+    dims = s.image_dims
+    assert dims == mesh_scenes.mixed_dims(m) and len(set(dims)) == m
+    assert any(w > h for w, h in dims[:3]) and any(w < h for w, h in dims[:3])
+    per_axis = 0
+    for j, (w, h) in enumerate(dims):
+        K = s.cams[j][0]
+        assert K[0, 0] != K[1, 1] and K[0, 1] != 0.0 and K[0, 2] != K[1, 2]
+        t = s.surface.tracks[s.surface.seen(j), j]
+        assert t[:, 0].max() < w and t[:, 1].max() < h and t.min() >= 0
+        per_axis += int(((t[:, 0] >= min(w, h)) | (t[:, 1] >= min(w, h))).sum())
+    assert per_axis > 1000
+    polys = mesh_scenes.polygons(s, i)
+    near = ref_mesh.near_threshold(s.surface, polys, camera_i=i, project_to_image=i)
+    assert near.empty(), (near.polygons, near.cells, near.tracks)
+    assert len(ref_mesh.camera_points(s.surface, i)[0]) > 1000
+    keep, stats = ref_mesh.cull(s.surface, i, polys)
+    for j in range(m):
+        if j != i:
+            assert 0.05 * len(polys) <= stats[j][3] <= 0.95 * len(polys), (j, stats[j])
+    plain = mesh_scenes.scene(m)
+    assert plain.image_dims == [(mesh_scenes.SIZE, mesh_scenes.SIZE)] * m and np.array_equal(plain.cams[0][0], plain.cams[m - 1][0])

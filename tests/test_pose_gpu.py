@@ -2,6 +2,7 @@
 import numpy as np
 import pytest
 
+import mixed_scenes
 import pose_checks
 import pose_scenes
 import ref_pose as rp
@@ -334,3 +335,27 @@ def test_reconstruct_perspective_2048(gpu_device):
     assert cos_t > 0.998
     assert third["count"] >= rp.RANSAC_D_PERCENT_EARLY_EXIT * third["linked"] // 100
     assert i1 != 0 or np.median(err) < 0.074
+
+
+def test_find_projection_matrix_with_two_calibrations(gpu_device):
+    """cvhip_find_projection_matrix with K1 != K2 on every ordered pair (i, j) of a 3-camera mixed scene (3000 tracks, a
+    K and an image size per camera) and the pair's two-K true F, as test_find_projection_matrix_matches_restatement
+    compares: the restatement's score, the runner-up strictly lower, out_P2 and out_r2 to 1e-9 - and out_KP2 against
+    K_j P2.  E = K2^T F K1: with the two K exchanged the restatement finds another winner or a strictly lower score on
+    every one of these pairs (tests/test_pose_ref.py), which one shared K cannot show."""
+    import ctypes as C
+
+    tracks, Ks, poses, _, _ = pose_scenes.mixed_multiview_scene(3, 3000, seed=3, miss=0.0)
+    for i, j in [(0, 1), (1, 0), (0, 2), (2, 0), (1, 2), (2, 1)]:
+        F = np.ascontiguousarray(mixed_scenes.true_f(Ks[i], Ks[j], poses[i], poses[j]))
+        short = np.ascontiguousarray(tracks[:, [i, j]])
+        k1, k2 = np.ascontiguousarray(Ks[i]), np.ascontiguousarray(Ks[j])
+        p2, r2, kp2 = np.zeros((3, 4)), np.zeros(3), np.zeros((3, 4))
+        score = C.c_double(0)
+        _lib.check(_lib.lib().cvhip_find_projection_matrix(gpu_device.handle, _p(F), _p(k1), _p(k2), _p(short), len(short),
+                                                           _p(p2), C.byref(score), _p(r2), _p(kp2)), "fpm")
+        wp2, wcount, counts = rp.find_projection_matrix(F, k1, k2, short)
+        assert score.value == wcount and sorted(counts)[-2] < wcount, (i, j)
+        assert np.allclose(p2, wp2, rtol=1e-9, atol=1e-9), (i, j)
+        assert np.allclose(r2, rt.Camera.from_matrix(k2, p2[:, :3], p2[:, 3]).r, rtol=1e-9, atol=1e-12), (i, j)
+        assert np.allclose(kp2, k2 @ wp2, rtol=1e-9, atol=1e-9), (i, j)

@@ -181,6 +181,8 @@ def _stage_scene(name):
         return pose_scenes.few_links_scene()
     if name == "scrambled_5":
         return pose_scenes.scrambled_scene()
+    if name == "mixed_4":
+        return pose_scenes.sparse_mixed_scene()
     tracks, K, poses, X = pose_scenes.multiview_scene(8, 260, seed=11, miss=0.3)
     return tracks, K, poses, X, pose_scenes.planted_matches(tracks, K, poses)
 
@@ -201,10 +203,13 @@ def _recorded_failure(tracks, points, ok, projections, image, K, max_dimension, 
 def _run_stage(dev, oracle, name, bundle_adjustment, seed=3):
     """The device's sparse stage and the restated one on the same planted matches, compared call by call.
     -> (tri, st, order, info)."""
-    tracks, K, poses, _, matches = _stage_scene(name)
-    m, size = tracks.shape[1], 512
-    tri = _Recording(m, [(size, size)] * m, bundle_adjustment=bundle_adjustment, calibration=[K] * m)
-    st = rp.SparseTriangulation(m, [(size, size)] * m, [K] * m, oracle.extend_tracks)
+    scene = _stage_scene(name)
+    tracks, K, poses, _, matches = scene[:5]
+    m = tracks.shape[1]
+    shapes = scene[5] if len(scene) > 5 else [(512, 512)] * m  # (mixed_4: a size and a K per image)
+    calibration = K if isinstance(K, list) else [K] * m
+    tri = _Recording(m, shapes, bundle_adjustment=bundle_adjustment, calibration=calibration)
+    st = rp.SparseTriangulation(m, shapes, calibration, oracle.extend_tracks)
     want_pairs = pose_scenes.restated_pairs(st, matches)
     for (i, j), (rows, F) in sorted(matches.items()):
         p2, score = tri.add_image_pair_sparse(dev, i, j, F, rows)
@@ -245,7 +250,7 @@ def _run_stage(dev, oracle, name, bundle_adjustment, seed=3):
     return tri, st, order, info, calls
 
 
-@pytest.mark.parametrize("name", ["equal_counts_4", "few_links_5", "scrambled_5", "ragged_8"])
+@pytest.mark.parametrize("name", ["equal_counts_4", "few_links_5", "scrambled_5", "ragged_8", "mixed_4"])
 def test_sparse_stage_from_planted_matches(gpu_device, oracle, name):
     """add_image_pair_sparse for every pair, reconstruction.recover_camera_poses and triangulate_all_recovered (no bundle
     adjustment) against ref_pose.SparseTriangulation / recover_camera_poses and
@@ -254,7 +259,12 @@ def test_sparse_stage_from_planted_matches(gpu_device, oracle, name):
     points; then the same kept set and points.  equal_counts_4: images 0 and 1 tie and the later one is taken.
     few_links_5: image 3's call fails at once, appears in the info and takes a seed; the image is pruned from the surface.
     scrambled_5: image 3 is tried first, fails after 100 batches (its restated run is tests/golden/pose_runs.json's
-    stage_scrambled), and images 0 and 1 are placed after it with the next seeds."""
+    stage_scrambled), and images 0 and 1 are placed after it with the next seeds.
+    mixed_4 (pose_scenes.sparse_mixed_scene): a K and a (width, height) per image, landscape and portrait, only image 2
+    past 1000 pixels - find_projection_matrix gets k1, k2 = the pair's own, recover_pose the image's own K and longer
+    side, extend_tracks image 1's (width, height) for its grid and image 2's longer side for its radius, which is 4 for
+    the pairs that end in image 2 and 3 for the others; tests/test_pose_ref.py shows that the table changes when the
+    radius comes from the other image."""
     tri, st, order, info, calls = _run_stage(gpu_device, oracle, name, bundle_adjustment=False)
     m = tri.images_count
     if name == "equal_counts_4":
@@ -298,3 +308,40 @@ def test_sparse_stage_bundle_adjustment_matches_restatement(gpu_device, oracle):
     assert (rel <= 1e-4).all(), rel.max()
     for dc, rc in zip(surf.cameras, rcams):
         assert np.allclose(dc.r, rc.r, rtol=1e-4, atol=1e-12) and np.allclose(dc.t, rc.t, rtol=1e-4, atol=1e-12)
+
+
+# ---- a K per image, images of different shapes (tests/mixed_scenes.py) -----------------------------------------------------
+@pytest.mark.parametrize("m,image,placed", pc.MIXED_CONFIGS)
+def test_pose_models_match_restatement_on_mixed_cameras(gpu_device, m, image, placed):
+    """test_pose_models_match_restatement_at_every_view_count's comparison (pose_checks.check_models as it is) where
+    every image has its own K and its own (width, height): the known views' projections use their own K, the recovered
+    image's K is its own, and max_dimension is that image's longer side, which is not its shorter one."""
+    tracks, Ks, P, has, projections, sizes = pc.multiview_config_mixed(m, image, placed)
+    size = max(sizes[image])
+    assert size != min(sizes[image])
+    rc, pts, ok = _triangulate(gpu_device, tracks, m, P, has)
+    assert rc == 0
+    ok = ok.astype(bool)
+    lt, lp = rp.linked(tracks, pts, ok, image)
+    samples = pc.sample_triples(lp, pc.MULTIVIEW_TRIPLES)
+    got = pc.device_models(gpu_device, tracks, pts, ok, P, has, image, Ks[image], size, samples)
+    pc.check_models(got, lt, lp, projections, image, Ks[image], size, samples, label=f"mixed m={m} image={image} known={placed}: ")
+
+
+def test_recover_pose_whole_call_on_mixed_cameras(gpu_device):
+    """cvhip_recover_pose, one whole call, on the mixed configuration (6, 3, (0, 1, 5)) - image 3 is 256 x 384 with its own
+    K - against ref_pose.recover_pose on the same inputs (both sides get the restatement's points), compared as
+    test_recover_pose_leaves_in_a_middle_batch compares: winner (batch, hypothesis, root), count, batches; error, r, t and
+    projection to 1e-9.  The run leaves after batch 0 with at least 95 % of the linked tracks.  A second call gives the
+    same bits."""
+    tracks, K, P, has, image, pts, ok, md, seed, projections = pc.mixed_run_inputs()
+    rc, a = pc.device_recover_pose(gpu_device, tracks, pts, ok, P, has, image, K, md, seed)
+    rc2, b = pc.device_recover_pose(gpu_device, tracks, pts, ok, P, has, image, K, md, seed)
+    assert rc == 0 and rc2 == 0
+    assert all(np.array_equal(a[k], b[k]) for k in a)
+    want = rp.recover_pose(tracks, pts, ok, projections, image, K, md, seed)
+    print("mixed whole call: device", a["winner"], a["count"], a["batches"], "restated", want["winner"], want["count"],
+          want["batches"], "of", want["linked"])
+    assert want["camera"] is not None and want["batches"] == 1
+    assert want["count"] >= rp.RANSAC_D_PERCENT_EARLY_EXIT * want["linked"] / 100 and want["linked"] > 300
+    _compare_run(a, want["count"], want["error"], want["batches"], want["winner"], *want["camera"])

@@ -323,3 +323,154 @@ def test_recover_camera_poses_keeps_the_failure_message_and_goes_on():
     assert info[0] == {"images": [0, 1]} and info[2] == {"images": [3], "image": 3, "error": 0.25, "count": 9}
     assert "images" not in info[1] and "Unable to find projection matrix" in info[1]["failure"]
     assert info[1]["image"] == 2 and info[1]["error"] == 0.5 and info[1]["count"] == 4
+
+
+# ---- the mixed scenes (a K and an image size per camera): tests/mixed_scenes.py ---------------------------------------------
+def test_two_k_true_f_fits_the_mixed_projections():
+    """mixed_scenes.true_f: x2^T F x1 = 0 for exact projections through K1 [R1 | t1] and K2 [R2 | t2] with K1 != K2; with
+    the two K exchanged it does not hold; with one K it is synth.sfm_true_f."""
+    import mixed_scenes
+    import pose_scenes
+
+    _, Ks, poses, X, _ = pose_scenes.mixed_multiview_scene(3, 200, seed=3, miss=0.0)
+    for i in range(3):
+        for j in range(3):
+            if i == j:
+                continue
+            x1 = (pose_scenes.projection(Ks[i], *poses[i]) @ np.hstack([X, np.ones((len(X), 1))]).T).T
+            x2 = (pose_scenes.projection(Ks[j], *poses[j]) @ np.hstack([X, np.ones((len(X), 1))]).T).T
+            x1, x2 = x1 / x1[:, 2:], x2 / x2[:, 2:]
+
+            def distance(F):
+                line = x1 @ F.T
+                return np.abs((x2 * line).sum(axis=1)) / np.linalg.norm(line[:, :2], axis=1)
+
+            assert distance(mixed_scenes.true_f(Ks[i], Ks[j], poses[i], poses[j])).max() < 1e-8
+            assert distance(mixed_scenes.true_f(Ks[j], Ks[i], poses[i], poses[j])).max() > 1.0
+    K = Ks[0]
+    assert np.allclose(mixed_scenes.true_f(K, K, poses[1], poses[2]), synth.sfm_true_f(K, poses[1], poses[2]), rtol=1e-12, atol=0)
+
+
+def test_find_projection_matrix_tells_k1_from_k2():
+    """The scene of test_find_projection_matrix_with_two_calibrations: on every ordered pair the restatement's winner
+    beats the runner-up strictly (no tie for the SVD's signs to decide) and sees (nearly) every track in front of both
+    cameras; called with the two K exchanged - E = K1^T F K2 - it finds another winner or a strictly lower score."""
+    import mixed_scenes
+    import pose_scenes
+
+    tracks, Ks, poses, _, sizes = pose_scenes.mixed_multiview_scene(3, 3000, seed=3, miss=0.0)
+    assert len(set(sizes)) == 3 and (tracks >= 0).all()
+    for i, j in [(0, 1), (1, 0), (0, 2), (2, 0), (1, 2), (2, 1)]:
+        F = mixed_scenes.true_f(Ks[i], Ks[j], poses[i], poses[j])
+        short = tracks[:, [i, j]]
+        p2, count, counts = rp.find_projection_matrix(F, Ks[i], Ks[j], short)
+        assert count > 0.99 * len(short) and sorted(counts)[-2] < count, (i, j, counts)
+        R = poses[j][0] @ poses[i][0].T
+        assert np.abs(p2[:, :3] - R).max() < 1e-9, (i, j)
+        q2, qcount, qcounts = rp.find_projection_matrix(F, Ks[j], Ks[i], short)
+        print((i, j), counts, "exchanged:", qcounts)
+        assert qcount < count or np.abs(q2 - p2).max() > 1e-3, (i, j)
+
+
+def _mixed_configs():
+    import pose_checks as pc
+
+    return pc.MIXED_CONFIGS
+
+
+@pytest.mark.parametrize("m,image,placed", _mixed_configs())
+def test_mixed_config_scores_enough_poses(m, image, placed):
+    """A mixed configuration of the per-sample parity test, from the restatement alone: it is one of MULTIVIEW_CONFIGS,
+    the image is not square, more than 1000 poses pass the 3-sample check (check_models' floor) over more than 200 linked
+    tracks; and the image's own K matters - with camera 0's K in its place the first poses differ by far more than the
+    comparison's 1e-6."""
+    import pose_checks as pc
+
+    assert (m, image, placed) in pc.MULTIVIEW_CONFIGS
+    tracks, Ks, P, has, projections, sizes = pc.multiview_config_mixed(m, image, placed)
+    size = max(sizes[image])
+    assert size != min(sizes[image]) and len(set(sizes)) == m
+    seen = tracks[..., 0] >= 0
+    for j, (w, h) in enumerate(sizes):
+        assert tracks[seen[:, j], j, 0].max() < w and tracks[seen[:, j], j, 1].max() < h
+    pts, ok = pc.restated_points(tracks, P, has)
+    lt, lp = rp.linked(tracks, pts, ok, image)
+    samples = pc.sample_triples(lp, pc.MULTIVIEW_TRIPLES)
+    passed = sum(c[5] for s in samples for c in rp.pose_candidates(lt, lp, projections, image, Ks[image], size,
+                                                                   [int(v) for v in s], score=False))
+    print("mixed", m, image, placed, len(lt), "linked,", passed, "poses pass the 3-sample check")
+    assert passed > 1000 and len(lt) > 200
+    differ = 0
+    for s in samples[-20:]:  # (random triples: the special ones come first)
+        own = rp.pose_candidates(lt, lp, projections, image, Ks[image], size, [int(v) for v in s], score=False)
+        other = rp.pose_candidates(lt, lp, projections, image, Ks[0], size, [int(v) for v in s], score=False)
+        differ += [c[0] for c in own] != [c[0] for c in other] or any(np.abs(a[4] - b[4]).max() > 1e-3 for a, b in zip(own, other))
+    assert differ >= 15
+
+
+def test_mixed_whole_call_leaves_after_the_first_batch():
+    """pose_checks.mixed_run_inputs: the restated recover_pose is accepted after batch 0 with at least 95 % of more than
+    300 linked tracks, no contender within 1 of the winner's count has a track within 1e-6 max_dimension of the
+    threshold; with camera 0's K for the image's own it ends with another winner."""
+    import pose_checks as pc
+
+    tracks, K, P, has, image, pts, ok, md, seed, projections = pc.mixed_run_inputs()
+    contenders = []
+
+    def observe(_b, _h, _s, count, _e, errs):
+        with np.errstate(all="ignore"):
+            contenders.append((count, float(np.nanmin(np.abs(errs - rp.RANSAC_T * md)))))
+
+    res = rp.recover_pose(tracks, pts, ok, projections, image, K, md, seed, observe=observe)
+    print("mixed whole call:", res["count"], "of", res["linked"], "after", res["batches"], "batch(es), winner", res["winner"])
+    assert res["camera"] is not None and res["batches"] == 1 and res["linked"] > 300
+    assert res["count"] >= rp.RANSAC_D_PERCENT_EARLY_EXIT * res["linked"] / 100
+    assert _near_threshold_margin(contenders, res["count"]) > 1e-6 * md
+    k0 = pc.multiview_config_mixed(*pc.MIXED_RUN["config"])[1][0]
+    other = rp.recover_pose(tracks, pts, ok, projections, image, k0, md, seed)
+    assert other["winner"] != res["winner"] or other["count"] != res["count"]
+
+
+def test_sparse_mixed_scene_tells_the_images_apart(oracle):
+    """pose_scenes.sparse_mixed_scene through the restated stage: no two image sizes alike, landscape and portrait, only
+    image 2 has a side past 1000 pixels (extend_tracks' radius is 4 for pairs ending in image 2, else 3); every pixel
+    lies inside its image and inside the images before it; every pair's find_projection_matrix has a strict winner; all
+    four cameras are placed, each recover_pose in one batch.  The table hangs on whose size gives the radius: with image
+    1's longer side in place of image 2's, extend_tracks builds another table."""
+    import pose_scenes
+
+    tracks, Ks, poses, _, matches, sizes = pose_scenes.sparse_mixed_scene()
+    assert len(set(sizes)) == 4 and any(w > h for w, h in sizes) and any(w < h for w, h in sizes)
+    assert [3 * max(s) // 1000 if max(s) > 1000 else 3 for s in sizes] == [3, 3, 4, 3]
+    seen = tracks[..., 0] >= 0
+    for j in range(4):
+        for i in range(j + 1):
+            assert tracks[seen[:, j], j, 0].max() < sizes[i][0] and tracks[seen[:, j], j, 1].max() < sizes[i][1], (i, j)
+    assert len(matches) == 6
+
+    def stage(extend):
+        st = rp.SparseTriangulation(4, sizes, Ks, extend)
+        pairs = pose_scenes.restated_pairs(st, matches)
+        return st, pairs, st.tracks.copy()
+
+    st, pairs, table = stage(oracle.extend_tracks)
+    for (i, j), (rows, F) in matches.items():
+        both = (table[:, i, 0] >= 0) & (table[:, j, 0] >= 0)
+        counts = rp.find_projection_matrix(F, Ks[i], Ks[j], table[both][:, [i, j]])[2]
+        assert sorted(counts)[-2] < max(counts) == pairs[(i, j)][1], (i, j, counts)
+    order, calls = rp.recover_camera_poses(st, seed=3)
+    print("mixed_4:", len(table), "tracks, order", order, [(c["image"], c["pose"] and (c["pose"]["linked"], c["pose"]["count"],
+                                                                                       c["pose"]["batches"])) for c in calls])
+    assert sorted(order) == [0, 1, 2, 3] and all("failure" not in c for c in calls)
+    assert all(c["pose"]["batches"] == 1 for c in calls[1:])
+    # the planted companions: their match is taken into the neighbour's track in the pair (0, 2) only
+    n = len(tracks) - 12
+    for k in range(12):
+        a, b = tracks[k], tracks[n + k]
+        other = 2 if k % 2 == 0 else 3
+        merged = ((table[:, 0] == a[0]).all(axis=1) & (table[:, other] == b[other]).all(axis=1)).any()
+        alone = ((table[:, 0] == b[0]).all(axis=1) & (table[:, other] == b[other]).all(axis=1)).any()
+        assert merged == (other == 2) and alone, k  # (B keeps a track of its own: the merged match is cleared at its image-2 pixel)
+    # image 1's longer side for image 2's: radius 3 for (0, 2) and (1, 2), 4 for (2, 3)
+    _, _, wrong = stage(lambda grid, tp1, max_dimension: oracle.extend_tracks(grid, tp1, max(grid.shape[:2])))
+    assert wrong.shape != table.shape or not np.array_equal(wrong, table)

@@ -6,14 +6,15 @@ import time
 import numpy as np
 import pytest
 
+import mixed_scenes
 import ref_triangulation as rt
 import tri_scenes
 from cybervision_amd import _lib, reconstruction, synth, triangulation
 
 
-def run_device(dev, tracks, cams, bundle_adjustment):
+def run_device(dev, tracks, cams, bundle_adjustment, image_shapes=None):
     m = tracks.shape[1]
-    tri = triangulation.PerspectiveTriangulation(m, [(2048, 2048)] * m, bundle_adjustment=bundle_adjustment)
+    tri = triangulation.PerspectiveTriangulation(m, image_shapes or [(2048, 2048)] * m, bundle_adjustment=bundle_adjustment)
     tri.tracks = np.ascontiguousarray(tracks, dtype=np.int32)
     return tri.triangulate_all(dev, cams)
 
@@ -192,7 +193,7 @@ def _compare_ba(surf, idx, pts, cams, ba, tol, tol_res):
 
 def _case_id(case):
     m, n, seed, far, accepts = case
-    return f"m{m}-n{n}-seed{seed}-{'accepts' if accepts else 'rejects'}"
+    return f"m{m}-n{n}-seed{seed}-{'accepts' if accepts else 'rejects'}" + ("-mixed" if isinstance(case, tri_scenes.MixedCase) else "")
 
 
 @pytest.mark.gpu
@@ -308,3 +309,93 @@ def test_sfm3_surface_2048_properties(gpu_device):
     assert len(surf.points) > 0.5 * len(table)
     assert rms_after <= rms_before
     assert np.median(err) < 0.02
+
+
+# ---- the mixed rig: a K per camera (fx != fy, skew, off-centre principal point), no two images of one size ---------------
+@pytest.mark.gpu
+@pytest.mark.parametrize("m", [2, 3, 8])
+def test_triangulate_and_filter_match_restatement_on_the_mixed_rig(gpu_device, m):
+    """test_triangulate_and_filter_match_restatement's comparison on tri_scenes.mixed_rig(m) - every camera's K its own,
+    images of mixed_scenes.DIMS -, 20 k tracks (~78 blocks of 256): the same kept set in the same order, points to 1e-9,
+    every branch deciding some tracks.  With one shared, symmetric K a kernel that takes camera j's K from camera 0, or
+    K[1] for K[3], computes the same numbers; here it does not (tests/test_triangulation_ref.py)."""
+    cams = tri_scenes.mixed_rig(m, near_duplicate=m > 2)
+    tracks = tri_scenes.track_table(cams, 20_000, seed=m)
+    close = tri_scenes.near_threshold(tracks, cams)
+    assert len(close) == 0, f"tracks at a threshold: {close[:20].tolist()}"
+    ref_idx, ref_pts, _, _ = rt.triangulate_all(tracks, cams, bundle_adjustment=False)
+    surf = run_device(gpu_device, tracks, cams, False, image_shapes=mixed_scenes.DIMS[:m])
+    k = (tracks[..., 0] >= 0).sum(axis=1)
+    kept = np.zeros(len(tracks), dtype=bool)
+    kept[ref_idx] = True
+    assert (k < 2).any() and not kept[k < 2].any()
+    assert 0.3 * len(tracks) < len(ref_idx) < 0.9 * len(tracks)
+    assert np.array_equal(surf.track_index, ref_idx)
+    assert (rel_err(surf.points, ref_pts) <= 1e-9).all(), rel_err(surf.points, ref_pts).max()
+    assert surf.ba_iterations == 0 and np.isnan(surf.ba_residual_norms[0])
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("case", tri_scenes.BA_MIXED_CASES, ids=_case_id)
+def test_bundle_adjustment_on_the_mixed_rig(gpu_device, case):
+    """test_bundle_adjustment_every_camera_count's comparison (1e-6 points and cameras, 1e-9 residual norms, the exact
+    accept / reject sequence) with a K per camera: d * K of the Jacobians uses all nine entries of the camera's own K.
+    m = 6 and m = 8 run the second camera group of ba_jtr_kernel.  The scenes' claims: tests/test_triangulation_ref.py's
+    test_ba_scene_claims, as for BA_RIG_CASES, and test_ba_mixed_scene_keeps_its_history_however_v_is_inverted."""
+    m, n, seed, far, accepts = case
+    _, given, tracks = tri_scenes.ba_case_scene(case)
+    idx, pts, cams, ba = tri_scenes.ba_restatement(given, tracks)
+    assert any(ba.history) == accepts
+    surf = run_device(gpu_device, tracks, given, True, image_shapes=mixed_scenes.DIMS[:m])
+    print(f"mixed m={m}: {len(idx)} kept, history {surf.ba_history}")
+    _compare_ba(surf, idx, pts, cams, ba, 1e-6, 1e-9)
+
+
+@pytest.mark.gpu
+def test_perspective_cameras_on_the_mixed_rig(gpu_device):
+    """cvhip_triangulate_perspective_cameras with three mixed cameras given as pose recovery leaves them: r =
+    from_matrix's, and the projection K_j [matrix_r(r) | t] of a P3P camera - not K_j [R | t] -, which is where such a
+    projection and a K of its own meet.  No bundle adjustment, 5 k tracks: the restatement's kept set in order and points
+    to 1e-9 (no track at a threshold: tests/test_triangulation_ref.py); then the device-resident test's comparison:
+    table and outputs in device memory give the host call's bytes, rows from out_n on keep what they held."""
+    import ctypes as C
+
+    import torch
+
+    given, cams, P, tracks = tri_scenes.mixed_p3p_case()
+    n, m = tracks.shape[:2]
+    K = np.ascontiguousarray(np.stack([c.k.reshape(9) for c in cams]))
+    r = np.ascontiguousarray(np.stack([c.r for c in cams]))
+    t = np.ascontiguousarray(np.stack([c.t for c in cams]))
+    Pc = np.ascontiguousarray(P)
+    POINT, INDEX = -7.25, 0x5A5A5A5A5A5A5A5A
+
+    def ptr(a):
+        return C.c_void_p(a.data_ptr() if hasattr(a, "data_ptr") else a.ctypes.data)
+
+    def call(table, pts, idx):
+        out_r, out_t, out_p = np.zeros((m, 3)), np.zeros((m, 3)), np.zeros((m, 3, 4))
+        out_n = C.c_uint64(0)
+        _lib.check(_lib.lib().cvhip_triangulate_perspective_cameras(
+            gpu_device.handle, ptr(table), n, m, ptr(K), ptr(r), ptr(t), ptr(Pc), 0, ptr(pts), ptr(idx), ptr(out_r),
+            ptr(out_t), ptr(out_p), C.byref(out_n), None, None, None, _lib.NULL_PROGRESS, None),
+            "cvhip_triangulate_perspective_cameras")
+        return out_n.value, out_r, out_t, out_p
+
+    want_idx, want_pts = rt.triangulate_and_filter(tracks, cams, P)
+    pts, idx = np.full((n, 3), POINT), np.full(n, INDEX, dtype=np.uint64)
+    k, out_r, out_t, out_p = call(tracks, pts, idx)
+    assert 0.3 * n < k < 0.9 * n and np.array_equal(idx[:k].astype(np.int64), want_idx)
+    assert (rel_err(pts[:k], want_pts) <= 1e-9).all(), rel_err(pts[:k], want_pts).max()
+    assert (pts[k:] == POINT).all() and (idx[k:] == INDEX).all()
+    for j, c in enumerate(cams):  # the cameras come back as given
+        assert np.array_equal(out_r[j], c.r) and np.array_equal(out_t[j], c.t)
+        assert np.allclose(out_p[j], c.projection(), rtol=1e-9, atol=1e-9)
+    d_tracks = torch.from_numpy(tracks).cuda()
+    d_pts = torch.full((n, 3), POINT, dtype=torch.float64, device="cuda")
+    d_idx = torch.full((n,), INDEX, dtype=torch.int64, device="cuda")
+    torch.cuda.synchronize()
+    got_k, got_r, got_t, got_p = call(d_tracks, d_pts, d_idx)
+    assert got_k == k and got_r.tobytes() == out_r.tobytes() and got_p.tobytes() == out_p.tobytes()
+    assert d_pts.cpu().numpy().tobytes() == pts.tobytes() and d_idx.cpu().numpy().view(np.uint64).tobytes() == idx.tobytes()
+    assert d_tracks.cpu().numpy().tobytes() == tracks.tobytes()

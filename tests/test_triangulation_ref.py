@@ -98,10 +98,11 @@ def test_bundle_adjustment_as_written_reaches_found_without_raising_the_residual
     assert turned.residual_norm_squared() < 0.5 * before
 
 
-SCENE_CASES = tri_scenes.BA_RIG_CASES + [tri_scenes.BA_GRID_CASE]
+SCENE_CASES = tri_scenes.BA_RIG_CASES + [tri_scenes.BA_GRID_CASE] + tri_scenes.BA_MIXED_CASES
 
 
-@pytest.mark.parametrize("case", SCENE_CASES, ids=lambda c: f"m{c[0]}-n{c[1]}-seed{c[2]}")
+@pytest.mark.parametrize("case", SCENE_CASES,
+                         ids=lambda c: f"m{c[0]}-n{c[1]}-seed{c[2]}" + ("-mixed" if isinstance(c, tri_scenes.MixedCase) else ""))
 def test_ba_scene_claims(case, monkeypatch):
     """What the device tests rely on for each bundle-adjustment scene: no track's DLT / filter decision lies within 1e-9
     of its threshold, the restatement reaches "found", every V it pseudo-inverts keeps its singular values far above the
@@ -138,3 +139,93 @@ def test_ba_scene_claims(case, monkeypatch):
     for a, b in zip(rcams, cams):
         assert tri_scenes.vec_close(a.r, b.r, 0.2 * tol, 1e-12) and tri_scenes.vec_close(a.t, b.t, 0.2 * tol, 1e-12)
         assert tri_scenes.vec_close(a.projection(), b.projection(), 0.2 * tol, 1e-9)
+
+
+@pytest.mark.parametrize("case", tri_scenes.BA_MIXED_CASES, ids=lambda c: f"m{c[0]}-n{c[1]}-seed{c[2]}-mixed")
+def test_ba_mixed_scene_keeps_its_history_however_v_is_inverted(case, monkeypatch):
+    """A further claim for the mixed bundle-adjustment scenes (tri_scenes.BA_MIXED_CASES says why): with V inverted as the
+    device inverts it - adjugate over determinant - in place of the SVD pseudo-inverse, the restatement runs the same
+    accept / reject sequence, every rho stays RHO_MARGIN away from 0, and points, cameras and the residual norm stay
+    within a fifth of the device test's bounds."""
+    _, given, tracks = tri_scenes.ba_case_scene(case)
+    idx, pts, cams, ba = tri_scenes.ba_restatement(given, tracks)
+    monkeypatch.setattr(rt, "_pinv3", tri_scenes.adjugate_inverse)
+    _, apts, acams, aba = tri_scenes.ba_restatement(given, tracks)
+    assert aba.history == ba.history, (aba.history, aba.rhos)
+    assert min(abs(r) for r in aba.rhos) >= tri_scenes.RHO_MARGIN, aba.rhos
+    tol, tol_res = 1e-6, 1e-9
+    assert abs(aba.final_residual_norm - ba.final_residual_norm) <= 0.2 * tol_res * ba.final_residual_norm
+    assert (np.linalg.norm(apts - pts, axis=1) <= 0.2 * tol * np.linalg.norm(pts, axis=1)).all()
+    for a, b in zip(acams, cams):
+        assert tri_scenes.vec_close(a.r, b.r, 0.2 * tol, 1e-12) and tri_scenes.vec_close(a.t, b.t, 0.2 * tol, 1e-12)
+        assert tri_scenes.vec_close(a.projection(), b.projection(), 0.2 * tol, 1e-9)
+
+
+# ---- the mixed rig (tests/mixed_scenes.py): what the device tests on it rely on, and what they can tell apart -------------
+def test_mixed_calibrations_are_general_and_all_different():
+    """Every K of the mixed rig has fx != fy (ratio 0.8 or 1.25), skew of ~1.5 % of fx with either sign among the first
+    two, a principal point off the centre by a different (signed) number of pixels in x and y, last row (0, 0, 1); no two K and no two image
+    sizes are alike, and landscape and portrait both occur among the first three."""
+    import mixed_scenes
+
+    Ks = mixed_scenes.calibrations(mixed_scenes.DIMS)
+    for j, (K, (w, h)) in enumerate(zip(Ks, mixed_scenes.DIMS)):
+        assert K[1, 1] / K[0, 0] == pytest.approx(1.25 if j % 2 else 0.8) and abs(K[0, 1]) == pytest.approx(0.015 * K[0, 0])
+        assert (K[0, 1] < 0) == bool(j % 2) and K[1, 0] == 0.0 and K[2].tolist() == [0.0, 0.0, 1.0]
+        dx, dy = K[0, 2] - w / 2.0, K[1, 2] - h / 2.0
+        assert dx != dy and dx != 0.0 and dy != 0.0 and K[0, 2] != K[1, 2]
+    assert len({K.tobytes() for K in Ks}) == 8 and len(set(mixed_scenes.DIMS)) == 8
+    assert len({(w, h) for w, h in mixed_scenes.DIMS} & {(h, w) for w, h in mixed_scenes.DIMS if w != h}) >= 4
+    shapes = [w > h for w, h in mixed_scenes.DIMS[:3]]
+    assert any(shapes) and not all(shapes)
+    # rig's poses and track tables are what they were
+    for a, b in zip(tri_scenes.rig(8), tri_scenes.mixed_rig(8)):
+        assert np.array_equal(a[1], b[1]) and np.array_equal(a[2], b[2])
+
+
+def _with_k(cams, change):
+    return [(change(j, K), R, t) for j, (K, R, t) in enumerate(cams)]
+
+
+@pytest.mark.parametrize("m", [2, 3, 8])
+def test_mixed_rig_table_claims(m):
+    """What test_triangulate_and_filter_match_restatement_on_the_mixed_rig relies on: no track at a threshold, 30 % to
+    90 % of the tracks kept, 1-view tracks present.  And what the scene tells apart - each of these changes of the
+    cameras given to the restatement, which one shared symmetric K would hide, moves the kept points by far more than the
+    device test's 1e-9 (and changes the kept set or not): every camera with camera 0's K; K[0][1] and K[1][0] exchanged
+    (the skew read from the other side of the diagonal); fx and fy exchanged; cx and cy exchanged."""
+    cams = tri_scenes.mixed_rig(m, near_duplicate=m > 2)
+    tracks = tri_scenes.track_table(cams, 20_000, seed=m)
+    assert len(tri_scenes.near_threshold(tracks, cams)) == 0
+    idx, pts, _, _ = rt.triangulate_all(tracks, cams, bundle_adjustment=False)
+    k = (tracks[..., 0] >= 0).sum(axis=1)
+    assert (k < 2).any() and 0.3 * len(tracks) < len(idx) < 0.9 * len(tracks)
+    print(f"m={m}: {len(idx)} of {len(tracks)} kept")
+
+    def swap(a, b):
+        def change(j, K):
+            K = K.copy()
+            K[a], K[b] = K[b], K[a]
+            return K
+        return change
+
+    k0 = cams[0][0]
+    for name, change in (("camera 0's K for every camera", lambda j, K: k0), ("K[1] read for K[3]", swap((0, 1), (1, 0))),
+                         ("fx and fy exchanged", swap((0, 0), (1, 1))), ("cx and cy exchanged", swap((0, 2), (1, 2)))):
+        idx2, pts2, _, _ = rt.triangulate_all(tracks, _with_k(cams, change), bundle_adjustment=False)
+        both = np.intersect1d(idx, idx2)
+        a, b = pts[np.searchsorted(idx, both)], pts2[np.searchsorted(idx2, both)]
+        moved = np.linalg.norm(a - b, axis=1) / np.linalg.norm(a, axis=1)
+        assert not np.array_equal(idx, idx2) or moved.max() > 1e-3, name
+        assert len(both) == 0 or moved.max() > 1e-3, (name, moved.max())
+
+
+def test_mixed_p3p_case_claims():
+    """test_perspective_cameras_on_the_mixed_rig's scene: no track at a threshold with the P3P-style projections, 30 % to
+    90 % kept, and the projections are not K [R | t] of the given matrices - the DLT with those keeps other points."""
+    given, cams, P, tracks = tri_scenes.mixed_p3p_case()
+    assert len(tri_scenes.near_threshold(tracks, given, projections=P)) == 0
+    idx, pts = rt.triangulate_and_filter(tracks, cams, P)
+    assert 0.3 * len(tracks) < len(idx) < 0.9 * len(tracks)
+    idx2, pts2 = rt.triangulate_and_filter(tracks, cams, [rt.given_projection(*c) for c in given])
+    assert not np.array_equal(idx, idx2) or np.abs(pts - pts2).max() > 1e-3

@@ -6,6 +6,7 @@ import math
 
 import numpy as np
 
+import mixed_scenes
 import ref_triangulation as rt
 
 
@@ -27,6 +28,13 @@ def rig(m, size=2048, near_duplicate=True):
         R = rot_y(-theta)
         cams.append((K, R, -R @ C))
     return cams
+
+
+def mixed_rig(m, near_duplicate=True):
+    """rig(m)'s poses with mixed_scenes' cameras: camera j has its own K (fx != fy, skew, an off-centre principal point)
+    for its own image size mixed_scenes.DIMS[j] - the scene centre still projects near the middle of every image."""
+    return [(mixed_scenes.calibration(j, mixed_scenes.DIMS[j]), R, t)
+            for j, (_, R, t) in enumerate(rig(m, near_duplicate=near_duplicate))]
 
 
 def project(cam, X):
@@ -84,11 +92,12 @@ def ref_cameras(cams):
     return [rt.Camera.from_matrix(K, R, t) for K, R, t in cams]
 
 
-def near_threshold(tracks, cams, tol=1e-9):
+def near_threshold(tracks, cams, tol=1e-9, projections=None):
     """Rows whose deciding quantity lies within tol (relative) of its threshold: |w| vs 1e-4, the smallest depth of a seen
-    view vs 0, the smallest |cos| between rays vs cos(0.5 deg)."""
+    view vs 0, the smallest |cos| between rays vs cos(0.5 deg).  projections: what the DLT projects with, when it is not
+    K [R | t] as given."""
     rc = ref_cameras(cams)
-    P = np.stack([rt.given_projection(*c) for c in cams])
+    P = np.stack([rt.given_projection(*c) for c in cams]) if projections is None else np.asarray(projections)
     pts, ok, w_abs = rt.triangulate_tracks(tracks, P)
     _, depth_min, min_cos = rt.filter_decisions(tracks, pts, ok, rc)
     thr = math.cos(rt.MIN_ANGLE_BETWEEN_RAYS)
@@ -118,14 +127,15 @@ def ba_scene(n, seed=5, size=2048):
     return cams, pert, tracks
 
 
-def ba_rig_scene(m, n, seed, perturb=True, far=0.1):
-    """n tracks over rig(m, near_duplicate=False) (no camera pair the ray-angle test drops whole): points of the box
+def ba_rig_scene(m, n, seed, perturb=True, far=0.1, mixed=False):
+    """n tracks over rig(m, near_duplicate=False) (no camera pair the ray-angle test drops whole; with `mixed`,
+    mixed_rig's cameras: the same poses, a K per camera): points of the box
     [-1.5, 1.5]^2 x [3.5, 6.5], a fraction `far` of them scattered through track_table's large box instead (some far
     or behind a camera: the tracks that can make the reference's uphill first step land lower), each seen in a uniform
     number of 2..m views (a random subset; the others (-1, -1)) with integer observations; with perturb, the cameras
     1..m-1 perturbed by ~1e-3 in r and t as ba_scene's.  -> (true cams, cams given to the triangulation, tracks)."""
     rng = np.random.default_rng(seed)
-    cams = rig(m, near_duplicate=False)
+    cams = mixed_rig(m, near_duplicate=False) if mixed else rig(m, near_duplicate=False)
     n_far = int(far * n)
     X = np.stack([rng.uniform(-1.5, 1.5, n), rng.uniform(-1.5, 1.5, n), rng.uniform(3.5, 6.5, n)], axis=1)
     X[:n_far] = np.stack([rng.uniform(-8, 8, n_far), rng.uniform(-3, 3, n_far), rng.uniform(-4, 10, n_far)], axis=1)
@@ -163,12 +173,66 @@ BA_RIG_CASES = [
     (7, 20_000, 3, 0.0, False),
     (8, 20_000, 5, 0.0, False),
 ]
+
+
+class MixedCase(tuple):
+    """A case (m, n, seed, far, accepts) of ba_rig_scene(..., mixed=True): mixed_rig's cameras."""
+
+
+# The bundle-adjustment scenes on mixed_rig, n = 6000, picked on the CPU like BA_RIG_CASES; tests/test_triangulation_ref.py
+# checks their claims with the same test.  All-rejected, like every scene above.  Tried with mixed cameras, far = 0,
+# n = 6000: m = 2, seeds 1..32 - all rejected everywhere, but the smallest |rho| is below RHO_MARGIN (0.002 .. 0.0999) except
+# for seeds 12 (0.109) and 30 (0.179); m = 3, seeds 1..8 - seeds 1, 3, 4, 5, 7, 8 qualify (seed 4: every rho is 1), seeds 2
+# and 6 have a rho ~1e-3.
+# m >= 5 (the second camera group of ba_jtr_kernel), seeds 1..16 x far 0 / 0.01 / 0.05 / 0.1 at n = 6000: no scene has an
+# accepted step, and 26 of the 256 pass test_ba_scene_claims as all-rejected scenes (the others miss RHO_MARGIN or change
+# under reversed order).  That test does not suffice here: on the mixed rig with 5 or more cameras some track's V (summed
+# over every view, seen or not) has a condition number of 1e14 .. 1e17, and the restatement's rhos then follow the way V
+# is inverted - the SVD pseudo-inverse, or the device's adjugate / determinant (adjugate_inverse below).  m = 5 seed 1
+# (smallest |rho| 0.139, condition 3.8e15) passes every claim of test_ba_scene_claims, yet with the adjugate the
+# restatement itself accepts steps 6 and 10 and runs 22 iterations for 14; the device accepted steps 4 and 8 of 21.
+# m = 5 seed 11 at n = 20 k and m = 7 seed 3 change their history the same way.  So a mixed scene must also keep its
+# history under adjugate_inverse (test_ba_mixed_scene_keeps_its_history_however_v_is_inverted); m = 6 seed 10 and
+# m = 8 seed 1 do, with every rho <= -1 both ways, and are taken.  No m = 5 scene was found that does.
+BA_MIXED_CASES = [
+    MixedCase((2, 6000, 30, 0.0, False)),
+    MixedCase((3, 6000, 4, 0.0, False)),
+    MixedCase((6, 6000, 10, 0.0, False)),
+    MixedCase((8, 6000, 1, 0.0, False)),
+]
+
+
+def adjugate_inverse(v):
+    """The inverse of [..., 3, 3] symmetric matrices as the device forms it (v_inverse, csrc/triangulation_kernels.hip):
+    adjugate over determinant, in its order of operations - a stand-in for ref_triangulation._pinv3."""
+    v = np.asarray(v, dtype=np.float64)
+    V = np.moveaxis(v.reshape(-1, 9), 1, 0)
+    c00, c01, c02 = V[4] * V[8] - V[5] * V[7], V[5] * V[6] - V[3] * V[8], V[3] * V[7] - V[4] * V[6]
+    inv = 1.0 / (V[0] * c00 + V[1] * c01 + V[2] * c02)
+    out = np.stack([c00 * inv, (V[2] * V[7] - V[1] * V[8]) * inv, (V[1] * V[5] - V[2] * V[4]) * inv,
+                    c01 * inv, (V[0] * V[8] - V[2] * V[6]) * inv, (V[2] * V[3] - V[0] * V[5]) * inv,
+                    c02 * inv, (V[1] * V[6] - V[0] * V[7]) * inv, (V[0] * V[4] - V[1] * V[3]) * inv], axis=1)
+    return out.reshape(v.shape)
+
+
 # more than MAX_GRID (1024) blocks of 256 kept tracks: the grid-stride loops of the bundle-adjustment kernels
 BA_GRID_CASE = (3, 270_000, 2, 0.0, False)
 GRID_STRIDE_TRACKS = 1024 * 256
 # every rho of a scene at least this far from 0: the decisions then do not hang on the rounding of rho itself (an
 # all-rejected scene's rhos are O(1) or larger; a scene whose rho was 2e-3 at one step took the other branch on the device)
 RHO_MARGIN = 0.1
+
+
+def mixed_p3p_case(n=5000, seed=3):
+    """Three mixed cameras as pose recovery leaves them, for cvhip_triangulate_perspective_cameras: the Camera that
+    from_matrix makes of mixed_rig(3)'s (K_j, R, t), and ITS projection K_j [matrix_r(r) | t] - a P3P camera's; as the
+    reference writes from_matrix that is a rotation by atan2(2 sin, cos) of R's angle, so the tracks are observed
+    through these projections.  -> (given [(K, R, t)], cameras, projections [3, 3, 4], tracks of track_table)."""
+    given = mixed_rig(3)
+    cams = ref_cameras(given)
+    seen_through = [(c.k, c.r_matrix, c.t) for c in cams]
+    tracks = np.ascontiguousarray(track_table(seen_through, n, seed), dtype=np.int32)
+    return given, cams, np.stack([c.projection() for c in cams]), tracks
 
 
 def vec_close(a, b, rtol, atol):
@@ -179,7 +243,7 @@ def vec_close(a, b, rtol, atol):
 
 def ba_case_scene(case):
     m, n, seed, far, _ = case
-    return ba_rig_scene(m, n, seed, far=far)
+    return ba_rig_scene(m, n, seed, far=far, mixed=isinstance(case, MixedCase))
 
 
 def ba_restatement(given, tracks, order=None):
