@@ -1271,7 +1271,7 @@ __global__ __launch_bounds__(1024) void ransac_round_max_kernel(const uint32_t *
         }
     __syncthreads();
     if (threadIdx.x == 0) {
-        tied[0] = s_n; // > TIED_CAP (never seen): the sum kernel then scans the live list for counts == top itself
+        tied[0] = s_n; // > TIED_CAP: the list is not used, whoever reads it scans the live list for counts == top (see ransac_tied_approx)
         tied[1 + TIED_CAP] = top;
     }
 }
@@ -1384,12 +1384,59 @@ __device__ double block_ordered_sum(const double (&f)[9], const uint4 *__restric
     return *result;
 }
 
+// A round's range of the live list, for the rounds with more than TIED_CAP hypotheses at the maximum count: the list of
+// the tied ones does not hold them, so they are found again by their counts (every live hypothesis of the range has its
+// count written by the counting kernel; the ones at the maximum are never abandoned, so theirs are exact).
+struct RoundRange {
+    const uint32_t *counts, *live, *n_live;
+    uint32_t first, end; // live[first .. min(*n_live, end))
+};
+// More than TIED_CAP hypotheses at the round's maximum (clean data: every sample of inliers gives a model that accepts
+// exactly the inliers): the round is decided like any other, by Ord over everybody at the maximum - without the screen
+// by parallel sums.  EVERY hypothesis of the range whose count is the maximum gets the reference's ordered fold here
+// (spread over the launch's workgroups), and ransac_pick_best_approx takes the smallest mean error, the smaller slot
+// among equals.  Slow (one fold per tied hypothesis), and only ever run where the list overflows.
+__device__ void ransac_tied_overflow(const double *__restrict__ F, const uint4 *__restrict__ matches, uint32_t N, double t,
+                                     const uint32_t *tied, RansacBest *best, double *__restrict__ out_err_sum, uint32_t block,
+                                     uint32_t blocks, const RoundRange &rr)
+{
+    __shared__ double errs[1024];
+    __shared__ double s_result;
+    const uint32_t top = tied[1 + TIED_CAP], j1 = min(*rr.n_live, rr.end);
+    if (top == 0u) return;
+    for (uint32_t j = rr.first + block; j < j1; j += blocks) {
+        const uint32_t h = rr.live[j];
+        if (rr.counts[h] != top) continue; // (uniform per workgroup)
+        double f[9];
+#pragma unroll
+        for (int i = 0; i < 9; i++) f[i] = F[(size_t)h * 9 + i];
+        const double sum = block_ordered_sum(f, matches, N, t, errs, &s_result);
+        if (threadIdx.x == 0) out_err_sum[h] = sum;
+        __syncthreads();
+    }
+    if (block == 0u && best->valid && top == best->matches_count && best->err_known != 2u) { // the carried best ties with them
+        double f[9];
+#pragma unroll
+        for (int i = 0; i < 9; i++) f[i] = best->f[i];
+        const double sum = block_ordered_sum(f, matches, N, t, errs, &s_result);
+        if (threadIdx.x == 0) {
+            best->best_error = sum / (double)best->matches_count;
+            best->err_known = 2u;
+        }
+        __syncthreads();
+    }
+}
+
 __device__ void ransac_tied_approx(const double *__restrict__ F, const uint4 *__restrict__ matches, uint32_t N, double t,
                                    const uint32_t *tied, RansacBest *best, double *__restrict__ out_err_sum, uint32_t block,
-                                   uint32_t blocks)
+                                   uint32_t blocks, const RoundRange &rr)
 {
     __shared__ double scratch[16];
-    if (tied[0] == 0u || tied[0] > TIED_CAP || !ransac_round_needs_errors(tied, best)) return;
+    if (tied[0] == 0u || !ransac_round_needs_errors(tied, best)) return;
+    if (tied[0] > TIED_CAP) {
+        ransac_tied_overflow(F, matches, N, t, tied, best, out_err_sum, block, blocks, rr);
+        return;
+    }
     const uint32_t n_items = tied[0], top = tied[1 + TIED_CAP];
     const uint32_t n_all = n_items + ((best->valid && top == best->matches_count && !best->err_known) ? 1u : 0u);
     for (uint32_t b = block; b < n_all; b += blocks) {
@@ -1412,9 +1459,12 @@ __device__ void ransac_tied_approx(const double *__restrict__ F, const uint4 *__
 }
 __global__ __launch_bounds__(1024) void ransac_tied_approx_kernel(const double *__restrict__ F, const uint4 *__restrict__ matches,
                                                                    uint32_t N, double t, const uint32_t *__restrict__ tied,
-                                                                   RansacBest *best, double *__restrict__ out_err_sum)
+                                                                   RansacBest *best, double *__restrict__ out_err_sum,
+                                                                   const uint32_t *__restrict__ counts, const uint32_t *__restrict__ live,
+                                                                   const uint32_t *__restrict__ n_live, uint32_t live_first, uint32_t live_end)
 {
-    ransac_tied_approx(F, matches, N, t, tied, best, out_err_sum, blockIdx.x, gridDim.x);
+    const RoundRange rr = {counts, live, n_live, live_first, live_end};
+    ransac_tied_approx(F, matches, N, t, tied, best, out_err_sum, blockIdx.x, gridDim.x, rr);
 }
 
 // The counting kernel's copy of the match list, reordered whenever the best hypothesis changes: the matches the best
@@ -1480,84 +1530,126 @@ __device__ void ransac_reorder_matches(const double *best_f, const uint4 *__rest
 __device__ void ransac_pick_best_approx(const double *__restrict__ F, const uint4 *__restrict__ matches, uint32_t N, double t,
                                         double *__restrict__ err_sums, uint32_t min_count, const uint32_t *tied,
                                         RansacBest *best, uint4 *__restrict__ order_u32, float *__restrict__ order_planes,
-                                        uint32_t slot_base = 0u)
+                                        uint32_t slot_base, const RoundRange &rr)
 {
     __shared__ double errs[1024];
     __shared__ uint32_t s_replaced;
     __shared__ double s_result;
-    __shared__ uint32_t s_close[64]; // candidates within the margin of the smallest parallel sum (slots; ~0u = the carried best)
+    __shared__ uint32_t s_close[66]; // candidates within the margin of the smallest parallel sum (slots; ~0u = the carried best): 63 + the carried best + the winner
     __shared__ uint32_t s_nclose, s_winner, s_exact;
     __shared__ double s_winner_err;
     const uint32_t n = tied[0], top = tied[1 + TIED_CAP];
-    if (n == 0u || n > TIED_CAP || top < min_count) return; // (more than TIED_CAP ties: never seen; the round is then skipped)
+    if (n == 0u || top < min_count) return;
+    const bool overflow = n > TIED_CAP; // more ties than the list holds: ransac_tied_overflow left everybody's ordered sum
     const bool errors = ransac_round_needs_errors(tied, best); // were this round's sums computed?
     const bool carried_ties = best->valid && top == best->matches_count;
     constexpr double MARGIN = 1e-10;
-    if (threadIdx.x == 0) {
-        // smallest parallel sum among the round's candidates (smaller slot first among equals)
+    // (e, h) before (be, bi): finite before not finite, the smaller error, the smaller slot among equal errors
+    const auto before = [](double e, uint32_t h, double be, uint32_t bi) {
+        const bool ef = fabs(e) < __builtin_inf(), bf = fabs(be) < __builtin_inf();
+        return bi == 0xFFFFFFFFu || (ef && !bf) || (ef == bf && (e < be || (e == be && h < bi)));
+    };
+    if (overflow) {
+        // the smallest ordered mean error among the hypotheses of the range at the maximum count
+        __shared__ uint32_t s_slot[1024];
         uint32_t bi = 0xFFFFFFFFu;
         double be = 0.0;
-        for (uint32_t k = 0; k < n; k++) {
-            const uint32_t h = tied[1 + k];
-            const double e = errors ? err_sums[h] / (double)top : 0.0;
-            const bool ef = fabs(e) < __builtin_inf(), bf = fabs(be) < __builtin_inf();
-            if (bi == 0xFFFFFFFFu || (ef && !bf) || (ef == bf && (e < be || (e == be && h < bi)))) {
+        const uint32_t j1 = min(*rr.n_live, rr.end);
+        for (uint32_t j = rr.first + threadIdx.x; j < j1; j += 1024u) {
+            const uint32_t h = rr.live[j];
+            if (rr.counts[h] != top) continue;
+            const double e = err_sums[h] / (double)top;
+            if (before(e, h, be, bi)) {
                 bi = h;
                 be = e;
             }
         }
-        s_winner = bi;
-        s_winner_err = be;
-        s_exact = 0u;
-        uint32_t nc = 0;
-        if (errors) {
-            // who else is within the margin of it - the other candidates of the round, and the carried best
-            const double lim = be + MARGIN * fabs(be);
-            for (uint32_t k = 0; k < n && nc < 63u; k++) {
-                const uint32_t h = tied[1 + k];
-                if (h != bi && err_sums[h] / (double)top <= lim) s_close[nc++] = h;
-            }
-            if (carried_ties && fabs(best->best_error - be) <= MARGIN * fmax(fabs(best->best_error), fabs(be)) && best->err_known != 2u)
-                s_close[nc++] = 0xFFFFFFFFu;
-            if (nc > 0) s_close[nc++] = bi; // the winner itself needs its ordered sum too
-        }
-        s_nclose = nc;
-    }
-    __syncthreads();
-    if (s_nclose > 0) { // (rare) the reference's ordered fold for everybody inside the margin
-        for (uint32_t k = 0; k < s_nclose; k++) {
-            const uint32_t h = s_close[k];
-            double f[9];
-#pragma unroll
-            for (int i = 0; i < 9; i++) f[i] = h == 0xFFFFFFFFu ? best->f[i] : F[(size_t)h * 9 + i];
-            const double sum = block_ordered_sum(f, matches, N, t, errs, &s_result);
-            if (threadIdx.x == 0) {
-                if (h == 0xFFFFFFFFu) {
-                    best->best_error = sum / (double)best->matches_count;
-                    best->err_known = 2u;
-                } else {
-                    err_sums[h] = sum;
+        errs[threadIdx.x] = be;
+        s_slot[threadIdx.x] = bi;
+        __syncthreads();
+        for (uint32_t st = 512; st > 0; st >>= 1) {
+            if (threadIdx.x < st) {
+                const uint32_t o = threadIdx.x + st;
+                if (s_slot[o] != 0xFFFFFFFFu && before(errs[o], s_slot[o], errs[threadIdx.x], s_slot[threadIdx.x])) {
+                    errs[threadIdx.x] = errs[o];
+                    s_slot[threadIdx.x] = s_slot[o];
                 }
             }
             __syncthreads();
         }
-        if (threadIdx.x == 0) { // the winner among them by the ordered sums
+        if (threadIdx.x == 0) {
+            s_winner = s_slot[0];
+            s_winner_err = errs[0];
+            s_exact = 1u;
+        }
+        __syncthreads();
+        if (s_winner == 0xFFFFFFFFu) return; // (cannot happen: somebody of the range has the maximum)
+    } else {
+        if (threadIdx.x == 0) {
+            // smallest parallel sum among the round's candidates (smaller slot first among equals)
             uint32_t bi = 0xFFFFFFFFu;
             double be = 0.0;
-            for (uint32_t k = 0; k < s_nclose; k++) {
-                const uint32_t h = s_close[k];
-                if (h == 0xFFFFFFFFu) continue;
-                const double e = err_sums[h] / (double)top;
-                if (bi == 0xFFFFFFFFu || e < be || (e == be && h < bi)) {
+            for (uint32_t k = 0; k < n; k++) {
+                const uint32_t h = tied[1 + k];
+                const double e = errors ? err_sums[h] / (double)top : 0.0;
+                if (before(e, h, be, bi)) {
                     bi = h;
                     be = e;
                 }
             }
             s_winner = bi;
             s_winner_err = be;
-            s_exact = 1u;
+            s_exact = 0u;
+            uint32_t nc = 0;
+            if (errors) {
+                // who else is within the margin of it - the other candidates of the round, and the carried best
+                const double lim = be + MARGIN * fabs(be);
+                for (uint32_t k = 0; k < n && nc < 63u; k++) {
+                    const uint32_t h = tied[1 + k];
+                    if (h != bi && err_sums[h] / (double)top <= lim) s_close[nc++] = h;
+                }
+                if (carried_ties && fabs(best->best_error - be) <= MARGIN * fmax(fabs(best->best_error), fabs(be)) && best->err_known != 2u)
+                    s_close[nc++] = 0xFFFFFFFFu;
+                if (nc > 0) s_close[nc++] = bi; // the winner itself needs its ordered sum too
+            }
+            s_nclose = nc;
         }
         __syncthreads();
+        if (s_nclose > 0) { // (rare) the reference's ordered fold for everybody inside the margin
+            for (uint32_t k = 0; k < s_nclose; k++) {
+                const uint32_t h = s_close[k];
+                double f[9];
+#pragma unroll
+                for (int i = 0; i < 9; i++) f[i] = h == 0xFFFFFFFFu ? best->f[i] : F[(size_t)h * 9 + i];
+                const double sum = block_ordered_sum(f, matches, N, t, errs, &s_result);
+                if (threadIdx.x == 0) {
+                    if (h == 0xFFFFFFFFu) {
+                        best->best_error = sum / (double)best->matches_count;
+                        best->err_known = 2u;
+                    } else {
+                        err_sums[h] = sum;
+                    }
+                }
+                __syncthreads();
+            }
+            if (threadIdx.x == 0) { // the winner among them by the ordered sums
+                uint32_t bi = 0xFFFFFFFFu;
+                double be = 0.0;
+                for (uint32_t k = 0; k < s_nclose; k++) {
+                    const uint32_t h = s_close[k];
+                    if (h == 0xFFFFFFFFu) continue;
+                    const double e = err_sums[h] / (double)top;
+                    if (bi == 0xFFFFFFFFu || e < be || (e == be && h < bi)) {
+                        bi = h;
+                        be = e;
+                    }
+                }
+                s_winner = bi;
+                s_winner_err = be;
+                s_exact = 1u;
+            }
+            __syncthreads();
+        }
     }
     if (threadIdx.x == 0) {
         const uint32_t w = s_winner;
@@ -1588,10 +1680,11 @@ __global__ __launch_bounds__(1024) void ransac_pick_best_approx_kernel(const dou
                                                                         double *__restrict__ err_sums, uint32_t min_count,
                                                                         const uint32_t *__restrict__ tied, RansacBest *best,
                                                                         uint4 *__restrict__ order_u32, float *__restrict__ order_planes,
-                                                                        uint32_t slot_base)
+                                                                        uint32_t slot_base, const uint32_t *__restrict__ live,
+                                                                        const uint32_t *__restrict__ n_live, uint32_t live_first, uint32_t live_end)
 {
-    (void)counts;
-    ransac_pick_best_approx(F, matches, N, t, err_sums, min_count, tied, best, order_u32, order_planes, slot_base);
+    const RoundRange rr = {counts, live, n_live, live_first, live_end};
+    ransac_pick_best_approx(F, matches, N, t, err_sums, min_count, tied, best, order_u32, order_planes, slot_base, rr);
 }
 
 // The device loops' round end in ONE launch behind the counting kernel: the round's maximum list from the counting
@@ -1611,18 +1704,18 @@ __device__ void ransac_round_tied_list(uint32_t *__restrict__ cand, uint32_t *ti
         for (uint32_t i = threadIdx.x; i < listed; i += blockDim.x)
             if (cand[3 + 2 * i] == top) s_slots[atomicAdd(&s_n, 1u)] = cand[2 + 2 * i];
     __syncthreads();
-    if (threadIdx.x == 0) {
-        uint32_t n = 0;
-        if (listed > TIED_CAP) {
-            n = TIED_CAP + 1u; // (never seen: more record holders than the list takes; the round is skipped, as above)
-        } else {
-            for (uint32_t i = 0; i < s_n; i++) { // insertion by slot
-                const uint32_t h = s_slots[i];
-                uint32_t at = n++;
-                for (; at > 0 && tied[at] > h; at--) tied[1 + at] = tied[at];
-                tied[1 + at] = h;
-            }
+    // more record holders than the list takes: tied[0] = TIED_CAP + 1, and the round is decided over the live list
+    // (ransac_tied_overflow); otherwise every slot goes to its rank (the slots are distinct)
+    const uint32_t n = listed > TIED_CAP ? TIED_CAP + 1u : s_n;
+    if (listed <= TIED_CAP)
+        for (uint32_t i = threadIdx.x; i < n; i += blockDim.x) {
+            const uint32_t h = s_slots[i];
+            uint32_t rank = 0;
+            for (uint32_t k = 0; k < n; k++) rank += s_slots[k] < h ? 1u : 0u;
+            tied[1 + rank] = h;
         }
+    __syncthreads();
+    if (threadIdx.x == 0) {
         tied[0] = n;
         tied[1 + TIED_CAP] = top;
         cand[0] = 0u;
@@ -1634,13 +1727,16 @@ __global__ __launch_bounds__(1024) void ransac_round_finish_kernel(const double 
                                                                     uint32_t min_count, uint32_t *__restrict__ cand,
                                                                     uint32_t *tied, RansacBest *best,
                                                                     uint4 *__restrict__ order_u32, float *__restrict__ order_planes,
-                                                                    uint32_t slot_base)
+                                                                    uint32_t slot_base, const uint32_t *__restrict__ counts,
+                                                                    const uint32_t *__restrict__ live, const uint32_t *__restrict__ n_live,
+                                                                    uint32_t live_first, uint32_t live_end)
 {
+    const RoundRange rr = {counts, live, n_live, live_first, live_end};
     ransac_round_tied_list(cand, tied);
     __syncthreads();
-    ransac_tied_approx(F, matches, N, t, tied, best, err_sums, 0u, 1u);
+    ransac_tied_approx(F, matches, N, t, tied, best, err_sums, 0u, 1u, rr);
     __syncthreads();
-    ransac_pick_best_approx(F, matches, N, t, err_sums, min_count, tied, best, order_u32, order_planes, slot_base);
+    ransac_pick_best_approx(F, matches, N, t, err_sums, min_count, tied, best, order_u32, order_planes, slot_base, rr);
 }
 // the same in three launches, for rounds with several hypotheses at the maximum count (a batch of rounds scored as one:
 // each costs ~10 us of one workgroup's time in the kernel above, ~100 us per batch): the list, the sums spread over
@@ -1712,7 +1808,8 @@ static void launch_ransac_score_round(const double *F, uint32_t H, const uint32_
     hipLaunchKernelGGL(ransac_round_max_kernel, dim3(1), dim3(1024), 0, s, (const uint32_t *)out_count, (const uint32_t *)live,
                        (const uint32_t *)n_live, min_count, tied);
     if (approx_sums) // the device loops: parallel sums now, the ordered fold inside ransac_pick_best_approx_kernel where it decides
-        hipLaunchKernelGGL(ransac_tied_approx_kernel, dim3(16), dim3(1024), 0, s, F, m4, N, t, (const uint32_t *)tied, best, out_err_sum);
+        hipLaunchKernelGGL(ransac_tied_approx_kernel, dim3(16), dim3(1024), 0, s, F, m4, N, t, (const uint32_t *)tied, best, out_err_sum,
+                           (const uint32_t *)out_count, (const uint32_t *)live, (const uint32_t *)n_live, live_first, live_end);
     else
         hipLaunchKernelGGL(ransac_tied_sum_kernel, dim3(16), dim3(1024), 0, s, F, m4, N, t, (const uint32_t *)tied,
                            (const uint32_t *)out_count, (const uint32_t *)live, (const uint32_t *)n_live, best, out_err_sum);
@@ -1726,7 +1823,8 @@ static void launch_ransac_score_round(const double *F, uint32_t H, const uint32_
 // sampling from the top 5000 matches, >= 10 px apart), calculate_model_affine (:260-286: mean-centred
 // 4x4, right-singular vector of the smallest singular value — here via Jacobi on A^T A), validate_f's
 // finiteness and sample-fit checks (:197-209).  The reference seeds its RNG from the OS and is not
-// reproducible run to run, so parity for this row is statistical (tests compare with the known model).
+// reproducible run to run, so parity WITH THE REFERENCE is statistical for this row (tests compare with the known model); the
+// loop itself is pinned, bit for bit, to a replay of the sampler below and of its other parts (tests/ransac_replay.py).
 // ---------------------------------------------------------------------------------------------
 __device__ __forceinline__ unsigned long long mix64(unsigned long long z)
 {
@@ -3124,7 +3222,8 @@ extern "C" int cvhip_ransac_rounds_pick(cvhip_device *dev, const double *F, uint
         launch_ransac_score_round(F_round, n, d_m, d_mo, d_mf, N, t, d_live, d_live + per, d_tied, d_coord_max, true, true, min_count, d_best,
                                   d_cnt, d_err, s, d_cand, 0u, 0xFFFFFFFFu, dev->d.ransac_count_mfma ? &ws : nullptr);
         hipLaunchKernelGGL(ransac_round_finish_kernel, dim3(1), dim3(1024), 0, s, F_round, m4, N, t, d_err, min_count, d_cand, d_tied, d_best,
-                           reinterpret_cast<uint4 *>(d_mo), reinterpret_cast<float *>(d_mf), first);
+                           reinterpret_cast<uint4 *>(d_mo), reinterpret_cast<float *>(d_mf), first, (const uint32_t *)d_cnt, (const uint32_t *)d_live,
+                           (const uint32_t *)(d_live + per), 0u, 0xFFFFFFFFu);
     }
     CVHIP_TRY_HIP(hipGetLastError());
     RansacBest h_best;
@@ -3213,7 +3312,7 @@ extern "C" int cvhip_ransac_affine(cvhip_device *dev, const uint32_t *matches, u
                                   d_cnt, d_err, s);
         hipLaunchKernelGGL(ransac_pick_best_approx_kernel, dim3(1), dim3(1024), 0, s, d_F, m4, N, RANSAC_T, (const uint32_t *)d_cnt, d_err,
                            RANSAC_D + RANSAC_N, (const uint32_t *)(d_live + CHECK_INTERVAL + 1), d_best, (uint4 *)nullptr, (float *)nullptr,
-                           round * CHECK_INTERVAL);
+                           round * CHECK_INTERVAL, (const uint32_t *)d_live, (const uint32_t *)(d_live + CHECK_INTERVAL), 0u, 0xFFFFFFFFu);
         e = hipGetLastError();
         if (e == hipSuccess) e = hipMemcpyAsync(&h_best, d_best, sizeof(RansacBest), hipMemcpyDeviceToHost, s);
         if (e == hipSuccess) e = hipStreamSynchronize(s);
@@ -3533,10 +3632,11 @@ int ransac_rounds(cvhip_device *dev, DevAllocs &mem, const uint32_t *matches, ui
                 launch_ransac_score_round(F_unit, HS, d_m, d_mo, d_mf, N, t, lv, lv + HS, d_tied, d_coord_max, true, true, min_count, d_best, d_cnt,
                                           d_err, s, d_cand, first, end, ws);
                 hipLaunchKernelGGL(ransac_round_tied_list_kernel, dim3(1), dim3(1024), 0, s, d_cand, d_tied);
-                hipLaunchKernelGGL(ransac_tied_approx_kernel, dim3(16), dim3(1024), 0, s, F_unit, m4, N, t, (const uint32_t *)d_tied, d_best, d_err);
-                hipLaunchKernelGGL(ransac_pick_best_approx_kernel, dim3(1), dim3(1024), 0, s, F_unit, m4, N, t, (const uint32_t *)nullptr, d_err,
+                hipLaunchKernelGGL(ransac_tied_approx_kernel, dim3(16), dim3(1024), 0, s, F_unit, m4, N, t, (const uint32_t *)d_tied, d_best, d_err,
+                                   (const uint32_t *)d_cnt, (const uint32_t *)lv, (const uint32_t *)(lv + HS), first, end);
+                hipLaunchKernelGGL(ransac_pick_best_approx_kernel, dim3(1), dim3(1024), 0, s, F_unit, m4, N, t, (const uint32_t *)d_cnt, d_err,
                                    min_count, (const uint32_t *)d_tied, d_best, reinterpret_cast<uint4 *>(d_mo), reinterpret_cast<float *>(d_mf),
-                                   r0 * H);
+                                   r0 * H, (const uint32_t *)lv, (const uint32_t *)(lv + HS), first, end);
                 e = hipGetLastError();
             }
             if (e == hipSuccess) e = hipEventRecord(scored[b], s);
@@ -3559,9 +3659,11 @@ int ransac_rounds(cvhip_device *dev, DevAllocs &mem, const uint32_t *matches, ui
             launch_ransac_score_round(late->F, late->cap, d_m, d_mo, d_mf, N, t, d_late_live, d_late_live + late->cap, d_tied, d_coord_max, true, true,
                                       min_count, d_best, d_cnt, d_err, s, d_cand, 0u, 0xFFFFFFFFu, ws);
             hipLaunchKernelGGL(ransac_round_tied_list_kernel, dim3(1), dim3(1024), 0, s, d_cand, d_tied);
-            hipLaunchKernelGGL(ransac_tied_approx_kernel, dim3(16), dim3(1024), 0, s, late->F, m4, N, t, (const uint32_t *)d_tied, d_best, d_err);
-            hipLaunchKernelGGL(ransac_pick_best_approx_kernel, dim3(1), dim3(1024), 0, s, late->F, m4, N, t, (const uint32_t *)nullptr, d_err, min_count,
-                               (const uint32_t *)d_tied, d_best, reinterpret_cast<uint4 *>(d_mo), reinterpret_cast<float *>(d_mf), rounds * H);
+            hipLaunchKernelGGL(ransac_tied_approx_kernel, dim3(16), dim3(1024), 0, s, late->F, m4, N, t, (const uint32_t *)d_tied, d_best, d_err,
+                               (const uint32_t *)d_cnt, (const uint32_t *)d_late_live, (const uint32_t *)(d_late_live + late->cap), 0u, 0xFFFFFFFFu);
+            hipLaunchKernelGGL(ransac_pick_best_approx_kernel, dim3(1), dim3(1024), 0, s, late->F, m4, N, t, (const uint32_t *)d_cnt, d_err, min_count,
+                               (const uint32_t *)d_tied, d_best, reinterpret_cast<uint4 *>(d_mo), reinterpret_cast<float *>(d_mf), rounds * H,
+                               (const uint32_t *)d_late_live, (const uint32_t *)(d_late_live + late->cap), 0u, 0xFFFFFFFFu);
             if (e == hipSuccess) e = hipGetLastError();
             if (e == hipSuccess) e = hipMemcpyAsync(&late_count, late->list, sizeof(uint32_t), hipMemcpyDeviceToHost, s);
         }
@@ -3600,13 +3702,15 @@ int ransac_rounds(cvhip_device *dev, DevAllocs &mem, const uint32_t *matches, ui
                                       s, d_cand, first, end, ws);
             if (score_batches) {
                 hipLaunchKernelGGL(ransac_round_tied_list_kernel, dim3(1), dim3(1024), 0, s, d_cand, d_tied);
-                hipLaunchKernelGGL(ransac_tied_approx_kernel, dim3(16), dim3(1024), 0, s, F_round, m4, N, t, (const uint32_t *)d_tied, d_best, d_err);
-                hipLaunchKernelGGL(ransac_pick_best_approx_kernel, dim3(1), dim3(1024), 0, s, F_round, m4, N, t, (const uint32_t *)nullptr, d_err,
+                hipLaunchKernelGGL(ransac_tied_approx_kernel, dim3(16), dim3(1024), 0, s, F_round, m4, N, t, (const uint32_t *)d_tied, d_best, d_err,
+                                   (const uint32_t *)d_cnt, (const uint32_t *)lv, (const uint32_t *)(lv + HS), first, end);
+                hipLaunchKernelGGL(ransac_pick_best_approx_kernel, dim3(1), dim3(1024), 0, s, F_round, m4, N, t, (const uint32_t *)d_cnt, d_err,
                                    min_count, (const uint32_t *)d_tied, d_best, reinterpret_cast<uint4 *>(d_mo), reinterpret_cast<float *>(d_mf),
-                                   round * H);
+                                   round * H, (const uint32_t *)lv, (const uint32_t *)(lv + HS), first, end);
             } else {
                 hipLaunchKernelGGL(ransac_round_finish_kernel, dim3(1), dim3(1024), 0, s, F_round, m4, N, t, d_err, min_count, d_cand, d_tied, d_best,
-                                   reinterpret_cast<uint4 *>(d_mo), reinterpret_cast<float *>(d_mf), round * H);
+                                   reinterpret_cast<uint4 *>(d_mo), reinterpret_cast<float *>(d_mf), round * H, (const uint32_t *)d_cnt,
+                                   (const uint32_t *)lv, (const uint32_t *)(lv + HS), first, end);
             }
         }
         if (e == hipSuccess) e = hipGetLastError();

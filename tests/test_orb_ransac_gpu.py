@@ -550,6 +550,107 @@ def test_device_rounds_pick_ord_maximum(gpu_device, rounds):
     assert fundamentalmatrix.ransac_rounds_pick(gpu_device, F, rounds, m, t, len(m) + 1)[0] == -1
 
 
+_MASS_TIE_SETS = []
+
+
+def _mass_tie_sets(gpu_device):
+    """-> (matches, t, hypothesis sets): rounds in which far more hypotheses share the maximal count than the round's
+    list of them holds, and a cluster of near-equal ones that only the reference's ordered sums can order.  (Built once.)"""
+    import cases
+
+    if _MASS_TIE_SETS:
+        return _MASS_TIE_SETS[0]
+    m, truth, _, _ = cases.perspective_matches(n=3000, outlier_frac=0.3, seed=19)
+    t = fundamentalmatrix.RANSAC_T_PERSPECTIVE * 2048.0
+    F0, _ = fundamentalmatrix.find_ransac_perspective_device(gpu_device, m, 2048.0, seed=4, rounds=1, refit=False)
+    rng = np.random.default_rng(77)
+    # (b) 200 matrices F0 (1 + 1e-13 xi), F22 = 1: equal counts, mean errors that agree to nine or ten digits (the epipolar
+    # residual is a difference of large terms: it moves by 1e3 .. 1e4 times as much as F) - around the 1e-10 margin below
+    # which parallel sums decide nothing; (c) the same a few ulps apart (2e-16 xi): all of them well inside that margin
+    family = F0.reshape(1, 9) * (1.0 + 1e-13 * rng.standard_normal((200, 9)))
+    family /= family[:, 8:9]
+    ulps = F0.reshape(1, 9) * (1.0 + 2e-16 * rng.standard_normal((400, 9)))
+    ulps /= ulps[:, 8:9]
+    ulps = np.unique(ulps, axis=0)
+    ulps = ulps[rng.permutation(len(ulps))][:200]
+    floor = int(fundamentalmatrix.ransac_score(gpu_device, np.concatenate([family, ulps, F0.reshape(1, 9)]), m, t)[0].min())
+    # the usual perturbed ones - those that stay below the best matrix and its family
+    pert = F0.reshape(1, 9) * (1.0 + 10.0 ** rng.uniform(-5, -1, size=(3000, 1)) * rng.standard_normal((3000, 9)))
+    pert[:, 8] = 1.0
+    pert = pert[fundamentalmatrix.ransac_score(gpu_device, pert, m, t)[0] < floor][:600]
+    assert len(pert) == 600
+    # (a) 5 000 exact copies of the best matrix among them
+    copies = np.concatenate([pert, np.repeat(F0.reshape(1, 9), 5000, axis=0)])
+    copies = copies[rng.permutation(len(copies))]
+    close = np.concatenate([pert[:300], family])
+    close = close[rng.permutation(len(close))]
+    closest = np.concatenate([pert[:300], ulps])
+    closest = closest[rng.permutation(len(closest))]
+    _MASS_TIE_SETS.append((m, t, {"copies": copies, "close": close, "closest": closest}))
+    return _MASS_TIE_SETS[0]
+
+
+def _ord_maximum(gpu_device, F, m, t, min_count):
+    """Ord's maximum (fundamentalmatrix.rs:623-649) over the exact fold of every hypothesis, first of equals by index."""
+    cnt, err = fundamentalmatrix.ransac_score(gpu_device, F, m, t)
+    cnt = cnt.astype(np.int64)
+    best = -1
+    for h in np.flatnonzero(cnt >= min_count):
+        if best < 0 or cnt[h] > cnt[best] or (cnt[h] == cnt[best] and err[h] / cnt[h] < err[best] / cnt[best]):
+            best = int(h)
+    return best, cnt, err
+
+
+@pytest.mark.parametrize("mfma", [False, True])
+@pytest.mark.parametrize("rounds", [1, 3])
+@pytest.mark.parametrize("which", ["copies", "close", "closest"])
+def test_device_rounds_pick_mass_ties(gpu_device, which, rounds, mfma):
+    """cvhip_ransac_rounds_pick where a round is NOT generic: (copies) 5 000 hypotheses at the maximal count - more than
+    the round's list of them (TIED_CAP = 4096) holds: the first copy by index wins, the round is not skipped; (close)
+    200 near-equal hypotheses of the top count whose mean errors differ in the tenth digit or so, (closest) 200 a few ulps
+    apart, more than 63 of them inside the 1e-10 margin of the parallel sums: the one with the smallest ORDERED mean error
+    (cvhip_ransac_score's) wins, although only 63 candidates inside the margin get the ordered fold."""
+    m, t, sets = _mass_tie_sets(gpu_device)
+    F = sets[which]
+    best, cnt, err = _ord_maximum(gpu_device, F, m, t, 207)
+    top = np.flatnonzero(cnt == cnt[best])
+    print(f"{which}: {len(top)} hypotheses at the top count {cnt[best]}, "
+          f"{(np.abs(err[top] / cnt[best] - err[best] / cnt[best]) <= 1e-10 * err[best] / cnt[best]).sum()} within 1e-10 of the best")
+    near = (np.abs(err[top] / cnt[best] - err[best] / cnt[best]) <= 1e-10 * err[best] / cnt[best]).sum()
+    assert len(top) >= {"copies": 5000, "close": 100, "closest": 100}[which]
+    assert which != "closest" or near > 63  # (63: the candidates that used to get the ordered fold)
+    fundamentalmatrix.set_count_mfma(gpu_device, mfma)
+    try:
+        got_idx, got_F, got_cnt, got_err = fundamentalmatrix.ransac_rounds_pick(gpu_device, F, rounds, m, t, 207)
+    finally:
+        fundamentalmatrix.set_count_mfma(gpu_device, False)
+    assert got_idx >= 0, "the round was skipped"
+    assert got_cnt == cnt[best]
+    assert (got_F.reshape(9) == F[best]).all(), (got_idx, best, err[got_idx] / cnt[got_idx], err[best] / cnt[best])
+    assert got_idx == int(np.flatnonzero((F == F[best]).all(axis=1))[0])
+    assert abs(got_err - err[best] / cnt[best]) <= 1e-9 * abs(err[best] / cnt[best])
+
+
+@pytest.mark.parametrize("mfma", [False, True])
+def test_round_score_mass_ties(gpu_device, mfma):
+    """cvhip_ransac_round_score with more hypotheses tied at the maximum than the list holds: every one of them still gets
+    its ordered sum, cvhip_ransac_score's bits."""
+    m, t, sets = _mass_tie_sets(gpu_device)
+    for which in ("copies", "close", "closest"):
+        F = sets[which]
+        want_c, want_e = fundamentalmatrix.ransac_score(gpu_device, F, m, t)
+        fundamentalmatrix.set_count_mfma(gpu_device, mfma)
+        try:
+            got_c, got_e = fundamentalmatrix.ransac_round_score(gpu_device, F, m, t)
+        finally:
+            fundamentalmatrix.set_count_mfma(gpu_device, False)
+        assert (got_c == want_c).all()
+        tied = want_c == want_c.max()
+        assert tied.sum() >= (5000 if which == "copies" else 64)
+        assert (got_e[tied].view(np.uint64) == want_e[tied].view(np.uint64)).all()
+        assert (got_e[~tied] == 0.0).all()
+
+
 def test_device_refit_equals_host_refit_bit_for_bit(gpu_device, oracle):
     """cvhip_optimize_perspective_f_device (one workgroup, eight threads per long dot product) against
     cvhip_optimize_perspective_f (one host thread) and the oracle: same loop, same accumulation order -> same bits.
