@@ -252,6 +252,18 @@ class PointCorrelations:
         _lib.check(_lib.lib().cvhip_ctx_get_box_counters(self._h, arr, int(reset)), "cvhip_ctx_get_box_counters")
         return {"waves65_rowmajor": arr[0], "waves65_transposed": arr[1], "max_steps": arr[2]}
 
+    def set_box_fold(self, on: bool):
+        """cvhip_ctx_set_box_fold: the lean box walk folds the two ends of a wave's union of displacement ranges into
+        shared steps (default on; results are identical either way)."""
+        _lib.check(_lib.lib().cvhip_ctx_set_box_fold(self._h, int(on)), "cvhip_ctx_set_box_fold")
+
+    def get_box_fold_counters(self, reset: bool = True):
+        """cvhip_ctx_get_box_fold_counters: steps of the lean waves' unions, steps walked after folding, pairs folded
+        ascending / descending (needs set_profiling(_, True))."""
+        arr = (C.c_uint64 * 4)()
+        _lib.check(_lib.lib().cvhip_ctx_get_box_fold_counters(self._h, arr, int(reset)), "cvhip_ctx_get_box_fold_counters")
+        return {"union_steps": arr[0], "folded_steps": arr[1], "pairs_ascending": arr[2], "pairs_descending": arr[3]}
+
     def set_borrow_inputs(self, borrow: bool):
         """Device-resident level images are used in place (no copy): the caller guarantees 64 readable bytes after
         the last pixel of each and keeps them unchanged until the call's work has completed (include/cvhip.h)."""

@@ -4,6 +4,235 @@
 // instead cost the stepped instantiations 22 more spilled VGPRs.  In scope at the point of inclusion: template
 // parameters COUNT, STEP, TR, WIDE and the names p, img1, img2, stats1, istats1, istats2, range, contenders, out, counters,
 // out_score, declined, whole_list.
+// This file has two sections.  With BOX_STEP_SECTION defined it is ONE STEP OF THE WALK, which the kernels' body below includes
+// into each of its loops: the stepped plans' one loop, and the lean plan's two - the steps nobody folded, where `step` is
+// wave-uniform (scalar addresses, a scalar record code), and the folded pairs, where it is the lane's own.  (As a lambda called
+// from the three places the step cost the stepped instantiations 300 bytes of scratch; in a file of its own it would escape the
+// hash of the kernels' sources that the committed counter profiles carry.)  In scope there: everything the body has set up before
+// its walk, and `step`.
+#ifdef BOX_STEP_SECTION
+            const int dx = mnx + step; // displacement along the lanes (x; y when TR)
+            const bool mx = has && (uint32_t)(dx - lou) < wu;
+            // first plane offset of this lane's candidates at this step, and the planes the wave needs for it
+            int bl = lov, s0 = ws0, n = wn;
+            if (wave_step) {
+                if (!__builtin_amdgcn_ballot_w64(mx)) continue; // nobody searches this step
+                // the wave's window at this step, from the table settled in setup (lane `step` holds it; step 64: step_last)
+                const uint32_t tw = step < STEP_TABLE ? (uint32_t)__builtin_amdgcn_readlane((int)step_tbl, step) : step_last;
+                s0 = ws0 + (int)(tw & 0xFFFFu);
+                n = (int)(tw >> 16);
+                if (COUNT && stepped && mx) {
+                    // (the candidate counter tests every plane's membership - and, while it is at it, that the table's window
+                    // holds this lane's stripes: a bracket that missed would show up as a wildly wrong candidate count)
+                    bl = step_first_plane(dx);
+                    if (bl < dy0 + s0 || bl + WV > dy0 + s0 + n) bracket_missed = true;
+                }
+            }
+            uint32_t raw[NDW];
+            const uint8_t *pIS = bIS + step * 8;
+            int dyb = dy0; // displacement (across the planes) of plane index 0 of this step's groups
+            int first = 0; // plane index of the wave's first plane at this step
+            if constexpr (STEP) {
+                // the tall copy: 24 bytes from the dword that holds this wave's first row at this step; the planes then
+                // start at byte `first` = 0..3 of it, and the statistics rows / displacements are counted from there
+                const int off = (int)w + s0;
+                first = off & 3;
+                const uint32_t *pc = bCOL + step * (int)PD + (off >> 2);
+#pragma unroll
+                for (int k = 0; k < NDW; k++) raw[k] = pc[k];
+                pIS += (s0 - first) * (ISP * 8);
+                dyb = dy0 + s0 - first;
+            } else {
+                const uint4 r4 = *reinterpret_cast<const uint4 *>(bB16 + step * 16);
+                raw[0] = r4.x;
+                raw[1] = r4.y;
+                raw[2] = r4.z;
+                raw[3] = r4.w;
+                raw[4] = *reinterpret_cast<const uint32_t *>(bB4 + step * TAIL_BYTES);
+            }
+            // one group of planes: s = S0 .. S0 + N - 1 (dy = dyb + s), all independent until the rare branch
+            auto group = [&](auto s0_tag, auto n_tag) {
+                constexpr int S0 = decltype(s0_tag)::value, N = decltype(n_tag)::value;
+                int num[N];
+                float rs[N]; // lean plan: 1 / stdev of the plane's candidate (0: none); stepped plan: the stdev (+inf: none)
+#pragma unroll
+                for (int q = 0; q < N; q++) {
+                    const int s = S0 + q, sh = s & 3, o = s >> 2;
+                    const uint2 is2 = *reinterpret_cast<const uint2 *>(pIS + s * (ISP * 8));
+                    uint32_t c = __builtin_amdgcn_udot4(a[sh][0], raw[o], 0u, false);
+                    c = __builtin_amdgcn_udot4(a[sh][1], raw[o + 1], c, false);
+                    c = __builtin_amdgcn_udot4(a[sh][2], raw[o + 2], c, false);
+                    if (sh >= 2) c = __builtin_amdgcn_udot4(a[sh][3], raw[o + 3 < NDW ? o + 3 : NDW - 1], c, false);
+                    const uint32_t pre = wave_prefix_sum(c);
+                    const uint32_t s12 = pre - (uint32_t)__builtin_amdgcn_ds_bpermute(idx_lo, (int)pre);
+                    num[q] = __mul24((int)s12, KERNEL_POINT_COUNT) + __mul24((int)s1, (int)is2.x);
+                    rs[q] = __uint_as_float(is2.y);
+                }
+                // one branch for the group: the largest margin decides - lean plan fl(x - T) against -2 D, stepped plan
+                // (float)N - limk sd2 against 0 (see record()); a hit is re-tested below against the state of that moment.
+                float mg[N];
+#pragma unroll
+                for (int q = 0; q < N; q++) mg[q] = RS ? __builtin_fmaf((float)num[q], rs[q], -T) : __builtin_fmaf(-limk, rs[q], (float)num[q]);
+                float margin = mg[0];
+#pragma unroll
+                for (int q = 1; q < N; q++) margin = fmaxf(margin, mg[q]);
+                const float mlo = RS ? M : 0.0f;
+                if (COUNT) {
+#pragma unroll
+                    for (int q = 0; q < N; q++)
+                        if (mx && (uint32_t)(dyb + S0 + q - bl) < wv && (RS ? rs[q] > 0.0f : rs[q] < __builtin_inff())) evaluated++;
+                }
+                if (margin >= mlo && !(dbg & 64)) {
+                    // (stepped lines: the lane's own first plane at this step, needed only here)
+                    // (behind an opaque copy of dx: the compiler otherwise evaluates the six f64 operations ahead of the branch,
+                    // in every step)
+                    // Where the table's window is exactly one pixel's stripes (n == WV) every searching lane's first plane IS the
+                    // window's - the bracket holds them all - and nothing is evaluated: the rule for parallel lines, except where
+                    // they pass a row.
+                    if (STEP && !COUNT && wave_step && stepped && mx) {
+                        bl = dy0 + s0;
+                        if (n != WV) {
+                            int dxl = dx;
+                            asm volatile("" : "+s"(dxl));
+                            bl = step_first_plane(dxl);
+                        }
+                    }
+                    if (STEP && LOOSE_OK && wave_loose) {
+                        // A wave with loose lanes (rare: lines within an ulp below a row 2^k): one plane at a time, in a loop
+                        // - this path exists once per group, not once per plane, and the usual one below stays as it was.
+                        // For a loose lane the reference's own expression (mod.rs:424-429) says which stripe lies on the
+                        // plane's row at this step; none: the row its stripes skip here.
+#pragma nounroll
+                        for (int j = 0; j < N; j++) {
+                            float rsj = rs[0];
+                            int numj = num[0];
+#pragma unroll
+                            for (int q = 1; q < N; q++) {
+                                rsj = j == q ? rs[q] : rsj;
+                                numj = j == q ? num[q] : numj;
+                            }
+                            const int dy = dyb + S0 + j;
+                            if (mx && (uint32_t)(dy - bl) < wv && rsj < __builtin_inff() && (float)numj >= limk * rsj) { // (stepped plan: rs IS the stdev)
+                                uint32_t stripe = (uint32_t)(dy - bl);
+                                if (wv == (uint32_t)WV + 1u) { // (a loose lane: six planes)
+                                    stripe = 0xFFFFFFFFu;
+                                    const uint32_t ci = (uint32_t)((TR ? (int)y : xi) + dx), crow = (uint32_t)((TR ? xi : (int)y) + dy);
+                                    for (int off = cs; off >= -cs; off--) {
+                                        const CandXY co = candidate_xy(e, ci, off);
+                                        if ((TR ? co.x : co.y) == crow) stripe = (uint32_t)(off + cs);
+                                    }
+                                }
+                                const int dmaj = (TR ? (int)y : xi) + dx - (int)r0; // position along the line (stepped lanes: major_x != TR)
+                                const float rr = __builtin_amdgcn_rcpf(rsj);
+                                if (stripe != 0xFFFFFFFFu)
+                                    record(__builtin_fmaf((float)numj, rr, -T) > 0.0f, __builtin_fmaf((float)numj, rr, D), (stripe << 11) | (uint32_t)dmaj);
+                            }
+                        }
+                        return;
+                    }
+                    // Planes from the middle of the group outwards: every record raises the bound, and the stripe through
+                    // the predicted position is where the best match usually is - once it is in, its neighbours
+                    // (typically 0.6 .. 0.9 against ~1) fail the re-test and their record bodies are skipped.  The
+                    // order is free: the contender list is unordered and re-evaluated exactly.
+#pragma unroll
+                    for (int qi = 0; qi < N; qi++) {
+                        const int q = (N - 1) / 2 + ((qi & 1) ? (qi + 1) / 2 : -(qi / 2)); // m, m+1, m-1, m+2, ...
+                        const int dy = dyb + S0 + q; // displacement across the planes (y; x when TR)
+                        // (the plane's own pre-screen margin first - one compare; it was taken with a T that has only risen
+                        // since, so nothing that passes the test below is missed.  Lean plan: the first plane's margin IS the
+                        // test - nothing was recorded since.)
+                        const float mgc = qi == 0 ? mg[q] : __builtin_fmaf((float)num[q], rs[q], -T); // (lean plan)
+                        if (mg[q] >= mlo && mx && (uint32_t)(dy - bl) < wv &&
+                            (RS ? mgc >= M : (rs[q] < __builtin_inff() && (float)num[q] >= limk * rs[q]))) {
+                            if (RS) {
+                                record(mgc > 0.0f, __builtin_fmaf((float)num[q], rs[q], D), ((uint32_t)(S0 + q) << 7) | (uint32_t)step);
+                            } else {
+                                // back to image axes: candidate (x + ddx, y + ddy), stripe origin (ox, oy)
+                                const int ddx = TR ? dy : dx, ddy = TR ? dx : dy, ox = TR ? bl : lox, oy = TR ? loy : bl;
+                                const uint32_t code = major_x ? ((uint32_t)(ddy - oy) << 11) | (uint32_t)(xi + ddx - (int)r0)
+                                                              : ((uint32_t)(ddx - ox) << 11) | (uint32_t)((int)y + ddy - (int)r0);
+                                const float rr = __builtin_amdgcn_rcpf(rs[q]);
+                                record(__builtin_fmaf((float)num[q], rr, -T) > 0.0f, __builtin_fmaf((float)num[q], rr, D), code);
+                            }
+                        }
+                    }
+                }
+            };
+            using I0 = std::integral_constant<int, 0>;
+            using I1 = std::integral_constant<int, 1>;
+            using I2 = std::integral_constant<int, 2>;
+            using I3 = std::integral_constant<int, 3>;
+            using I4 = std::integral_constant<int, 4>;
+            using I5 = std::integral_constant<int, 5>;
+            if (!STEP) { // rectangles only: the workgroup's planes 0..4, and 5..8 when its box is taller
+                group(I0{}, I5{});
+                if (NPL > 5) group(I5{}, I4{});
+                continue;
+            }
+            if constexpr (STEP) {
+                using I6 = std::integral_constant<int, 6>;
+                using I7 = std::integral_constant<int, 7>;
+                using I8 = std::integral_constant<int, 8>;
+                using I9 = std::integral_constant<int, 9>;
+                using I10 = std::integral_constant<int, 10>;
+                using I11 = std::integral_constant<int, 11>;
+                using I12 = std::integral_constant<int, 12>;
+                using I13 = std::integral_constant<int, 13>;
+                // planes are register-indexed, so the window position selects an instantiation: five planes from
+                // `first` in one interleaved group (n >= 5: every pixel has at least five stripes), ...
+                if (n == 6) { // (one row straddled inside a five-stripe window: six interleaved planes, not five and one alone)
+                    switch (first) {
+                    case 0: group(I0{}, I6{}); break;
+                    case 1: group(I1{}, I6{}); break;
+                    case 2: group(I2{}, I6{}); break;
+                    default: group(I3{}, I6{}); break;
+                    }
+                    continue;
+                }
+                switch (first) {
+                case 0: group(I0{}, I5{}); break;
+                case 1: group(I1{}, I5{}); break;
+                case 2: group(I2{}, I5{}); break;
+                default: group(I3{}, I5{}); break;
+                }
+                // ... then one more interleaved group where three or more remain (nine stripes), the rest singly
+                // (five stripes whose lines step inside the box).  first + n <= 3 + S3_MAXH = 14 planes in 24 bytes.
+                int sx = first + 5, left = n - 5;
+                if (left >= 5) {
+                    switch (sx) {
+                    case 5: group(I5{}, I5{}); break;
+                    case 6: group(I6{}, I5{}); break;
+                    case 7: group(I7{}, I5{}); break;
+                    default: group(I8{}, I5{}); break;
+                    }
+                    sx += 5;
+                    left -= 5;
+                } else if (left >= 3) {
+                    const bool four = left == 4;
+                    switch (sx) {
+                    case 5: four ? group(I5{}, I4{}) : group(I5{}, I3{}); break;
+                    case 6: four ? group(I6{}, I4{}) : group(I6{}, I3{}); break;
+                    case 7: four ? group(I7{}, I4{}) : group(I7{}, I3{}); break;
+                    default: four ? group(I8{}, I4{}) : group(I8{}, I3{}); break;
+                    }
+                    sx += four ? 4 : 3;
+                    left = 0;
+                }
+                for (; left > 0; left--, sx++) {
+                    switch (sx) {
+                    case 5: group(I5{}, I1{}); break;
+                    case 6: group(I6{}, I1{}); break;
+                    case 7: group(I7{}, I1{}); break;
+                    case 8: group(I8{}, I1{}); break;
+                    case 9: group(I9{}, I1{}); break;
+                    case 10: group(I10{}, I1{}); break;
+                    case 11: group(I11{}, I1{}); break;
+                    case 12: group(I12{}, I1{}); break;
+                    default: group(I13{}, I1{}); break;
+                    }
+                }
+            }
+#else // ---- the kernels' body ----------------------------------------------------------------------------------------
     // (CorrParams::debug switches parts of the kernel off for the ablation scripts; only -DCVHIP_ABLATIONS builds ever set it,
     // and only they pay for looking at it - in the walk that was a scalar load and a test per step)
 #ifdef CVHIP_ABLATIONS
@@ -202,6 +431,33 @@
     const bool wave_odd = __any(active && !(simple || stepped));
     const bool wave_step = STEP && __any(has && stepped);
     const int wave_loose = STEP && LOOSE_OK && __any(has && loose) ? 1 : 0;
+    // Lean plan: fold the two ends of the wave's union (DESIGN 4.2).  The wave walks n = mxx - mnx + 1 steps, the union of
+    // its lanes' intervals [lo, hi]; where the intervals drift along the wave, the first steps are searched only at one end
+    // of it and the last steps only at the other.  Low step k and high step n - K + k (k = 0 .. K-1) then run as ONE step,
+    // every lane at the one of the two that its side of a seam takes - valid when each lane that searches one of them has its
+    // 11 window columns (lanes l-10 .. l) on its own side: S12 = P(l) - P(l-11) only sums those.  Ascending (low steps at low
+    // lanes): the pair breaks iff some lane a with lo_a <= k and some lane b <= a + 10 with hi_b >= n - K + k exist; with
+    // Mh(a) = max hi over the lanes up to a + 10 lane a forbids exactly the K >= n + lo_a - Mh(a), so the largest K is the
+    // wave's minimum of that, less one (and at most n / 2).  A lane takes the high step of pair k iff Mh(l) >= n - K + k: true
+    // for a lane that searches it and for its ten lower neighbours, false for every lane up to one that searches step k.
+    // Descending (low steps at high lanes): with ml(b) = min lo over the lanes up to b + 10, lane b forbids
+    // K >= n + ml(b) - hi_b, and a lane takes the high step iff ml(l) > k.  One rule for the walk: fold_sel >= fold_base + k.
+    [[maybe_unused]] int fold_k = 0, fold_base = 0, fold_sel = 0;
+    [[maybe_unused]] bool fold_desc = false;
+    if constexpr (!STEP) {
+        if (p.box_fold && wave_has) {
+            const int n = mxx - mnx + 1, lo = lou - mnx, hi = lo + (int)wu - 1;
+            const int hpre = -wave_prefix_min_i32(has ? -hi : 1), lpre = wave_prefix_min_i32(has ? lo : 0x3FFFFFFF);
+            const int up10 = (int)min(lane + 10u, 63u) * 4;
+            const int mh = __builtin_amdgcn_ds_bpermute(up10, hpre), ml = __builtin_amdgcn_ds_bpermute(up10, lpre);
+            const int ka = min(wave_min_i32(has ? n + lo - mh : 0x7FFFFFFF) - 1, n >> 1);
+            const int kd = min(wave_min_i32(has ? n + ml - hi : 0x7FFFFFFF) - 1, n >> 1);
+            fold_desc = kd > ka;
+            fold_k = fold_desc ? kd : ka;
+            fold_sel = fold_desc ? ml : mh;
+            fold_base = fold_desc ? 1 : n - fold_k;
+        }
+    }
     // Stepped boxes: the wave's plane window at EVERY step, settled here, before the walk - lane t holds step t's.  A
     // lane's first plane at step t (displacement mnx + t) is floor(v(t)) - cs - v0 with v(t) the reference's own f64
     // evaluation of ITS line (mod.rs:424-429); in real arithmetic that line is g(t) = a + c t (a: its position relative to
@@ -325,6 +581,15 @@
             const int nst = mxx - mnx + 1;
             if (nst == STEP_TABLE + 1) atomicAdd(&counters[TR ? 5 : 4], 1ull);
             atomicMax(&counters[6], (unsigned long long)nst);
+        }
+    }
+    if constexpr (COUNT && !STEP) {
+        // diagnostics (cvhip_ctx_get_box_fold_counters; counters 8..11): the steps of the waves' unions, the steps they walk
+        // after folding, and the pairs folded in either orientation
+        if (counters && lane == 0 && wave_has) {
+            atomicAdd(&counters[8], (unsigned long long)(mxx - mnx + 1));
+            atomicAdd(&counters[9], (unsigned long long)(mxx - mnx + 1 - fold_k));
+            if (fold_k) atomicAdd(&counters[fold_desc ? 11 : 10], (unsigned long long)fold_k);
         }
     }
     const int NPL = H > 9 ? S3_MAXH : (H > 5 ? 9 : 5); // planes staged (lean: group A = 0..4, group B = 5..8)
@@ -639,231 +904,28 @@
         // its start.  The ranges are centred on the positions predicted by the previous level, so the best matches
         // sit around the middle and are met first; the near-misses next to them (which pass the initial threshold
         // and would each cost a trip through the hit branch) then come after the bound has risen.  Any order is exact.
-        const int mid = nsteps >> 1;
-        for (int t = 0; t < nsteps; t++) {
-            const int step = t < nsteps - mid ? mid + t : nsteps - 1 - t;
-            const int dx = mnx + step; // displacement along the lanes (x; y when TR)
-            const bool mx = has && (uint32_t)(dx - lou) < wu;
-            // first plane offset of this lane's candidates at this step, and the planes the wave needs for it
-            int bl = lov, s0 = ws0, n = wn;
-            if (wave_step) {
-                if (!__builtin_amdgcn_ballot_w64(mx)) continue; // nobody searches this step
-                // the wave's window at this step, from the table settled in setup (lane `step` holds it; step 64: step_last)
-                const uint32_t tw = step < STEP_TABLE ? (uint32_t)__builtin_amdgcn_readlane((int)step_tbl, step) : step_last;
-                s0 = ws0 + (int)(tw & 0xFFFFu);
-                n = (int)(tw >> 16);
-                if (COUNT && stepped && mx) {
-                    // (the candidate counter tests every plane's membership - and, while it is at it, that the table's window
-                    // holds this lane's stripes: a bracket that missed would show up as a wildly wrong candidate count)
-                    bl = step_first_plane(dx);
-                    if (bl < dy0 + s0 || bl + WV > dy0 + s0 + n) bracket_missed = true;
-                }
+        // Lean plan: that is the order of the steps [K, n - K) nobody folded; the K folded pairs - the ends of the range - come
+        // after them, pair K-1 first, and there `step` is the lane's own: the low or the high step of the pair (setup).  The
+        // step's body is the BOX_STEP_SECTION at the top of this file, included once per loop.
+        const int nmid = nsteps - 2 * fold_k, nwalk = nsteps - fold_k;
+        const int mid = nmid >> 1;
+#define BOX_STEP_SECTION
+        if constexpr (STEP) {
+            for (int t = 0; t < nsteps; t++) {
+                const int step = t < nsteps - mid ? mid + t : nsteps - 1 - t;
+#include "box_body.inc"
             }
-            uint32_t raw[NDW];
-            const uint8_t *pIS = bIS + step * 8;
-            int dyb = dy0; // displacement (across the planes) of plane index 0 of this step's groups
-            int first = 0; // plane index of the wave's first plane at this step
-            if constexpr (STEP) {
-                // the tall copy: 24 bytes from the dword that holds this wave's first row at this step; the planes then
-                // start at byte `first` = 0..3 of it, and the statistics rows / displacements are counted from there
-                const int off = (int)w + s0;
-                first = off & 3;
-                const uint32_t *pc = bCOL + step * (int)PD + (off >> 2);
-#pragma unroll
-                for (int k = 0; k < NDW; k++) raw[k] = pc[k];
-                pIS += (s0 - first) * (ISP * 8);
-                dyb = dy0 + s0 - first;
-            } else {
-                const uint4 r4 = *reinterpret_cast<const uint4 *>(bB16 + step * 16);
-                raw[0] = r4.x;
-                raw[1] = r4.y;
-                raw[2] = r4.z;
-                raw[3] = r4.w;
-                raw[4] = *reinterpret_cast<const uint32_t *>(bB4 + step * TAIL_BYTES);
+        } else {
+            for (int t = 0; t < nmid; t++) {
+                const int step = fold_k + (t < nmid - mid ? mid + t : nmid - 1 - t);
+#include "box_body.inc"
             }
-            // one group of planes: s = S0 .. S0 + N - 1 (dy = dyb + s), all independent until the rare branch
-            auto group = [&](auto s0_tag, auto n_tag) {
-                constexpr int S0 = decltype(s0_tag)::value, N = decltype(n_tag)::value;
-                int num[N];
-                float rs[N]; // lean plan: 1 / stdev of the plane's candidate (0: none); stepped plan: the stdev (+inf: none)
-#pragma unroll
-                for (int q = 0; q < N; q++) {
-                    const int s = S0 + q, sh = s & 3, o = s >> 2;
-                    const uint2 is2 = *reinterpret_cast<const uint2 *>(pIS + s * (ISP * 8));
-                    uint32_t c = __builtin_amdgcn_udot4(a[sh][0], raw[o], 0u, false);
-                    c = __builtin_amdgcn_udot4(a[sh][1], raw[o + 1], c, false);
-                    c = __builtin_amdgcn_udot4(a[sh][2], raw[o + 2], c, false);
-                    if (sh >= 2) c = __builtin_amdgcn_udot4(a[sh][3], raw[o + 3 < NDW ? o + 3 : NDW - 1], c, false);
-                    const uint32_t pre = wave_prefix_sum(c);
-                    const uint32_t s12 = pre - (uint32_t)__builtin_amdgcn_ds_bpermute(idx_lo, (int)pre);
-                    num[q] = __mul24((int)s12, KERNEL_POINT_COUNT) + __mul24((int)s1, (int)is2.x);
-                    rs[q] = __uint_as_float(is2.y);
-                }
-                // one branch for the group: the largest margin decides - lean plan fl(x - T) against -2 D, stepped plan
-                // (float)N - limk sd2 against 0 (see record()); a hit is re-tested below against the state of that moment.
-                float mg[N];
-#pragma unroll
-                for (int q = 0; q < N; q++) mg[q] = RS ? __builtin_fmaf((float)num[q], rs[q], -T) : __builtin_fmaf(-limk, rs[q], (float)num[q]);
-                float margin = mg[0];
-#pragma unroll
-                for (int q = 1; q < N; q++) margin = fmaxf(margin, mg[q]);
-                const float mlo = RS ? M : 0.0f;
-                if (COUNT) {
-#pragma unroll
-                    for (int q = 0; q < N; q++)
-                        if (mx && (uint32_t)(dyb + S0 + q - bl) < wv && (RS ? rs[q] > 0.0f : rs[q] < __builtin_inff())) evaluated++;
-                }
-                if (margin >= mlo && !(dbg & 64)) {
-                    // (stepped lines: the lane's own first plane at this step, needed only here)
-                    // (behind an opaque copy of dx: the compiler otherwise evaluates the six f64 operations ahead of the branch,
-                    // in every step)
-                    // Where the table's window is exactly one pixel's stripes (n == WV) every searching lane's first plane IS the
-                    // window's - the bracket holds them all - and nothing is evaluated: the rule for parallel lines, except where
-                    // they pass a row.
-                    if (STEP && !COUNT && wave_step && stepped && mx) {
-                        bl = dy0 + s0;
-                        if (n != WV) {
-                            int dxl = dx;
-                            asm volatile("" : "+s"(dxl));
-                            bl = step_first_plane(dxl);
-                        }
-                    }
-                    if (STEP && LOOSE_OK && wave_loose) {
-                        // A wave with loose lanes (rare: lines within an ulp below a row 2^k): one plane at a time, in a loop
-                        // - this path exists once per group, not once per plane, and the usual one below stays as it was.
-                        // For a loose lane the reference's own expression (mod.rs:424-429) says which stripe lies on the
-                        // plane's row at this step; none: the row its stripes skip here.
-#pragma nounroll
-                        for (int j = 0; j < N; j++) {
-                            float rsj = rs[0];
-                            int numj = num[0];
-#pragma unroll
-                            for (int q = 1; q < N; q++) {
-                                rsj = j == q ? rs[q] : rsj;
-                                numj = j == q ? num[q] : numj;
-                            }
-                            const int dy = dyb + S0 + j;
-                            if (mx && (uint32_t)(dy - bl) < wv && rsj < __builtin_inff() && (float)numj >= limk * rsj) { // (stepped plan: rs IS the stdev)
-                                uint32_t stripe = (uint32_t)(dy - bl);
-                                if (wv == (uint32_t)WV + 1u) { // (a loose lane: six planes)
-                                    stripe = 0xFFFFFFFFu;
-                                    const uint32_t ci = (uint32_t)((TR ? (int)y : xi) + dx), crow = (uint32_t)((TR ? xi : (int)y) + dy);
-                                    for (int off = cs; off >= -cs; off--) {
-                                        const CandXY co = candidate_xy(e, ci, off);
-                                        if ((TR ? co.x : co.y) == crow) stripe = (uint32_t)(off + cs);
-                                    }
-                                }
-                                const int dmaj = (TR ? (int)y : xi) + dx - (int)r0; // position along the line (stepped lanes: major_x != TR)
-                                const float rr = __builtin_amdgcn_rcpf(rsj);
-                                if (stripe != 0xFFFFFFFFu)
-                                    record(__builtin_fmaf((float)numj, rr, -T) > 0.0f, __builtin_fmaf((float)numj, rr, D), (stripe << 11) | (uint32_t)dmaj);
-                            }
-                        }
-                        return;
-                    }
-                    // Planes from the middle of the group outwards: every record raises the bound, and the stripe through
-                    // the predicted position is where the best match usually is - once it is in, its neighbours
-                    // (typically 0.6 .. 0.9 against ~1) fail the re-test and their record bodies are skipped.  The
-                    // order is free: the contender list is unordered and re-evaluated exactly.
-#pragma unroll
-                    for (int qi = 0; qi < N; qi++) {
-                        const int q = (N - 1) / 2 + ((qi & 1) ? (qi + 1) / 2 : -(qi / 2)); // m, m+1, m-1, m+2, ...
-                        const int dy = dyb + S0 + q; // displacement across the planes (y; x when TR)
-                        // (the plane's own pre-screen margin first - one compare; it was taken with a T that has only risen
-                        // since, so nothing that passes the test below is missed.  Lean plan: the first plane's margin IS the
-                        // test - nothing was recorded since.)
-                        const float mgc = qi == 0 ? mg[q] : __builtin_fmaf((float)num[q], rs[q], -T); // (lean plan)
-                        if (mg[q] >= mlo && mx && (uint32_t)(dy - bl) < wv &&
-                            (RS ? mgc >= M : (rs[q] < __builtin_inff() && (float)num[q] >= limk * rs[q]))) {
-                            if (RS) {
-                                record(mgc > 0.0f, __builtin_fmaf((float)num[q], rs[q], D), ((uint32_t)(S0 + q) << 7) | (uint32_t)step);
-                            } else {
-                                // back to image axes: candidate (x + ddx, y + ddy), stripe origin (ox, oy)
-                                const int ddx = TR ? dy : dx, ddy = TR ? dx : dy, ox = TR ? bl : lox, oy = TR ? loy : bl;
-                                const uint32_t code = major_x ? ((uint32_t)(ddy - oy) << 11) | (uint32_t)(xi + ddx - (int)r0)
-                                                              : ((uint32_t)(ddx - ox) << 11) | (uint32_t)((int)y + ddy - (int)r0);
-                                const float rr = __builtin_amdgcn_rcpf(rs[q]);
-                                record(__builtin_fmaf((float)num[q], rr, -T) > 0.0f, __builtin_fmaf((float)num[q], rr, D), code);
-                            }
-                        }
-                    }
-                }
-            };
-            using I0 = std::integral_constant<int, 0>;
-            using I1 = std::integral_constant<int, 1>;
-            using I2 = std::integral_constant<int, 2>;
-            using I3 = std::integral_constant<int, 3>;
-            using I4 = std::integral_constant<int, 4>;
-            using I5 = std::integral_constant<int, 5>;
-            if (!STEP) { // rectangles only: the workgroup's planes 0..4, and 5..8 when its box is taller
-                group(I0{}, I5{});
-                if (NPL > 5) group(I5{}, I4{});
-                continue;
-            }
-            if constexpr (STEP) {
-                using I6 = std::integral_constant<int, 6>;
-                using I7 = std::integral_constant<int, 7>;
-                using I8 = std::integral_constant<int, 8>;
-                using I9 = std::integral_constant<int, 9>;
-                using I10 = std::integral_constant<int, 10>;
-                using I11 = std::integral_constant<int, 11>;
-                using I12 = std::integral_constant<int, 12>;
-                using I13 = std::integral_constant<int, 13>;
-                // planes are register-indexed, so the window position selects an instantiation: five planes from
-                // `first` in one interleaved group (n >= 5: every pixel has at least five stripes), ...
-                if (n == 6) { // (one row straddled inside a five-stripe window: six interleaved planes, not five and one alone)
-                    switch (first) {
-                    case 0: group(I0{}, I6{}); break;
-                    case 1: group(I1{}, I6{}); break;
-                    case 2: group(I2{}, I6{}); break;
-                    default: group(I3{}, I6{}); break;
-                    }
-                    continue;
-                }
-                switch (first) {
-                case 0: group(I0{}, I5{}); break;
-                case 1: group(I1{}, I5{}); break;
-                case 2: group(I2{}, I5{}); break;
-                default: group(I3{}, I5{}); break;
-                }
-                // ... then one more interleaved group where three or more remain (nine stripes), the rest singly
-                // (five stripes whose lines step inside the box).  first + n <= 3 + S3_MAXH = 14 planes in 24 bytes.
-                int sx = first + 5, left = n - 5;
-                if (left >= 5) {
-                    switch (sx) {
-                    case 5: group(I5{}, I5{}); break;
-                    case 6: group(I6{}, I5{}); break;
-                    case 7: group(I7{}, I5{}); break;
-                    default: group(I8{}, I5{}); break;
-                    }
-                    sx += 5;
-                    left -= 5;
-                } else if (left >= 3) {
-                    const bool four = left == 4;
-                    switch (sx) {
-                    case 5: four ? group(I5{}, I4{}) : group(I5{}, I3{}); break;
-                    case 6: four ? group(I6{}, I4{}) : group(I6{}, I3{}); break;
-                    case 7: four ? group(I7{}, I4{}) : group(I7{}, I3{}); break;
-                    default: four ? group(I8{}, I4{}) : group(I8{}, I3{}); break;
-                    }
-                    sx += four ? 4 : 3;
-                    left = 0;
-                }
-                for (; left > 0; left--, sx++) {
-                    switch (sx) {
-                    case 5: group(I5{}, I1{}); break;
-                    case 6: group(I6{}, I1{}); break;
-                    case 7: group(I7{}, I1{}); break;
-                    case 8: group(I8{}, I1{}); break;
-                    case 9: group(I9{}, I1{}); break;
-                    case 10: group(I10{}, I1{}); break;
-                    case 11: group(I11{}, I1{}); break;
-                    case 12: group(I12{}, I1{}); break;
-                    default: group(I13{}, I1{}); break;
-                    }
-                }
+            for (int k = fold_k - 1; k >= 0; k--) {
+                const int step = fold_sel >= fold_base + k ? nwalk + k : k;
+#include "box_body.inc"
             }
         }
+#undef BOX_STEP_SECTION
     }
 
     // ---- exact re-evaluation of the contenders: mod.rs:442-464, the reference's serial f32 chain and acceptance rule; the
@@ -1038,8 +1100,8 @@
     if (is_out && !whole) store_cell(p, out, out_score, pix_e, cell);
     if (counters) {
         uint32_t v0 = evaluated, v1 = exact_evals, v2 = ecount > 1u ? 1u : 0u, v3 = whole; // (v2: pixels with more than one contender)
-        if (dbg & 32) { // diagnostics: displacements walked per wave, waves that walked
-            v1 = lane == 0 && wave_has ? (uint32_t)((mxx - mnx + 1) * NPL) : 0u;
+        if (dbg & 32) { // diagnostics: displacements walked per wave (lean plan: after folding), waves that walked
+            v1 = lane == 0 && wave_has ? (uint32_t)((mxx - mnx + 1 - fold_k) * NPL) : 0u;
             v2 = lane == 0 && wave_has ? 1u : 0u;
         }
 #pragma unroll
@@ -1065,3 +1127,4 @@
         if (threadIdx.x == 0 && any_whole)
             worklist_push(whole_list, TR ? (V0 | (tid.x << 16) | 0x40000000u) : ((uint32_t)U0 | (tid.y << 16)));
     }
+#endif // BOX_STEP_SECTION

@@ -1574,7 +1574,7 @@ __device__ __forceinline__ uint32_t wave_prefix_sum(uint32_t v)
     return v;
 }
 // wave-wide min / max with the same DPP pattern (lane 63 ends up with the total); EXEC all ones
-__device__ __forceinline__ int wave_min_i32(int v)
+__device__ __forceinline__ int wave_prefix_min_i32(int v) // lane l: the minimum over lanes 0 .. l
 {
     const int id = 0x7FFFFFFF;
     v = min(v, __builtin_amdgcn_update_dpp(id, v, 0x111, 0xF, 0xF, false));
@@ -1583,8 +1583,9 @@ __device__ __forceinline__ int wave_min_i32(int v)
     v = min(v, __builtin_amdgcn_update_dpp(id, v, 0x118, 0xF, 0xF, false));
     v = min(v, __builtin_amdgcn_update_dpp(id, v, 0x142, 0xA, 0xF, false));
     v = min(v, __builtin_amdgcn_update_dpp(id, v, 0x143, 0xC, 0xF, false));
-    return __builtin_amdgcn_readlane(v, 63);
+    return v;
 }
+__device__ __forceinline__ int wave_min_i32(int v) { return __builtin_amdgcn_readlane(wave_prefix_min_i32(v), 63); }
 __device__ __forceinline__ int wave_max_i32(int v) { return -wave_min_i32(-v); }
 
 __device__ __forceinline__ uint32_t load_dword_checked(const uint8_t *__restrict__ img, int w, int h, int row, int col)
@@ -1612,8 +1613,8 @@ __device__ __forceinline__ uint32_t load_dword_checked(const uint8_t *__restrict
 // transposed one takes 95 and loses the sixth wave).  7 waves - what its 22.5 KB of LDS would
 // admit - was measured 1.8 % faster (5.89 vs 6.00 ms per 4096^2 pair) but only with 10 VGPRs spilled: 28 B of scratch
 // per lane x 54 M threads put +1.17 GB per step on the L2 write-back counter (whole step 3.0 -> 4.2 GB).  Not taken.
-// (the candidate-counting instantiations - profiling and tests only - need 80 registers (lean) and ~115 (stepped): five and
-// four waves rather than 28 B of scratch)
+// (the candidate-counting instantiations - profiling and tests only - need 86 registers (lean: both copies of the walk's step
+// carry the per-plane membership tests) and ~115 (stepped): five and four waves rather than scratch)
 #ifndef CVHIP_STEP_WAVES
 #define CVHIP_STEP_WAVES 5
 #endif

@@ -415,6 +415,7 @@ static int plan_pass(cvhip_ctx *c, int a, int b, uint32_t lw1, uint32_t lh1, uin
     p.k = (uint32_t)k;
     p.first_pass = first_pass ? 1 : 0;
     p.need_scores = (dir == 0 && k == 0) || c->exact_scores ? 1 : 0;
+    p.box_fold = c->box_fold ? 1 : 0;
     const double *F = p.F;
     const bool affine_form = F[0] == 0.0 && F[1] == 0.0 && F[3] == 0.0 && F[4] == 0.0;
     p.affine = 0;
@@ -1808,6 +1809,27 @@ int cvhip_ctx_get_box_counters(cvhip_ctx *ctx, uint64_t out[4], int reset)
     CVHIP_TRY_HIP(hipMemcpy(v, ctx->d_cand, sizeof(v), hipMemcpyDeviceToHost));
     for (int i = 0; i < 4; i++) out[i] = (uint64_t)v[4 + i];
     if (reset) CVHIP_TRY_HIP(hipMemset(ctx->d_cand + 4, 0, 4 * sizeof(unsigned long long)));
+    return CVHIP_OK;
+}
+
+int cvhip_ctx_get_box_fold_counters(cvhip_ctx *ctx, uint64_t out[4], int reset)
+{
+    if (!ctx || !out) return fail(CVHIP_ERR_INVALID, "null argument");
+    CVHIP_TRY(flush_level_calls(ctx));
+    CVHIP_TRY(set_device(ctx->dev));
+    CVHIP_TRY_HIP(hipStreamSynchronize(ctx->dev->d.stream));
+    unsigned long long v[cvhip_ctx::N_COUNTERS] = {};
+    CVHIP_TRY_HIP(hipMemcpy(v, ctx->d_cand, sizeof(v), hipMemcpyDeviceToHost));
+    for (int i = 0; i < 4; i++) out[i] = (uint64_t)v[8 + i];
+    if (reset) CVHIP_TRY_HIP(hipMemset(ctx->d_cand + 8, 0, 4 * sizeof(unsigned long long)));
+    return CVHIP_OK;
+}
+
+int cvhip_ctx_set_box_fold(cvhip_ctx *ctx, int on)
+{
+    if (!ctx) return fail(CVHIP_ERR_INVALID, "ctx is null");
+    CVHIP_TRY(flush_level_calls(ctx));
+    ctx->box_fold = on != 0;
     return CVHIP_OK;
 }
 

@@ -81,6 +81,9 @@ struct CorrParams {
     // workgroup, 8 / 16 = the box kernel skips its walk / its exact phase, 32 = box statistics in counters 1 and 2, 64 = the walk never enters its hit branch,
     // 256 = the box kernel stops after per-pixel setup, 512 = it skips staging (and its exact phase).
     int debug;
+    // lean box walk: fold the two ends of a wave's union of displacement ranges into shared steps (box_body.inc;
+    // cvhip_ctx_set_box_fold).  0: every wave walks its whole union, one step at a time.
+    int box_fold;
 };
 
 // ---- kernel launchers (corr_kernels.hip) ----------------------------------------------------
@@ -563,6 +566,7 @@ struct cvhip_ctx {
     bool pool_waited = false;          // stream waits for it before its first upload into the pool
     bool async_readback = false; // cvhip_ctx_set_async_readback
     bool exact_scores = false; // cvhip_ctx_set_exact_scores: every pass writes the reference's scores (tests)
+    bool box_fold = true;      // cvhip_ctx_set_box_fold: the lean box walk folds the ends of a wave's union (CorrParams::box_fold)
     int search_version = 3; // (5: version 3 with the rectified box launches on the matrix pipe, search4_mfma_kernel - measured slower;
                             //  6: version 3 with the rectified box launches on two columns per lane, search3_box2_kernel)
     int range_mode = 0; // search_range_kernel: 0 = integer box sums + chain where needed, 1 = chain only, 2 / 3 = test hooks
@@ -589,8 +593,9 @@ struct cvhip_ctx {
     BandPlan band[16];
 
     int time_kernels = 0, count_candidates = 0;
-    // device counters of the counting search instantiations: [0..3] cvhip_ctx_get_counters, [4..7] cvhip_ctx_get_box_counters
-    static constexpr int N_COUNTERS = 8;
+    // device counters of the counting search instantiations: [0..3] cvhip_ctx_get_counters, [4..7] cvhip_ctx_get_box_counters,
+    // [8..11] cvhip_ctx_get_box_fold_counters
+    static constexpr int N_COUNTERS = 12;
     unsigned long long *d_cand = nullptr;
     // kernel classes timed with HIP events when time_kernels is set
     enum { K_STATS = 0, K_RANGE, K_SEARCH, K_EXACT, K_CROSS, K_EXPAND, K_FILTER, K_COUNT };

@@ -662,6 +662,17 @@ int cvhip_ctx_get_counters(cvhip_ctx *ctx, uint64_t out[4], int reset);
  * is 65 steps (one more than the walk's 64-lane step table), out[1] the same for transposed tiles, out[2] the
  * most steps any stepped wave walked, out[3] 0.  reset clears these four only.  Synchronises. */
 int cvhip_ctx_get_box_counters(cvhip_ctx *ctx, uint64_t out[4], int reset);
+/* The lean box walk (rectified pairs) folds the two ends of a wave's union of displacement ranges: where the ranges drift
+ * along a wave's 53 pixels, the first steps of the union are searched only at one end of the wave and the last steps only
+ * at the other, and one low and one high step then run as a single step, every lane at its own displacement (DESIGN.md
+ * section 4.2).  Every candidate is still evaluated once, by the same instructions; results are identical either way.
+ * on = 1 (default) / 0: every wave walks its whole union.  Takes effect with the next pass. */
+int cvhip_ctx_set_box_fold(cvhip_ctx *ctx, int on);
+/* Diagnostics of the fold since the last reset (needs count_candidates = 1; kept apart from the counters above), summed
+ * over the lean box waves that walked: out[0] steps of their unions, out[1] steps walked after folding, out[2] pairs
+ * folded with the low steps at the low lanes (ascending), out[3] pairs folded the other way (descending);
+ * out[0] - out[1] == out[2] + out[3].  reset clears these four only.  Synchronises. */
+int cvhip_ctx_get_box_fold_counters(cvhip_ctx *ctx, uint64_t out[4], int reset);
 /* Select the search kernel: 1 = every candidate through the exact serial f32 chain, 2 = exact-integer
  * filter per candidate + exact re-evaluation of the contenders, 3 (default) = the same filter evaluated
  * as displacement-plane box sums for whole row segments where the epipolar lines keep one major axis, with 2 for
