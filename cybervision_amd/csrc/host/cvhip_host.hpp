@@ -691,7 +691,7 @@ struct ObjSections {
 
 // Mesh::output with an ObjWriter -> the file's bytes.  images: one per image of a track - their pixels are read in Color mode,
 // only their sizes in Texture mode (pixels may be empty there); each polygon's camera_i is read in Texture mode; stem: the
-// output path's file stem.  Saving the {stem}-{i}.png images is the caller's.
+// output path's file stem.  The {stem}-{i}.png images the .mtl names: png_encode of each image.
 inline std::vector<uint8_t> mesh_obj(GpuDevice &dev, const Surface &s, const std::vector<Polygon> &polygons, const std::vector<RgbImage> &images,
                                      VertexMode mode, const std::array<double, 3> &out_scale, const std::string &stem,
                                      ObjSections *sections = nullptr)
@@ -716,6 +716,24 @@ inline std::string mesh_obj_mtl(const std::string &stem, uint32_t m)
     check(cvhip_mesh_obj_mtl(stem.c_str(), m, nullptr, 0, &size), "cvhip_mesh_obj_mtl");
     std::string out(size, '\0');
     check(cvhip_mesh_obj_mtl(stem.c_str(), m, out.data(), size, &size), "cvhip_mesh_obj_mtl");
+    return out;
+}
+
+// ---- the PNG encoder: what img.save writes for the textures (:845-875) and the depth map (:1141) -----------------
+struct PngSections {
+    uint64_t before = 0, idat = 0, after = 0; // the bytes before the IDAT data, the IDAT data, the bytes after it
+};
+enum class PngFilter : uint32_t { None = 0, Sub = 1, Up = 2, Average = 3, Paeth = 4, Adaptive = 5 };
+
+// The PNG file's bytes of width x height pixels of `channels` (1: grey, 2: grey and alpha, 3: RGB, 4: RGBA) bytes each.
+inline std::vector<uint8_t> png_encode(GpuDevice &dev, const uint8_t *pixels, uint32_t width, uint32_t height, uint32_t channels,
+                                       PngFilter filter = PngFilter::Adaptive, PngSections *sections = nullptr)
+{
+    uint64_t sec[3] = {0, 0, 0};
+    std::vector<uint8_t> out = detail::size_then_fill([&](uint8_t *dst, uint64_t cap, uint64_t *size) {
+        check(cvhip_png_encode(dev.handle(), pixels, width, height, channels, (uint32_t)filter, dst, cap, size, sec), "cvhip_png_encode");
+    });
+    if (sections) *sections = PngSections{sec[0], sec[1], sec[2]};
     return out;
 }
 

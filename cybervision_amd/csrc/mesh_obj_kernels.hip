@@ -16,7 +16,7 @@
 // passes but 8 bytes per block) and hands its records to the writer the PLY shares (mesh_records.hpp): placed by an in-block
 // scan, assembled in LDS and copied out as aligned dwords.  A block with more bytes than the staging buffer (a block of
 // subnormals is ~250 KB) stores its records directly.
-// Not here: saving the {stem}-{i}.png images (there is no PNG encoder).
+// The {stem}-{i}.png images the .mtl names are cvhip_png_encode's (png_kernels.hip), one call per image.
 #include <cstdio>
 #include <cstring>
 #include <string>

@@ -9,7 +9,7 @@
 //   face:   0x03, then big-endian u32 of vertices[2], vertices[1], vertices[0].
 // The colour map is f64, one IEEE operation per written operation in the written order (-ffp-contract=off).
 // The records are placed and stored by the writer the OBJ shares (mesh_records.hpp; the OBJ is mesh_obj_kernels.hip).
-// Not here: the colour table (an argument) and the PNG encoder.
+// Not here: the colour table (an argument).  The RGBA's PNG file is cvhip_png_encode's (png_kernels.hip).
 #include <cmath>
 #include <cstdio>
 #include <string>

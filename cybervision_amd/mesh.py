@@ -5,7 +5,8 @@ reconstruct_perspective_mesh) is one, `delaunay_device(device)` - cvhip_mesh_del
 and needs no scipy.
 The mesh output: `ply` / `write_ply` - PlyWriter's binary file image - and `colour_map` /
 `depth_image_rgba` - ImageWriter::complete's colours; the colour table is the caller's.  `obj` / `write_obj` / `obj_mtl` - ObjWriter's
-Wavefront OBJ text and its .mtl, `f64_display` - the decimal text of doubles that it rests on.
+Wavefront OBJ text and its .mtl, `f64_display` - the decimal text of doubles that it rests on.  `png` / `write_png` /
+`write_depth_png` - the PNG file image of the textures and of the depth map.
 No compute in Python - array bookkeeping and the calls only.
 
 Defined where the reference's result depends on its thread order: a depth-buffer cell is the minimum of its depths (a
@@ -261,10 +262,11 @@ def obj_mtl(stem, m: int):
     return _size_then_fill("cvhip_mesh_obj_mtl", [str(stem).encode("utf-8"), int(m)]).tobytes()
 
 
-def write_obj(path, device, surface, polygons, camera, images=None, vertex_mode=VertexMode.Plain, out_scale=(1.0, 1.0, 1.0)):
+def write_obj(path, device, surface, polygons, camera, images=None, vertex_mode=VertexMode.Plain, out_scale=(1.0, 1.0, 1.0),
+              save_textures=False):
     """`obj` written to `path` with the path's file stem and, in Texture mode, `obj_mtl` to {stem}.mtl next to it
-    -> (header, v, vt, f) byte counts.  The .mtl names {stem}-{i}.png for image i: saving those images is the caller's (there is
-    no PNG encoder here)."""
+    -> (header, v, vt, f) byte counts.  The .mtl names {stem}-{i}.png for image i: with save_textures, in Texture mode and with
+    `images` given as arrays, `png` of image i is written there (ObjWriter::write_materials' img.save, output.rs:845-875)."""
     import pathlib
 
     path = pathlib.Path(path)
@@ -273,7 +275,23 @@ def write_obj(path, device, surface, polygons, camera, images=None, vertex_mode=
     if int(vertex_mode) == VertexMode.Texture:
         m = np.asarray(surface.tracks).reshape(len(surface.points), -1, 2).shape[1] if len(surface.points) else len(images or [])
         (path.parent / (path.stem + ".mtl")).write_bytes(obj_mtl(path.stem, m))
+        if save_textures:
+            write_obj_textures(path, device, images)
     return tuple(sections)
+
+
+def write_obj_textures(obj_path, device, images):
+    """The {stem}-{i}.png files that the .mtl of the OBJ at obj_path names: `png` of image i, for `images` given as arrays
+    (nothing for a list of sizes, or None) -> the paths written."""
+    import pathlib
+
+    path, written = pathlib.Path(obj_path), []
+    if images is None or not all(hasattr(im, "shape") and len(im.shape) == 3 for im in images):
+        return written
+    for i, im in enumerate(images):
+        written.append(path.parent / ("%s-%d.png" % (path.stem, i)))
+        write_png(written[-1], device, np.ascontiguousarray(im, dtype=np.uint8))  # (as _image_args takes them)
+    return written
 
 
 def f64_display(device, values):
@@ -328,6 +346,92 @@ def depth_image_rgba(device, surface, image_shapes, project_to_image: int, scale
                                        float(minmax[1]), _p(t), _p(rgba)), "cvhip_mesh_colour_map")
     return {"rgba": rgba, "origin": (float(origin[0]), float(origin[1])), "min_depth": float(minmax[0]),
             "max_depth": float(minmax[1])}
+
+
+class PngFilter(enum.IntEnum):
+    """The `filter` of cvhip_png_encode (CVHIP_PNG_FILTER_*): one PNG filter on every row, or per row the one of least sum of
+    |signed byte|."""
+    Nothing = 0
+    Sub = 1
+    Up = 2
+    Average = 3
+    Paeth = 4
+    Adaptive = 5
+
+
+def _pixel_args(pixels):
+    """(pixels, width, height, channels) of cvhip_png_encode from [h, w] or [h, w, c] uint8, as numpy or as a device tensor, and
+    what keeps the memory alive."""
+    if hasattr(pixels, "data_ptr"):  # a torch tensor
+        import torch
+
+        t = pixels.contiguous()
+        if t.dtype != torch.uint8:
+            raise ValueError("pixels are uint8")
+        if t.is_cuda:
+            torch.cuda.current_stream(t.device).synchronize()  # (filled on torch's stream; the library works on its own)
+        shape, ptr, keep = tuple(t.shape), C.c_void_p(t.data_ptr()), t
+    else:
+        a = np.ascontiguousarray(pixels)
+        if a.dtype != np.uint8:
+            raise ValueError("pixels are uint8")
+        shape, ptr, keep = a.shape, C.c_void_p(a.ctypes.data), a
+    if len(shape) == 2:
+        shape = (*shape, 1)
+    if len(shape) != 3:
+        raise ValueError("pixels are [height, width] or [height, width, channels]")
+    return [ptr, int(shape[1]), int(shape[0]), int(shape[2])], keep
+
+
+def png(device, pixels, filter=PngFilter.Adaptive, sections=None):
+    """The PNG file image of an 8-bit image (cvhip_png_encode) -> uint8 array.  pixels: [h, w] or [h, w, c]
+    uint8 with c = 1 (grey), 2 (grey and alpha), 3 (RGB) or 4 (RGBA), as a numpy array or as a device tensor (then they do
+    not leave the device).  filter: a PngFilter.  `sections`, a list, receives the bytes before the IDAT data, the IDAT
+    data's, and the bytes after it.  Any PNG decoder returns `pixels`; the bytes themselves are defined by this library."""
+    args, _keep = _pixel_args(pixels)
+    return _file_image("cvhip_png_encode", [device.handle, *args, int(filter)], 3, sections)
+
+
+def write_png(path, device, pixels, filter=PngFilter.Adaptive):
+    """`png` written to `path` -> (before, IDAT data, after) byte counts."""
+    sections = []
+    png(device, pixels, filter, sections=sections).tofile(path)
+    return tuple(sections)
+
+
+def _depth_rgba_device(device, surface, image_shapes, project_to_image, scale, polygons, table):
+    """depth_image_rgba's two calls with the map AND the RGBA in device memory -> (rgba tensor [h, w, 4], origin, minmax)."""
+    import torch
+
+    args, _keep = _surface_args(surface, image_shapes)
+    poly = np.ascontiguousarray(polygons, dtype=np.uint32).reshape(-1, 3)
+    t = _table(table)
+    w, h = C.c_uint64(0), C.c_uint64(0)
+    origin, minmax = np.zeros(2), np.zeros(2)
+    L = _lib.lib()
+    _lib.check(L.cvhip_mesh_depth_image(device.handle, *args, int(project_to_image), float(scale), _p(poly), len(poly), None, 0,
+                                        C.byref(w), C.byref(h), _p(origin), None, None), "cvhip_mesh_depth_image")
+    ordinal = getattr(device, "ordinal", -1)
+    where = torch.device("cuda", ordinal) if ordinal >= 0 else "cuda"
+    d_map = torch.empty((h.value, w.value), dtype=torch.float64, device=where)
+    d_rgba = torch.empty((h.value, w.value, 4), dtype=torch.uint8, device=where)
+    _lib.check(L.cvhip_mesh_depth_image(device.handle, *args, int(project_to_image), float(scale), _p(poly), len(poly),
+                                        C.c_void_p(d_map.data_ptr()), d_map.numel(), C.byref(w), C.byref(h), _p(origin), _p(minmax),
+                                        None), "cvhip_mesh_depth_image")
+    _lib.check(L.cvhip_mesh_colour_map(device.handle, C.c_void_p(d_map.data_ptr()), w.value, h.value, float(minmax[0]),
+                                       float(minmax[1]), _p(t), C.c_void_p(d_rgba.data_ptr())), "cvhip_mesh_colour_map")
+    return d_rgba, origin, minmax
+
+
+def write_depth_png(path, device, surface, image_shapes, project_to_image: int, scale: float, polygons, table,
+                    filter=PngFilter.Adaptive):
+    """ImageWriter::complete with its img.save (output.rs:1016-1229, 1141): cvhip_mesh_depth_image, cvhip_mesh_colour_map and
+    cvhip_png_encode chained in device memory - neither the map nor the RGBA crosses to the host, only the file does -> dict:
+    width, height, origin, min_depth, max_depth, sections.  The file decodes to depth_image_rgba(...)["rgba"]."""
+    d_rgba, origin, minmax = _depth_rgba_device(device, surface, image_shapes, project_to_image, scale, polygons, table)
+    sections = write_png(path, device, d_rgba, filter)
+    return {"width": int(d_rgba.shape[1]), "height": int(d_rgba.shape[0]), "origin": (float(origin[0]), float(origin[1])),
+            "min_depth": float(minmax[0]), "max_depth": float(minmax[1]), "sections": sections}
 
 
 def set_delaunay_lane_cells(device, cells: int):

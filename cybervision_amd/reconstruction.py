@@ -380,7 +380,7 @@ def reconstruct_perspective(device, pyramids, K, bundle_adjustment: bool = True,
 
 def reconstruct_perspective_mesh(device, pyramids, K, triangulate=None, project_to_image=None, depth_scale: float = -1.0,
                                  ply_path=None, images=None, vertex_mode=0, out_scale=(1.0, 1.0, 1.0), colour_table=None,
-                                 obj_path=None, **kwargs):
+                                 obj_path=None, save_textures=False, depth_png_path=None, **kwargs):
     """reconstruct_perspective, then the mesh stage of output::output (output.rs:567-611; DESIGN.md 4.11) on its surface:
     mesh.create - per camera the Delaunay input, `triangulate(xy) -> [f, 3]` (the caller's Delaunay; default
     mesh.delaunay_scipy; mesh.delaunay_device(device) runs on the device and needs no scipy), the occlusion culling and the
@@ -393,11 +393,17 @@ def reconstruct_perspective_mesh(device, pyramids, K, triangulate=None, project_
     colour_table ([256, 3] uint8, with project_to_image) - out["depth_image"]["rgba"] is the depth map through
     mesh.colour_map; obj_path - the Wavefront OBJ of the surface and the merged list with its cameras is
     written there (mesh.write_obj with the same images, vertex_mode and out_scale; in Texture mode the .mtl goes next to it and
-    the caller saves the {stem}-{i}.png images), its section sizes are out["obj_sections"], its time timings_ms["obj"]."""
+    the caller saves the {stem}-{i}.png images), its section sizes are out["obj_sections"], its time timings_ms["obj"].
+    The PNG files, their time in timings_ms["png"]: save_textures - with obj_path, in Texture mode and with
+    `images` given as arrays, the {stem}-{i}.png files the .mtl names are written next to it (mesh.write_obj_textures);
+    depth_png_path - the depth map's RGBA is written there (mesh.write_depth_png, out["depth_png"] is its dict); it needs
+    project_to_image and colour_table (ValueError otherwise)."""
     import time
 
     from . import mesh
 
+    if depth_png_path is not None and (project_to_image is None or colour_table is None):
+        raise ValueError("depth_png_path needs project_to_image and colour_table")
     out = reconstruct_perspective(device, pyramids, K, **kwargs)
     shapes = [(int(p[0].shape[1]), int(p[0].shape[0])) for p in pyramids]
     # (the surface's cameras are the placed images, in image order: prune_projections keeps the order)
@@ -426,17 +432,28 @@ def reconstruct_perspective_mesh(device, pyramids, K, triangulate=None, project_
                                              shapes if images is None and int(vertex_mode) == mesh.VertexMode.Texture else images,
                                              mesh.VertexMode(int(vertex_mode)), out_scale)
         out["timings_ms"]["obj"] = (time.perf_counter() - t3) * 1e3
+    t4 = time.perf_counter()
+    textures = obj_path is not None and save_textures and int(vertex_mode) == mesh.VertexMode.Texture
+    if textures:
+        mesh.write_obj_textures(obj_path, device, images)
+    if depth_png_path is not None:
+        out["depth_png"] = mesh.write_depth_png(depth_png_path, device, out["surface"], shapes, project_to_image, depth_scale,
+                                                out["mesh"]["polygons"], colour_table)
+    if textures or depth_png_path is not None:
+        out["timings_ms"]["png"] = (time.perf_counter() - t4) * 1e3
     return out
 
 
 def reconstruct_affine_mesh(device, pyramid1, pyramid2, f, triangulate=None, project_to_image=None, depth_scale: float = -1.0,
-                            ply_path=None, obj_path=None, images=None, vertex_mode=0, out_scale=(1.0, 1.0, 1.0), colour_table=None):
+                            ply_path=None, obj_path=None, images=None, vertex_mode=0, out_scale=(1.0, 1.0, 1.0), colour_table=None,
+                            save_textures=False, depth_png_path=None):
     """The affine `reconstruct` of one pair, through to the mesh and its outputs: the dense correlation of the two pyramids
     with the affine F, AffineTriangulation::triangulate straight from the device grid (PointCorrelations.triangulate_affine),
     its Surface (triangulation.affine_surface: two cameras with K = diag(1, 1, 0)), mesh.create - both cameras are
     triangulated and culled as the reference does; the second camera's triangles are the first's, and the merge leaves them
     with camera 0 - and the outputs of reconstruct_perspective_mesh, each only when asked for: project_to_image (with
-    depth_scale, colour_table), ply_path, obj_path (with images - one per image of the pair -, vertex_mode, out_scale).
+    depth_scale, colour_table), ply_path, obj_path (with images - one per image of the pair -, vertex_mode, out_scale),
+    save_textures and depth_png_path (the PNG files; timings_ms["png"]).
     triangulate: the Delaunay of a camera's points; the default is mesh.delaunay_device(device, lattice=True) - the camera
     points are integer pixels, every star is an exact tie, and cvhip_mesh_delaunay decides those as defined, on the device
     (scipy's tie choices are not the defined ones).
@@ -444,6 +461,8 @@ def reconstruct_affine_mesh(device, pyramid1, pyramid2, f, triangulate=None, pro
     ply_sections / obj_sections when those files were written."""
     from . import mesh, triangulation
 
+    if depth_png_path is not None and (project_to_image is None or colour_table is None):
+        raise ValueError("depth_png_path needs project_to_image and colour_table")
     rec = ImageReconstruction(device, ProjectionMode.Affine)
     shapes = [(int(p[0].shape[1]), int(p[0].shape[0])) for p in (pyramid1, pyramid2)]
     pc = correlation.PointCorrelations(device, shapes[0], shapes[1], f, correlation.ProjectionMode(int(ProjectionMode.Affine)))
@@ -479,5 +498,10 @@ def reconstruct_affine_mesh(device, pyramid1, pyramid2, f, triangulate=None, pro
         dims = shapes if images is None and int(vertex_mode) == mesh.VertexMode.Texture else images
         out["obj_sections"] = rec._timed("obj", lambda: mesh.write_obj(obj_path, device, out["surface"], polygons, out["mesh"]["camera"],
                                                                       dims, mesh.VertexMode(int(vertex_mode)), out_scale))
+        if save_textures and int(vertex_mode) == mesh.VertexMode.Texture:
+            rec._timed("png", lambda: mesh.write_obj_textures(obj_path, device, images))
+    if depth_png_path is not None:
+        out["depth_png"] = rec._timed("png", lambda: mesh.write_depth_png(depth_png_path, device, out["surface"], shapes, project_to_image,
+                                                                         depth_scale, polygons, colour_table))
     out["timings_ms"] = dict(rec.timings_ms)
     return out

@@ -324,8 +324,8 @@ int cvhip_recover_pose_models(cvhip_device *dev, const int32_t *tracks, uint64_t
  * (Surface::project_point, triangulation.rs:63-74); it is IN RANGE when the projection lies in [c - 4 size, c + 4 size) on
  * both axes, c = size / 2 (img_range, output.rs:613-624); its depth is Camera::point_depth (triangulation.rs:492-495).
  * The Delaunay construction is cvhip_mesh_delaunay below (a caller may still supply triangles of its own: the other entries
- * take any).  Not here: the colour table (an argument of cvhip_mesh_colour_map) and the PNG encoder.  The PLY and OBJ
- * writers and the colour mapping are the mesh OUTPUT entries below.
+ * take any).  Not here: the colour table (an argument of cvhip_mesh_colour_map).  The PLY and OBJ writers, the colour
+ * mapping and the PNG encoder (cvhip_png_encode) are the mesh OUTPUT entries below.
  * Two of the reference's results depend on its thread order, and are DEFINED here:
  *  - DepthBuffer::new folds a cell's points in par_bridge's order, keeping a new depth iff cur - new > f64::EPSILON; here
  *    the cell is the MINIMUM of its depths (one of the reference's outcomes unless two depths of a cell differ by a
@@ -460,7 +460,7 @@ int cvhip_mesh_delaunay_get_lattice_stars(cvhip_device *dev, uint64_t *out_stars
  * Mesh output (csrc/mesh_output_kernels.hip): what output::output writes once the polygon list exists -
  * PlyWriter's binary file image (output.rs:648-772) and ImageWriter::complete's colour mapping (:1117-1229) -, pinned
  * byte for byte.  Neither touches the cameras: an affine surface works the same, and m is the number of images per track.
- * The OBJ writer, with its vt / UV tables, is cvhip_mesh_obj further below.  Not here: the PNG encoder. */
+ * The OBJ writer, with its vt / UV tables, is cvhip_mesh_obj further below, the PNG encoder cvhip_png_encode. */
 
 /* VertexMode (output.rs): what a vertex carries.  In a PLY, Texture writes what Plain writes; in an OBJ it adds the vt table. */
 #define CVHIP_VERTEX_PLAIN 0
@@ -526,7 +526,8 @@ int cvhip_mesh_colour_map(cvhip_device *dev, const double *map, uint64_t width, 
  * outside Texture mode).
  * Errors, each with nothing written: CVHIP_ERR_INVALID "Track has no images" (Color and Texture mode: a track without a point,
  * or m = 0 with n > 0; Plain mode accepts such a track), CVHIP_ERR_INVALID for a vertex >= n, CVHIP_ERR_UNSUPPORTED for 2^32 - 1
- * or more tracks or polygons, or n * m >= 2^32 - 1 in Color and Texture mode.  Saving the {stem}-{i}.png images is the caller's. */
+ * or more tracks or polygons, or n * m >= 2^32 - 1 in Color and Texture mode.  The {stem}-{i}.png images the .mtl names are
+ * cvhip_png_encode's, one call per image. */
 int cvhip_mesh_obj(cvhip_device *dev, const double *points, const int32_t *tracks, uint64_t n, uint32_t m,
                    const uint8_t *images, const uint64_t *image_offsets, const uint32_t *image_dims,
                    uint32_t vertex_mode, const double *out_scale,
@@ -544,6 +545,40 @@ int cvhip_mesh_obj_mtl(const char *stem, uint32_t m, char *out, uint64_t cap, ui
  * CVHIP_ERR_UNSUPPORTED with 2^32 - 1 or more values. */
 int cvhip_f64_display(cvhip_device *dev, const double *values, uint64_t n, uint8_t *out, uint64_t cap, uint64_t *out_size,
                       uint64_t *offsets);
+
+/* ------------------------------------------------------------------------------------------
+ * The PNG file image (csrc/png_kernels.hip, csrc/png_common.hpp): what the reference saves with img.save - the
+ * {stem}-{i}.png textures of an OBJ (output.rs:845-875: 8-bit RGB, colour type 2) and ImageWriter's depth map (:1141: 8-bit
+ * RGBA, colour type 6) - made on the device.  The reference's encoder is not restated: every decoder returns the same pixels,
+ * the bytes are DEFINED here (tests/ref_png.py is the definition), deterministically:
+ *  - the signature; IHDR: width, height, depth 8, colour type 0 / 4 / 2 / 6 for channels 1 / 2 / 3 / 4, compression 0,
+ *    filter 0, interlace 0; ONE IDAT; IEND.  No other chunk;
+ *  - the IDAT data: 78 01, one deflate block (BFINAL = 1, dynamic Huffman), the Adler-32 of the filtered bytes;
+ *  - filtered bytes: per row the filter's number and width * channels bytes under that filter (bpp = channels).  filter 0 to 4
+ *    (CVHIP_PNG_FILTER_NONE .. _PAETH): that filter on every row.  CVHIP_PNG_FILTER_ADAPTIVE: per row the filter with the
+ *    least sum over its filtered bytes of (v < 128 ? v : 256 - v), the lowest number on equal sums;
+ *  - tokens, per row (nothing crosses a row): byte 0 is a literal; position i >= 1 repeats iff it equals byte i - 1; of every
+ *    maximal run of L repeating positions: while L >= 3 a match of min(L, 258) at distance 1, the remaining 0 to 2 literals;
+ *    the end-of-block symbol behind the last row;
+ *  - codes: lengths by package-merge over the whole image's literal/length counts, limit 15 (leaves sorted by (count,
+ *    symbol); in the merges a leaf goes before a package of equal weight); canonical codes; HLIT = the highest used symbol + 1;
+ *    HDIST = 1 with one distance code of one bit; the HLIT + 1 code lengths sent as themselves (no symbols 16 to 18), their
+ *    code by the same routine with limit 7, HCLEN up to the last non-zero entry and at least 4.
+ * pixels (height x width x channels bytes, rows packed) and out are host or device pointers, out of any alignment.
+ * out_sections[3] (may be NULL) = the bytes before the IDAT data (41), the IDAT data, the bytes after it (16).
+ * cap = 0 sizes the image - it filters, counts, gets the code from the host and scans the rows' bits - and writes nothing;
+ * 0 < cap < size is CVHIP_ERR_INVALID with nothing written.  CVHIP_ERR_INVALID too: width or height 0, channels not 1 to 4,
+ * filter above 5.  CVHIP_ERR_UNSUPPORTED: 2^32 - 1 or more filtered bytes, or IDAT data of 2^31 or more bytes.  There is no
+ * stored-block fallback: noise grows by the code's overhead.  Not here: interlacing, 16-bit and palette images, ancillary
+ * chunks, matches at other distances, decoding. */
+#define CVHIP_PNG_FILTER_NONE 0u
+#define CVHIP_PNG_FILTER_SUB 1u
+#define CVHIP_PNG_FILTER_UP 2u
+#define CVHIP_PNG_FILTER_AVERAGE 3u
+#define CVHIP_PNG_FILTER_PAETH 4u
+#define CVHIP_PNG_FILTER_ADAPTIVE 5u
+int cvhip_png_encode(cvhip_device *dev, const uint8_t *pixels, uint32_t width, uint32_t height, uint32_t channels, uint32_t filter,
+                     uint8_t *out, uint64_t cap, uint64_t *out_size, uint64_t *out_sections);
 
 /* Row sharding (multi-GPU): restrict the SEARCH passes of this context to shard `num` of `den`
  * equal row chunks of the searched level image: rows [num*rps, min((num+1)*rps, h_level)) with
