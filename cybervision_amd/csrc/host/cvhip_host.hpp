@@ -749,4 +749,43 @@ inline std::vector<uint8_t> colour_map(GpuDevice &dev, const DepthImage &img, co
 
 } // namespace mesh
 
+// ---- image files in: SourceImage::load / load_rgb (reconstruction.rs:40-60) for baseline JPEG -----------------------
+namespace image {
+
+struct JpegInfo {
+    uint32_t width = 0, height = 0, components = 0, h = 0, v = 0; // h, v: the luma sampling factors
+    uint32_t focal_length_35mm = 0;                               // EXIF FocalLengthIn35mmFilm (:138-142), 0 = none
+};
+enum class Format : uint32_t { Luma8 = CVHIP_IMAGE_LUMA8, Rgb8 = CVHIP_IMAGE_RGB8 };
+
+// the frame and the EXIF focal length of a JPEG file's bytes (host only)
+inline JpegInfo jpeg_info(const uint8_t *file, uint64_t size)
+{
+    uint32_t v[6] = {0, 0, 0, 0, 0, 0};
+    check(cvhip_jpeg_info(file, size, v), "cvhip_jpeg_info");
+    JpegInfo info;
+    info.width = v[0], info.height = v[1], info.components = v[2], info.h = v[3], info.v = v[4], info.focal_length_35mm = v[5];
+    return info;
+}
+
+// image::open(path)?.into_luma8() / into_rgb8() of the file's bytes, drop_rows (databar_height) rows cut from the bottom ->
+// width x (height - drop_rows) pixels of 1 or 3 bytes
+inline std::vector<uint8_t> jpeg_decode(GpuDevice &dev, const uint8_t *file, uint64_t size, Format format = Format::Luma8, uint32_t drop_rows = 0)
+{
+    return mesh::detail::size_then_fill([&](uint8_t *dst, uint64_t cap, uint64_t *out_size) {
+        check(cvhip_jpeg_decode(dev.handle(), file, size, (uint32_t)format, drop_rows, dst, cap, out_size), "cvhip_jpeg_decode");
+    });
+}
+
+// SourceImage::calibration_matrix (:164-185), row-major; focal_length_35mm 0 = none: 1
+inline std::array<double, 9> calibration_matrix(uint32_t width, uint32_t height, uint32_t focal_length_35mm)
+{
+    const double diagonal_35mm = std::sqrt(24.0 * 24.0 + 36.0 * 36.0);
+    const double w = (double)width, h = (double)height, diagonal = std::sqrt(w * w + h * h);
+    const double focal = (double)(focal_length_35mm ? focal_length_35mm : 1u) * diagonal / diagonal_35mm;
+    return {focal, 0.0, w / 2.0, 0.0, focal, h / 2.0, 0.0, 0.0, 1.0};
+}
+
+} // namespace image
+
 } // namespace cvhip_host

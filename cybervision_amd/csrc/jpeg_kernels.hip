@@ -1,0 +1,639 @@
+// jpeg_kernels.hip — cvhip_jpeg_decode: a baseline JPEG file to Luma8 or RGB8 pixels, everything behind the marker walk on the
+// device.  The reference opens its inputs with image::open(path)?.into_luma8() / into_rgb8()
+// (src/reconstruction.rs:40-60); the pixels are DEFINED here as libjpeg's default decode (tests/ref_jpeg.py restates it and
+// is pinned to Pillow on encoder-made files).  The host (jpeg_common.hpp) walks the markers, builds one 16-bit-prefix
+// lookup per Huffman table and finds the scan's bytes; tables and scan go up in one copy.
+//
+//   jpeg_mark_kernel      a lane per byte of the scan: data byte, dropped byte (the 00 behind an FF, FF fill, a marker's
+//                         bytes) or RSTn; a ballot per wave -> per 64 bytes the data bytes and the markers; launch_scan_u64
+//   jpeg_compact_kernel   the data bytes to the clean buffer (no stuffing, no markers); marker k must be RST(k mod 8) and
+//                         gives restart interval k + 1 its first byte
+//   jpeg_segments_kernel  the subsequences (SUBSEQ_BITS bits) of every restart interval; a scan places them
+//   jpeg_sync_kernel      the self-synchronising decode: a lane decodes its subsequence from a guessed state (its first bit,
+//                         block slot 0, coefficient 0), records its exit state (bit, slot in the MCU, zig-zag index) and
+//                         the blocks it completed, and decodes again from its left neighbour's exit state until no state in
+//                         the workgroup changes.  Across workgroups the kernel is launched again, each first lane taking
+//                         the last exit state of the workgroup before it from the launch before, until a launch changes
+//                         no workgroup's last exit state.  The first subsequence of an interval starts from the known
+//                         state, so the settled states are the sequential decoder's, whatever the number of rounds
+//   jpeg_write_kernel     a scan of the block counts gives every subsequence its first block; one more decode from the
+//                         settled states stores DC differences and AC coefficients as int16 blocks in natural order
+//   jpeg_dc_kernel        per MCU and component the sum of its DC differences; a scan (the DC value of a block is a
+//                         difference of two prefix sums plus the differences before it in its MCU, 16-bit wrap)
+//   jpeg_idct_kernel      a lane per block: DC, dequantisation, jidctint in 64-bit integers, clamp, the 8 x 8 samples
+//                         into the component's plane
+//   jpeg_pixels_kernel    a lane per aligned dword of `out`: fancy upsampling, YCbCr -> RGB, luma, crop and drop_rows;
+//                         single bytes only in front of the first and behind the last whole dword
+// A decode from a wrong state is harmless: every read is bounded by the interval's end (the bits past it read as ones), an
+// unknown code consumes 16 bits and restarts the block, a run past coefficient 63 ends the block.  In the write pass, whose
+// states are the true ones, the same events are the file's errors.
+#include <cstring>
+#include <vector>
+
+#include "cvhip_internal.hpp"
+
+#include "jpeg_common.hpp"
+
+namespace cvhip {
+namespace {
+
+namespace jc = jpeg_common;
+
+constexpr int WAVE = 64;
+constexpr uint32_t BLOCK = 256;      // lanes of a workgroup; of jpeg_sync_kernel: the subsequences that settle within one launch
+constexpr uint32_t KIND_DROP = 0, KIND_DATA = 1, KIND_RST = 2;
+constexpr uint32_t ERR_RST = 1, ERR_CODE = 2, ERR_RUN = 4, ERR_DATA = 8;
+constexpr uint32_t FLAG_ERR = 0, FLAG_CHANGED = 1, FLAG_ROUNDS = 2, FLAG_SUBSEQUENCES = 3, FLAGS = 4;
+constexpr uint32_t SHORT_BITS = 10, SHORT_ENTRIES = 1u << SHORT_BITS, MAX_LUTS = 6; // the codes of up to 10 bits, per table, in LDS
+constexpr uint64_t MAX_SCAN_BYTES = 1ull << 31, MAX_BLOCKS = 1ull << 25;
+
+struct JpegParams {
+    uint32_t width, height, ncomp, hmax, vmax, mcus_x, mcus_y, bpm;
+    uint32_t interval; // MCUs of a restart interval (all of them without DRI)
+    uint32_t nseg, mcus;
+    uint32_t luma_blocks;          // the first component's blocks in an MCU; the others have one each
+    uint32_t dc_lut[3], ac_lut[3]; // the component's tables among the uploaded ones
+    uint32_t n_luts;
+};
+
+// (selects, not indexed loads: a lane-dependent index into the kernel's arguments would put them into scratch memory)
+__device__ __forceinline__ uint32_t slot_component(const JpegParams &P, uint32_t slot) { return slot < P.luma_blocks ? 0u : slot - P.luma_blocks + 1u; }
+__device__ __forceinline__ uint32_t pick(const uint32_t (&v)[3], uint32_t c) { return c == 0 ? v[0] : c == 1 ? v[1] : v[2]; }
+
+__device__ const uint8_t d_zigzag[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
+                                         41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
+                                         30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
+
+// What byte i of the scan[0 .. n) is.  One byte back and one ahead decide it (tests/ref_jpeg.py: segments).
+__device__ __forceinline__ uint32_t classify(const uint8_t *__restrict__ scan, unsigned long long n, unsigned long long i)
+{
+    const uint32_t b = scan[i], prev = i ? scan[i - 1] : 0u, next = i + 1 < n ? scan[i + 1] : 0x100u;
+    if (b == 0xFF) return (next == 0x00 || next == 0x100) ? KIND_DATA : KIND_DROP; // stuffed; fill, or a marker's first byte
+    if (prev == 0xFF) {
+        if (b == 0x00) return KIND_DROP;
+        if (b >= 0xD0 && b <= 0xD7) return KIND_RST;
+    }
+    return KIND_DATA;
+}
+
+// counts[i / 64] = data bytes | markers << 32 of bytes 64 (i / 64) .. + 63
+__global__ __launch_bounds__(BLOCK) void jpeg_mark_kernel(const uint8_t *__restrict__ scan, unsigned long long n, unsigned long long *__restrict__ counts)
+{
+    const unsigned long long i = (unsigned long long)blockIdx.x * BLOCK + threadIdx.x;
+    const uint32_t kind = i < n ? classify(scan, n, i) : KIND_DROP;
+    const unsigned long long data = __ballot(kind == KIND_DATA), rst = __ballot(kind == KIND_RST);
+    if ((threadIdx.x & 63u) == 0 && i < n) counts[i >> 6] = (unsigned long long)__popcll(data) | (unsigned long long)__popcll(rst) << 32;
+}
+
+// counts: scanned.  clean: the data bytes in order.  seg_start[k + 1] = the data bytes in front of marker k (zeroed before).
+__global__ __launch_bounds__(BLOCK) void jpeg_compact_kernel(const uint8_t *__restrict__ scan, unsigned long long n,
+                                                             const unsigned long long *__restrict__ counts, uint8_t *__restrict__ clean,
+                                                             unsigned long long *__restrict__ seg_start, uint32_t nseg, uint32_t *__restrict__ flags)
+{
+    const unsigned long long i = (unsigned long long)blockIdx.x * BLOCK + threadIdx.x;
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t kind = i < n ? classify(scan, n, i) : KIND_DROP;
+    const unsigned long long data = __ballot(kind == KIND_DATA), rst = __ballot(kind == KIND_RST), below = (1ull << lane) - 1ull;
+    if (i >= n) return;
+    const unsigned long long off = counts[i >> 6];
+    const unsigned long long at = (off & 0xFFFFFFFFull) + (unsigned long long)__popcll(data & below);
+    if (kind == KIND_DATA) clean[at] = scan[i]; // (at < the data bytes of the scan <= n)
+    if (kind == KIND_RST) {
+        const unsigned long long k = (off >> 32) + (unsigned long long)__popcll(rst & below);
+        if (k + 1 >= nseg || scan[i] != 0xD0u + (uint32_t)(k & 7u)) atomicOr(&flags[FLAG_ERR], ERR_RST); // surplus or misnumbered
+        else seg_start[k + 1] = at;
+    }
+}
+
+// sub_count[s] = the subsequences of interval s (at least one); *totals = the scan's data bytes | markers << 32
+__global__ __launch_bounds__(BLOCK) void jpeg_segments_kernel(unsigned long long *__restrict__ seg_start, uint32_t nseg,
+                                                              const unsigned long long *__restrict__ totals,
+                                                              unsigned long long *__restrict__ sub_count, uint32_t *__restrict__ flags)
+{
+    const uint32_t s = blockIdx.x * BLOCK + threadIdx.x;
+    if (s >= nseg) return;
+    const unsigned long long bytes = *totals & 0xFFFFFFFFull, markers = *totals >> 32;
+    if (s == 0 && markers + 1 != nseg) atomicOr(&flags[FLAG_ERR], ERR_RST); // a missing RSTn
+    const unsigned long long a = seg_start[s];
+    unsigned long long b = s + 1 < nseg ? seg_start[s + 1] : bytes;
+    if (b < a || b > bytes) b = a, atomicOr(&flags[FLAG_ERR], ERR_RST); // (only with a marker missing: the entry was never written)
+    const unsigned long long subs = ((b - a) * 8 + jc::SUBSEQ_BITS - 1) / jc::SUBSEQ_BITS;
+    sub_count[s] = subs ? subs : 1;
+    if (s + 1 == nseg) seg_start[nseg] = bytes;
+}
+
+// ---- the entropy decoder of one subsequence ---------------------------------------------------------------------------------------
+// A state: the next bit (of the clean buffer) | the block's slot in its MCU << 40 | the zig-zag index << 44
+__device__ __forceinline__ unsigned long long pack_state(unsigned long long p, uint32_t slot, uint32_t k)
+{
+    return p | (unsigned long long)slot << 40 | (unsigned long long)k << 44;
+}
+
+// the 64 bits of the clean buffer (big-endian) from word wi on, those at and past seg_end_bits read as ones; 32 wi < seg_end_bits
+__device__ __forceinline__ unsigned long long load_window(const uint32_t *__restrict__ words, unsigned long long wi, unsigned long long seg_end_bits)
+{
+    const unsigned long long base = wi << 5;
+    unsigned long long v = (unsigned long long)__builtin_bswap32(words[wi]) << 32 | __builtin_bswap32(words[wi + 1]);
+    if (seg_end_bits < base + 64) v |= ~0ull >> (seg_end_bits - base); // (1 .. 63 valid bits)
+    return v;
+}
+
+// s_short[t][the next SHORT_BITS bits] = table t's entry where the code there has at most SHORT_BITS bits, else 0 (look in the
+// whole table).  Nearly every symbol of a photograph is decoded from LDS; the whole tables stay in global memory.
+__device__ __forceinline__ void load_short_tables(const uint16_t *__restrict__ luts, uint32_t n_luts, uint16_t *s_short)
+{
+    for (uint32_t at = threadIdx.x; at < n_luts * SHORT_ENTRIES; at += BLOCK) {
+        const uint16_t entry = luts[(size_t)(at >> SHORT_BITS) * jc::LUT_ENTRIES + ((at & (SHORT_ENTRIES - 1u)) << (16 - SHORT_BITS))];
+        s_short[at] = (entry >> 8) <= SHORT_BITS ? entry : (uint16_t)0;
+    }
+    __syncthreads();
+}
+
+// Decodes from `state` while the next bit is below end_bit -> the exit state; blocks += the blocks completed.  WRITE: the
+// coefficients of blocks `block` .. below block_limit go to coef (the DC as its difference), and what the file does wrong is
+// flagged.
+template <bool WRITE>
+__device__ __forceinline__ unsigned long long decode_subsequence(const uint32_t *__restrict__ words, const uint16_t *__restrict__ luts,
+                                                                 const uint16_t *s_short, const JpegParams &P, unsigned long long state, unsigned long long end_bit,
+                                                                 unsigned long long seg_end_bits, unsigned long long &blocks,
+                                                                 short *__restrict__ coef, unsigned long long block, unsigned long long block_limit,
+                                                                 uint32_t *__restrict__ flags)
+{
+    unsigned long long p = state & ((1ull << 40) - 1ull);
+    uint32_t slot = (uint32_t)(state >> 40) & 15u, k = (uint32_t)(state >> 44) & 127u;
+    unsigned long long held_word = ~0ull, held = 0; // the window of word `held_word`: loaded once for the symbols that begin in it
+    while (p < end_bit) {
+        if (WRITE && block >= block_limit) break;
+        const uint32_t c = slot_component(P, slot);
+        const uint32_t table = k == 0 ? pick(P.dc_lut, c) : pick(P.ac_lut, c);
+        if ((p >> 5) != held_word) held_word = p >> 5, held = load_window(words, held_word, seg_end_bits);
+        const uint32_t win = (uint32_t)((held << (p & 31u)) >> 32); // the 32 bits at p
+        uint32_t entry = s_short[table * SHORT_ENTRIES + (win >> (32 - SHORT_BITS))];
+        if (entry == 0) entry = luts[(size_t)table * jc::LUT_ENTRIES + (win >> 16)];
+        const uint32_t len = entry >> 8, sym = entry & 255u;
+        if (len == 0) { // no such code: 16 bits are consumed and the block starts again
+            if (WRITE) atomicOr(&flags[FLAG_ERR], ERR_CODE);
+            p += 16, k = 0;
+            continue;
+        }
+        const uint32_t run = k == 0 ? 0u : sym >> 4, size = k == 0 ? sym : sym & 15u; // (a DC category is at most 15: jpeg_common.hpp)
+        p += len + size;
+        if (WRITE && p > seg_end_bits) atomicOr(&flags[FLAG_ERR], ERR_DATA); // the data ends inside a symbol
+        if (k != 0 && size == 0) {
+            if (run == 15 && k + 16 <= 64) k += 16;
+            else {
+                if (WRITE && run == 15) atomicOr(&flags[FLAG_ERR], ERR_RUN);
+                k = 64; // end of block
+            }
+        } else {
+            k += run;
+            if (k > 63) {
+                if (WRITE) atomicOr(&flags[FLAG_ERR], ERR_RUN);
+                k = 64;
+            } else {
+                if (WRITE) {
+                    int v = size ? (int)((win << len) >> (32 - size)) : 0;
+                    if (size && v < (1 << (size - 1))) v -= (1 << size) - 1;
+                    coef[block * 64 + d_zigzag[k]] = (short)v;
+                }
+                k++;
+            }
+        }
+        if (k >= 64) {
+            k = 0;
+            slot = slot + 1 == P.bpm ? 0u : slot + 1;
+            blocks++, block++;
+        }
+    }
+    return pack_state(p, slot, k);
+}
+
+// the interval of subsequence i: the last s with sub_first[s] <= i (sub_first[nseg] = the subsequences of the scan > i)
+__device__ __forceinline__ uint32_t interval_of(const unsigned long long *__restrict__ sub_first, uint32_t nseg, unsigned long long i)
+{
+    uint32_t lo = 0, hi = nseg;
+    while (hi - lo > 1) {
+        const uint32_t mid = lo + (hi - lo) / 2;
+        if (sub_first[mid] <= i) lo = mid;
+        else hi = mid;
+    }
+    return lo;
+}
+
+// round 0: every subsequence from its guess, settled within the workgroup.  round > 0: the first lane of a workgroup takes
+// exit_in[i - 1], the launch before's; flags[FLAG_CHANGED] is set when a workgroup's last exit state differs from exit_in's.
+__global__ __launch_bounds__(BLOCK) void jpeg_sync_kernel(const uint32_t *__restrict__ words, const uint16_t *__restrict__ luts, JpegParams P,
+                                                          const unsigned long long *__restrict__ seg_start,
+                                                          const unsigned long long *__restrict__ sub_first, unsigned long long *__restrict__ entry,
+                                                          const unsigned long long *__restrict__ exit_in, unsigned long long *__restrict__ exit_out,
+                                                          unsigned long long *__restrict__ counts, uint32_t round, uint32_t *__restrict__ flags)
+{
+    __shared__ unsigned long long s_exit[BLOCK];
+    __shared__ uint16_t s_short[MAX_LUTS * SHORT_ENTRIES];
+    if (flags[FLAG_ERR]) return; // (set by the kernels before this one only: the same for every lane)
+    load_short_tables(luts, P.n_luts, s_short);
+    const unsigned long long i = (unsigned long long)blockIdx.x * BLOCK + threadIdx.x, total = sub_first[P.nseg];
+    const bool active = i < total;
+    unsigned long long fixed = 0, end_bit = 0, seg_end_bits = 0, cur_entry = 0, cur_exit = 0, blocks = 0, old_exit = 0;
+    bool known = false;
+    if (active) {
+        const uint32_t s = interval_of(sub_first, P.nseg, i);
+        const unsigned long long j = i - sub_first[s], first_bit = seg_start[s] * 8 + j * jc::SUBSEQ_BITS;
+        seg_end_bits = seg_start[s + 1] * 8;
+        end_bit = first_bit + jc::SUBSEQ_BITS < seg_end_bits ? first_bit + jc::SUBSEQ_BITS : seg_end_bits;
+        known = j == 0;
+        fixed = pack_state(first_bit, 0, 0); // the true state of an interval's first subsequence, the guess of the others
+        if (round == 0) {
+            cur_entry = fixed;
+            cur_exit = decode_subsequence<false>(words, luts, s_short, P, cur_entry, end_bit, seg_end_bits, blocks, nullptr, 0, 0, nullptr);
+        } else {
+            cur_entry = entry[i], cur_exit = old_exit = exit_in[i], blocks = counts[i];
+        }
+    }
+    s_exit[threadIdx.x] = cur_exit;
+    uint32_t rounds = 0;
+    for (;;) {
+        __syncthreads();
+        unsigned long long want = cur_entry;
+        if (active && !known) {
+            if (threadIdx.x) want = s_exit[threadIdx.x - 1];
+            else if (round) want = exit_in[i - 1];
+        }
+        const bool change = want != cur_entry;
+        if (!__syncthreads_or(change)) break; // (and every lane has read before any lane writes)
+        if (change) {
+            cur_entry = want, blocks = 0;
+            cur_exit = decode_subsequence<false>(words, luts, s_short, P, cur_entry, end_bit, seg_end_bits, blocks, nullptr, 0, 0, nullptr);
+            s_exit[threadIdx.x] = cur_exit;
+        }
+        rounds++;
+    }
+    if (active) {
+        entry[i] = cur_entry, exit_out[i] = cur_exit, counts[i] = blocks;
+        if (threadIdx.x == BLOCK - 1 && (round == 0 || cur_exit != old_exit)) atomicOr(&flags[FLAG_CHANGED], 1u);
+    }
+    if (threadIdx.x == 0 && rounds) atomicMax(&flags[FLAG_ROUNDS], rounds);
+}
+
+// counts: scanned, counts[the launch's lanes] = their total.  coef was zeroed.
+__global__ __launch_bounds__(BLOCK) void jpeg_write_kernel(const uint32_t *__restrict__ words, const uint16_t *__restrict__ luts, JpegParams P,
+                                                           const unsigned long long *__restrict__ seg_start,
+                                                           const unsigned long long *__restrict__ sub_first,
+                                                           const unsigned long long *__restrict__ entry, const unsigned long long *__restrict__ counts,
+                                                           short *__restrict__ coef, uint32_t *__restrict__ flags)
+{
+    __shared__ uint16_t s_short[MAX_LUTS * SHORT_ENTRIES];
+    if (flags[FLAG_ERR] & ERR_RST) return; // (set by the kernels before this one only: the same for every lane)
+    load_short_tables(luts, P.n_luts, s_short);
+    const unsigned long long i = (unsigned long long)blockIdx.x * BLOCK + threadIdx.x;
+    if (i == 0) flags[FLAG_SUBSEQUENCES] = (uint32_t)sub_first[P.nseg];
+    if (i >= sub_first[P.nseg]) return;
+    const uint32_t s = interval_of(sub_first, P.nseg, i);
+    const unsigned long long j = i - sub_first[s], first_bit = seg_start[s] * 8 + j * jc::SUBSEQ_BITS, seg_end_bits = seg_start[s + 1] * 8;
+    const unsigned long long end_bit = first_bit + jc::SUBSEQ_BITS < seg_end_bits ? first_bit + jc::SUBSEQ_BITS : seg_end_bits;
+    // the interval's blocks: those of its MCUs, the last interval's may be fewer
+    const unsigned long long first_mcu = (unsigned long long)s * P.interval;
+    const unsigned long long mcus = P.mcus - first_mcu < P.interval ? P.mcus - first_mcu : P.interval, want = mcus * P.bpm;
+    const unsigned long long before = counts[i] - counts[sub_first[s]], here = counts[i + 1] - counts[i];
+    if (i + 1 == sub_first[s + 1] && before + here < want) atomicOr(&flags[FLAG_ERR], ERR_DATA); // the data ends before the last MCU
+    if (before >= want) return; // (what follows an interval's last block is not read)
+    unsigned long long blocks = 0;
+    decode_subsequence<true>(words, luts, s_short, P, entry[i], end_bit, seg_end_bits, blocks, coef, first_mcu * P.bpm + before, first_mcu * P.bpm + want, flags);
+}
+
+// sums[c * mcus + m] = the sum of the DC differences of component c's blocks in MCU m
+__global__ __launch_bounds__(BLOCK) void jpeg_dc_kernel(const short *__restrict__ coef, JpegParams P, unsigned long long *__restrict__ sums)
+{
+    const uint32_t m = blockIdx.x * BLOCK + threadIdx.x;
+    if (m >= P.mcus) return;
+    long long luma = 0;
+    for (uint32_t slot = 0; slot < P.bpm; slot++) {
+        const long long diff = coef[((unsigned long long)m * P.bpm + slot) * 64];
+        if (slot < P.luma_blocks) luma += diff;
+        else sums[(unsigned long long)(slot - P.luma_blocks + 1) * P.mcus + m] = (unsigned long long)diff;
+    }
+    sums[m] = (unsigned long long)luma;
+}
+
+// jidctint's one-dimensional pass (CONST_BITS 13) over v[0 .. 8), descaled by SHIFT
+template <int SHIFT> __device__ __forceinline__ void idct_pass(long long (&v)[8])
+{
+    long long z2 = v[2], z3 = v[6];
+    long long z1 = (z2 + z3) * 4433;
+    long long tmp2 = z1 - z3 * 15137, tmp3 = z1 + z2 * 6270;
+    long long tmp0 = (v[0] + v[4]) * 8192, tmp1 = (v[0] - v[4]) * 8192;
+    const long long tmp10 = tmp0 + tmp3, tmp13 = tmp0 - tmp3, tmp11 = tmp1 + tmp2, tmp12 = tmp1 - tmp2;
+    tmp0 = v[7], tmp1 = v[5], tmp2 = v[3], tmp3 = v[1];
+    z1 = tmp0 + tmp3, z2 = tmp1 + tmp2, z3 = tmp0 + tmp2;
+    long long z4 = tmp1 + tmp3;
+    const long long z5 = (z3 + z4) * 9633;
+    tmp0 *= 2446, tmp1 *= 16819, tmp2 *= 25172, tmp3 *= 12299;
+    z1 *= -7373, z2 *= -20995, z3 = z3 * -16069 + z5, z4 = z4 * -3196 + z5;
+    tmp0 += z1 + z3, tmp1 += z2 + z4, tmp2 += z2 + z3, tmp3 += z1 + z4;
+    const long long half = 1ll << (SHIFT - 1);
+    v[0] = (tmp10 + tmp3 + half) >> SHIFT, v[7] = (tmp10 - tmp3 + half) >> SHIFT;
+    v[1] = (tmp11 + tmp2 + half) >> SHIFT, v[6] = (tmp11 - tmp2 + half) >> SHIFT;
+    v[2] = (tmp12 + tmp1 + half) >> SHIFT, v[5] = (tmp12 - tmp1 + half) >> SHIFT;
+    v[3] = (tmp13 + tmp0 + half) >> SHIFT, v[4] = (tmp13 - tmp0 + half) >> SHIFT;
+}
+
+struct Planes {
+    uint8_t *base[3];
+    uint32_t stride[3]; // bytes of a row: the component's blocks across, times 8
+};
+
+// sums: scanned.  quant: [component][64], natural order.  64-bit integers throughout: |coefficient| <= 2^15 times a table entry
+// < 2^16 is < 2^31, a pass multiplies by < 2^15 and adds 8 terms, so the columns stay below 2^50 (2^39 descaled) and the rows
+// below 2^58 - what an encoder emits would fit 32 bits, what a file may hold does not, and the definition clamps.
+__global__ __launch_bounds__(WAVE) void jpeg_idct_kernel(const short *__restrict__ coef, JpegParams P, const unsigned long long *__restrict__ sums,
+                                                         const uint16_t *__restrict__ quant, Planes planes, unsigned long long n_blocks,
+                                                         const uint32_t *__restrict__ flags)
+{
+    __shared__ uint32_t s_quant[3 * 64];
+    if (flags[FLAG_ERR]) return;
+    for (uint32_t k = threadIdx.x; k < P.ncomp * 64; k += WAVE) s_quant[k] = quant[k];
+    __syncthreads();
+    const unsigned long long b = (unsigned long long)blockIdx.x * WAVE + threadIdx.x;
+    if (b >= n_blocks) return;
+    const uint32_t m = (uint32_t)(b / P.bpm), slot = (uint32_t)(b % P.bpm), c = slot_component(P, slot);
+    const short *in = coef + b * 64;
+    // the DC value: the differences of the component from the interval's first MCU on, in 16 bits
+    const unsigned long long *comp_sums = sums + (unsigned long long)c * P.mcus;
+    long long dc = (long long)(comp_sums[m] - comp_sums[m / P.interval * P.interval]);
+    const uint32_t first_slot = c == 0 ? 0u : slot; // the component's first slot in the MCU
+    for (uint32_t q = first_slot; q <= slot; q++) dc += coef[((unsigned long long)m * P.bpm + q) * 64];
+    long long ws[64];
+#pragma unroll
+    for (int col = 0; col < 8; col++) {
+        long long v[8];
+#pragma unroll
+        for (int r = 0; r < 8; r++) v[r] = (long long)in[r * 8 + col] * (long long)s_quant[c * 64 + r * 8 + col];
+        if (col == 0) v[0] = (long long)(short)dc * (long long)s_quant[c * 64];
+        idct_pass<11>(v);
+#pragma unroll
+        for (int r = 0; r < 8; r++) ws[r * 8 + col] = v[r];
+    }
+    const uint32_t q = slot - first_slot, across = c == 0 ? P.hmax : 1u, down = c == 0 ? P.vmax : 1u;
+    const uint32_t bx = (m % P.mcus_x) * across + q % across, by = (m / P.mcus_x) * down + q / across;
+    uint8_t *dst = planes.base[c] + ((unsigned long long)by * 8) * planes.stride[c] + (unsigned long long)bx * 8;
+#pragma unroll
+    for (int r = 0; r < 8; r++) {
+        long long v[8];
+#pragma unroll
+        for (int col = 0; col < 8; col++) v[col] = ws[r * 8 + col];
+        idct_pass<18>(v);
+        uint32_t lo = 0, hi = 0;
+#pragma unroll
+        for (int col = 0; col < 8; col++) {
+            const long long x = v[col] + 128;
+            const uint32_t px = x < 0 ? 0u : x > 255 ? 255u : (uint32_t)x;
+            if (col < 4) lo |= px << (8 * col);
+            else hi |= px << (8 * (col - 4));
+        }
+        *reinterpret_cast<uint2 *>(dst + (unsigned long long)r * planes.stride[c]) = make_uint2(lo, hi); // (8-byte aligned: strides and bx * 8 are)
+    }
+}
+
+// libjpeg's fancy upsampling of a chroma plane of dw x dh samples that count, at pixel (x, y) (tests/ref_jpeg.py: upsample)
+__device__ __forceinline__ int chroma_at(const uint8_t *__restrict__ plane, uint32_t stride, uint32_t dw, uint32_t dh, uint32_t hs, uint32_t vs,
+                                         uint32_t x, uint32_t y)
+{
+    if (hs == 1) return plane[(unsigned long long)y * stride + x];
+    const uint32_t i = x >> 1;
+    if (vs == 1) {
+        const uint8_t *row = plane + (unsigned long long)y * stride;
+        if (dw <= 2 || x == 0 || x == 2 * dw - 1) return row[i];
+        return (x & 1u) ? (3 * row[i] + row[i + 1] + 2) >> 2 : (3 * row[i] + row[i - 1] + 1) >> 2;
+    }
+    const uint32_t r = y >> 1;
+    if (dw <= 2) return plane[(unsigned long long)r * stride + i];
+    const uint32_t other = (y & 1u) ? (r + 1 < dh ? r + 1 : dh - 1) : (r ? r - 1 : 0u);
+    const uint8_t *near = plane + (unsigned long long)r * stride, *far = plane + (unsigned long long)other * stride;
+    const int t = 3 * near[i] + far[i];
+    if (x == 0) return (4 * t + 8) >> 4;
+    if (x == 2 * dw - 1) return (4 * t + 7) >> 4;
+    return (x & 1u) ? (3 * t + 3 * near[i + 1] + far[i + 1] + 7) >> 4 : (3 * t + 3 * near[i - 1] + far[i - 1] + 8) >> 4;
+}
+
+__device__ __forceinline__ uint32_t clamp_byte(int v) { return v < 0 ? 0u : v > 255 ? 255u : (uint32_t)v; }
+
+// pixel `pix` of the width x rows result: r | g << 8 | b << 16 (a grey file: its sample three times)
+__device__ __forceinline__ uint32_t pixel_rgb(const JpegParams &P, const Planes &planes, uint32_t dw, uint32_t dh, uint32_t pix)
+{
+    const uint32_t x = pix % P.width, y = pix / P.width;
+    const int luma = planes.base[0][(unsigned long long)y * planes.stride[0] + x];
+    if (P.ncomp == 1) return (uint32_t)luma * 0x010101u;
+    const int cb = chroma_at(planes.base[1], planes.stride[1], dw, dh, P.hmax, P.vmax, x, y) - 128;
+    const int cr = chroma_at(planes.base[2], planes.stride[2], dw, dh, P.hmax, P.vmax, x, y) - 128;
+    const uint32_t r = clamp_byte(luma + ((91881 * cr + 32768) >> 16)), b = clamp_byte(luma + ((116130 * cb + 32768) >> 16));
+    const uint32_t g = clamp_byte(luma + ((-22554 * cb - 46802 * cr + 32768) >> 16));
+    return r | g << 8 | b << 16;
+}
+
+// byte `at` of the result (channels: 1 = Luma8, 3 = RGB8)
+__device__ __forceinline__ uint32_t result_byte(const JpegParams &P, const Planes &planes, uint32_t dw, uint32_t dh, uint32_t channels,
+                                                unsigned long long at)
+{
+    if (channels == 3) return (pixel_rgb(P, planes, dw, dh, (uint32_t)(at / 3)) >> (8 * (uint32_t)(at % 3))) & 255u;
+    if (P.ncomp == 1) return pixel_rgb(P, planes, dw, dh, (uint32_t)at) & 255u;
+    const uint32_t rgb = pixel_rgb(P, planes, dw, dh, (uint32_t)at);
+    return (2126u * (rgb & 255u) + 7152u * ((rgb >> 8) & 255u) + 722u * (rgb >> 16)) / 10000u; // into_luma8, as remembered
+}
+
+// out[0 .. bytes): `lead` single bytes up to the first 4-byte aligned address, whole dwords, the rest single bytes - a lane
+// per dword and a lane per single byte
+__global__ __launch_bounds__(BLOCK) void jpeg_pixels_kernel(JpegParams P, Planes planes, uint32_t channels, uint8_t *__restrict__ out,
+                                                            unsigned long long bytes, uint32_t lead, const uint32_t *__restrict__ flags)
+{
+    if (flags[FLAG_ERR]) return;
+    const uint32_t dw = (P.width + P.hmax - 1) / P.hmax, dh = (P.height + P.vmax - 1) / P.vmax;
+    const unsigned long long t = (unsigned long long)blockIdx.x * BLOCK + threadIdx.x, dwords = (bytes - lead) / 4;
+    if (t < dwords) {
+        const unsigned long long at = lead + 4 * t;
+        uint32_t word = 0;
+        if (channels == 3) {
+            const uint32_t pix = (uint32_t)(at / 3), c = (uint32_t)(at % 3);
+            const unsigned long long both = (unsigned long long)pixel_rgb(P, planes, dw, dh, pix) |
+                                            (unsigned long long)(at + 3 - c < bytes ? pixel_rgb(P, planes, dw, dh, pix + 1) : 0u) << 24;
+            word = (uint32_t)(both >> (8 * c));
+        } else {
+#pragma unroll
+            for (uint32_t k = 0; k < 4; k++) word |= result_byte(P, planes, dw, dh, 1, at + k) << (8 * k);
+        }
+        *reinterpret_cast<uint32_t *>(out + at) = word;
+        return;
+    }
+    const unsigned long long single = t - dwords, singles = bytes - 4 * dwords;
+    if (single >= singles) return;
+    const unsigned long long at = single < lead ? single : 4 * dwords + single;
+    out[at] = (uint8_t)result_byte(P, planes, dw, dh, channels, at);
+}
+
+thread_local uint64_t t_stats[4] = {0, 0, 0, 0}; // of the thread's last decode: intervals, subsequences, sync launches, rounds within a workgroup
+
+int refused(const char *what, int code, const char *why) { return fail(code == jc::UNSUPPORTED ? CVHIP_ERR_UNSUPPORTED : CVHIP_ERR_INVALID, std::string(what) + ": " + why); }
+
+} // namespace
+} // namespace cvhip
+
+using namespace cvhip;
+
+extern "C" int cvhip_jpeg_info(const uint8_t *file, uint64_t size, uint32_t *out_info)
+{
+    if (!file || !out_info) return fail(CVHIP_ERR_INVALID, "jpeg_info: null argument");
+    jc::Header h;
+    const int rc = jc::parse(file, (size_t)size, h);
+    if (rc != jc::OK) return refused("jpeg_info", rc, h.error);
+    out_info[0] = h.width, out_info[1] = h.height, out_info[2] = h.components, out_info[3] = h.hmax, out_info[4] = h.vmax;
+    out_info[5] = h.focal_length_35mm;
+    return CVHIP_OK;
+}
+
+extern "C" int cvhip_jpeg_last_stats(uint64_t *out_stats)
+{
+    if (!out_stats) return fail(CVHIP_ERR_INVALID, "jpeg_last_stats: null argument");
+    for (int k = 0; k < 4; k++) out_stats[k] = t_stats[k];
+    return CVHIP_OK;
+}
+
+extern "C" int cvhip_jpeg_decode(cvhip_device *dev, const uint8_t *file, uint64_t size, uint32_t format, uint32_t drop_rows, uint8_t *out,
+                                 uint64_t cap, uint64_t *out_size)
+{
+    if (!dev || !file || !out_size || (cap && !out)) return fail(CVHIP_ERR_INVALID, "jpeg_decode: null argument");
+    if (format != CVHIP_IMAGE_LUMA8 && format != CVHIP_IMAGE_RGB8) return fail(CVHIP_ERR_INVALID, "jpeg_decode: format is not CVHIP_IMAGE_LUMA8 or CVHIP_IMAGE_RGB8");
+    jc::Header h;
+    const int rc = jc::parse(file, (size_t)size, h);
+    if (rc != jc::OK) return refused("jpeg_decode", rc, h.error);
+    if (drop_rows >= h.height) return fail(CVHIP_ERR_INVALID, "jpeg_decode: drop_rows leaves no row");
+    const uint32_t channels = format == CVHIP_IMAGE_RGB8 ? 3u : 1u;
+    const unsigned long long bytes = (unsigned long long)h.width * (h.height - drop_rows) * channels;
+    *out_size = bytes;
+    if (!cap) return CVHIP_OK;
+    if (cap < bytes) return fail(CVHIP_ERR_INVALID, "jpeg_decode: the buffer is smaller than the image");
+    const unsigned long long n = h.scan_end - h.scan_begin, nseg = jc::segments(h);
+    JpegParams P{};
+    P.width = h.width, P.height = h.height, P.ncomp = h.components, P.hmax = h.hmax, P.vmax = h.vmax, P.mcus_x = h.mcus_x, P.mcus_y = h.mcus_y;
+    P.bpm = jc::blocks_per_mcu(h), P.mcus = h.mcus_x * h.mcus_y, P.interval = h.restart ? h.restart : P.mcus, P.nseg = (uint32_t)nseg;
+    const unsigned long long n_blocks = (unsigned long long)P.mcus * P.bpm;
+    if (n == 0) return fail(CVHIP_ERR_INVALID, "jpeg_decode: the data ends before the last MCU");
+    if (n >= MAX_SCAN_BYTES) return fail(CVHIP_ERR_UNSUPPORTED, "jpeg_decode: a scan of 2^31 or more bytes");
+    if (n_blocks > MAX_BLOCKS) return fail(CVHIP_ERR_UNSUPPORTED, "jpeg_decode: more than 2^25 blocks");
+    if (nseg > n) return fail(CVHIP_ERR_INVALID, "jpeg_decode: a missing RSTn"); // (every marker takes two bytes)
+    P.luma_blocks = h.hmax * h.vmax;
+    // ---- the one upload: the components' quantisation tables, the lookups of the tables the scan uses, the scan's bytes
+    int lut_of[2][4] = {{-1, -1, -1, -1}, {-1, -1, -1, -1}};
+    uint32_t n_luts = 0;
+    for (uint32_t c = 0; c < P.ncomp; c++) {
+        if (lut_of[0][h.comp[c].td] < 0) lut_of[0][h.comp[c].td] = (int)n_luts++;
+        if (lut_of[1][h.comp[c].ta] < 0) lut_of[1][h.comp[c].ta] = (int)n_luts++;
+        P.dc_lut[c] = (uint32_t)lut_of[0][h.comp[c].td], P.ac_lut[c] = (uint32_t)lut_of[1][h.comp[c].ta];
+    }
+    P.n_luts = n_luts;
+    const size_t quant_bytes = 3 * 64 * sizeof(uint16_t), lut_bytes = (size_t)n_luts * jc::LUT_ENTRIES * sizeof(uint16_t);
+    std::vector<uint8_t> blob(quant_bytes + lut_bytes + (size_t)n);
+    for (uint32_t c = 0; c < P.ncomp; c++) std::memcpy(blob.data() + c * 64 * sizeof(uint16_t), h.quant[h.comp[c].tq], 64 * sizeof(uint16_t));
+    for (int cls = 0; cls < 2; cls++)
+        for (int id = 0; id < 4; id++)
+            if (lut_of[cls][id] >= 0)
+                jc::build_lut(h.huff[cls][id], reinterpret_cast<uint16_t *>(blob.data() + quant_bytes) + (size_t)lut_of[cls][id] * jc::LUT_ENTRIES);
+    std::memcpy(blob.data() + quant_bytes + lut_bytes, file + h.scan_begin, (size_t)n);
+
+    CVHIP_TRY_HIP(hipSetDevice(dev->d.ordinal));
+    hipStream_t s = dev->d.stream;
+    CallScratch sc;
+    const unsigned long long chunks = (n + 63) / 64, sub_cap = n / (jc::SUBSEQ_BITS / 8) + nseg + 1;
+    const uint32_t sync_blocks = (uint32_t)((sub_cap + BLOCK - 1) / BLOCK);
+    uint8_t *d_blob = nullptr, *clean = nullptr, *plane_bytes = nullptr, *d_out = nullptr;
+    unsigned long long *chunk_counts = nullptr, *seg_start = nullptr, *sub_first = nullptr, *states = nullptr, *counts = nullptr, *sums = nullptr;
+    uint32_t *flags = nullptr, h_flags[FLAGS] = {0, 0, 0, 0};
+    short *coef = nullptr;
+    Planes planes{};
+    size_t plane_total = 0, plane_at[3] = {0, 0, 0};
+    for (uint32_t c = 0; c < P.ncomp; c++) {
+        planes.stride[c] = h.mcus_x * (c == 0 ? h.hmax : 1u) * 8u;
+        plane_at[c] = plane_total;
+        plane_total += (size_t)planes.stride[c] * h.mcus_y * (c == 0 ? h.vmax : 1u) * 8u; // (a multiple of 64 bytes)
+    }
+    // one allocation, carved: an allocation costs more than most of these kernels
+    size_t arena_bytes = 0;
+    auto reserve = [&](size_t nbytes) {
+        const size_t at = arena_bytes;
+        arena_bytes += (nbytes + 255) / 256 * 256;
+        return at;
+    };
+    const size_t at_blob = reserve(blob.size()), at_clean = reserve((size_t)n + 16); // (window() reads the word behind a position's own)
+    const size_t at_chunks = reserve(((size_t)chunks + 1) * 8), at_seg = reserve(((size_t)nseg + 1) * 8), at_sub = reserve(((size_t)nseg + 1) * 8);
+    const size_t at_states = reserve((size_t)sub_cap * 3 * 8); // entry states, and the exit states of two launches
+    const size_t at_counts = reserve(((size_t)sub_cap + 1) * 8), at_flags = reserve(FLAGS * sizeof(uint32_t));
+    const size_t at_coef = reserve((size_t)n_blocks * 64 * sizeof(short)), at_sums = reserve(((size_t)P.ncomp * P.mcus + 1) * 8);
+    const size_t at_planes = reserve(plane_total);
+    uint8_t *arena = nullptr;
+    hipError_t e = sc.alloc(&arena, arena_bytes);
+    if (e == hipSuccess) e = sc.output(out, (size_t)bytes, &d_out);
+    if (e != hipSuccess) return device_error("jpeg_decode", e);
+    d_blob = arena + at_blob, clean = arena + at_clean, plane_bytes = arena + at_planes;
+    chunk_counts = reinterpret_cast<unsigned long long *>(arena + at_chunks), seg_start = reinterpret_cast<unsigned long long *>(arena + at_seg);
+    sub_first = reinterpret_cast<unsigned long long *>(arena + at_sub), states = reinterpret_cast<unsigned long long *>(arena + at_states);
+    counts = reinterpret_cast<unsigned long long *>(arena + at_counts), sums = reinterpret_cast<unsigned long long *>(arena + at_sums);
+    flags = reinterpret_cast<uint32_t *>(arena + at_flags), coef = reinterpret_cast<short *>(arena + at_coef);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_blob, blob.data(), blob.size(), hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemsetAsync(seg_start, 0, ((size_t)nseg + 1) * sizeof(unsigned long long), s);
+    if (e == hipSuccess) e = hipMemsetAsync(counts, 0, ((size_t)sub_cap + 1) * sizeof(unsigned long long), s);
+    if (e == hipSuccess) e = hipMemsetAsync(flags, 0, FLAGS * sizeof(uint32_t), s);
+    if (e == hipSuccess) e = hipMemsetAsync(coef, 0, (size_t)n_blocks * 64 * sizeof(short), s);
+    if (e != hipSuccess) return device_error("jpeg_decode", e);
+    for (uint32_t c = 0; c < P.ncomp; c++) planes.base[c] = plane_bytes + plane_at[c];
+    const uint16_t *d_quant = reinterpret_cast<const uint16_t *>(d_blob), *d_luts = reinterpret_cast<const uint16_t *>(d_blob + quant_bytes);
+    const uint8_t *d_scan = d_blob + quant_bytes + lut_bytes;
+    const uint32_t *words = reinterpret_cast<const uint32_t *>(clean);
+    unsigned long long *entry = states, *exits[2] = {states + sub_cap, states + 2 * sub_cap};
+    const dim3 block(BLOCK), byte_grid((uint32_t)((n + BLOCK - 1) / BLOCK));
+    hipLaunchKernelGGL(jpeg_mark_kernel, byte_grid, block, 0, s, d_scan, n, chunk_counts);
+    launch_scan_u64(chunk_counts, chunks, chunk_counts + chunks, s);
+    hipLaunchKernelGGL(jpeg_compact_kernel, byte_grid, block, 0, s, d_scan, n, chunk_counts, clean, seg_start, P.nseg, flags);
+    hipLaunchKernelGGL(jpeg_segments_kernel, dim3((uint32_t)((nseg + BLOCK - 1) / BLOCK)), block, 0, s, seg_start, P.nseg, chunk_counts + chunks, sub_first,
+                       flags);
+    launch_scan_u64(sub_first, nseg, sub_first + nseg, s);
+    // ---- the states settle: within the workgroups, then across them, a launch and one flag back per round
+    hipLaunchKernelGGL(jpeg_sync_kernel, dim3(sync_blocks), block, 0, s, words, d_luts, P, seg_start, sub_first, entry, exits[0], exits[0], counts, 0u,
+                       flags);
+    uint32_t launches = 1;
+    for (uint32_t from = 0; sync_blocks > 1; from ^= 1u, launches++) {
+        if (launches > sync_blocks + 1) return fail(CVHIP_ERR_DEVICE, "jpeg_decode: the decoder's states did not settle");
+        e = hipGetLastError();
+        if (e == hipSuccess) e = hipMemsetAsync(flags + FLAG_CHANGED, 0, sizeof(uint32_t), s);
+        if (e != hipSuccess) return device_error("jpeg_decode", e);
+        hipLaunchKernelGGL(jpeg_sync_kernel, dim3(sync_blocks), block, 0, s, words, d_luts, P, seg_start, sub_first, entry, exits[from], exits[from ^ 1u],
+                           counts, launches, flags);
+        e = hipGetLastError();
+        if (e == hipSuccess) e = hipMemcpyAsync(h_flags, flags, sizeof(h_flags), hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        if (e != hipSuccess) return device_error("jpeg_decode", e);
+        if (h_flags[FLAG_ERR] || !h_flags[FLAG_CHANGED]) {
+            launches++;
+            break;
+        }
+    }
+    launch_scan_u64(counts, sub_cap, counts + sub_cap, s);
+    hipLaunchKernelGGL(jpeg_write_kernel, dim3(sync_blocks), block, 0, s, words, d_luts, P, seg_start, sub_first, entry, counts, coef, flags);
+    hipLaunchKernelGGL(jpeg_dc_kernel, dim3((P.mcus + BLOCK - 1) / BLOCK), block, 0, s, coef, P, sums);
+    launch_scan_u64(sums, (unsigned long long)P.ncomp * P.mcus, sums + (size_t)P.ncomp * P.mcus, s);
+    hipLaunchKernelGGL(jpeg_idct_kernel, dim3((uint32_t)((n_blocks + WAVE - 1) / WAVE)), dim3(WAVE), 0, s, coef, P, sums, d_quant, planes, n_blocks, flags);
+    const uint32_t lead = (uint32_t)std::min<unsigned long long>(bytes, (4 - (reinterpret_cast<uintptr_t>(d_out) & 3u)) & 3u);
+    const unsigned long long lanes = (bytes - lead) / 4 + lead + (bytes - lead) % 4;
+    hipLaunchKernelGGL(jpeg_pixels_kernel, dim3((uint32_t)((lanes + BLOCK - 1) / BLOCK)), block, 0, s, P, planes, channels, d_out, bytes, lead, flags);
+    e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(h_flags, flags, sizeof(h_flags), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) return device_error("jpeg_decode", e);
+    t_stats[0] = nseg, t_stats[1] = h_flags[FLAG_SUBSEQUENCES], t_stats[2] = launches, t_stats[3] = h_flags[FLAG_ROUNDS];
+    const uint32_t err = h_flags[FLAG_ERR];
+    if (err & ERR_RST) return fail(CVHIP_ERR_INVALID, "jpeg_decode: a missing, surplus or misnumbered RSTn");
+    if (err & ERR_CODE) return fail(CVHIP_ERR_INVALID, "jpeg_decode: a code that is not in its table");
+    if (err & ERR_RUN) return fail(CVHIP_ERR_INVALID, "jpeg_decode: a run past coefficient 63");
+    if (err & ERR_DATA) return fail(CVHIP_ERR_INVALID, "jpeg_decode: the data ends before the last MCU");
+    e = sc.copy_out(out, d_out, (size_t)bytes, s);
+    if (e == hipSuccess) e = sc.drain(s);
+    if (e != hipSuccess) return device_error("jpeg_decode", e);
+    return CVHIP_OK;
+}

@@ -1,0 +1,105 @@
+"""Image files in: what SourceImage::load / load_rgb do with a path (src/reconstruction.rs:39-60) - the
+file's pixels as Luma8 or RGB8 with `databar_height` rows cut from the bottom, the EXIF FocalLengthIn35mmFilm (:138-142) -
+and SourceImage::calibration_matrix (:164-185).  JPEG only (baseline; cvhip_jpeg_decode): the host walks the markers, the
+entropy decode, IDCT, upsampling and colour conversion run on the device.  TIFF, PNG and progressive JPEG input are not
+built."""
+from __future__ import annotations
+
+import ctypes as C
+import math
+from dataclasses import dataclass
+from pathlib import Path
+
+import numpy as np
+
+from . import _lib
+
+LUMA8, RGB8 = 0, 1  # CVHIP_IMAGE_LUMA8, CVHIP_IMAGE_RGB8
+_MODES = {"L": LUMA8, "RGB": RGB8}
+
+
+def _file(data):
+    buf = np.frombuffer(bytes(data), dtype=np.uint8) if not isinstance(data, np.ndarray) else np.ascontiguousarray(data, dtype=np.uint8).reshape(-1)
+    one = np.zeros(1, dtype=np.uint8)  # (an address for an empty file: the library reports what is wrong)
+    return C.c_void_p((buf if buf.size else one).ctypes.data), int(buf.size), (buf, one)
+
+
+def jpeg_info(data) -> dict:
+    """cvhip_jpeg_info of a file's bytes (host only) -> width, height, components, h, v (the luma sampling factors) and
+    focal_length_35mm (None when the file has none)."""
+    p, n, _keep = _file(data)
+    info = np.zeros(6, dtype=np.uint32)
+    _lib.check(_lib.lib().cvhip_jpeg_info(p, n, C.c_void_p(info.ctypes.data)), "cvhip_jpeg_info")
+    w, h, comps, hs, vs, focal = (int(v) for v in info)
+    return {"width": w, "height": h, "components": comps, "h": hs, "v": vs, "focal_length_35mm": focal or None}
+
+
+def decode_jpeg(device, data, mode: str = "L", drop_rows: int = 0, out=None):
+    """cvhip_jpeg_decode of a file's bytes -> [height - drop_rows, width] (mode "L") or [.., .., 3] (mode "RGB") uint8.
+    out: None - a numpy array; "device" - a torch tensor on the device; or the numpy array / device tensor to fill (its
+    first bytes; it is returned as given)."""
+    if mode not in _MODES:
+        raise ValueError('mode is "L" or "RGB"')
+    p, n, _keep = _file(data)
+    L = _lib.lib()
+    size = C.c_uint64(0)
+    _lib.check(L.cvhip_jpeg_decode(device.handle, p, n, _MODES[mode], int(drop_rows), None, 0, C.byref(size)), "cvhip_jpeg_decode")
+    info = jpeg_info(data)
+    shape = (info["height"] - int(drop_rows), info["width"]) + ((3,) if mode == "RGB" else ())
+    if out is None:
+        out = np.empty(shape, dtype=np.uint8)
+    elif isinstance(out, str):
+        if out != "device":
+            raise ValueError('out is None, "device", an array or a tensor')
+        import torch
+
+        ordinal = getattr(device, "ordinal", -1)
+        out = torch.empty(shape, dtype=torch.uint8, device=torch.device("cuda", ordinal) if ordinal >= 0 else "cuda")
+    if hasattr(out, "data_ptr"):
+        ptr, cap = C.c_void_p(out.data_ptr()), out.numel() * out.element_size()
+    else:
+        ptr, cap = C.c_void_p(out.ctypes.data), out.nbytes
+    _lib.check(L.cvhip_jpeg_decode(device.handle, p, n, _MODES[mode], int(drop_rows), ptr, cap, C.byref(size)), "cvhip_jpeg_decode")
+    return out
+
+
+def jpeg_last_stats() -> dict:
+    """cvhip_jpeg_last_stats: of this thread's last decode - restart intervals, subsequences, launches of the synchronisation
+    kernel, the most rounds a workgroup needed within a launch."""
+    s = np.zeros(4, dtype=np.uint64)
+    _lib.check(_lib.lib().cvhip_jpeg_last_stats(C.c_void_p(s.ctypes.data)), "cvhip_jpeg_last_stats")
+    return {"intervals": int(s[0]), "subsequences": int(s[1]), "sync_launches": int(s[2]), "workgroup_rounds": int(s[3])}
+
+
+@dataclass
+class SourceImage:
+    """SourceImage (reconstruction.rs:28-37) as far as it is built: img (Luma8), rgb (on request), the EXIF focal length
+    and the file's name.  scale and tilt_angle (the SEM metadata tags) are not read."""
+    img: object
+    rgb: object
+    focal_length_35mm: int | None
+    filename: str
+
+    def calibration_matrix(self, focal_length_35mm=None):
+        h, w = int(self.img.shape[0]), int(self.img.shape[1])
+        return calibration_matrix(w, h, focal_length_35mm if focal_length_35mm is not None else self.focal_length_35mm)
+
+
+def load(device, path, rgb: bool = False, drop_rows: int = 0, out=None) -> SourceImage:
+    """SourceImage::load (and load_rgb with rgb=True) of a JPEG file; drop_rows: the reference's databar_height (its SEM tag
+    is not read here).  out: None or "device", as decode_jpeg takes it, for img; rgb is a numpy array."""
+    data = Path(path).read_bytes()
+    info = jpeg_info(data)
+    img = decode_jpeg(device, data, "L", drop_rows, out)
+    colour = decode_jpeg(device, data, "RGB", drop_rows) if rgb else None
+    return SourceImage(img, colour, info["focal_length_35mm"], str(path))
+
+
+def calibration_matrix(width: int, height: int, focal_length_35mm=None) -> np.ndarray:
+    """SourceImage::calibration_matrix (reconstruction.rs:164-185) in f64: the focal length scaled by the image's diagonal
+    over the 24 x 36 mm frame's; None or 0 falls back to 1 (`.unwrap_or(1)`)."""
+    diagonal_35mm = math.sqrt(24.0 * 24.0 + 36.0 * 36.0)
+    w, h = float(width), float(height)
+    diagonal = math.sqrt(w * w + h * h)
+    focal = float(focal_length_35mm or 1) * diagonal / diagonal_35mm
+    return np.array([[focal, 0.0, w / 2.0], [0.0, focal, h / 2.0], [0.0, 0.0, 1.0]], dtype=np.float64)

@@ -505,3 +505,36 @@ def reconstruct_affine_mesh(device, pyramid1, pyramid2, f, triangulate=None, pro
                                                                          depth_scale, polygons, colour_table))
     out["timings_ms"] = dict(rec.timings_ms)
     return out
+
+
+def reconstruct_perspective_files(device, paths, focal_length_35mm=None, mesh=True, drop_rows: int = 0, on_device: bool = True, **kwargs):
+    """The perspective `reconstruct` from image FILES (reconstruction.rs:39-60, 164-185, 261-277): image.load
+    of every path - its Luma8 decoded on the device (JPEG, cvhip_jpeg_decode), its EXIF FocalLengthIn35mmFilm -, K per image
+    by image.calibration_matrix (focal_length_35mm, when given, overrides the files' values, as `:170` does; neither: 1),
+    the Lanczos3 pyramids (correlation.lanczos_pyramid with correlation.optimal_scale_steps levels), then
+    reconstruct_perspective_mesh (mesh=True) or reconstruct_perspective with kwargs.  With a vertex_mode of Color or Texture
+    and no `images=`, the files' decoded RGB8 is passed.  on_device: the decoded Luma8 and the pyramids stay in device
+    memory (torch tensors); False: numpy arrays.  drop_rows: the reference's databar_height (its SEM tag is not read).
+    -> that call's dict with source_images (the image.SourceImage list), K and timings_ms["decode"] added."""
+    import time
+
+    from . import image
+    from . import mesh as mesh_mod
+
+    t0 = time.perf_counter()
+    mode = int(kwargs.get("vertex_mode", 0))
+    want_rgb = bool(mesh) and kwargs.get("images") is None and mode in (int(mesh_mod.VertexMode.Color), int(mesh_mod.VertexMode.Texture))
+    sources = [image.load(device, p, rgb=want_rgb, drop_rows=drop_rows, out="device" if on_device else None) for p in paths]
+    decode_ms = (time.perf_counter() - t0) * 1e3
+    Ks = np.stack([s.calibration_matrix(focal_length_35mm) for s in sources]) if sources else np.zeros((0, 3, 3))
+    pyramids = [correlation.lanczos_pyramid(device, s.img, correlation.optimal_scale_steps(int(s.img.shape[1]), int(s.img.shape[0])))
+                for s in sources]
+    if mesh:
+        if want_rgb:
+            kwargs = {**kwargs, "images": [s.rgb for s in sources]}
+        out = reconstruct_perspective_mesh(device, pyramids, Ks, **kwargs)
+    else:
+        out = reconstruct_perspective(device, pyramids, Ks, **kwargs)
+    out["source_images"], out["K"] = sources, Ks
+    out["timings_ms"]["decode"] = decode_ms
+    return out

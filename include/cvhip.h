@@ -580,6 +580,39 @@ int cvhip_f64_display(cvhip_device *dev, const double *values, uint64_t n, uint8
 int cvhip_png_encode(cvhip_device *dev, const uint8_t *pixels, uint32_t width, uint32_t height, uint32_t channels, uint32_t filter,
                      uint8_t *out, uint64_t cap, uint64_t *out_size, uint64_t *out_sections);
 
+/* ------------------------------------------------------------------------------------------
+ * JPEG files in (csrc/jpeg_kernels.hip, csrc/jpeg_common.hpp): what the reference opens with
+ * image::open(path)?.into_luma8() / into_rgb8() and crops by databar_height (src/reconstruction.rs:40-60), and the EXIF
+ * FocalLengthIn35mmFilm it reads (:138-142).  The host walks the markers; the entropy decode and everything behind it runs on
+ * the device.  The `image` crate's decoder is not restated: the pixels are DEFINED here (tests/ref_jpeg.py is the definition)
+ * as libjpeg's default decode - sequential Huffman, jidctint (CONST_BITS 13, PASS1_BITS 2; here in 64-bit integers with a
+ * clamp), fancy upsampling (replication where a chroma plane has at most 2 columns), the fixed-point YCbCr -> RGB - and are
+ * what libjpeg-turbo returns for every file an encoder makes.  Luma8 of a colour file is (2126 r + 7152 g + 722 b) / 10000,
+ * truncated, of that RGB (into_luma8 as remembered, not pinned to the crate); of a grey file its plane.  EXIF orientation is
+ * not applied (image::open does not apply it).
+ * Supported: SOF0, 8 bits, 1 component or 3 (YCbCr) in one interleaved scan, luma sampling 1x1, 2x1 or 2x2 over 1x1 chroma, any
+ * DRI or none, any number of DQT / DHT segments before the scan, APPn and COM skipped, FF fill in front of a marker.
+ * CVHIP_ERR_UNSUPPORTED: every other SOF, 12 bits, 2 or 4 components, an Adobe transform other than YCbCr, a second scan,
+ * other sampling factors, DNL (a frame height of 0 announces it); a scan of 2^31 or more bytes, more than 2^25 blocks.
+ * CVHIP_ERR_INVALID: anything malformed - a truncated segment, a missing table, a code that is not in its table, a run past
+ * coefficient 63, a missing, surplus or misnumbered RSTn, data that ends before the last MCU, width 0, drop_rows >= height;
+ * nothing is written then. */
+#define CVHIP_IMAGE_LUMA8 0u
+#define CVHIP_IMAGE_RGB8 1u
+/* Host only, no device.  out_info[6] = width, height, components (1 or 3), the luma sampling factors h and v, and
+ * FocalLengthIn35mmFilm (APP1 "Exif", either byte order, IFD0 -> 0x8769 -> 0xA405 as SHORT or LONG; 0 = none: a missing or
+ * broken EXIF block is none, as get_metadata falls back, reconstruction.rs:62-73). */
+int cvhip_jpeg_info(const uint8_t *file, uint64_t size, uint32_t *out_info);
+/* file[0 .. size): the JPEG file in host memory.  out: width x (height - drop_rows) pixels of 1 (CVHIP_IMAGE_LUMA8) or 3
+ * (CVHIP_IMAGE_RGB8: a grey file's plane three times) bytes, rows packed, in host or device memory at any alignment;
+ * drop_rows rows are cut from the bottom (the reference's databar_height).  cap = 0 sizes (*out_size, from the header alone)
+ * and writes nothing; 0 < cap < size is CVHIP_ERR_INVALID with nothing written. */
+int cvhip_jpeg_decode(cvhip_device *dev, const uint8_t *file, uint64_t size, uint32_t format, uint32_t drop_rows, uint8_t *out,
+                      uint64_t cap, uint64_t *out_size);
+/* Of the calling thread's last cvhip_jpeg_decode that reached the device: out_stats[4] = restart intervals, subsequences,
+ * launches of the synchronisation kernel, the most rounds a workgroup needed within a launch. */
+int cvhip_jpeg_last_stats(uint64_t *out_stats);
+
 /* Row sharding (multi-GPU): restrict the SEARCH passes of this context to shard `num` of `den`
  * equal row chunks of the searched level image: rows [num*rps, min((num+1)*rps, h_level)) with
  * rps = ceil(h_level / den).  Rows outside the band keep whatever the level grid holds until
