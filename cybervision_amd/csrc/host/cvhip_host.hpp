@@ -749,7 +749,7 @@ inline std::vector<uint8_t> colour_map(GpuDevice &dev, const DepthImage &img, co
 
 } // namespace mesh
 
-// ---- image files in: SourceImage::load / load_rgb (reconstruction.rs:40-60) for baseline JPEG -----------------------
+// ---- image files in: SourceImage::load / load_rgb (reconstruction.rs:40-60) for baseline JPEG and strip TIFF ---
 namespace image {
 
 struct JpegInfo {
@@ -774,6 +774,39 @@ inline std::vector<uint8_t> jpeg_decode(GpuDevice &dev, const uint8_t *file, uin
 {
     return mesh::detail::size_then_fill([&](uint8_t *dst, uint64_t cap, uint64_t *out_size) {
         check(cvhip_jpeg_decode(dev.handle(), file, size, (uint32_t)format, drop_rows, dst, cap, out_size), "cvhip_jpeg_decode");
+    });
+}
+
+// ---- TIFF: the SEM pairs of --projection=parallel, with the metadata of reconstruction.rs:80-144
+struct TiffInfo {
+    uint32_t width = 0, height = 0, samples = 0, bits = 0, compression = 0, photometric = 0, predictor = 0, strips = 0, rows_per_strip = 0;
+    uint32_t focal_length_35mm = 0; // EXIF FocalLengthIn35mmFilm, 0 = none
+    uint32_t databar_height = 0;    // [PrivateFei] DatabarHeight of the SEM block (tag 34683 or 34682), 0 = none
+    bool sem = false;               // an SEM block was found
+    bool has_tilt_angle = false;    // tilt_angle is Some
+    float scale[2] = {1.0f, 1.0f}, tilt_angle = 0.0f;
+};
+constexpr uint32_t DROP_DATABAR = CVHIP_TIFF_DROP_DATABAR; // as drop_rows: the file's own databar_height
+
+// the first IFD, the EXIF focal length and the SEM block of a TIFF file's bytes (host only)
+inline TiffInfo tiff_info(const uint8_t *file, uint64_t size)
+{
+    uint32_t v[12] = {0};
+    float s[3] = {0.0f, 0.0f, 0.0f};
+    check(cvhip_tiff_info(file, size, v, s), "cvhip_tiff_info");
+    TiffInfo info;
+    info.width = v[0], info.height = v[1], info.samples = v[2], info.bits = v[3], info.compression = v[4], info.photometric = v[5];
+    info.predictor = v[6], info.strips = v[7], info.rows_per_strip = v[8], info.focal_length_35mm = v[9], info.databar_height = v[10];
+    info.sem = (v[11] & 1u) != 0, info.has_tilt_angle = (v[11] & 2u) != 0;
+    info.scale[0] = s[0], info.scale[1] = s[1], info.tilt_angle = s[2];
+    return info;
+}
+
+// as jpeg_decode, of a TIFF file; drop_rows = DROP_DATABAR (the default) cuts the file's own databar_height, as SourceImage::load does
+inline std::vector<uint8_t> tiff_decode(GpuDevice &dev, const uint8_t *file, uint64_t size, Format format = Format::Luma8, uint32_t drop_rows = DROP_DATABAR)
+{
+    return mesh::detail::size_then_fill([&](uint8_t *dst, uint64_t cap, uint64_t *out_size) {
+        check(cvhip_tiff_decode(dev.handle(), file, size, (uint32_t)format, drop_rows, dst, cap, out_size), "cvhip_tiff_decode");
     });
 }
 

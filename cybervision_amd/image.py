@@ -1,8 +1,10 @@
 """Image files in: what SourceImage::load / load_rgb do with a path (src/reconstruction.rs:39-60) - the
 file's pixels as Luma8 or RGB8 with `databar_height` rows cut from the bottom, the EXIF FocalLengthIn35mmFilm (:138-142) -
-and SourceImage::calibration_matrix (:164-185).  JPEG only (baseline; cvhip_jpeg_decode): the host walks the markers, the
-entropy decode, IDCT, upsampling and colour conversion run on the device.  TIFF, PNG and progressive JPEG input are not
-built."""
+and SourceImage::calibration_matrix (:164-185).  Baseline JPEG (cvhip_jpeg_decode): the host walks the markers, the
+entropy decode, IDCT, upsampling and colour conversion run on the device.  Strip TIFF (cvhip_tiff_decode):
+the host walks the IFD and reads the SEM text block of tag 34683 / 34682 - scale, tilt_angle, databar_height (:80-144) -,
+LZW / PackBits decompression, Predictor 2 and the conversion run on the device.  PNG input, Deflate and tiled TIFF and
+progressive JPEG are not built."""
 from __future__ import annotations
 
 import ctypes as C
@@ -15,6 +17,7 @@ import numpy as np
 from . import _lib
 
 LUMA8, RGB8 = 0, 1  # CVHIP_IMAGE_LUMA8, CVHIP_IMAGE_RGB8
+TIFF_DROP_DATABAR = 0xFFFFFFFF  # CVHIP_TIFF_DROP_DATABAR
 _MODES = {"L": LUMA8, "RGB": RGB8}
 
 
@@ -34,18 +37,17 @@ def jpeg_info(data) -> dict:
     return {"width": w, "height": h, "components": comps, "h": hs, "v": vs, "focal_length_35mm": focal or None}
 
 
-def decode_jpeg(device, data, mode: str = "L", drop_rows: int = 0, out=None):
-    """cvhip_jpeg_decode of a file's bytes -> [height - drop_rows, width] (mode "L") or [.., .., 3] (mode "RGB") uint8.
-    out: None - a numpy array; "device" - a torch tensor on the device; or the numpy array / device tensor to fill (its
-    first bytes; it is returned as given)."""
+def _decode(name, device, data, mode, drop_rows, out, width_of):
+    """The sizing call, the buffer and the filling call of cvhip_jpeg_decode / cvhip_tiff_decode; width_of(data): the
+    image's width, asked once the sizing call has accepted the file."""
     if mode not in _MODES:
         raise ValueError('mode is "L" or "RGB"')
     p, n, _keep = _file(data)
-    L = _lib.lib()
+    call = getattr(_lib.lib(), name)
     size = C.c_uint64(0)
-    _lib.check(L.cvhip_jpeg_decode(device.handle, p, n, _MODES[mode], int(drop_rows), None, 0, C.byref(size)), "cvhip_jpeg_decode")
-    info = jpeg_info(data)
-    shape = (info["height"] - int(drop_rows), info["width"]) + ((3,) if mode == "RGB" else ())
+    _lib.check(call(device.handle, p, n, _MODES[mode], int(drop_rows), None, 0, C.byref(size)), name)
+    width = width_of(data)
+    shape = (size.value // (width * (3 if mode == "RGB" else 1)), width) + ((3,) if mode == "RGB" else ())
     if out is None:
         out = np.empty(shape, dtype=np.uint8)
     elif isinstance(out, str):
@@ -59,8 +61,41 @@ def decode_jpeg(device, data, mode: str = "L", drop_rows: int = 0, out=None):
         ptr, cap = C.c_void_p(out.data_ptr()), out.numel() * out.element_size()
     else:
         ptr, cap = C.c_void_p(out.ctypes.data), out.nbytes
-    _lib.check(L.cvhip_jpeg_decode(device.handle, p, n, _MODES[mode], int(drop_rows), ptr, cap, C.byref(size)), "cvhip_jpeg_decode")
+    _lib.check(call(device.handle, p, n, _MODES[mode], int(drop_rows), ptr, cap, C.byref(size)), name)
     return out
+
+
+def decode_jpeg(device, data, mode: str = "L", drop_rows: int = 0, out=None):
+    """cvhip_jpeg_decode of a file's bytes -> [height - drop_rows, width] (mode "L") or [.., .., 3] (mode "RGB") uint8.
+    out: None - a numpy array; "device" - a torch tensor on the device; or the numpy array / device tensor to fill (its
+    first bytes; it is returned as given)."""
+    return _decode("cvhip_jpeg_decode", device, data, mode, drop_rows, out, lambda d: jpeg_info(d)["width"])
+
+
+def tiff_info(data) -> dict:
+    """cvhip_tiff_info of a file's bytes (host only) -> width, height, samples, bits, compression, photometric, predictor,
+    strips, rows_per_strip, focal_length_35mm (None when the file has none), databar_height, sem (a block was found),
+    scale (width, height; 1.0 each by default) and tilt_angle (None when the block sets none)."""
+    p, n, _keep = _file(data)
+    info, scale = np.zeros(12, dtype=np.uint32), np.zeros(3, dtype=np.float32)
+    _lib.check(_lib.lib().cvhip_tiff_info(p, n, C.c_void_p(info.ctypes.data), C.c_void_p(scale.ctypes.data)), "cvhip_tiff_info")
+    names = ("width", "height", "samples", "bits", "compression", "photometric", "predictor", "strips", "rows_per_strip")
+    out = {k: int(v) for k, v in zip(names, info)}
+    out.update(focal_length_35mm=int(info[9]) or None, databar_height=int(info[10]), sem=bool(info[11] & 1), scale=(float(scale[0]), float(scale[1])),
+               tilt_angle=float(scale[2]) if info[11] & 2 else None)
+    return out
+
+
+def decode_tiff(device, data, mode: str = "L", drop_rows=None, out=None):
+    """cvhip_tiff_decode of a file's bytes, as decode_jpeg; drop_rows=None cuts the file's own DatabarHeight."""
+    return _decode("cvhip_tiff_decode", device, data, mode, TIFF_DROP_DATABAR if drop_rows is None else drop_rows, out, lambda d: tiff_info(d)["width"])
+
+
+def tiff_last_stats() -> dict:
+    """cvhip_tiff_last_stats: of this thread's last decode - strips, LZW codes read, Clear codes met, the longest string."""
+    s = np.zeros(4, dtype=np.uint64)
+    _lib.check(_lib.lib().cvhip_tiff_last_stats(C.c_void_p(s.ctypes.data)), "cvhip_tiff_last_stats")
+    return {"strips": int(s[0]), "codes": int(s[1]), "clears": int(s[2]), "longest": int(s[3])}
 
 
 def jpeg_last_stats() -> dict:
@@ -73,22 +108,34 @@ def jpeg_last_stats() -> dict:
 
 @dataclass
 class SourceImage:
-    """SourceImage (reconstruction.rs:28-37) as far as it is built: img (Luma8), rgb (on request), the EXIF focal length
-    and the file's name.  scale and tilt_angle (the SEM metadata tags) are not read."""
+    """SourceImage (reconstruction.rs:28-37): img (Luma8), rgb (on request), the EXIF focal length, the file's name, and of
+    a TIFF file's SEM block scale, tilt_angle and the databar_height that was cut (the defaults for every other file)."""
     img: object
     rgb: object
     focal_length_35mm: int | None
     filename: str
+    scale: tuple = (1.0, 1.0)
+    tilt_angle: float | None = None
+    databar_height: int = 0
 
     def calibration_matrix(self, focal_length_35mm=None):
         h, w = int(self.img.shape[0]), int(self.img.shape[1])
         return calibration_matrix(w, h, focal_length_35mm if focal_length_35mm is not None else self.focal_length_35mm)
 
 
-def load(device, path, rgb: bool = False, drop_rows: int = 0, out=None) -> SourceImage:
-    """SourceImage::load (and load_rgb with rgb=True) of a JPEG file; drop_rows: the reference's databar_height (its SEM tag
-    is not read here).  out: None or "device", as decode_jpeg takes it, for img; rgb is a numpy array."""
+def load(device, path, rgb: bool = False, drop_rows=None, out=None) -> SourceImage:
+    """SourceImage::load (and load_rgb with rgb=True) of a TIFF or JPEG file, told apart by the first four bytes (anything
+    that is no TIFF gets the JPEG path and its error).  drop_rows: the rows cut from the bottom; None - the file's own
+    databar_height (the DatabarHeight of a TIFF file's SEM block; 0 for JPEG).  out: None or "device", as decode_jpeg takes
+    it, for img; rgb is a numpy array."""
     data = Path(path).read_bytes()
+    if data[:4] in (b"II*\0", b"MM\0*"):
+        info = tiff_info(data)
+        img = decode_tiff(device, data, "L", drop_rows, out)
+        colour = decode_tiff(device, data, "RGB", drop_rows) if rgb else None
+        return SourceImage(img, colour, info["focal_length_35mm"], str(path), info["scale"], info["tilt_angle"],
+                           info["databar_height"] if drop_rows is None else int(drop_rows))
+    drop_rows = 0 if drop_rows is None else drop_rows
     info = jpeg_info(data)
     img = decode_jpeg(device, data, "L", drop_rows, out)
     colour = decode_jpeg(device, data, "RGB", drop_rows) if rgb else None

@@ -538,3 +538,42 @@ def reconstruct_perspective_files(device, paths, focal_length_35mm=None, mesh=Tr
     out["source_images"], out["K"] = sources, Ks
     out["timings_ms"]["decode"] = decode_ms
     return out
+
+
+def reconstruct_affine_files(device, path1, path2, f=None, seed: int = 0, on_device: bool = True, depth_scale: float = -1.0, **kwargs):
+    """The affine `reconstruct` (--projection=parallel) of an SEM pair from its two FILES (reconstruction.rs:39-60, 80-144,
+    223-231, 261-277, 358-362): image.load of both paths - TIFF or JPEG, the Luma8 decoded on the device
+    with the file's own DatabarHeight cut, the SEM block's scale and tilt angle read -, the Lanczos3 pyramids
+    (correlation.lanczos_pyramid with correlation.optimal_scale_steps levels), the sparse stage when no `f` is given
+    (reconstruct_pairs in ProjectionMode.Affine with dense=False and `seed`; a pair without an F raises the reference's
+    "Failed to match images"), then reconstruct_affine_mesh with kwargs and out_scale = (1, 1, depth_scale * 1): the
+    reference resets the image scale to 1 (:223-231), so the files' scales are reported, not applied.  With a vertex_mode of
+    Color or Texture and no `images=`, the files' decoded RGB8 is passed.  on_device: the decoded Luma8 and the pyramids stay
+    in device memory (torch tensors); False: numpy arrays.
+    -> that call's dict with source_images (the two image.SourceImage), f, relative_tilt_angle (the second file's tilt angle
+    minus the first's, None unless both have one) and timings_ms["decode"] added."""
+    import time
+
+    from . import image
+    from . import mesh as mesh_mod
+
+    t0 = time.perf_counter()
+    mode = int(kwargs.get("vertex_mode", 0))
+    want_rgb = kwargs.get("images") is None and mode in (int(mesh_mod.VertexMode.Color), int(mesh_mod.VertexMode.Texture))
+    sources = [image.load(device, p, rgb=want_rgb, out="device" if on_device else None) for p in (path1, path2)]
+    decode_ms = (time.perf_counter() - t0) * 1e3
+    pyramids = [correlation.lanczos_pyramid(device, s.img, correlation.optimal_scale_steps(int(s.img.shape[1]), int(s.img.shape[0])))
+                for s in sources]
+    if f is None:
+        entry = reconstruct_pairs(device, pyramids, ProjectionMode.Affine, dense=False, seed=seed)["pairs"][(0, 1)]
+        if entry["f"] is None:
+            raise RuntimeError("Failed to match images")
+        f = entry["f"]
+    if want_rgb:
+        kwargs = {**kwargs, "images": [s.rgb for s in sources]}
+    out = reconstruct_affine_mesh(device, pyramids[0], pyramids[1], f, depth_scale=depth_scale, out_scale=(1.0, 1.0, depth_scale * 1.0), **kwargs)
+    a1, a2 = sources[0].tilt_angle, sources[1].tilt_angle
+    out["source_images"], out["f"] = sources, f
+    out["relative_tilt_angle"] = a2 - a1 if a1 is not None and a2 is not None else None
+    out["timings_ms"]["decode"] = decode_ms
+    return out

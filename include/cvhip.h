@@ -613,6 +613,38 @@ int cvhip_jpeg_decode(cvhip_device *dev, const uint8_t *file, uint64_t size, uin
  * launches of the synchronisation kernel, the most rounds a workgroup needed within a launch. */
 int cvhip_jpeg_last_stats(uint64_t *out_stats);
 
+/* ------------------------------------------------------------------------------------------
+ * TIFF files in (csrc/tiff_kernels.hip, csrc/tiff_common.hpp): the reference's SEM pairs
+ * (--projection=parallel), opened like every input with image::open(path)?.into_luma8() / into_rgb8() and cropped by the
+ * DatabarHeight of the microscope's text block in tag 34683 or 34682 (src/reconstruction.rs:40-60, 80-144).  The host walks the
+ * first IFD of a classic TIFF file (II or MM) and reads the block; decompression, Predictor 2 and the conversion run on the
+ * device, a wave per strip.  The pixels are DEFINED by tests/ref_tiff.py: the decompressed samples are libtiff's (pinned to
+ * Pillow); 16 -> 8 bits is (v + 128) / 257, Luma8 of RGB is (2126 r + 7152 g + 722 b) / 10000 truncated (of 16-bit samples
+ * in 16 bits, then reduced), WhiteIsZero is inverted and a fourth sample dropped - into_luma8 / into_rgb8 as remembered, not
+ * pinned to the `image` crate.
+ * Supported: strips, PlanarConfiguration 1, 8 or 16 bits (unsigned integers), 1 sample (photometric 0 or 1), 3 or 4 samples
+ * (photometric 2), compression 1, 5 (LZW) and 32773 (PackBits), Predictor 1 or 2, strips anywhere in the file in any order.
+ * CVHIP_ERR_UNSUPPORTED: BigTIFF, tiles, PlanarConfiguration 2, other depths or sample formats, palette / CMYK / YCbCr / CIELab,
+ * 2 or more than 4 samples, every other compression, Predictor 3, FillOrder 2, a dimension of 65536 or more, a strip of 2^31
+ * or more bytes, old-style (bit-reversed) LZW.  CVHIP_ERR_INVALID: anything malformed - a truncated header or IFD, an entry or
+ * strip past the file, width or height 0, a missing required tag, a wrong number of strip offsets or byte counts, byte counts
+ * missing on a compressed file, an uncompressed strip shorter than its rows, PackBits input that ends before the strip's rows
+ * are full, an LZW code above the next entry, an LZW EOI or end of input before the rows are full, drop_rows >= height;
+ * nothing is written then. */
+#define CVHIP_TIFF_DROP_DATABAR 0xFFFFFFFFu
+/* Host only, no device.  out_info[12] = width, height, samples per pixel, bits per sample, compression, photometric,
+ * predictor, strips, rows per strip, FocalLengthIn35mmFilm (IFD0 -> 34665 -> 0xA405 as SHORT or LONG; 0 = none),
+ * databar_height, flags (bit 0: an SEM block was found, bit 1: tilt_angle is Some).  out_scale[3] = scale width, scale height
+ * (1.0 each by default), tilt angle.  A missing or broken block gives the defaults, as get_metadata falls back. */
+int cvhip_tiff_info(const uint8_t *file, uint64_t size, uint32_t *out_info, float *out_scale);
+/* cvhip_jpeg_decode's arguments and contract for a TIFF file; drop_rows = CVHIP_TIFF_DROP_DATABAR cuts the file's own
+ * DatabarHeight, as SourceImage::load does. */
+int cvhip_tiff_decode(cvhip_device *dev, const uint8_t *file, uint64_t size, uint32_t format, uint32_t drop_rows, uint8_t *out,
+                      uint64_t cap, uint64_t *out_size);
+/* Of the calling thread's last cvhip_tiff_decode that reached the device: out_stats[4] = strips, LZW codes read, Clear codes
+ * met, the longest string copied. */
+int cvhip_tiff_last_stats(uint64_t *out_stats);
+
 /* Row sharding (multi-GPU): restrict the SEARCH passes of this context to shard `num` of `den`
  * equal row chunks of the searched level image: rows [num*rps, min((num+1)*rps, h_level)) with
  * rps = ceil(h_level / den).  Rows outside the band keep whatever the level grid holds until
