@@ -749,7 +749,7 @@ inline std::vector<uint8_t> colour_map(GpuDevice &dev, const DepthImage &img, co
 
 } // namespace mesh
 
-// ---- image files in: SourceImage::load / load_rgb (reconstruction.rs:40-60) for baseline JPEG and strip TIFF ---
+// ---- image files in: SourceImage::load / load_rgb (reconstruction.rs:40-60) for baseline JPEG, strip TIFF and PNG ---
 namespace image {
 
 struct JpegInfo {
@@ -807,6 +807,32 @@ inline std::vector<uint8_t> tiff_decode(GpuDevice &dev, const uint8_t *file, uin
 {
     return mesh::detail::size_then_fill([&](uint8_t *dst, uint64_t cap, uint64_t *out_size) {
         check(cvhip_tiff_decode(dev.handle(), file, size, (uint32_t)format, drop_rows, dst, cap, out_size), "cvhip_tiff_decode");
+    });
+}
+
+// ---- PNG: every colour type and bit depth, not interlaced; the SEM fields keep their defaults
+struct PngInfo {
+    uint32_t width = 0, height = 0, colour_type = 0, bit_depth = 0, interlace = 0, idat_chunks = 0;
+    uint32_t focal_length_35mm = 0; // the eXIf chunk's FocalLengthIn35mmFilm, 0 = none
+    bool plte = false, trns = false; // such a chunk was read
+};
+
+// IHDR, the chunks counted and the eXIf focal length of a PNG file's bytes (host only)
+inline PngInfo png_info(const uint8_t *file, uint64_t size)
+{
+    uint32_t v[8] = {0};
+    check(cvhip_png_info(file, size, v), "cvhip_png_info");
+    PngInfo info;
+    info.width = v[0], info.height = v[1], info.colour_type = v[2], info.bit_depth = v[3], info.interlace = v[4], info.idat_chunks = v[5];
+    info.focal_length_35mm = v[6], info.plte = (v[7] & 1u) != 0, info.trns = (v[7] & 2u) != 0;
+    return info;
+}
+
+// as jpeg_decode, of a PNG file
+inline std::vector<uint8_t> png_decode(GpuDevice &dev, const uint8_t *file, uint64_t size, Format format = Format::Luma8, uint32_t drop_rows = 0)
+{
+    return mesh::detail::size_then_fill([&](uint8_t *dst, uint64_t cap, uint64_t *out_size) {
+        check(cvhip_png_decode(dev.handle(), file, size, (uint32_t)format, drop_rows, dst, cap, out_size), "cvhip_png_decode");
     });
 }
 

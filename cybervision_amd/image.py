@@ -3,8 +3,10 @@ file's pixels as Luma8 or RGB8 with `databar_height` rows cut from the bottom, t
 and SourceImage::calibration_matrix (:164-185).  Baseline JPEG (cvhip_jpeg_decode): the host walks the markers, the
 entropy decode, IDCT, upsampling and colour conversion run on the device.  Strip TIFF (cvhip_tiff_decode):
 the host walks the IFD and reads the SEM text block of tag 34683 / 34682 - scale, tilt_angle, databar_height (:80-144) -,
-LZW / PackBits decompression, Predictor 2 and the conversion run on the device.  PNG input, Deflate and tiled TIFF and
-progressive JPEG are not built."""
+LZW / PackBits decompression, Predictor 2 and the conversion run on the device.  PNG (cvhip_png_decode):
+the host walks the chunks and reads IHDR, PLTE and the eXIf chunk's focal length, inflate, the IDAT CRCs, the Adler-32, the
+five filters and the conversion run on the device; every colour type and bit depth, alpha and tRNS dropped, the SEM fields
+keep their defaults.  Adam7 PNG, Deflate and tiled TIFF and progressive JPEG are not built."""
 from __future__ import annotations
 
 import ctypes as C
@@ -38,7 +40,7 @@ def jpeg_info(data) -> dict:
 
 
 def _decode(name, device, data, mode, drop_rows, out, width_of):
-    """The sizing call, the buffer and the filling call of cvhip_jpeg_decode / cvhip_tiff_decode; width_of(data): the
+    """The sizing call, the buffer and the filling call of cvhip_jpeg_decode / cvhip_tiff_decode / cvhip_png_decode; width_of(data): the
     image's width, asked once the sizing call has accepted the file."""
     if mode not in _MODES:
         raise ValueError('mode is "L" or "RGB"')
@@ -98,6 +100,32 @@ def tiff_last_stats() -> dict:
     return {"strips": int(s[0]), "codes": int(s[1]), "clears": int(s[2]), "longest": int(s[3])}
 
 
+def png_info(data) -> dict:
+    """cvhip_png_info of a file's bytes (host only) -> width, height, colour_type, bit_depth, interlace, idat_chunks,
+    focal_length_35mm (the eXIf chunk's; None when the file has none), plte and trns (such a chunk was read)."""
+    p, n, _keep = _file(data)
+    info = np.zeros(8, dtype=np.uint32)
+    _lib.check(_lib.lib().cvhip_png_info(p, n, C.c_void_p(info.ctypes.data)), "cvhip_png_info")
+    names = ("width", "height", "colour_type", "bit_depth", "interlace", "idat_chunks")
+    out = {k: int(v) for k, v in zip(names, info)}
+    out.update(focal_length_35mm=int(info[6]) or None, plte=bool(info[7] & 1), trns=bool(info[7] & 2))
+    return out
+
+
+def decode_png(device, data, mode: str = "L", drop_rows: int = 0, out=None):
+    """cvhip_png_decode of a file's bytes, as decode_jpeg."""
+    return _decode("cvhip_png_decode", device, data, mode, drop_rows, out, lambda d: png_info(d)["width"])
+
+
+def png_last_stats() -> dict:
+    """cvhip_png_last_stats: of this thread's last decode - stored, fixed and dynamic deflate blocks, subsequences, the most
+    settle rounds one window needed, settle windows, rounds of the copy resolution, row segments of the unfilter pass."""
+    s = np.zeros(8, dtype=np.uint64)
+    _lib.check(_lib.lib().cvhip_png_last_stats(C.c_void_p(s.ctypes.data)), "cvhip_png_last_stats")
+    names = ("stored_blocks", "fixed_blocks", "dynamic_blocks", "subsequences", "settle_rounds", "settle_windows", "copy_rounds", "row_segments")
+    return {k: int(v) for k, v in zip(names, s)}
+
+
 def jpeg_last_stats() -> dict:
     """cvhip_jpeg_last_stats: of this thread's last decode - restart intervals, subsequences, launches of the synchronisation
     kernel, the most rounds a workgroup needed within a launch."""
@@ -124,9 +152,9 @@ class SourceImage:
 
 
 def load(device, path, rgb: bool = False, drop_rows=None, out=None) -> SourceImage:
-    """SourceImage::load (and load_rgb with rgb=True) of a TIFF or JPEG file, told apart by the first four bytes (anything
-    that is no TIFF gets the JPEG path and its error).  drop_rows: the rows cut from the bottom; None - the file's own
-    databar_height (the DatabarHeight of a TIFF file's SEM block; 0 for JPEG).  out: None or "device", as decode_jpeg takes
+    """SourceImage::load (and load_rgb with rgb=True) of a TIFF, PNG or JPEG file, told apart by the first four (TIFF) or
+    eight (PNG) bytes (anything else gets the JPEG path and its error).  drop_rows: the rows cut from the bottom; None - the
+    file's own databar_height (the DatabarHeight of a TIFF file's SEM block; 0 for PNG and JPEG).  out: None or "device", as decode_jpeg takes
     it, for img; rgb is a numpy array."""
     data = Path(path).read_bytes()
     if data[:4] in (b"II*\0", b"MM\0*"):
@@ -136,6 +164,11 @@ def load(device, path, rgb: bool = False, drop_rows=None, out=None) -> SourceIma
         return SourceImage(img, colour, info["focal_length_35mm"], str(path), info["scale"], info["tilt_angle"],
                            info["databar_height"] if drop_rows is None else int(drop_rows))
     drop_rows = 0 if drop_rows is None else drop_rows
+    if data[:8] == b"\x89PNG\r\n\x1a\n":
+        info = png_info(data)
+        img = decode_png(device, data, "L", drop_rows, out)
+        colour = decode_png(device, data, "RGB", drop_rows) if rgb else None
+        return SourceImage(img, colour, info["focal_length_35mm"], str(path))
     info = jpeg_info(data)
     img = decode_jpeg(device, data, "L", drop_rows, out)
     colour = decode_jpeg(device, data, "RGB", drop_rows) if rgb else None

@@ -509,7 +509,7 @@ def reconstruct_affine_mesh(device, pyramid1, pyramid2, f, triangulate=None, pro
 
 def reconstruct_perspective_files(device, paths, focal_length_35mm=None, mesh=True, drop_rows: int = 0, on_device: bool = True, **kwargs):
     """The perspective `reconstruct` from image FILES (reconstruction.rs:39-60, 164-185, 261-277): image.load
-    of every path - its Luma8 decoded on the device (JPEG, cvhip_jpeg_decode), its EXIF FocalLengthIn35mmFilm -, K per image
+    of every path - its Luma8 decoded on the device (JPEG, TIFF or PNG: cvhip_jpeg_decode, cvhip_tiff_decode, cvhip_png_decode), its EXIF FocalLengthIn35mmFilm -, K per image
     by image.calibration_matrix (focal_length_35mm, when given, overrides the files' values, as `:170` does; neither: 1),
     the Lanczos3 pyramids (correlation.lanczos_pyramid with correlation.optimal_scale_steps levels), then
     reconstruct_perspective_mesh (mesh=True) or reconstruct_perspective with kwargs.  With a vertex_mode of Color or Texture
@@ -542,7 +542,7 @@ def reconstruct_perspective_files(device, paths, focal_length_35mm=None, mesh=Tr
 
 def reconstruct_affine_files(device, path1, path2, f=None, seed: int = 0, on_device: bool = True, depth_scale: float = -1.0, **kwargs):
     """The affine `reconstruct` (--projection=parallel) of an SEM pair from its two FILES (reconstruction.rs:39-60, 80-144,
-    223-231, 261-277, 358-362): image.load of both paths - TIFF or JPEG, the Luma8 decoded on the device
+    223-231, 261-277, 358-362): image.load of both paths - TIFF, PNG or JPEG, the Luma8 decoded on the device
     with the file's own DatabarHeight cut, the SEM block's scale and tilt angle read -, the Lanczos3 pyramids
     (correlation.lanczos_pyramid with correlation.optimal_scale_steps levels), the sparse stage when no `f` is given
     (reconstruct_pairs in ProjectionMode.Affine with dense=False and `seed`; a pair without an F raises the reference's

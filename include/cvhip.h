@@ -645,6 +645,41 @@ int cvhip_tiff_decode(cvhip_device *dev, const uint8_t *file, uint64_t size, uin
  * met, the longest string copied. */
 int cvhip_tiff_last_stats(uint64_t *out_stats);
 
+/* ------------------------------------------------------------------------------------------
+ * PNG files in (csrc/png_decode_kernels.hip, csrc/png_decode_common.hpp): the third format the reference's
+ * `image` crate is built with, and the one this library writes (cvhip_png_encode).  The host walks the chunks, checks the CRC
+ * of every chunk that is not an IDAT and reads IHDR, PLTE and eXIf; inflate, the IDAT CRCs, the Adler-32, the five filters
+ * and the conversion run on the device.  The pixels are DEFINED by tests/ref_png_in.py: the samples are what inflate and the
+ * filters give (bpp = max(1, channels * bits / 8), Paeth's tie order a, b, c; pinned to Pillow); 16-bit samples are
+ * big-endian and reduce by (v + 128) / 257, 1/2/4-bit grey scales by 255 / (2^bits - 1), a palette index becomes its PLTE
+ * entry, alpha and tRNS are dropped (not blended), Luma8 of a colour pixel is (2126 r + 7152 g + 722 b) / 10000 truncated (of
+ * 16-bit samples in 16 bits, then reduced), grey as RGB8 is the plane three times, gAMA / sRGB / iCCP are ignored -
+ * into_luma8 / into_rgb8 as remembered, not pinned to the crate.  The SEM text tags are not read from a PNG file.
+ * Supported: colour types 0, 2, 3, 4, 6 at every legal bit depth, no interlacing, any number of IDAT chunks split anywhere,
+ * stored, fixed and dynamic deflate blocks in any mix; bytes behind the Adler-32 are ignored, distances up to 32 768 are
+ * accepted whatever CINFO says; ancillary chunks (APNG's among them: the default image is decoded) are skipped.
+ * CVHIP_ERR_UNSUPPORTED: Adam7, a dimension of 65 536 or more, a filtered image or IDAT data of 2^31 or more bytes.
+ * CVHIP_ERR_INVALID: anything malformed - a bad signature, a first chunk that is not a 13-byte IHDR, a zero dimension, an
+ * illegal colour type / bit depth pair, compression or filter method other than 0, interlace above 1, colour type 3 without
+ * PLTE, a PLTE of a wrong length or out of place, a palette index beyond it, no IDAT, IDAT chunks that are not consecutive, a
+ * chunk past the file, no IEND, an unknown critical chunk, a CRC mismatch, a bad zlib header, block type 3, NLEN that is not
+ * ~LEN, over-subscribed code lengths, incomplete ones (unless no code is longer than one bit), HLIT above 286 or HDIST above
+ * 30, a repeat with nothing before it or past HLIT + HDIST, no code for 256, a used symbol 286 / 287 or distance 30 / 31, a
+ * distance before the first byte, a stream that ends early, output that is not height x (1 + row bytes) bytes, a wrong
+ * Adler-32, a filter type above 4, drop_rows >= height; nothing is written then. */
+/* Host only, no device (the IDAT CRCs and the stream are the device's).  out_info[8] = width, height, colour type, bit depth,
+ * interlace method, IDAT chunks, FocalLengthIn35mmFilm (the eXIf chunk: IFD0 -> 0x8769 -> 0xA405 as SHORT or LONG, either
+ * byte order; 0 = none, and a broken block is none), flags (bit 0: a PLTE was read, bit 1: a tRNS was read). */
+int cvhip_png_info(const uint8_t *file, uint64_t size, uint32_t *out_info);
+/* cvhip_jpeg_decode's arguments and contract for a PNG file. */
+int cvhip_png_decode(cvhip_device *dev, const uint8_t *file, uint64_t size, uint32_t format, uint32_t drop_rows, uint8_t *out,
+                     uint64_t cap, uint64_t *out_size);
+/* Of the calling thread's last cvhip_png_decode that reached the device: out_stats[8] = stored, fixed and dynamic blocks,
+ * subsequences (of the fixed and dynamic blocks), the most settle rounds one window needed, settle windows (of 256
+ * subsequences; a stored block's 256 records count as one), rounds of the copy resolution (the one that changed nothing
+ * included), row segments of the unfilter pass. */
+int cvhip_png_last_stats(uint64_t *out_stats);
+
 /* Row sharding (multi-GPU): restrict the SEARCH passes of this context to shard `num` of `den`
  * equal row chunks of the searched level image: rows [num*rps, min((num+1)*rps, h_level)) with
  * rps = ceil(h_level / den).  Rows outside the band keep whatever the level grid holds until

@@ -1,0 +1,37 @@
+"""The PNG decoder through the C++ host layer (cybervision_amd/csrc/host/cvhip_host.hpp, namespace image: png_info,
+png_decode, calibration_matrix) on a real GPU: a g++-built program decodes two scenes; the pixels must equal
+tests/ref_png_in.py's byte for byte, the matrix ref_jpeg's f64 values."""
+import json
+import subprocess
+from pathlib import Path
+
+import numpy as np
+import pytest
+
+import png_in_scenes
+import ref_jpeg
+import ref_png_in
+
+pytestmark = pytest.mark.gpu
+ROOT = Path(__file__).resolve().parent.parent
+
+
+def test_cpp_host_png_in(gpu_device, tmp_path):
+    exe = tmp_path / "host_png_in"
+    lib_dir = ROOT / "cybervision_amd"
+    subprocess.check_call(["g++", "-std=c++17", "-O2", "-o", str(exe), str(ROOT / "tests" / "cpp" / "host_png_in.cpp"),
+                           f"-L{lib_dir}", "-lcvhip", f"-Wl,-rpath,{lib_dir}", "-Wl,-rpath,/opt/rocm/lib"])
+    for name, drop in (("x_long_be", 2), ("s_pal2_trns", 0)):
+        data = png_in_scenes.scene(name)
+        want = png_in_scenes.restated(name)
+        (tmp_path / "in.png").write_bytes(data)
+        res = subprocess.run([str(exe), str(tmp_path / "in.png"), str(drop), str(tmp_path / "luma.bin"), str(tmp_path / "rgb.bin")],
+                             capture_output=True, text=True, timeout=120)
+        assert res.returncode == 0, res.stderr
+        got = json.loads(res.stdout.strip().splitlines()[-1])
+        h, w = want["luma"].shape
+        assert (tmp_path / "luma.bin").read_bytes() == want["luma"][:h - drop].tobytes(), name
+        assert (tmp_path / "rgb.bin").read_bytes() == want["rgb"][:h - drop].tobytes(), name
+        info = ref_png_in.info(data)
+        assert tuple(got["info"]) == info and info[6] == png_in_scenes.FOCAL.get(name, 0)
+        assert np.array(got["k"]).tobytes() == ref_jpeg.calibration_matrix(w, h - drop, info[6] or None).tobytes()
