@@ -115,6 +115,9 @@ SIGNATURES = {
     "cvhip_recover_pose_models": (C.c_int, [_vp, _vp, C.c_uint64, _u32, _vp, _vp, _vp, _vp, _u32, _vp, _u32, _vp, _u32, _vp,
                                             _vp, _vp, _vp]),
     "cvhip_merge_tracks": (C.c_int, [_vp, _vp, C.c_uint64, _u32, _u32, _u32, _u32, _vp, _vp, C.POINTER(C.c_uint64), _vp]),
+    # max_points: (n, max_points, seed, points, tracks, m_cams, out_rows, out_points, out_tracks, out_n); (keys, n, m, out_rows, out_n)
+    "cvhip_surface_subset": (C.c_int, [_vp, C.c_uint64, C.c_uint64, C.c_uint64, _vp, _vp, _u32, _vp, _vp, _vp, C.POINTER(C.c_uint64)]),
+    "cvhip_select_smallest_u64": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint64, _vp, C.POINTER(C.c_uint64)]),
     # the mesh stage; the surface is (points, tracks, n, m, projection, r, t, image_dims) in every entry
     "cvhip_mesh_set_wide_threshold": (C.c_int, [_vp, _u32]),
     "cvhip_mesh_camera_points": (C.c_int, [_vp, _vp, _vp, C.c_uint64, _u32, _vp, _vp, _vp, _vp, _u32, _vp, _vp, C.c_uint64,

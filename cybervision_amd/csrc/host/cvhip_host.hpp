@@ -484,6 +484,25 @@ struct Surface { // triangulation::Surface (triangulation.rs:142-150) as the cvh
     uint32_t cameras_len() const { return (uint32_t)(projection.size() / 12); }
 };
 
+// max_points (triangulation.rs:837-843) on the device -> the surface of the max_points rows of `s` with the
+// smallest keys of `seed` (the binding passes rand::random()), in ascending row order; every row when max_points >= the
+// surface's length.  Cameras and image dimensions are carried over.  rows (optional): the kept rows, for the caller's own
+// per-track data.
+inline Surface surface_subset(GpuDevice &dev, const Surface &s, uint64_t max_points, uint64_t seed, std::vector<uint64_t> *rows = nullptr)
+{
+    const uint64_t n = s.tracks_len(), k = n < max_points ? n : max_points;
+    Surface out = s;
+    out.points.assign(3 * k, 0.0);
+    out.tracks.assign(2 * k * s.cameras_len(), 0);
+    std::vector<uint64_t> kept(k);
+    uint64_t out_n = 0;
+    check(cvhip_surface_subset(dev.handle(), n, max_points, seed, s.points.data(), s.tracks.data(), s.cameras_len(), kept.data(),
+                               out.points.data(), out.tracks.data(), &out_n),
+          "cvhip_surface_subset");
+    if (rows) *rows = std::move(kept);
+    return out;
+}
+
 struct Polygon { // output.rs:49-53
     uint32_t camera_i;
     std::array<uint32_t, 3> vertices;

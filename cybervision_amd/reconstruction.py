@@ -236,7 +236,7 @@ def match_count(xy) -> int:
 
 
 def reconstruct_perspective_surface(device, pyramids, pairs_result, cameras, bundle_adjustment: bool = True,
-                                    progress=None, merge_tracks: bool = False):
+                                    progress=None, merge_tracks: bool = False, max_points=None, max_points_seed: int = 0):
     """The perspective tail of `reconstruct` for n views: reconstruct_dense's pair loop (reconstruction.rs:668-730) -
     for img1 in order, for every later img2 whose pair has an F in `pairs_result` (reconstruct_pairs' output; its
     dense grids are not needed, dense=False is enough), the dense correlation and extend_tracks into one track table
@@ -244,9 +244,11 @@ def reconstruct_perspective_surface(device, pyramids, pairs_result, cameras, bun
     points, filter_outliers and, unless bundle_adjustment is False (--no-bundle-adjustment), the bundle adjustment.
     merge_tracks=True is the reference's flow: merge_tracks (:1421-1540, run after every img1 at reconstruction.rs:726) after each
     image's pairs, every view counting as linked; False (the default) skips it.  Departures, as stated
-    in DESIGN.md: the cameras come from the caller (no P3P / recover_pose), and max_points (a random subset) stays with
-    the caller.  -> dict: surface (triangulation.Surface), tracks (the whole table), timings_ms per stage (dense,
-    tracks, merge, triangulate); with merge_tracks, merges (per image: PerspectiveTriangulation.merge_tracks' counts)."""
+    in DESIGN.md: the cameras come from the caller (no P3P / recover_pose).  max_points (not None): triangulate_all's random
+    subset (:837-843) right behind it, on the device - triangulation.subset with max_points_seed.
+    -> dict: surface (triangulation.Surface), tracks (the whole table), timings_ms per stage (dense,
+    tracks, merge, triangulate); with merge_tracks, merges (per image: PerspectiveTriangulation.merge_tracks' counts); with
+    max_points, surface is the subset, subset its info (triangulation.subset's) and timings_ms["subset"] its time."""
     from . import triangulation
 
     rec = ImageReconstruction(device, ProjectionMode.Perspective)
@@ -276,9 +278,13 @@ def reconstruct_perspective_surface(device, pyramids, pairs_result, cameras, bun
         if merge_tracks:
             merges.append(rec._timed("merge", lambda i=i: tri.merge_tracks(device, i)))
     surface = rec._timed("triangulate", lambda: tri.triangulate_all(device, cameras, progress=progress))
+    if max_points is not None:
+        surface, subset_info = rec._timed("subset", lambda: triangulation.subset(device, surface, max_points, max_points_seed))
     out = {"surface": surface, "tracks": tri.tracks, "timings_ms": dict(rec.timings_ms)}
     if merge_tracks:
         out["merges"] = merges
+    if max_points is not None:
+        out["subset"] = subset_info
     return out
 
 
@@ -308,17 +314,19 @@ def recover_camera_poses(device, tri, seed: int = 0, log=None):
 
 
 def reconstruct_perspective(device, pyramids, K, bundle_adjustment: bool = True, seed: int = 0, pairs_result=None,
-                            progress=None, merge_tracks: bool = False):
+                            progress=None, merge_tracks: bool = False, max_points=None, max_points_seed: int = 0):
     """The perspective `reconstruct` in the reference's order for n views (reconstruction.rs:261-277, 380-395, 627-752):
     the sparse stage per pair (ORB, matcher, RANSAC - reconstruct_pairs with dense=False, or the caller's `pairs_result`),
     add_image_pair_sparse for every pair with an F (a pair that fails is skipped), recover_camera_poses, the dense
     correlation and extend_tracks of the pairs of linked images only, and triangulate_all with the recovered cameras.
     merge_tracks=True is the reference's flow: merge_tracks (triangulation.rs:1421-1540) after every linked image's
     pairs, the last linked image included (reconstruction.rs:726); False (the default) skips it.
-    K: one 3 x 3 matrix for every view, or one per view.  max_points stays out.
+    K: one 3 x 3 matrix for every view, or one per view.  max_points (not None; --max-points): triangulate_all's random subset
+    (:837-843) right behind it, on the device - triangulation.subset with max_points_seed.
     -> dict: surface, camera_order, poses (per recover call), initial_pair, sparse ({pair: (p2, score, the short tracks scored)}), sparse_tracks (the
     table before complete_sparse_triangulation), tracks, cameras, projections, pairs, timings_ms; with merge_tracks, merges
-    (per linked image: PerspectiveTriangulation.merge_tracks' counts)."""
+    (per linked image: PerspectiveTriangulation.merge_tracks' counts); with max_points, surface is the subset, subset its info
+    (triangulation.subset's) and timings_ms["subset"] its time."""
     from . import triangulation
 
     n = len(pyramids)
@@ -369,12 +377,16 @@ def reconstruct_perspective(device, pyramids, K, bundle_adjustment: bool = True,
         if merge_tracks:
             merges.append(rec._timed("merge", lambda i=i: tri.merge_tracks(device, i)))
     surface = rec._timed("triangulate", lambda: tri.triangulate_all_recovered(device, progress=progress))
+    if max_points is not None:
+        surface, subset_info = rec._timed("subset", lambda: triangulation.subset(device, surface, max_points, max_points_seed))
     out = {"surface": surface, "camera_order": order, "poses": poses, "initial_pair": initial, "sparse": sparse,
            "sparse_tracks": sparse_tracks, "tracks": tri.tracks,
            "cameras": list(tri.cameras), "projections": list(tri.projections), "pairs": pairs_result,
            "timings_ms": dict(rec.timings_ms)}
     if merge_tracks:
         out["merges"] = merges
+    if max_points is not None:
+        out["subset"] = subset_info
     return out
 
 

@@ -3,7 +3,8 @@ extend_tracks builds pair by pair, and triangulate_all (:817-865) - DLT points, 
 adjustment - in one call of cvhip_triangulate_perspective - and the sparse half that recovers the cameras
 (add_image_pair_sparse, recover_next_cameras, :620-811): find_projection_matrix, triangulate_tracks and the P3P RANSAC of
 recover_pose run on the device - and merge_tracks (:1421-1540, cvhip_merge_tracks), which reconstruct_dense runs after
-each linked image's pairs.
+each linked image's pairs.  `subset` is triangulate_all's max_points (:837-843, cvhip_surface_subset): a seeded random subset
+of a surface's rows, selected and gathered on the device.
 `affine_surface` is the Surface of AffineTriangulation::triangulate (:268-330) around cvhip_triangulate_affine's points.
 No compute in Python - the track table's bookkeeping and the calls only.
 """
@@ -18,6 +19,8 @@ from . import _lib
 
 MAX_CAMERAS = 8  # CVHIP_TRIANGULATE_MAX_CAMERAS
 BUNDLE_ADJUSTMENT_MAX_ITERATIONS = 100  # triangulation.rs:15
+SUBSET_WG_ROWS = 1024      # CVHIP_SUBSET_WG_ROWS: rows of one workgroup trip of the subset's selection kernels
+SUBSET_GRID_ROWS = 524288  # CVHIP_SUBSET_GRID_ROWS: rows of one trip of their whole grid
 
 
 @dataclass
@@ -60,6 +63,73 @@ def affine_surface(points3d, p2) -> Surface:
     projection[0, 0] = projection[1, 1] = 1.0
     return Surface(points=pts, track_index=np.arange(len(pts), dtype=np.int64), tracks=tracks,
                    cameras=[Camera(np.zeros(3), np.zeros(3), projection.copy()) for _ in range(2)])
+
+
+def _array_ptr(a):
+    """The address of a numpy array or a device tensor (None stays NULL)."""
+    if a is None:
+        return None
+    return C.c_void_p(a.data_ptr() if hasattr(a, "data_ptr") else a.ctypes.data)
+
+
+def _empty_like_rows(a, rows: int):
+    """Room for `rows` rows of `a`, where `a` lives: a numpy array, or a tensor on a's device."""
+    shape = (max(int(rows), 1), *a.shape[1:])
+    if hasattr(a, "data_ptr"):
+        import torch
+
+        return torch.empty(shape, dtype=a.dtype, device=a.device)
+    return np.empty(shape, dtype=a.dtype)
+
+
+def select_smallest(device, keys, m: int):
+    """The rows of the m smallest (key, row) pairs of the uint64 `keys` - of equal keys the lower row -, ascending
+    (cvhip_select_smallest_u64: a radix select and a stable compaction on the device).  keys: a numpy array, or
+    a device tensor of 64-bit integers (its bits are the keys).  -> [min(n, m)] uint64."""
+    if not hasattr(keys, "data_ptr"):
+        keys = np.ascontiguousarray(keys, dtype=np.uint64).reshape(-1)
+    elif not keys.is_contiguous() or keys.element_size() != 8 or keys.dim() != 1:
+        raise ValueError("keys: a contiguous one-dimensional tensor of 64-bit integers")
+    n = int(keys.shape[0])
+    rows = np.empty(max(min(n, int(m)), 1), dtype=np.uint64)
+    out_n = C.c_uint64(0)
+    _lib.check(_lib.lib().cvhip_select_smallest_u64(device.handle, _array_ptr(keys) if n else None, n, int(m), _array_ptr(rows),
+                                                    C.byref(out_n)), "cvhip_select_smallest_u64")
+    return rows[:out_n.value]
+
+
+def subset(device, surface: Surface, max_points: int, seed: int = 0):
+    """max_points (triangulation.rs:837-843) on the device (cvhip_surface_subset): the Surface of the
+    max_points rows of `surface` with the smallest keys key(seed, row), in ascending row order - every row when max_points >=
+    len(surface.points).  The kept set is distributed as the reference's shuffle + truncate; its order is the surface's, not a
+    random one.  points, track_index and tracks are those of the kept rows (points and tracks gathered on the device; they may
+    be numpy arrays or device tensors, the results live where they do); the cameras and the ba_* fields are carried over.
+    Perspective surfaces and affine_surface's alike.
+    -> (Surface, info): info = {rows_in, rows_out, seed, rows (the kept rows, [rows_out] uint64)}."""
+    max_points, seed = int(max_points), int(seed)
+    if max_points < 0 or not 0 <= seed < 1 << 64:
+        raise ValueError("max_points >= 0 and a 64-bit seed")
+    on_dev = hasattr(surface.points, "data_ptr")
+    points = surface.points.contiguous() if on_dev else np.ascontiguousarray(surface.points, dtype=np.float64)
+    tracks = (surface.tracks.contiguous() if hasattr(surface.tracks, "data_ptr")
+              else np.ascontiguousarray(surface.tracks, dtype=np.int32))
+    n = int(points.shape[0])
+    if int(tracks.shape[0]) != n or len(surface.track_index) != n:
+        raise ValueError("one track row and one track index per point")
+    m_cams = int(tracks.shape[1])
+    k = min(n, max_points)
+    rows = np.empty(max(k, 1), dtype=np.uint64)
+    out_points, out_tracks = _empty_like_rows(points, k), _empty_like_rows(tracks, k)
+    out_n = C.c_uint64(0)
+    _lib.check(_lib.lib().cvhip_surface_subset(device.handle, n, max_points, seed, _array_ptr(points), _array_ptr(tracks), m_cams,
+                                               _array_ptr(rows), _array_ptr(out_points), _array_ptr(out_tracks), C.byref(out_n)),
+               "cvhip_surface_subset")
+    k = out_n.value
+    rows = rows[:k]
+    index = surface.track_index[rows.astype(np.int64)]
+    out = Surface(points=out_points[:k], track_index=index, tracks=out_tracks[:k], cameras=surface.cameras,
+                  ba_iterations=surface.ba_iterations, ba_history=surface.ba_history, ba_residual_norms=surface.ba_residual_norms)
+    return out, {"rows_in": n, "rows_out": k, "seed": seed, "rows": rows}
 
 
 class PerspectiveTriangulation:
@@ -286,7 +356,7 @@ class PerspectiveTriangulation:
 
     def triangulate_all(self, device, cameras, progress=None) -> Surface:
         """triangulate_all (:817-865) with the given cameras [(K, R, t)] (None = no camera for that image).  max_points
-        (a random subset in the reference) stays with the caller.  Raises CvhipError with the reference's
+        (:837-843, a random subset) is `subset`, applied to the surface this returns.  Raises CvhipError with the reference's
         TriangulationError message (CVHIP_ERR_NO_SURFACE) when the bundle adjustment fails."""
         cams, tracks = self.prune_projections(cameras)
         m = len(cams)

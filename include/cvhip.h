@@ -252,6 +252,37 @@ int cvhip_merge_tracks(cvhip_device *dev, const int32_t *tracks, uint64_t n, uin
                        uint32_t width, uint32_t height, uint64_t *out_rows, int32_t *out_tracks, uint64_t *out_n,
                        uint64_t *out_stats);
 
+/* max_points (triangulation.rs:837-843; the tail of triangulate_all, after filter_outliers and the bundle adjustment):
+ * `if tracks.len() > max_points { tracks.shuffle(rng); tracks.truncate(max_points) }` with an OS-seeded generator.  Here, as
+ * for the RANSAC samplers, a counter-based one: row i of the n rows has the key
+ *   key(seed, i) = mix64(mix64(seed) + (i + 1) * 0x9E3779B97F4A7C15)   (mod 2^64; output i of splitmix64 started at mix64(seed);
+ *                                                                        mix64 = splitmix64's finaliser)
+ * - pairwise distinct for one seed - and the max_points rows with the smallest keys are kept; max_points >= n keeps every row
+ * (no selection runs, the arrays are copied), max_points = 0 none.  Departure: the kept SET has the distribution of the
+ * reference's shuffle + truncate, the ORDER does not - the kept rows come in ascending row order, where the reference's order
+ * is random (nothing downstream reads it: polygons are sorted, the writers go by row).
+ * points: n x 3 f64, tracks: n x m_cams x 2 int32; each may be NULL when its output is NULL.  Out (each with room for
+ * min(n, max_points) rows, each may be NULL, none may alias an input): out_rows = the kept rows, out_points and out_tracks =
+ * their points and track rows; *out_n = min(n, max_points).  The threshold key is found by a radix select on the device
+ * (8 passes of 8 bits, the keys recomputed in every pass), the kept rows are compacted in row order: integer only, exact.
+ * Errors (nothing written): CVHIP_ERR_INVALID for a NULL dev or out_n, an output whose input is NULL, tracks with m_cams = 0;
+ * CVHIP_ERR_UNSUPPORTED above CVHIP_TRIANGULATE_MAX_CAMERAS cameras or with 2^32 - 1 or more rows.  points, tracks and the
+ * three outputs: host or device pointers; out_n: host memory.
+ * CVHIP_SUBSET_WG_ROWS: the rows a workgroup of the selection kernels handles per trip; CVHIP_SUBSET_GRID_ROWS: the rows of one
+ * trip of their whole grid (more rows: the workgroups loop). */
+#define CVHIP_SUBSET_WG_ROWS 1024
+#define CVHIP_SUBSET_GRID_ROWS 524288
+int cvhip_surface_subset(cvhip_device *dev, uint64_t n, uint64_t max_points, uint64_t seed, const double *points,
+                         const int32_t *tracks, uint32_t m_cams, uint64_t *out_rows, double *out_points, int32_t *out_tracks,
+                         uint64_t *out_n);
+
+/* The same selection on keys given by the caller (n u64): out_rows = the m rows with the smallest (key, row) pairs - of equal
+ * keys the lower row is taken - in ascending row order; m >= n: every row; *out_n = min(n, m).  out_rows (room for min(n, m),
+ * may be NULL) and keys: host or device pointers.  Errors (nothing written): CVHIP_ERR_INVALID for a NULL dev or out_n, or
+ * NULL keys with n > 0; CVHIP_ERR_UNSUPPORTED with 2^32 - 1 or more rows. */
+int cvhip_select_smallest_u64(cvhip_device *dev, const uint64_t *keys, uint64_t n, uint64_t m, uint64_t *out_rows,
+                              uint64_t *out_n);
+
 /* ------------------------------------------------------------------------------------------
  * Pose recovery, perspective pipeline (sparse stage).  All f64 on the device (csrc/pose_kernels.hip).
  * tracks: n x m x 2 int32, (-1, -1) = no point; m <= CVHIP_TRIANGULATE_MAX_CAMERAS.  projections: m x 12 row-major
