@@ -140,6 +140,10 @@ SIGNATURES = {
     "cvhip_f64_display": (C.c_int, [_vp, _vp, C.c_uint64, _vp, C.c_uint64, C.POINTER(C.c_uint64), _vp]),
     # the PNG file image: (pixels, width, height, channels, filter, out, cap, out_size, out_sections[3])
     "cvhip_png_encode": (C.c_int, [_vp, _vp, _u32, _u32, _u32, _u32, _vp, C.c_uint64, C.POINTER(C.c_uint64), _vp]),
+    # the JPEG file image: (pixels, width, height, channels, quality, sampling, optimize, out, cap, out_size, out_sections[3]);
+    # (out_stats[4])
+    "cvhip_jpeg_encode": (C.c_int, [_vp, _vp, _u32, _u32, _u32, _u32, _u32, _u32, _vp, C.c_uint64, C.POINTER(C.c_uint64), _vp]),
+    "cvhip_jpeg_encode_last_stats": (C.c_int, [_vp]),
     # JPEG files in: (file, size, out_info[6]); (file, size, format, drop_rows, out, cap, out_size); (out_stats[4])
     "cvhip_jpeg_info": (C.c_int, [_vp, C.c_uint64, _vp]),
     "cvhip_jpeg_decode": (C.c_int, [_vp, _vp, C.c_uint64, _u32, _u32, _vp, C.c_uint64, C.POINTER(C.c_uint64)]),

@@ -756,6 +756,38 @@ inline std::vector<uint8_t> png_encode(GpuDevice &dev, const uint8_t *pixels, ui
     return out;
 }
 
+// ---- the JPEG encoder: what img.save writes for a depth map whose path ends in .jpg (:1141) ---------------------
+struct JpegSections {
+    uint64_t before = 0, data = 0, after = 0; // the bytes before the scan's data, the data, the bytes after it
+};
+enum class JpegSampling : uint32_t { S444 = 0, S422 = 1, S420 = 2 };
+struct JpegEncodeStats {
+    uint64_t blocks = 0, dummy_blocks = 0, bits = 0, stuffed = 0;
+};
+
+// The baseline JPEG file's bytes, libjpeg's file, of width x height pixels of `channels` (1: grey, 2: grey and alpha, 3: RGB,
+// 4: RGBA; alpha is dropped) bytes each.  The OBJ writer's textures stay PNG.
+inline std::vector<uint8_t> jpeg_encode(GpuDevice &dev, const uint8_t *pixels, uint32_t width, uint32_t height, uint32_t channels,
+                                        uint32_t quality = 75, JpegSampling sampling = JpegSampling::S420, bool optimize = false,
+                                        JpegSections *sections = nullptr)
+{
+    uint64_t sec[3] = {0, 0, 0};
+    std::vector<uint8_t> out = detail::size_then_fill([&](uint8_t *dst, uint64_t cap, uint64_t *size) {
+        check(cvhip_jpeg_encode(dev.handle(), pixels, width, height, channels, quality, (uint32_t)sampling, optimize ? 1u : 0u, dst, cap, size, sec),
+              "cvhip_jpeg_encode");
+    });
+    if (sections) *sections = JpegSections{sec[0], sec[1], sec[2]};
+    return out;
+}
+
+// of this thread's last jpeg_encode
+inline JpegEncodeStats jpeg_encode_last_stats()
+{
+    uint64_t st[4] = {0, 0, 0, 0};
+    check(cvhip_jpeg_encode_last_stats(st), "cvhip_jpeg_encode_last_stats");
+    return JpegEncodeStats{st[0], st[1], st[2], st[3]};
+}
+
 // ImageWriter::complete: the depth map through `table` (256 x R, G, B) -> width x height x RGBA
 inline std::vector<uint8_t> colour_map(GpuDevice &dev, const DepthImage &img, const std::array<uint8_t, 768> &table)
 {

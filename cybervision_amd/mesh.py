@@ -6,7 +6,8 @@ and needs no scipy.
 The mesh output: `ply` / `write_ply` - PlyWriter's binary file image - and `colour_map` /
 `depth_image_rgba` - ImageWriter::complete's colours; the colour table is the caller's.  `obj` / `write_obj` / `obj_mtl` - ObjWriter's
 Wavefront OBJ text and its .mtl, `f64_display` - the decimal text of doubles that it rests on.  `png` / `write_png` /
-`write_depth_png` - the PNG file image of the textures and of the depth map.
+`write_depth_png` - the PNG file image of the textures and of the depth map.  `jpeg` / `write_jpeg` /
+`write_depth_jpeg` - the baseline JPEG file image, libjpeg's file, of the depth map.
 No compute in Python - array bookkeeping and the calls only.
 
 Defined where the reference's result depends on its thread order: a depth-buffer cell is the minimum of its depths (a
@@ -430,6 +431,53 @@ def write_depth_png(path, device, surface, image_shapes, project_to_image: int, 
     width, height, origin, min_depth, max_depth, sections.  The file decodes to depth_image_rgba(...)["rgba"]."""
     d_rgba, origin, minmax = _depth_rgba_device(device, surface, image_shapes, project_to_image, scale, polygons, table)
     sections = write_png(path, device, d_rgba, filter)
+    return {"width": int(d_rgba.shape[1]), "height": int(d_rgba.shape[0]), "origin": (float(origin[0]), float(origin[1])),
+            "min_depth": float(minmax[0]), "max_depth": float(minmax[1]), "sections": sections}
+
+
+class JpegSampling(enum.IntEnum):
+    """The `sampling` of cvhip_jpeg_encode (CVHIP_JPEG_SAMPLING_*, Pillow's subsampling numbers): the luma blocks of an MCU
+    over one block of each chroma component."""
+    S444 = 0
+    S422 = 1
+    S420 = 2
+
+
+JPEG_ENCODE_STATS = ("blocks", "dummy_blocks", "bits", "stuffed")
+
+
+def jpeg(device, pixels, quality=75, sampling=JpegSampling.S420, optimize=False, sections=None):
+    """The baseline JPEG file image of an 8-bit image (cvhip_jpeg_encode) -> uint8 array: the file that
+    libjpeg writes at this quality (1 .. 100), sampling (a JpegSampling; a grey image ignores it) and with the Annex K Huffman
+    tables or, with optimize, its optimal ones.  pixels: [h, w] or [h, w, c] uint8 with c = 1 (grey), 2 (grey and alpha), 3
+    (RGB) or 4 (RGBA), as a numpy array or as a device tensor (then they do not leave the device); alpha is dropped.
+    `sections`, a list, receives the bytes before the scan's data, the data's, and the bytes after it."""
+    args, _keep = _pixel_args(pixels)
+    return _file_image("cvhip_jpeg_encode", [device.handle, *args, int(quality), int(sampling), int(bool(optimize))], 3, sections)
+
+
+def jpeg_encode_last_stats() -> dict:
+    """cvhip_jpeg_encode_last_stats: of this thread's last `jpeg` - blocks, dummy blocks (luma blocks of an edge MCU beyond the
+    image), the bits of the data before padding and stuffing, the zero bytes stuffed in."""
+    s = np.zeros(len(JPEG_ENCODE_STATS), dtype=np.uint64)
+    _lib.check(_lib.lib().cvhip_jpeg_encode_last_stats(C.c_void_p(s.ctypes.data)), "cvhip_jpeg_encode_last_stats")
+    return dict(zip(JPEG_ENCODE_STATS, (int(v) for v in s)))
+
+
+def write_jpeg(path, device, pixels, quality=75, sampling=JpegSampling.S420, optimize=False):
+    """`jpeg` written to `path` -> (before, scan data, after) byte counts."""
+    sections = []
+    jpeg(device, pixels, quality, sampling, optimize, sections=sections).tofile(path)
+    return tuple(sections)
+
+
+def write_depth_jpeg(path, device, surface, image_shapes, project_to_image: int, scale: float, polygons, table, quality=75,
+                     sampling=JpegSampling.S420, optimize=False):
+    """write_depth_png with cvhip_jpeg_encode as the encoder: the depth map's RGBA stays in device memory, only the file
+    crosses -> dict: width, height, origin, min_depth, max_depth, sections.  The file is that of the RGB of
+    depth_image_rgba(...)["rgba"]: alpha is dropped, a cell without a depth is black."""
+    d_rgba, origin, minmax = _depth_rgba_device(device, surface, image_shapes, project_to_image, scale, polygons, table)
+    sections = write_jpeg(path, device, d_rgba, quality, sampling, optimize)
     return {"width": int(d_rgba.shape[1]), "height": int(d_rgba.shape[0]), "origin": (float(origin[0]), float(origin[1])),
             "min_depth": float(minmax[0]), "max_depth": float(minmax[1]), "sections": sections}
 

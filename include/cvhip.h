@@ -612,6 +612,39 @@ int cvhip_png_encode(cvhip_device *dev, const uint8_t *pixels, uint32_t width, u
                      uint8_t *out, uint64_t cap, uint64_t *out_size, uint64_t *out_sections);
 
 /* ------------------------------------------------------------------------------------------
+ * JPEG files out (csrc/jpeg_encode_kernels.hip, csrc/jpeg_encode_common.hpp): the fourth kind of output file
+ * of the reference - "if the filename ends with .jpg, this will save a JPEG depth map file" - which reaches every image format
+ * through one img.save (src/output.rs:1141).  The file is DEFINED as libjpeg's (tests/ref_jpeg_out.py restates it and is pinned
+ * to Pillow on libjpeg-turbo byte for byte): SOI, APP0 JFIF 1.01 (no units, 1:1), a DQT per table (the Annex K tables scaled by
+ * the quality as jpeg_set_quality does, clamped to 1 .. 255), SOF0, a DHT per table (DC0, AC0, DC1, AC1), SOS, the data, EOI.
+ *  - 1 channel is one component; 3 channels become Y, Cb, Cr by jccolor's fixed-point formulas; the second of 2 and the fourth
+ *    of 4 channels (alpha) is dropped, so a depth-map cell without a depth, (0, 0, 0, 0), comes out black;
+ *  - sampling: luma 1x1 (4:4:4), 2x1 (4:2:2) or 2x2 (4:2:0) over 1x1 chroma; a one-component image ignores it (its SOF0
+ *    says 1x1);  h2v1 is (a + b + bias) >> 1 with bias 0, 1, 0, 1, ..., h2v2 (a + b + c + d + bias) >> 2 with bias 1, 2, 1, 2, ...;
+ *    the source row is replicated to the right before the downsampling, at the bottom the source is padded to a multiple of
+ *    the vertical factor and the DOWNSAMPLED rows are replicated below that; a luma block of an edge MCU that lies beyond the
+ *    component has no AC and the DC of the block before it;
+ *  - jfdctint (CONST_BITS 13, PASS1_BITS 2) on samples minus 128, quantised by sign(c) * ((|c| + (8 q >> 1)) / (8 q));
+ *  - one interleaved scan without restart markers, one-bits pad the last byte, a 00 follows every FF byte of the data;
+ *  - optimize = 0: the Annex K Huffman tables.  optimize = 1: libjpeg's jpeg_gen_optimal_table per table from the scan's own
+ *    counts (one round trip to the host); counts are not capped and code lengths of any depth are folded down to 16.
+ * pixels (height x width x channels bytes, rows packed) and out are host or device pointers, out of any alignment.
+ * out_sections[3] (may be NULL) = the bytes before the scan's data, the data, the bytes after it (2).
+ * cap = 0 sizes the image - everything but the last copy runs, since the size is known only when the FF bytes are counted -
+ * and writes nothing; 0 < cap < size is CVHIP_ERR_INVALID with nothing written.  CVHIP_ERR_INVALID too: width or height 0 or
+ * above 65535, channels not 1 to 4, quality not 1 to 100, sampling above 2, optimize above 1.  CVHIP_ERR_UNSUPPORTED: more
+ * than 2^25 blocks.  Not here: restart markers, progressive and arithmetic coding, 12 bits, EXIF; the OBJ writer's textures
+ * stay PNG. */
+#define CVHIP_JPEG_SAMPLING_444 0u /* Pillow's subsampling numbers */
+#define CVHIP_JPEG_SAMPLING_422 1u
+#define CVHIP_JPEG_SAMPLING_420 2u
+int cvhip_jpeg_encode(cvhip_device *dev, const uint8_t *pixels, uint32_t width, uint32_t height, uint32_t channels, uint32_t quality,
+                      uint32_t sampling, uint32_t optimize, uint8_t *out, uint64_t cap, uint64_t *out_size, uint64_t *out_sections);
+/* Of the calling thread's last cvhip_jpeg_encode that sized or wrote a file: out_stats[4] = blocks, dummy blocks, the bits of
+ * the data before padding and stuffing, the 00 bytes stuffed in. */
+int cvhip_jpeg_encode_last_stats(uint64_t *out_stats);
+
+/* ------------------------------------------------------------------------------------------
  * JPEG files in (csrc/jpeg_kernels.hip, csrc/jpeg_common.hpp): what the reference opens with
  * image::open(path)?.into_luma8() / into_rgb8() and crops by databar_height (src/reconstruction.rs:40-60), and the EXIF
  * FocalLengthIn35mmFilm it reads (:138-142).  The host walks the markers; the entropy decode and everything behind it runs on
