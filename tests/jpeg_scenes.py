@@ -202,7 +202,7 @@ def forced_grey():
 
 
 FORCED = {"w_codes16": forced_codes16, "w_restart": forced_restart, "w_plain422": forced_plain422, "w_grey": forced_grey}
-FORCED_IN_ENCODER_RANGE = ("w_restart", "w_plain422", "w_grey")
+FORCED_IN_ENCODER_RANGE = ("w_restart", "w_plain422", "w_grey", "w_fill_straddles")
 
 
 def _ff00_at_chunk_end(seed):
@@ -221,7 +221,92 @@ def noise160():
     raise AssertionError("no seed puts an FF 00 pair across a piece boundary")
 
 
+# ---- the seams of the kernels' units: 256 subsequences a workgroup of the sync kernel, 64 and 256 bytes of the scan a wave
+# and a workgroup of the byte kernels -------------------------------------------------------------------------------------
+SYNC_LANES, WAVE_BYTES, GROUP_BYTES = 256, 64, 256
+
+
+def seams(data):
+    """Where a file's restart intervals and markers lie relative to those units.  sub_first[s]: the number of interval s's
+    first subsequence; spanning: the intervals whose subsequences lie in two workgroups; lane0: those that begin at lane 0 of
+    a workgroup behind the first; straddles[unit]: per RSTn whose bytes or FF fill lie on both sides of a unit's edge, the
+    bytes of the run FF .. FF Dn in front of the edge."""
+    h = ref_jpeg.parse(data)
+    subs = [max(1, -(-8 * len(seg) // SUBSEQ_BITS)) for seg in ref_jpeg.segments(h)]
+    first = [0]
+    for n in subs:
+        first.append(first[-1] + n)
+    s0, s1 = h["scan"]
+    scan = data[s0:s1]
+    straddles = {WAVE_BYTES: [], GROUP_BYTES: []}
+    for i in range(1, len(scan)):
+        if scan[i - 1] == 0xFF and 0xD0 <= scan[i] <= 0xD7:
+            start = i - 1
+            while start and scan[start - 1] == 0xFF:
+                start -= 1
+            for unit, met in straddles.items():
+                met += [(i - start - k, i - start + 1) for k in range(i - start) if (i - k) % unit == 0]   # (bytes in front, bytes of the run)
+    return {"intervals": len(subs), "subsequences": first[-1], "sub_first": first,
+            "spanning": [s for s in range(len(subs)) if first[s] // SYNC_LANES != (first[s + 1] - 1) // SYNC_LANES],
+            "lane0": [s for s in range(1, len(subs)) if first[s] % SYNC_LANES == 0], "straddles": straddles}
+
+
+def restart_noise(size, more_than=SYNC_LANES, want="spanning", markers=False, grey=False, **options):
+    """Pillow's file of size x size noise with restart intervals, more subsequences than `more_than`, an interval that spans
+    two workgroups of the sync kernel (or begins at lane 0 of a later one) and, with markers, an RSTn whose FF is the last
+    byte of a 64-byte piece of the scan and another whose FF is the last of a 256-byte piece: the first seed that gives them."""
+    for seed in range(64):
+        data = pillow_jpeg(_picture(size, size, "noise", seed), grey=grey, **options)
+        at = seams(data)
+        split = {unit: [s for s in at["straddles"][unit] if s[0] == 1] for unit in (WAVE_BYTES, GROUP_BYTES)}   # FF | Dn
+        if markers and not (split[GROUP_BYTES] and len(split[WAVE_BYTES]) > len(split[GROUP_BYTES])):
+            continue
+        if at[want]:
+            assert at["subsequences"] > more_than and ref_jpeg.parse(data)["restart"] == options["restart_marker_blocks"]
+            return data
+    raise AssertionError("no seed gives the seams")
+
+
+def forced_fill_straddles():
+    """160 x 160 at 4:4:4, DRI 1 (400 intervals), FF FF fill in front of every marker: at the 64-byte and at the 256-byte
+    edges some marker has one fill byte, both fill bytes, and both with its own FF in front of the edge."""
+    n = _blocks(160, 160, (1, 1))
+    for seed in range(64):
+        data = write(160, 160, _small_coef(n, 100 + seed), QUANT_PLAIN, restart=1, fill=2)
+        at = seams(data)["straddles"]
+        if all({s for s in at[unit] if s[1] == 4} >= {(1, 4), (2, 4), (3, 4)} for unit in (WAVE_BYTES, GROUP_BYTES)):
+            return data
+    raise AssertionError("no seed puts the fill and the markers across the edges")
+
+
+def _dc_ramp(width, height, restart):
+    """4:4:4; the luma DC values climb by about 1 900 a block and the Cb values fall as fast (the largest difference a
+    baseline file can hold is 2 047), so within 18 MCUs of an interval's start the sums leave the int16 range: the
+    definition wraps them (and the coefficients are far outside an encoder's range: Pillow is no witness here)."""
+    n = _blocks(width, height, (1, 1))
+    coef = _small_coef(n, 11)
+    rng = np.random.RandomState(12)
+    per = restart or n // 3
+    for m in range(n // 3):
+        k = m % per + 1
+        coef[3 * m, 0] = 1900 * k + rng.randint(-40, 40)
+        coef[3 * m + 1, 0] = -1900 * k + rng.randint(-40, 40)
+    return write(width, height, coef, QUANT_PLAIN, restart=restart)
+
+
+FORCED.update({"w_dc_wrap": lambda: _dc_ramp(48, 48, 0), "w_dc_wrap_rst": lambda: _dc_ramp(48, 48, 20), "w_fill_straddles": forced_fill_straddles})
+# name: (size, options of restart_noise): the files with restart intervals over several workgroups of the sync kernel
+RESTART = {
+    "e_rst7_120_444": (120, dict(quality=95, subsampling=0, restart_marker_blocks=7)),
+    "e_rst1_120_444": (120, dict(quality=95, subsampling=0, restart_marker_blocks=1, want="lane0", markers=True)),
+    "e_rst5_128_422": (128, dict(quality=100, subsampling=1, restart_marker_blocks=5)),
+    "e_rst3_160_grey": (160, dict(quality=100, grey=True, restart_marker_blocks=3)),
+    "e_rst3_176_420": (176, dict(quality=100, subsampling=2, restart_marker_blocks=3)),
+    "e_rst5_200_444": (200, dict(quality=95, subsampling=0, restart_marker_blocks=5, more_than=2 * SYNC_LANES)),
+}
+
 ENCODED = {
+    **{name: functools.partial(restart_noise, size, **options) for name, (size, options) in RESTART.items()},
     "e_1x1_420": lambda: pillow_jpeg(_picture(1, 1, "smooth"), quality=90, subsampling=2),
     "e_3x5_420": lambda: pillow_jpeg(_picture(3, 5, "noise"), quality=90, subsampling=2),
     "e_4x4_420": lambda: pillow_jpeg(_picture(4, 4, "noise"), quality=95, subsampling=2),

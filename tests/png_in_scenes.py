@@ -185,8 +185,7 @@ class Deflate:
         self.put(final, 1), self.put(0, 2)
         self.n = (self.n + 7) & ~7
         self.put(len(data), 16), self.put(len(data) ^ 0xFFFF if nlen is None else nlen, 16)
-        for byte in data:
-            self.put(byte, 8)
+        self.put(int.from_bytes(bytes(data), "little"), 8 * len(data))   # (byte after byte, first bit lowest)
 
     def tokens(self, tokens, lit_lengths, dist_lengths, raw_symbols=()):
         lit, dist = canonical(lit_lengths), canonical(dist_lengths)
@@ -514,6 +513,56 @@ def _pillow(optimize):
 
 SCENES["p_default"] = functools.partial(_pillow, False)
 SCENES["p_optimize"] = functools.partial(_pillow, True)
+
+
+# ---- the seams of the unfilter kernel: tiles of 384 bytes of a row, batches of 64 rows of a segment ----------------------------
+TILE_BYTES, BATCH_ROWS = 384, 64
+BPP_KINDS = {1: (0, 8), 2: (4, 8), 3: (2, 8), 4: (6, 8), 6: (2, 16), 8: (6, 16)}   # bpp: (colour type, depth)
+SEAMS = {}   # name: (bpp, row bytes, the filter type of every row), what tests/test_png_in_ref.py finds in the file
+
+
+def segments_of(types):
+    """The lengths of the row segments: a segment begins at row 0 and at every None or Sub row."""
+    starts = [y for y, t in enumerate(types) if y == 0 or t < 2] + [len(types)]
+    return [b - a for a, b in zip(starts, starts[1:])]
+
+
+def _seam(name, colour, depth, w, h, filters):
+    row_bytes = (w * ref_png_in.CHANNELS[colour] * depth + 7) // 8
+    SEAMS[name] = (max(1, ref_png_in.CHANNELS[colour] * depth // 8), row_bytes, [filters[y % len(filters)] for y in range(h)])
+    SCENES[name] = functools.partial(_typed, colour, depth, h, w, name, filters=filters)
+
+
+# two full tiles and a pixel, two full batches and two rows, noise (zlib stores it: about 100 KB a file): one segment of 130
+# rows under Paeth, Average and Up / Average / Paeth in turn, and 130 segments of a Sub row, where `last` alone is carried
+for _bpp, (_colour, _depth) in BPP_KINDS.items():
+    for _tag, _filters in (("paeth", (4,)), ("average", (3,)), ("mixed", (2, 3, 4)), ("sub", (1,))):
+        _seam("m_bpp%d_%s" % (_bpp, _tag), _colour, _depth, 2 * TILE_BYTES // _bpp + 1, 2 * BATCH_ROWS + 2, _filters)
+    # a row of exactly one tile and of exactly two: the last tile has nothing behind it
+    for _tiles in (1, 2):
+        _seam("m_bpp%d_%dtiles" % (_bpp, _tiles), _colour, _depth, _tiles * TILE_BYTES // _bpp, 20, (1, 4, 3, 2, 4, 3, 2))
+# segments that end on batch edges, rows of 450 bytes: 64 rows (the next batch finds no row of its segment), 65 rows, 63 rows
+# (the next segment begins at lane 63 of the batch), and a last row alone
+SEGMENT_EDGES = (0,) + (4,) * 63 + (1,) + (2,) * 64 + (1,) + (3,) * 62 + (0,) + (0,)
+_seam("g_segment_edges", 2, 8, 150, len(SEGMENT_EDGES), SEGMENT_EDGES)
+# packed samples, rows of a tile and a byte and of two tiles and a byte
+for _kind, _colour, _depth in (("grey", 0, 1), ("grey", 0, 2), ("grey", 0, 4), ("pal", 3, 4)):
+    for _tiles in (1, 2):
+        _seam("k_%s_d%d_%d" % (_kind, _depth, _tiles * TILE_BYTES + 1), _colour, _depth, _tiles * TILE_BYTES * 8 // _depth + 1, 3, (1, 4, 3))
+
+
+@scene_of("t_stored_65535")
+def _():
+    # a stored block of the largest LEN, a second stored block behind it, then a dynamic block
+    w, h = 255, 260
+    filtered = apply_filters(pack(rng("st65535").integers(0, 256, (h, w, 1)), 8), (0, 1, 2, 3, 4), 1)
+    d = Deflate()
+    d.stored(filtered[:65535]), d.stored(filtered[65535:66000])
+    d.dynamic(list(filtered[66000:]), final=True)
+    return grey_file(filtered, w, h, d.finish(filtered))
+
+
+SEAMS["t_stored_65535"] = (1, 255, [y % 5 for y in range(260)])
 
 
 def names():

@@ -260,14 +260,14 @@ def segments(h):
 
 def entropy_decode(h):
     """-> coefficients [blocks, 64] int16 in natural order with the DC values summed (16-bit wrap), blocks in scan order; and
-    what the decode met: the longest code, the bits of the longest block."""
+    what the decode met: the longest code, the bits of the longest block, the range of the DC sums before the wrap."""
     comps = h["comps"]
     slots = [c for c, comp in enumerate(comps) for _ in range(comp["h"] * comp["v"])]
     bpm = len(slots)
     mcus = h["mcus_x"] * h["mcus_y"]
     ri = h["restart"] or mcus
     coef = np.zeros((mcus * bpm, 64), dtype=np.int16)
-    met = {"longest_code": 0, "longest_block_bits": 0}
+    met = {"longest_code": 0, "longest_block_bits": 0, "dc_min": 0, "dc_max": 0}
     dc_lut = [h["huff"][(0, comps[c]["td"])]["lut"].tolist() for c in range(len(comps))]
     ac_lut = [h["huff"][(1, comps[c]["ta"])]["lut"].tolist() for c in range(len(comps))]
     block = 0
@@ -276,6 +276,7 @@ def entropy_decode(h):
         buf = seg + b"\xff" * 8
         p = 0
         pred = [0] * len(comps)
+        plain = [0] * len(comps)   # the sums without the wrap: what they leave is what the wrap is there for
         for _ in range(min(ri, mcus - s * ri) * bpm):
             c = slots[block % bpm]
             p0 = p
@@ -314,6 +315,8 @@ def entropy_decode(h):
                     k += 1
                 if p > nbits:
                     _fail(INVALID, "the data ends before the last MCU")
+            plain[c] += row[0]
+            met["dc_min"], met["dc_max"] = min(met["dc_min"], plain[c]), max(met["dc_max"], plain[c])
             pred[c] = (pred[c] + row[0]) & 0xFFFF
             row[0] = pred[c]
             coef[block] = np.array(row, dtype=np.int64).astype(np.uint16).view(np.int16)

@@ -32,7 +32,10 @@ def test_pixels_are_the_restated_pixels(gpu_device, name):
     intervals of 1 and 3 MCUs and of an MCU row; an EXIF block; 160 x 160 noise without DRI (more subsequences than a
     workgroup has lanes, an FF 00 pair across two workgroups of the byte kernels); a flat image (dozens of MCUs in a
     subsequence); and the writer's files: 16-bit codes, a 16-bit DQT, ZRL chains, a block without EOB, a block longer than
-    a subsequence, thirteen intervals with a short last one and FF FF fill."""
+    a subsequence, thirteen intervals with a short last one and FF FF fill.  The seams (tests/test_jpeg_ref.py shows each on
+    the CPU): noise with restart intervals over two to four workgroups of the sync kernel in every sampling, an interval
+    across a workgroup boundary or at lane 0 of a later one; an RSTn, and FF FF fill with it, split by the 64-byte and 256-byte
+    pieces of the byte kernels; DC sums that leave the int16 range, with and without DRI."""
     data = jpeg_scenes.scene(name)
     want = jpeg_scenes.restated(name)
     assert same(image.decode_jpeg(gpu_device, data, "RGB"), want["rgb"])
@@ -122,6 +125,18 @@ def test_refused_files_leave_the_buffer_alone(gpu_device, name):
     with pytest.raises(_lib.CvhipError) as raised:
         image.decode_jpeg(gpu_device, data, "RGB")
     assert raised.value.code == code
+
+
+@pytest.mark.parametrize("name", sorted(jpeg_scenes.RESTART))
+def test_restart_scenes_need_more_than_one_workgroup(gpu_device, name):
+    """Restart intervals over several workgroups of the sync kernel (tests/test_jpeg_ref.py: an interval across a workgroup
+    boundary, or at lane 0 of a later one): the intervals and subsequences the restatement counts, and a second launch."""
+    data = jpeg_scenes.scene(name)
+    at = jpeg_scenes.seams(data)
+    assert same(image.decode_jpeg(gpu_device, data, "L"), jpeg_scenes.restated(name)["luma"])
+    stats = image.jpeg_last_stats()
+    assert (stats["intervals"], stats["subsequences"]) == (at["intervals"], at["subsequences"])
+    assert stats["subsequences"] > 256 and stats["sync_launches"] >= 2
 
 
 def test_the_noise_scene_needs_more_than_one_workgroup(gpu_device):

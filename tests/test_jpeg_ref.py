@@ -94,6 +94,94 @@ def test_encoded_scenes_reach_their_cases():
     assert jpeg_scenes.restated("e_17x9_420")["met"]["longest_code"] == 16
 
 
+def test_earlier_restart_scenes_stay_inside_one_workgroup():
+    """What the seam scenes below are there for: of the scenes before them, the one with more than 256 subsequences has no
+    DRI, and no RSTn has its FF as the last byte of a 64-byte piece of the scan."""
+    new = set(jpeg_scenes.RESTART) | {"w_dc_wrap", "w_dc_wrap_rst", "w_fill_straddles"}
+    for name in set(jpeg_scenes.names()) - new:
+        at = jpeg_scenes.seams(jpeg_scenes.scene(name))
+        assert at["intervals"] == 1 or at["subsequences"] <= 30
+        assert not [s for s in at["straddles"][jpeg_scenes.WAVE_BYTES] if s[0] == s[1] - 1] and not at["lane0"]
+        assert not at["spanning"] or at["intervals"] == 1
+        met = jpeg_scenes.restated(name)["met"]
+        assert -32768 <= met["dc_min"] and met["dc_max"] <= 32767
+
+
+@pytest.mark.parametrize("name", sorted(jpeg_scenes.RESTART))
+def test_restart_scenes_cross_the_sync_kernels_workgroups(name):
+    """More than 256 subsequences in a file with restart intervals: a second launch of the sync kernel, an interval whose
+    subsequences lie in two workgroups (the lanes behind its first take exit_in[i - 1] across the boundary), or one that
+    begins at lane 0 of a later workgroup (known: it takes nothing)."""
+    size, options = jpeg_scenes.RESTART[name]
+    data = jpeg_scenes.scene(name)
+    h, at = ref_jpeg.parse(data), jpeg_scenes.seams(data)
+    assert h["restart"] == options["restart_marker_blocks"] and (h["width"], h["height"]) == (size, size)
+    assert at["intervals"] == -(-h["mcus_x"] * h["mcus_y"] // h["restart"]) == len(ref_jpeg.segments(h)) > 25
+    assert at["subsequences"] > options.get("more_than", jpeg_scenes.SYNC_LANES)
+    assert at[options.get("want", "spanning")]
+    for s in at["spanning"]:
+        first, last = at["sub_first"][s], at["sub_first"][s + 1] - 1
+        assert first // 256 + 1 == last // 256 and last % 256 < first % 256
+    for s in at["lane0"]:
+        assert at["sub_first"][s] >= 256 and at["sub_first"][s] % 256 == 0
+    assert len(data) <= 100 * 1024
+
+
+def test_restart_scenes_as_a_set():
+    at = {name: jpeg_scenes.seams(jpeg_scenes.scene(name)) for name in jpeg_scenes.RESTART}
+    info = {name: ref_jpeg.info(jpeg_scenes.scene(name)) for name in jpeg_scenes.RESTART}
+    assert {(i["components"], i["h"], i["v"]) for i in info.values()} == {(3, 1, 1), (3, 2, 1), (3, 2, 2), (1, 1, 1)}
+    assert sum(1 for a in at.values() if a["spanning"]) >= 5 and any(a["lane0"] for a in at.values())
+    # a workgroup with a neighbour on both sides, and an interval across each of its boundaries
+    big = at["e_rst5_200_444"]
+    assert big["subsequences"] > 512 and {big["sub_first"][s] // 256 for s in big["spanning"]} >= {0, 1}
+    # the table of the scenes' sizes (libjpeg-turbo's encoder decides them; another encoder must not hollow them out)
+    assert {n: (a["intervals"], a["subsequences"] > 256) for n, a in at.items()} == {
+        "e_rst7_120_444": (33, True), "e_rst1_120_444": (225, True), "e_rst5_128_422": (26, True), "e_rst3_160_grey": (134, True),
+        "e_rst3_176_420": (41, True), "e_rst5_200_444": (125, True)}
+
+
+def test_markers_straddle_the_byte_kernels_pieces():
+    """An RSTn whose FF is the last byte of a 64-byte piece of the scan (two waves' ballots) and another whose FF is the last
+    of a 256-byte piece (two workgroups); with FF FF fill: the edge behind the first fill byte, behind the second and behind
+    the marker's own FF."""
+    W, G = jpeg_scenes.WAVE_BYTES, jpeg_scenes.GROUP_BYTES
+    at = jpeg_scenes.seams(jpeg_scenes.scene("e_rst1_120_444"))["straddles"]
+    assert (1, 2) in at[G] and at[W].count((1, 2)) > at[G].count((1, 2))
+    data = jpeg_scenes.scene("w_fill_straddles")
+    h, scan = _scan(data)
+    at = jpeg_scenes.seams(data)
+    assert h["restart"] == 1 and at["intervals"] == 400 and scan.count(b"\xff\xff\xff") == 399 and data.endswith(b"\xff\xff\xff\xd9")
+    for unit in (W, G):
+        assert {(1, 4), (2, 4), (3, 4)} <= set(at["straddles"][unit])
+    # (seams() is told by the bytes themselves)
+    for unit in (W, G):
+        for k in (1, 2, 3):
+            assert any(scan[i - k:i + 4 - k] == b"\xff\xff\xff" + bytes([scan[i + 3 - k]]) and 0xD0 <= scan[i + 3 - k] <= 0xD7
+                       for i in range(unit, len(scan) - 4, unit))
+
+
+def test_dc_sums_leave_the_int16_range():
+    """The luma sums climb past 32 767 and the Cb sums fall past -32 768: the restatement wraps them as the definition says
+    (4.16), and a decoder that keeps them in a wider integer differs.  With DRI the sums start again at zero."""
+    for name, restart in (("w_dc_wrap", 0), ("w_dc_wrap_rst", 20)):
+        data = jpeg_scenes.scene(name)
+        h = ref_jpeg.parse(data)
+        met = jpeg_scenes.restated(name)["met"]
+        assert h["restart"] == restart and met["dc_max"] > 32767 and met["dc_min"] < -32768
+        coef, _ = ref_jpeg.entropy_decode(h)
+        dc = coef[:, 0].astype(np.int64).reshape(-1, 3)
+        steps = np.diff(dc[:, 0])
+        wraps = np.flatnonzero(steps < -60000)
+        assert len(wraps) >= 1 and dc[wraps[0], 0] > 30000 and dc[wraps[0] + 1, 0] < -30000     # 32 7xx -> -3x xxx
+        assert (np.diff(dc[:, 1]) > 60000).any()
+        if restart:
+            assert abs(dc[restart, 0] - dc[0, 0]) < 100 and abs(dc[restart - 1, 0] - dc[restart, 0]) > 20000   # the sum starts again
+        # the pixels tell: the blocks behind the wrap are dark where an unwrapped sum would leave them bright
+        luma = jpeg_scenes.restated(name)["luma"]
+        assert luma.min() < 64 and luma.max() > 192
+
+
 def test_exif_walk():
     for short in (True, False):
         for big in (True, False):

@@ -153,10 +153,15 @@ def test_stats(gpu_device):
     # None and Sub rows start a segment
     assert stats("f_130_paeth")["row_segments"] == 1
     assert stats("f_third_sub")["row_segments"] == 24
+    # segments that end on batch edges (64, 65 and 63 rows, two rows alone); 130 rows as one segment and as 130
+    assert stats("g_segment_edges")["row_segments"] == len(scenes.segments_of(scenes.SEGMENT_EDGES)) == 5
+    assert stats("m_bpp3_paeth")["row_segments"] == 1 and stats("m_bpp1_sub")["row_segments"] == 130
     for name in scenes.names():
         want = scenes.restated(name)["stats"]
         s = stats(name)
         assert (s["stored_blocks"], s["fixed_blocks"], s["dynamic_blocks"]) == (want["stored"], want["fixed"], want["dynamic"]), name
+        if name in scenes.SEAMS:
+            assert s["row_segments"] == len(scenes.segments_of(scenes.SEAMS[name][2])), name
 
 
 def test_image_load(gpu_device, tmp_path):

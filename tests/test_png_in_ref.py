@@ -110,6 +110,83 @@ def test_forced_scenes_reach_their_cases():
     assert types[:3] == [1, 4, 3] and set(scenes.restated("f_130_paeth")["filtered"][::70]) == {4}
 
 
+def _rows(name):
+    """(bpp, row bytes, the filter type of every row) by zlib's inflate of the file's stream."""
+    data = scenes.scene(name)
+    h = ref.parse(data)
+    filtered = zlib.decompress(ref.stream_of(data, h))
+    stride = h["row_bytes"] + 1
+    assert len(filtered) == h["height"] * stride
+    return h["bpp"], h["row_bytes"], list(filtered[::stride])
+
+
+@pytest.mark.parametrize("name", sorted(scenes.SEAMS))
+def test_seam_scenes_reach_their_seams(name):
+    """Every scene of the unfilter kernel's seams: its bpp, its row bytes and its filter types as built, in the file; rows past
+    a tile (or exactly one, or two); a segment past a batch where the scene is there for that; under 100 KB or so."""
+    bpp, row_bytes, types = scenes.SEAMS[name]
+    assert _rows(name) == (bpp, row_bytes, types)
+    want = scenes.restated(name)
+    assert zlib.decompress(ref.stream_of(scenes.scene(name))) == want["filtered"]
+    T, B = scenes.TILE_BYTES, scenes.BATCH_ROWS
+    lengths = scenes.segments_of(types)
+    assert sum(lengths) == len(types) == want["header"]["height"]
+    assert len(scenes.scene(name)) <= 102 * 1024
+    kind = name.split("_")[-1]
+    if name.startswith("m_bpp") and kind.endswith("tiles"):
+        assert row_bytes == int(kind[0]) * T and set(types) == {1, 2, 3, 4} and len(types) == 20
+    elif name.startswith("m_bpp"):
+        assert row_bytes == 2 * T + bpp and len(types) == 2 * B + 2                      # two tiles and a pixel, two batches and two rows
+        assert want["header"]["width"] == {1: 769, 2: 385, 3: 257, 4: 193, 6: 129, 8: 97}[bpp]
+        assert (lengths, set(types)) == {"paeth": ([130], {4}), "average": ([130], {3}), "mixed": ([130], {2, 3, 4}), "sub": ([1] * 130, {1})}[kind]
+    elif name.startswith("k_"):
+        assert want["header"]["depth"] < 8 and bpp == 1 and row_bytes in (T + 1, 2 * T + 1) and types == [1, 4, 3]
+        assert (want["header"]["width"] * want["header"]["depth"] - 1) // 8 == row_bytes - 1 and want["header"]["width"] * want["header"]["depth"] % 8 != 0
+    # the samples are noise: every byte value at the tiles' edges, so a misplaced byte shows
+    rows = ref.unfilter_fast(want["filtered"], len(types), row_bytes, bpp)
+    if row_bytes > T:
+        assert len(np.unique(rows[:, T - 8:T + 8])) > 16
+
+
+def test_segment_edges_scene():
+    bpp, row_bytes, types = _rows("g_segment_edges")
+    assert (bpp, row_bytes) == (3, 450) and row_bytes > scenes.TILE_BYTES
+    assert scenes.segments_of(types) == [64, 65, 63, 1, 1]
+    starts = [y for y, t in enumerate(types) if y == 0 or t < 2]
+    assert starts == [0, 64, 129, 192, 193] and [types[y] for y in starts] == [0, 1, 1, 0, 0]
+    # the second batch of the first segment finds no row; of the second, one row; the third segment's batch meets the next
+    # segment's first row at lane 63
+    assert (starts[1] - starts[0]) % 64 == 0 and (starts[2] - starts[1]) % 64 == 1 and (starts[3] - starts[2]) == 63
+    assert {types[y] for y in range(1, 64)} == {4} and {types[y] for y in range(65, 129)} == {2} and {types[y] for y in range(130, 192)} == {3}
+
+
+def test_stored_block_of_65535():
+    st = _stats("t_stored_65535")
+    assert [(b[0], b[3]) for b in st["blocks"][:2]] == [(0, 65535), (0, 465)] and st["blocks"][2][0] == 2 and len(st["blocks"]) == 3
+    assert (st["stored"], st["fixed"], st["dynamic"]) == (2, 0, 1)
+    assert len(scenes.restated("t_stored_65535")["filtered"]) == 260 * 256 >= 65536
+
+
+def test_the_seam_matrix_is_whole():
+    """Over all scenes: for every bpp and every filter type but None, a row longer than a tile under that type; for every bpp
+    and Up, Average and Paeth, a row under that type that is the 65th or a later one of its segment."""
+    past_tile, past_batch = set(), set()
+    for name in scenes.names():
+        h = scenes.restated(name)["header"]
+        types = list(scenes.restated(name)["filtered"][::h["row_bytes"] + 1])
+        since = 0
+        for y, t in enumerate(types):
+            since = 0 if y == 0 or t < 2 else since + 1
+            if h["row_bytes"] > scenes.TILE_BYTES:
+                past_tile.add((h["bpp"], t))
+            if since >= scenes.BATCH_ROWS:
+                past_batch.add((h["bpp"], t))
+    assert past_tile >= {(bpp, t) for bpp in scenes.BPP_KINDS for t in (1, 2, 3, 4)}
+    assert past_batch >= {(bpp, t) for bpp in scenes.BPP_KINDS for t in (2, 3, 4)}
+    # ... and both at once (the carried pixels of a lane that is not in the first batch)
+    assert set(scenes.BPP_KINDS) == {1, 2, 3, 4, 6, 8}
+
+
 @pytest.mark.parametrize("name", sorted(scenes.refused()))
 def test_refused_files_raise_their_code(name):
     data, code = scenes.refused()[name]

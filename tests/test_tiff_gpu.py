@@ -39,7 +39,10 @@ def test_pixels_are_the_restated_pixels(gpu_device, name):
     compression, on rows of 257, 300 and 600 pixels (longer than a wave's and a workgroup's span of the scan); strips out of file
     order and at odd offsets; LZW: literals only, the self-overlapping code throughout, Clears in mid-stream and in pairs, no
     initial Clear, no EOI, junk behind EOI, 12-bit codes, a full table, libtiff's 600 x 500 noise file; PackBits: header 128,
-    runs and literals of 128, packets crossing row ends, a packet cut at the strip's end; Pillow's files of each kind."""
+    runs and literals of 128, packets crossing row ends, a packet cut at the strip's end; Pillow's files of each kind.  The
+    batches' seams (tests/test_tiff_ref.py shows each on the CPU): strips of 64, 65, 128, 129 and 200 packets in one launch,
+    a run, a literal, a header 128 and a cut packet as a batch's first; Clears at lane 63 and lane 0 of a 64-code batch, in
+    pairs too; rows that are full with a batch's last code, with EOI behind it and without."""
     data = tiff_scenes.scene(name)
     want = restated(name)
     assert same(image.decode_tiff(gpu_device, data, "RGB", 0), want["rgb"])

@@ -109,6 +109,78 @@ def test_scenes_reach_their_cases():
     assert sum(257 - b for b in headers("o_pb_cut") if b > 128) > 47 * 33
 
 
+def _packets(data):
+    """Per strip the headers the decoder meets until the strip's rows are full (a header 128 is a packet of no bytes), and
+    the bytes the last one reaches past the rows."""
+    h, out = ref_tiff.parse(data), []
+    for s in range(h["strips"]):
+        src, need = data[h["offsets"][s]:h["offsets"][s] + h["counts"][s]], h["rows"][s] * h["row_bytes"]
+        at, made, met = 0, 0, []
+        while made < need:
+            b = src[at]
+            met.append(b)
+            at += 1 + (b + 1 if b < 128 else 1 if b > 128 else 0)
+            made += b + 1 if b < 128 else 257 - b if b > 128 else 0
+        assert at == len(src)
+        out.append((met, made - need))
+    return out
+
+
+def test_packbits_strips_cross_the_64_packet_batches():
+    """o_pb_batches: one launch, a wave per strip, each at its own packet count; what the 64th and the 65th packet are."""
+    data = tiff_scenes.scene("o_pb_batches")
+    got = _packets(data)
+    assert len(got) == len(tiff_scenes.PB_BATCHES) == ref_tiff.parse(data)["strips"]
+    kind = lambda b: "noop" if b == 128 else "run" if b > 128 else "lit"
+    for (met, over), (count, run_first, noop, cut) in zip(got, tiff_scenes.PB_BATCHES):
+        assert len(met) == count and over == cut
+        assert [k for k, b in enumerate(met) if b == 128] == ([] if noop is None else [noop])
+        if count > 64 and noop is None and not (cut and count == 65):
+            assert (kind(met[63]), kind(met[64])) == (("lit", "run") if run_first else ("run", "lit"))
+        assert sum(1 for b in met if b in (0, 255)) >= count - 4   # one-byte literals and two-byte runs, but for the first
+    counts = [len(met) for met, _ in got]
+    assert counts[:6] == [64, 65, 65, 128, 129, 200]
+    orders = {(kind(met[63]), kind(met[64])) for met, _ in got if len(met) > 64}
+    assert {("run", "lit"), ("lit", "run"), ("lit", "noop")} <= orders          # both ways round; a header 128 first in a batch
+    assert any(noop is not None and noop % 64 == 0 for _, _, noop, _ in tiff_scenes.PB_BATCHES)
+    # a packet cut by the strip's rows as a batch's first packet: the 65th, and the 129th
+    assert [(len(met) - 1) % 64 for met, over in got if over] == [0, 0] and [over for _, over in got if over] == [7, 100]
+    # the other PackBits scenes stay inside one batch, but for Pillow's files
+    assert max(len(met) for name in ("o_pb_noop", "o_pb_128", "o_pb_crossing_rows", "o_pb_cut") for met, _ in _packets(tiff_scenes.scene(name))) < 64
+
+
+def _lzw_trace(a, **kw):
+    trace = {}
+    tiff_scenes.lzw(a.tobytes(), trace=trace, **kw)
+    return trace
+
+
+def test_lzw_clears_and_ends_sit_on_batch_edges():
+    """The c-th code since a Clear (the initial one: c = 0) is lane c % 64 of a 64-code batch."""
+    g8 = tiff_scenes.picture(47, 33, seed=2)
+    for n in tiff_scenes.LZW_CLEAR_EVERY:
+        trace = _lzw_trace(g8, clear_every=n)
+        assert trace["clear_at"][0] == 0 and len(trace["clear_at"]) >= 4 and set(trace["clear_at"][1:]) == {n}
+        assert n % 64 == (63 if n in (63, 127) else 0)
+        assert _stats("o_lzw_clear_%d" % n)["clears"] == len(trace["clear_at"])
+    trace = _lzw_trace(g8, clear_every=64, clears=2)
+    assert trace["clear_at"][:4] == [0, 0, 64, 0] and _stats("o_lzw_two_clears_64")["clears"] == len(trace["clear_at"])
+    # the earlier scenes: no mid-stream Clear at lane 0 or 63
+    for kw in ({"clear_every": 100}, {"clear_every": 70, "clears": 2}, {"clear_every": 200, "literals": True}):
+        assert not {c % 64 for c in _lzw_trace(g8, **kw)["clear_at"] if c} & {0, 63}
+    # the rows are full with a batch's last code: EOI is the next batch's first code, or there is none
+    a = ref_tiff.samples(tiff_scenes.scene("o_lzw_eoi_first_of_batch"))[1]
+    assert (a == ref_tiff.samples(tiff_scenes.scene("o_lzw_full_at_batch_end"))[1]).all() and a.shape[1:] == (33, 1)
+    with_eoi, without = _lzw_trace(a), _lzw_trace(a, eoi=False)
+    assert with_eoi["clear_at"] == without["clear_at"] == [0]
+    assert with_eoi["eoi_at"] % 64 == 0 and with_eoi["eoi_at"] >= 128 and without["eoi_at"] is None
+    assert without["codes_after_last_clear"] == with_eoi["eoi_at"]
+    assert _stats("o_lzw_full_at_batch_end")["codes"] == _stats("o_lzw_eoi_first_of_batch")["codes"] == 1 + with_eoi["eoi_at"]
+    one, other = tiff_scenes.scene("o_lzw_eoi_first_of_batch"), tiff_scenes.scene("o_lzw_full_at_batch_end")
+    assert ref_tiff.parse(one)["counts"][0] >= ref_tiff.parse(other)["counts"][0]
+    assert _lzw_trace(g8)["eoi_at"] % 64 != 0                                   # (the earlier scenes' strip does not)
+
+
 @pytest.mark.parametrize("name", sorted(tiff_scenes.refused()))
 def test_refused(name):
     data, code = tiff_scenes.refused()[name]

@@ -54,10 +54,11 @@ def lzw(data: bytes, clear_every=3836, initial_clear=True, clears=1, eoi=True, j
     """TIFF 6.0 LZW of data.  clear_every: a Clear after that many codes (libtiff clears when entry 4094 is next: 3836 codes);
     None - never, the table fills and stays.  clears: how many Clear codes stand where one does.  literals: no strings."""
     bits, table, w = _Bits(), {}, b""
-    self_overlaps = 0
+    self_overlaps, clear_at, eoi_at = 0, [], None
 
     def clear():
         for _ in range(clears):
+            clear_at.append(bits.c)   # (the Clear is the c-th code since the Clear before it: lane c % 64 of its batch)
             bits.code(256)
         table.clear()
 
@@ -86,10 +87,12 @@ def lzw(data: bytes, clear_every=3836, initial_clear=True, clears=1, eoi=True, j
             clear()
     if w:
         emit(w)
+    last = bits.c   # the codes since the last Clear: the rows are full behind them
     if eoi:
+        eoi_at = bits.c
         bits.code(257)
     if trace is not None:
-        trace.update(widths=bits.widths, self_overlaps=self_overlaps)
+        trace.update(widths=bits.widths, self_overlaps=self_overlaps, clear_at=clear_at, eoi_at=eoi_at, codes_after_last_clear=last)
     return bits.done() + junk
 
 
@@ -123,6 +126,81 @@ def packbits(data: bytes, noop_every=0, overshoot=False):
         out += data[at:end]
         at = end
     return bytes(out)
+
+
+def packets(plan):
+    """A PackBits stream written packet by packet.  plan: ("run", n, byte), ("lit", bytes) or ("noop",) -> (stream, the
+    bytes it expands to)."""
+    stream, data = bytearray(), bytearray()
+    for p in plan:
+        if p[0] == "noop":
+            stream.append(128)
+        elif p[0] == "run":
+            assert 2 <= p[1] <= 128
+            stream += bytes([257 - p[1], p[2]])
+            data += bytes([p[2]]) * p[1]
+        else:
+            assert 1 <= len(p[1]) <= 128
+            stream += bytes([len(p[1]) - 1]) + bytes(p[1])
+            data += bytes(p[1])
+    return bytes(stream), bytes(data)
+
+
+def short_packets(total, count, run_first, seed, noop_at=None, cut=0):
+    """A plan of `count` packets that expand to `total` bytes (+ `cut`, which the last packet, a run, reaches past the strip's
+    rows): two-byte runs and one-byte literals in turn, the first packets lengthened by what the short ones leave over.
+    noop_at: the packet of that number (from 0) is a header 128."""
+    rng = np.random.default_rng(seed)
+    kinds = [(k % 2 == 0) == run_first for k in range(count)]   # True: a run
+    if cut:
+        kinds[-1] = True
+    lens = [2 if run else 1 for run in kinds]
+    if noop_at is not None:
+        lens[noop_at] = 0
+    if cut:
+        lens[-1] = 1 + cut   # one byte inside the rows
+    slack = total + cut - sum(lens)
+    assert slack >= 0
+    for k in range(count):
+        if lens[k] and not (cut and k == count - 1):
+            add = min(slack, 128 - lens[k])
+            lens[k], slack = lens[k] + add, slack - add
+    assert slack == 0
+    plan, before = [], -1
+    for run, n in zip(kinds, lens):
+        if n == 0:
+            plan.append(("noop",))
+            continue
+        values = rng.integers(0, 256, size=1 if run else n)
+        values[0] = (values[0] if values[0] != before else values[0] + 1) % 256
+        plan.append(("run", n, int(values[0])) if run else ("lit", bytes(values.astype(np.uint8))))
+        before = int(values[-1])
+    return plan
+
+
+# the strips of "o_pb_batches", 300 bytes each (3 rows of 100): (packets, a run first, the number of a header 128, the bytes
+# the last packet reaches past the rows).  A batch of the kernel is 64 packets; the 64th and 65th have the numbers 63 and 64
+PB_BATCHES = ((64, True, None, 0), (65, True, None, 0), (65, False, None, 0), (128, False, None, 0), (129, True, None, 0), (200, True, None, 0),
+              (130, True, 64, 0), (193, False, 128, 0), (65, True, None, 7), (129, False, None, 100))
+
+
+def pb_batches():
+    plans = [short_packets(300, n, first, 40 + k, noop, cut) for k, (n, first, noop, cut) in enumerate(PB_BATCHES)]
+    made = [packets(plan) for plan in plans]
+    a = np.frombuffer(b"".join(data[:300] for _, data in made), dtype=np.uint8).reshape(3 * len(made), 100, 1)
+    streams = iter([stream for stream, _ in made])
+    return write(a, compression=32773, rps=3, encoder=lambda raw: next(streams))
+
+
+def _lzw_full_batches(eoi):
+    """33 pixels wide, the height at which the codes behind the initial Clear are a multiple of 64: the rows are full at a
+    batch's end and EOI, where there is one, would be the next batch's first code."""
+    for h in range(20, 200):
+        a, trace = picture(h, 33, seed=2), {}
+        lzw(a.tobytes(), trace=trace)
+        if trace["codes_after_last_clear"] % 64 == 0:
+            return write(a, compression=5, encoder=functools.partial(lzw, eoi=eoi))
+    raise AssertionError("no height ends its codes at a batch's end")
 
 
 # ---- the writer -----------------------------------------------------------------------------------------------------------------
@@ -220,6 +298,7 @@ def pillow(a, compression="raw", predictor=False, sem=None, strip_rows=None):
     return buf.getvalue()
 
 
+LZW_CLEAR_EVERY = (63, 64, 127, 128)   # the mid-stream Clears at lane 63 and at lane 0 of a batch
 SEM_TEXT = "[Scan]\r\nPixelWidth=2.5e-9\r\nPixelHeight=5e-9\r\n[Stage]\r\nStageT=0\r\n[PrivateFei]\r\nDatabarHeight=5\r\n"
 
 
@@ -268,6 +347,12 @@ def _scenes():
         "o_pb_128": lambda: write(np.concatenate([P(2, 300, kind="flat"), P(2, 300, seed=17, kind="noise")]), compression=32773, rps=2),
         "o_pb_crossing_rows": lambda: write(P(47, 33, kind="flat"), compression=32773, rps=7),
         "o_pb_cut": lambda: write(P(47, 33, kind="flat"), compression=32773, rps=7, encoder=functools.partial(packbits, overshoot=True)),
+        # the seams of the 64-packet and 64-code batches (the c-th code since a Clear is lane c % 64 of its batch)
+        "o_pb_batches": pb_batches,
+        **{"o_lzw_clear_%d" % n: functools.partial(write, g8, compression=5, encoder=functools.partial(lzw, clear_every=n)) for n in LZW_CLEAR_EVERY},
+        "o_lzw_two_clears_64": lambda: write(g8, compression=5, encoder=functools.partial(lzw, clear_every=64, clears=2)),
+        "o_lzw_eoi_first_of_batch": lambda: _lzw_full_batches(True),
+        "o_lzw_full_at_batch_end": lambda: _lzw_full_batches(False),
         "o_sem_exif": lambda: write(g8, rps=7, extra=[(34682, ASCII, SEM_TEXT.encode() + b"\0")], exif_focal=35),
         "o_exif_long_mm": lambda: write(g8, ">", rps=7, exif_focal=70000, exif_short=False),
         "p_g8_raw": lambda: pillow(g8[:, :, 0]),
