@@ -1,6 +1,7 @@
 """The images the JPEG encoder's tests encode (tests/ref_jpeg_out.py is the definition of the file): name -> (pixels, quality,
 sampling, optimize).  Every image is the smallest at which one part of the encoder can break; test_jpeg_out_ref.py asserts,
-on the restatement alone, that each scene does reach the case it is here for, and that the restated file is Pillow's."""
+on the restatement alone, that each scene does reach the case it is here for, and that the restated file is Pillow's.  Two
+scenes too slow to restate in every run stand beside scenes(): BIG."""
 from __future__ import annotations
 
 import functools
@@ -77,9 +78,36 @@ def scenes():
     }
     for q in (1, 49, 50, 51, 100):
         s["quality_%d" % q] = (smooth(12, 13, 19, 3), q, S420, False)
+    # past one launch of the transform's workgroups (32 blocks each): a ragged last group in the second trip, a dummy column
+    # in every MCU row and a dummy row at the bottom, so dummies in both trips; 65496 is the largest multiple of 8 that libjpeg takes
+    s["rgb_24x65496_420_optimize"] = (smooth(21, 65496, 24, 3), 75, S420, True)
+    # the largest width and height: SOF0's size bytes FF FF, the edge clamps at the last row and column, 8192 blocks in a line
+    s["grey_65535x8"] = (smooth(23, 8, 65535), 75, S444, False)
+    s["grey_8x65535"] = (smooth(23, 65535, 8), 75, S444, False)
     s["grey_alpha_copy"] = (with_alpha(s["last_byte_ff"][0], 13), 90, S444, False)
     s["rgba_copy"] = (with_alpha(s["rgb_9x17_420"][0], 14), 90, S420, False)
     return s
+
+
+# the scenes beyond libjpeg's 65500: Pillow refuses them (test_jpeg_out_ref.py asserts that it does), so no file of Pillow's
+# stands behind the restatement there
+OVERSIZE = ("grey_65535x8", "grey_8x65535")
+
+# Past one launch of a lane a block (mesh.GRID_LANES).  Not in scenes(): the restatement of a quarter of a million blocks takes
+# a quarter of a minute, so the device's file is compared with Pillow's (test_jpeg_out_gpu.py) and one CPU test pins the
+# restatement to Pillow on the first.
+#   grey_4104x4096_optimize  262656 blocks and 3.2 MB of unstuffed stream, past three launches of the stuffing tiles too
+#   rgb_3352x3352_420        264600 blocks with a dummy column in every MCU row and a dummy row: dummies in the second trip
+BIG = ("grey_4104x4096_optimize", "rgb_3352x3352_420")
+
+
+def big_scene(name):
+    """(pixels, quality, sampling, optimize) of a scene of BIG; the grey one is the smooth surface with noise of 0 .. 11 on it"""
+    if name == "grey_4104x4096_optimize":
+        pixels = smooth(22, 4096, 4104).astype(np.int64) + np.random.RandomState(22).randint(0, 12, size=(4096, 4104))
+        return (pixels & 0xFF).astype(np.uint8), 90, S444, True
+    assert name == "rgb_3352x3352_420"
+    return smooth(24, 3352, 3352, 3), 75, S420, False
 
 
 # the scene whose file a 2- or 4-channel scene must give: that of its grey or RGB part

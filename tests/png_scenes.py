@@ -1,6 +1,6 @@
 """The images the PNG tests encode (tests/ref_png.py is the definition of the file): name -> (pixels, filter).  Every image is
 the smallest at which one part of the encoder can break; test_png_ref.py asserts, on the restatement alone, that each scene
-does reach the case it is here for."""
+does reach the case it is here for (DESIGN.md 4.15 lists the tokeniser's and the trailer's seams and the scene of each)."""
 from __future__ import annotations
 
 import functools
@@ -27,6 +27,46 @@ def runs():
         img[y, :run + 1] = 200
         img[y, run + 1:] = 10 + (np.arange(width - run - 1) % 2) * 7 + (np.arange(width - run - 1) % 3)
     return img
+
+
+def filler(n: int):
+    """n bytes of 10 .. 19 of which no two neighbours are equal: the filler behind the runs of runs()"""
+    return 10 + (np.arange(n) % 2) * 7 + (np.arange(n) % 3)
+
+
+def run_row(width: int, start: int, run: int, value: int):
+    """A grey row for filter 0 whose filtered bytes (the filter's 0 first, so a pixel's position is its index + 1) repeat at
+    exactly the `run` positions from `start` on: `value` at the run + 1 pixels from position start - 1, filler around them."""
+    assert 2 <= start and start + run <= width + 1 and run >= 1
+    row = filler(width)
+    row[start - 2:start - 1 + run] = value
+    if start - 1 + run < width:
+        row[start - 1 + run:] = filler(width - (start - 1 + run))
+    return row.astype(np.uint8)
+
+
+# run_seams: one row per (first repeating position, repeating positions).  The tokeniser (row_tokens in png_kernels.hip)
+# takes 64 positions a step; the starts lie around lanes 0 .. 2 and 61 .. 63 of the first three steps, the lengths around
+# every count at which a run's chunks of 258, its rest of 0 .. 2 literals or its look of 320 bytes past a step change.
+SEAM_STARTS = (2, 61, 62, 63, 64, 65, 66, 126, 127, 128, 129)
+SEAM_RUNS = (*range(1, 9), *range(59, 68), 128, 129, *range(256, 263), *range(319, 328), *range(516, 520), *range(576, 584))
+SEAM_WIDTH = 999
+
+
+def run_seams():
+    return np.stack([run_row(SEAM_WIDTH, s, run, 200) for s in SEAM_STARTS for run in SEAM_RUNS])
+
+
+# run_ends_<w>: every row's run ends at the row's last byte, RUN_END_PAST[w] bytes past the step (the second, positions 64 ..
+# 127) in which it starts, at lane 62 (rows 0 and 2) or 63 (rows 1 and 3).  The run's byte is 0, the byte behind every row
+# but the last is the next row's filter byte, 0 too: a look past the step that did not stop at the row's end would find the
+# run one byte longer.  0: no byte follows the step, so there is no look; 12 gives a look that breaks in its third lane.
+RUN_END_PAST = {127: 0, 128: 1, 131: 4, 132: 5, 133: 6, 139: 12, 384: 257, 446: 319}
+RUN_END_STARTS = (126, 127, 126, 127)
+
+
+def run_ends(width: int):
+    return np.stack([run_row(width, s, width + 1 - s, 0) for s in RUN_END_STARTS])
 
 
 def channels(c: int):
@@ -111,7 +151,12 @@ def scenes():
         "tall_6x4500": ((rng.randint(0, 256, size=(4500, 6)) * (np.arange(4500)[:, None] % 3 > 0) + 9).astype(np.uint8), ref_png.FILTER_SUB),
         "flat": (np.full((120, 256, 3), 90, dtype=np.uint8), ref_png.FILTER_ADAPTIVE),
         "smooth_noise": (smooth_noise(), ref_png.FILTER_ADAPTIVE),
+        "run_seams": (run_seams(), ref_png.FILTER_NONE),
+        # more rows than Adler's modulus 65521: the trailer's reduction of the rows behind a row, and 18 rows a wave
+        "column_1x70000": ((np.arange(70000) * 7 % 251).astype(np.uint8).reshape(70000, 1), ref_png.FILTER_NONE),
     }
+    for w in RUN_END_PAST:
+        s["run_ends_%d" % w] = (run_ends(w), ref_png.FILTER_NONE)
     for c in (1, 2, 3, 4):
         s["channels_%d" % c] = (channels(c), ref_png.FILTER_ADAPTIVE)
         for k in range(5):

@@ -291,7 +291,8 @@ def encode(pixels, quality: int = 75, sampling: int = S420, optimize: bool = Fal
     tables = [optimal_table(hist[k]) for k in range(n_tables)] if optimize else list(STANDARD_TABLES[:n_tables])
     codes = [code_table(*t) for t in tables]
     nbits, pieces = 0, []
-    met = {"zrl": 0, "eob": 0, "coef63": 0, "dc_category": {}, "ac_category": 0, "longest_block": 0, "shortest_block": 1 << 30}
+    met = {"zrl": 0, "eob": 0, "coef63": 0, "dc_category": {}, "ac_category": 0, "longest_block": 0, "shortest_block": 1 << 30,
+           "ends_on_dword": 0, "long_from_dword": 0}
     for t, syms in symbols:
         before = nbits
         for is_ac, s, v, n in syms:
@@ -308,6 +309,10 @@ def encode(pixels, quality: int = 75, sampling: int = S420, optimize: bool = Fal
                 met["dc_category"][sign * n] = met["dc_category"].get(sign * n, 0) + 1
         met["coef63"] += syms[-1][0] == 1 and syms[-1][1] != 0
         met["longest_block"], met["shortest_block"] = max(met["longest_block"], nbits - before), min(met["shortest_block"], nbits - before)
+        # the 32-bit words of the unstuffed stream: a block that ends exactly on a word's boundary (nothing left to share with
+        # the next block), and a block of more than 32 bits that starts on one (its first word is not shared with the one before)
+        met["ends_on_dword"] += nbits % 32 == 0
+        met["long_from_dword"] += before % 32 == 0 and nbits - before > 32
     padding = -nbits % 8
     raw = int("".join(pieces) + "1" * padding, 2).to_bytes((nbits + padding) // 8, "big")
     data = raw.replace(b"\xFF", b"\xFF\x00")

@@ -10,6 +10,7 @@ import pytest
 
 import jpeg_out_scenes
 import ref_jpeg
+import ref_jpeg_out
 from cybervision_amd import _lib, mesh
 from cybervision_amd.mesh import jpeg_encode_last_stats  # (without the encoder every test here fails at this import)
 
@@ -33,7 +34,9 @@ def test_file_is_the_restated_file(gpu_device, name):
     two replications; odd sizes at every sampling; quality 1, 49, 50, 51, 100; AC category 10 and a coefficient 63; DC
     differences of category 11 in both signs; ZRL and EOB; 6-bit blocks, twenty to a dword, and tables of one symbol; two
     FF bytes in a row, an FF as the padded last byte and as the last byte of a stuffing tile; 5000 and 1536 blocks (more
-    than a workgroup, more than one step of the scan); 2 and 4 channels."""
+    than a workgroup, more than one step of the scan); 2 and 4 channels; 49128 blocks at 24 x 65496 (the transform's second
+    trip over its 1024 workgroups, a ragged last group, dummies in both trips); 65535 wide and 65535 high (SOF0's FF FF, the
+    clamps at the last row and column, 8192 blocks in a line)."""
     pixels, quality, sampling, optimize = jpeg_out_scenes.scenes()[name]
     want = jpeg_out_scenes.restated(name)
     sections = []
@@ -41,6 +44,47 @@ def test_file_is_the_restated_file(gpu_device, name):
     assert same(got, want["file"])
     assert tuple(sections) == want["sections"]
     assert jpeg_encode_last_stats() == want["stats"]
+
+
+def scan_of(file: bytes):
+    """(bytes up to and including the SOS segment, FF 00 pairs in the scan's data) of a baseline file with one scan"""
+    at = 2
+    while True:
+        assert file[at] == 0xFF
+        marker, at = file[at + 1], at + 2 + int.from_bytes(file[at + 2:at + 4], "big")
+        if marker == 0xDA:
+            return at, file[at:-2].count(b"\xFF\x00")
+
+
+@pytest.mark.parametrize("name", jpeg_out_scenes.BIG)
+def test_past_one_launch_of_lanes(gpu_device, name):
+    """More blocks than mesh.GRID_LANES, so the kernels that take a lane a block make a second trip: the histogram, the lengths
+    and the write in the grey scene (4104 x 4096 with optimize, 262656 blocks), whose 3.2 MB of unstuffed stream are also more
+    than three launches of 1024-byte tiles in the two stuffing kernels; the dummy-DC kernel in the colour scene (3352 x 3352 at
+    4:2:0, 264600 blocks), whose last MCUs hold dummy blocks.  The expected file is Pillow's - the restatement would take a
+    quarter of a minute, test_jpeg_out_ref.py pins it to Pillow on the grey scene once - and sections and stats are read
+    from that file and from the geometry."""
+    from PIL import Image
+
+    pixels, quality, sampling, optimize = jpeg_out_scenes.big_scene(name)
+    buf = io.BytesIO()
+    Image.fromarray(pixels).save(buf, format="JPEG", quality=quality, subsampling=sampling, optimize=optimize)
+    want = buf.getvalue()
+    head, stuffed = scan_of(want)
+    raw = len(want) - head - 2 - stuffed
+    g = ref_jpeg_out.geometry(pixels.shape[1], pixels.shape[0], 1 if pixels.ndim == 2 else 3, sampling)
+    blocks = g["mcus_x"] * g["mcus_y"] * g["blocks_per_mcu"]
+    dummies = g["mcus_x"] * g["mcus_y"] * g["hs"] * g["vs"] - g["blocks_x"] * g["blocks_y"]
+    assert blocks > mesh.GRID_LANES and (dummies > 0) == (pixels.ndim == 3)
+    if pixels.ndim == 2:
+        assert raw > 3 * (mesh.GRID_LANES // 256) * ref_jpeg_out.STUFF_TILE
+    sections = []
+    got = mesh.jpeg(gpu_device, pixels, quality, sampling, optimize, sections=sections)
+    assert same(got, want)
+    assert tuple(sections) == (head, len(want) - head - 2, 2)
+    stats = jpeg_encode_last_stats()
+    assert (stats["blocks"], stats["dummy_blocks"], stats["stuffed"]) == (blocks, dummies, stuffed)
+    assert 8 * (raw - 1) < stats["bits"] <= 8 * raw
 
 
 def test_grey_ignores_sampling(gpu_device):

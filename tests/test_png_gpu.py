@@ -31,7 +31,10 @@ def test_file_is_the_restated_file(gpu_device, name):
     3, 4, 258 .. 261, 516 and 517 (match splitting, symbol 285, HLIT = 286); every channel count at an odd width and every
     fixed filter; the adaptive choice with ties; the 15-bit limit; an 80 001-byte row (look-ahead across steps, Adler sums
     past 32 bits); 1025 rows, and 4500 rows (more than a launch has waves: a wave takes a second row); flat and smooth
-    images."""
+    images; run_seams, 517 rows of one run each that begins around lanes 0 .. 2 and 61 .. 63 with every length at which the
+    look past a step breaks in another lane or byte, the chunks of 258 or the rest of one or two literals change; the
+    run_ends images, whose runs of zeros end with their row 0 to 319 bytes past a step, a zero behind them; a column of 70000
+    rows (more than Adler's 65521 behind a row, 18 rows a wave)."""
     pixels, kind = png_scenes.scenes()[name]
     want = png_scenes.restated(name)
     sections = []
