@@ -144,6 +144,11 @@ SIGNATURES = {
     # (out_stats[4])
     "cvhip_jpeg_encode": (C.c_int, [_vp, _vp, _u32, _u32, _u32, _u32, _u32, _u32, _vp, C.c_uint64, C.POINTER(C.c_uint64), _vp]),
     "cvhip_jpeg_encode_last_stats": (C.c_int, [_vp]),
+    # the TIFF file image: (pixels, width, height, channels, compression, predictor, rows_per_strip, out, cap, out_size,
+    # out_sections[3]); (out_stats[4]); (out_ticks[3])
+    "cvhip_tiff_encode": (C.c_int, [_vp, _vp, _u32, _u32, _u32, _u32, _u32, _u32, _vp, C.c_uint64, C.POINTER(C.c_uint64), _vp]),
+    "cvhip_tiff_encode_last_stats": (C.c_int, [_vp]),
+    "cvhip_tiff_encode_last_phases": (C.c_int, [_vp]),
     # JPEG files in: (file, size, out_info[6]); (file, size, format, drop_rows, out, cap, out_size); (out_stats[4])
     "cvhip_jpeg_info": (C.c_int, [_vp, C.c_uint64, _vp]),
     "cvhip_jpeg_decode": (C.c_int, [_vp, _vp, C.c_uint64, _u32, _u32, _vp, C.c_uint64, C.POINTER(C.c_uint64)]),

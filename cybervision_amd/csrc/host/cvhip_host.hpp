@@ -788,6 +788,39 @@ inline JpegEncodeStats jpeg_encode_last_stats()
     return JpegEncodeStats{st[0], st[1], st[2], st[3]};
 }
 
+// ---- the TIFF encoder: what img.save writes for a depth map whose path ends in .tif (:1141) ---------------------
+struct TiffSections {
+    uint64_t before = 0, strips = 0, after = 0; // the bytes before the first strip, the strips with their padding, the bytes after
+};
+enum class TiffCompression : uint32_t { None = 1, Lzw = 5, PackBits = 32773 };
+struct TiffEncodeStats {
+    uint64_t strips = 0, codes = 0, clears = 0, packets = 0;
+};
+
+// The classic little-endian TIFF file's bytes of width x height pixels of `channels` (1: grey, 2: grey and alpha, 3: RGB, 4:
+// RGBA) bytes each.  predictor 0: 2 with LZW, 1 otherwise.  rows_per_strip 0: about 8 KB a strip.
+inline std::vector<uint8_t> tiff_encode(GpuDevice &dev, const uint8_t *pixels, uint32_t width, uint32_t height, uint32_t channels,
+                                        TiffCompression compression = TiffCompression::Lzw, uint32_t predictor = 0, uint32_t rows_per_strip = 0,
+                                        TiffSections *sections = nullptr)
+{
+    uint64_t sec[3] = {0, 0, 0};
+    if (!predictor) predictor = compression == TiffCompression::Lzw ? 2u : 1u;
+    std::vector<uint8_t> out = detail::size_then_fill([&](uint8_t *dst, uint64_t cap, uint64_t *size) {
+        check(cvhip_tiff_encode(dev.handle(), pixels, width, height, channels, (uint32_t)compression, predictor, rows_per_strip, dst, cap, size, sec),
+              "cvhip_tiff_encode");
+    });
+    if (sections) *sections = TiffSections{sec[0], sec[1], sec[2]};
+    return out;
+}
+
+// of this thread's last tiff_encode
+inline TiffEncodeStats tiff_encode_last_stats()
+{
+    uint64_t st[4] = {0, 0, 0, 0};
+    check(cvhip_tiff_encode_last_stats(st), "cvhip_tiff_encode_last_stats");
+    return TiffEncodeStats{st[0], st[1], st[2], st[3]};
+}
+
 // ImageWriter::complete: the depth map through `table` (256 x R, G, B) -> width x height x RGBA
 inline std::vector<uint8_t> colour_map(GpuDevice &dev, const DepthImage &img, const std::array<uint8_t, 768> &table)
 {

@@ -7,7 +7,8 @@ The mesh output: `ply` / `write_ply` - PlyWriter's binary file 
 `depth_image_rgba` - ImageWriter::complete's colours; the colour table is the caller's.  `obj` / `write_obj` / `obj_mtl` - ObjWriter's
 Wavefront OBJ text and its .mtl, `f64_display` - the decimal text of doubles that it rests on.  `png` / `write_png` /
 `write_depth_png` - the PNG file image of the textures and of the depth map.  `jpeg` / `write_jpeg` /
-`write_depth_jpeg` - the baseline JPEG file image, libjpeg's file, of the depth map.
+`write_depth_jpeg` - the baseline JPEG file image, libjpeg's file, of the depth map.  `tiff` / `write_tiff` /
+`write_depth_tiff` - the TIFF file image, uncompressed, LZW or PackBits, of the depth map.
 No compute in Python - array bookkeeping and the calls only.
 
 Defined where the reference's result depends on its thread order: a depth-buffer cell is the minimum of its depths (a
@@ -478,6 +479,55 @@ def write_depth_jpeg(path, device, surface, image_shapes, project_to_image: int,
     depth_image_rgba(...)["rgba"]: alpha is dropped, a cell without a depth is black."""
     d_rgba, origin, minmax = _depth_rgba_device(device, surface, image_shapes, project_to_image, scale, polygons, table)
     sections = write_jpeg(path, device, d_rgba, quality, sampling, optimize)
+    return {"width": int(d_rgba.shape[1]), "height": int(d_rgba.shape[0]), "origin": (float(origin[0]), float(origin[1])),
+            "min_depth": float(minmax[0]), "max_depth": float(minmax[1]), "sections": sections}
+
+
+class TiffCompression(enum.IntEnum):
+    """The `compression` of cvhip_tiff_encode (CVHIP_TIFF_COMPRESSION_*, the values of TIFF's tag 259)."""
+    NONE = 1
+    LZW = 5
+    PACKBITS = 32773
+
+
+TIFF_ENCODE_STATS = ("strips", "codes", "clears", "packets")
+
+
+def tiff(device, pixels, compression=TiffCompression.LZW, predictor=None, rows_per_strip=0, sections=None):
+    """The classic little-endian TIFF file image of an 8-bit image (cvhip_tiff_encode) -> uint8 array.
+    pixels: [h, w] or [h, w, c] uint8 with c = 1 (grey), 2 (grey and alpha), 3 (RGB) or 4 (RGBA), as a numpy array or as a
+    device tensor (then they do not leave the device).  compression: a TiffCompression; the LZW strips are libtiff's byte for
+    byte.  predictor: 1 or 2 (horizontal differencing, with LZW only); None - 2 with LZW, 1 otherwise.  rows_per_strip: 0 -
+    about 8 KB a strip.  `sections`, a list, receives the bytes before the first strip, the strips' with their padding, and
+    the bytes after (0)."""
+    args, _keep = _pixel_args(pixels)
+    if predictor is None:
+        predictor = 2 if int(compression) == TiffCompression.LZW else 1
+    return _file_image("cvhip_tiff_encode", [device.handle, *args, int(compression), int(predictor), int(rows_per_strip)], 3, sections)
+
+
+def tiff_encode_last_stats() -> dict:
+    """cvhip_tiff_encode_last_stats: of this thread's last `tiff` - strips, LZW codes (Clears and EOIs included), Clear codes,
+    PackBits packets."""
+    s = np.zeros(len(TIFF_ENCODE_STATS), dtype=np.uint64)
+    _lib.check(_lib.lib().cvhip_tiff_encode_last_stats(C.c_void_p(s.ctypes.data)), "cvhip_tiff_encode_last_stats")
+    return dict(zip(TIFF_ENCODE_STATS, (int(v) for v in s)))
+
+
+def write_tiff(path, device, pixels, compression=TiffCompression.LZW, predictor=None, rows_per_strip=0):
+    """`tiff` written to `path` -> (before, strips, after) byte counts."""
+    sections = []
+    tiff(device, pixels, compression, predictor, rows_per_strip, sections=sections).tofile(path)
+    return tuple(sections)
+
+
+def write_depth_tiff(path, device, surface, image_shapes, project_to_image: int, scale: float, polygons, table,
+                     compression=TiffCompression.LZW, predictor=None, rows_per_strip=0):
+    """write_depth_png with cvhip_tiff_encode as the encoder: the depth map's RGBA stays in device memory, only the file
+    crosses -> dict: width, height, origin, min_depth, max_depth, sections.  The file decodes to
+    depth_image_rgba(...)["rgba"]: four samples, the fourth unassociated alpha."""
+    d_rgba, origin, minmax = _depth_rgba_device(device, surface, image_shapes, project_to_image, scale, polygons, table)
+    sections = write_tiff(path, device, d_rgba, compression, predictor, rows_per_strip)
     return {"width": int(d_rgba.shape[1]), "height": int(d_rgba.shape[0]), "origin": (float(origin[0]), float(origin[1])),
             "min_depth": float(minmax[0]), "max_depth": float(minmax[1]), "sections": sections}
 

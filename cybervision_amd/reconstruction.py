@@ -393,7 +393,7 @@ def reconstruct_perspective(device, pyramids, K, bundle_adjustment: bool = True,
 def reconstruct_perspective_mesh(device, pyramids, K, triangulate=None, project_to_image=None, depth_scale: float = -1.0,
                                  ply_path=None, images=None, vertex_mode=0, out_scale=(1.0, 1.0, 1.0), colour_table=None,
                                  obj_path=None, save_textures=False, depth_png_path=None, depth_jpeg_path=None, jpeg_quality=75,
-                                 **kwargs):
+                                 depth_tiff_path=None, **kwargs):
     """reconstruct_perspective, then the mesh stage of output::output (output.rs:567-611; DESIGN.md 4.11) on its surface:
     mesh.create - per camera the Delaunay input, `triangulate(xy) -> [f, 3]` (the caller's Delaunay; default
     mesh.delaunay_scipy; mesh.delaunay_device(device) runs on the device and needs no scipy), the occlusion culling and the
@@ -412,7 +412,9 @@ def reconstruct_perspective_mesh(device, pyramids, K, triangulate=None, project_
     depth_png_path - the depth map's RGBA is written there (mesh.write_depth_png, out["depth_png"] is its dict); it needs
     project_to_image and colour_table (ValueError otherwise).
     depth_jpeg_path - the depth map's RGB is written there as a baseline JPEG file of quality jpeg_quality
-    (mesh.write_depth_jpeg, out["depth_jpeg"] is its dict, its time timings_ms["jpeg"]); the same two preconditions."""
+    (mesh.write_depth_jpeg, out["depth_jpeg"] is its dict, its time timings_ms["jpeg"]); the same two preconditions.
+    depth_tiff_path - the depth map's RGBA is written there as an LZW TIFF file (mesh.write_depth_tiff,
+    out["depth_tiff"] is its dict, its time timings_ms["tiff"]); the same two preconditions."""
     import time
 
     from . import mesh
@@ -421,6 +423,8 @@ def reconstruct_perspective_mesh(device, pyramids, K, triangulate=None, project_
         raise ValueError("depth_png_path needs project_to_image and colour_table")
     if depth_jpeg_path is not None and (project_to_image is None or colour_table is None):
         raise ValueError("depth_jpeg_path needs project_to_image and colour_table")
+    if depth_tiff_path is not None and (project_to_image is None or colour_table is None):
+        raise ValueError("depth_tiff_path needs project_to_image and colour_table")
     out = reconstruct_perspective(device, pyramids, K, **kwargs)
     shapes = [(int(p[0].shape[1]), int(p[0].shape[0])) for p in pyramids]
     # (the surface's cameras are the placed images, in image order: prune_projections keeps the order)
@@ -463,12 +467,17 @@ def reconstruct_perspective_mesh(device, pyramids, K, triangulate=None, project_
         out["depth_jpeg"] = mesh.write_depth_jpeg(depth_jpeg_path, device, out["surface"], shapes, project_to_image, depth_scale,
                                                   out["mesh"]["polygons"], colour_table, quality=jpeg_quality)
         out["timings_ms"]["jpeg"] = (time.perf_counter() - t5) * 1e3
+    if depth_tiff_path is not None:
+        t6 = time.perf_counter()
+        out["depth_tiff"] = mesh.write_depth_tiff(depth_tiff_path, device, out["surface"], shapes, project_to_image, depth_scale,
+                                                  out["mesh"]["polygons"], colour_table)
+        out["timings_ms"]["tiff"] = (time.perf_counter() - t6) * 1e3
     return out
 
 
 def reconstruct_affine_mesh(device, pyramid1, pyramid2, f, triangulate=None, project_to_image=None, depth_scale: float = -1.0,
                             ply_path=None, obj_path=None, images=None, vertex_mode=0, out_scale=(1.0, 1.0, 1.0), colour_table=None,
-                            save_textures=False, depth_png_path=None, depth_jpeg_path=None, jpeg_quality=75):
+                            save_textures=False, depth_png_path=None, depth_jpeg_path=None, jpeg_quality=75, depth_tiff_path=None):
     """The affine `reconstruct` of one pair, through to the mesh and its outputs: the dense correlation of the two pyramids
     with the affine F, AffineTriangulation::triangulate straight from the device grid (PointCorrelations.triangulate_affine),
     its Surface (triangulation.affine_surface: two cameras with K = diag(1, 1, 0)), mesh.create - both cameras are
@@ -476,7 +485,8 @@ def reconstruct_affine_mesh(device, pyramid1, pyramid2, f, triangulate=None, pro
     with camera 0 - and the outputs of reconstruct_perspective_mesh, each only when asked for: project_to_image (with
     depth_scale, colour_table), ply_path, obj_path (with images - one per image of the pair -, vertex_mode, out_scale),
     save_textures and depth_png_path (the PNG files; timings_ms["png"]), depth_jpeg_path and jpeg_quality (the JPEG file of
-    the depth map; out["depth_jpeg"], timings_ms["jpeg"]).
+    the depth map; out["depth_jpeg"], timings_ms["jpeg"]), depth_tiff_path (the TIFF file of the depth map's RGBA;
+    out["depth_tiff"], timings_ms["tiff"]).
     triangulate: the Delaunay of a camera's points; the default is mesh.delaunay_device(device, lattice=True) - the camera
     points are integer pixels, every star is an exact tie, and cvhip_mesh_delaunay decides those as defined, on the device
     (scipy's tie choices are not the defined ones).
@@ -488,6 +498,8 @@ def reconstruct_affine_mesh(device, pyramid1, pyramid2, f, triangulate=None, pro
         raise ValueError("depth_png_path needs project_to_image and colour_table")
     if depth_jpeg_path is not None and (project_to_image is None or colour_table is None):
         raise ValueError("depth_jpeg_path needs project_to_image and colour_table")
+    if depth_tiff_path is not None and (project_to_image is None or colour_table is None):
+        raise ValueError("depth_tiff_path needs project_to_image and colour_table")
     rec = ImageReconstruction(device, ProjectionMode.Affine)
     shapes = [(int(p[0].shape[1]), int(p[0].shape[0])) for p in (pyramid1, pyramid2)]
     pc = correlation.PointCorrelations(device, shapes[0], shapes[1], f, correlation.ProjectionMode(int(ProjectionMode.Affine)))
@@ -531,6 +543,9 @@ def reconstruct_affine_mesh(device, pyramid1, pyramid2, f, triangulate=None, pro
     if depth_jpeg_path is not None:
         out["depth_jpeg"] = rec._timed("jpeg", lambda: mesh.write_depth_jpeg(depth_jpeg_path, device, out["surface"], shapes, project_to_image,
                                                                             depth_scale, polygons, colour_table, quality=jpeg_quality))
+    if depth_tiff_path is not None:
+        out["depth_tiff"] = rec._timed("tiff", lambda: mesh.write_depth_tiff(depth_tiff_path, device, out["surface"], shapes, project_to_image,
+                                                                            depth_scale, polygons, colour_table))
     out["timings_ms"] = dict(rec.timings_ms)
     return out
 

@@ -645,6 +645,42 @@ int cvhip_jpeg_encode(cvhip_device *dev, const uint8_t *pixels, uint32_t width, 
 int cvhip_jpeg_encode_last_stats(uint64_t *out_stats);
 
 /* ------------------------------------------------------------------------------------------
+ * TIFF files out (csrc/tiff_encode_kernels.hip, csrc/tiff_encode_common.hpp): img.save (src/output.rs:1141)
+ * of a depth map whose path ends in .tif, and the format of the SEM pairs cvhip_tiff_decode reads.  The file is DEFINED here
+ * (tests/ref_tiff_out.py; the `image` crate's encoder is not restated): classic little-endian TIFF - II, 42, the one IFD at
+ * offset 8 - with the entries 256 ImageWidth and 257 ImageLength (LONG), 258 BitsPerSample (`channels` SHORTs of 8), 259
+ * Compression, 262 Photometric (1 for 1 or 2 channels, 2 for 3 or 4), 273 StripOffsets (LONG), 277 SamplesPerPixel, 278
+ * RowsPerStrip (LONG), 279 StripByteCounts (LONG), 284 PlanarConfiguration 1, 317 Predictor only when it is 2, 338 ExtraSamples 2
+ * (unassociated alpha) only for 2 or 4 channels; values of 4 bytes or less inline, the others behind the IFD in tag order;
+ * then the strips in order, each at an even offset (a 0 byte pads the strip in front); nothing else.
+ *  - rows_per_strip = 0 is max(1, 8192 / row_bytes) (TIFF 6.0's "about 8 KB"); any other value is clamped to height;
+ *  - compression 1: the rows;  32773 PackBits: row by row, greedily - from the position the maximal run of equal bytes (at most
+ *    128), 3 or more a run packet, otherwise a literal packet up to where three equal bytes begin, 128 bytes or the row's end
+ *    (not libtiff's packets; any PackBits reader returns the rows);  5 LZW: TIFF 6.0's as libtiff writes it byte for byte -
+ *    MSB-first codes, a Clear first, greedy longest match, the early change of the code width, a Clear after 3836 codes (also
+ *    when that code is the strip's last, in front of EOI), EOI, zero bits to the byte's end;
+ *  - predictor 2 (LZW only): each byte minus the byte `channels` before it in its row, modulo 256.
+ * pixels (height x width x channels bytes, rows packed) and out are host or device pointers, out of any alignment.
+ * out_sections[3] (may be NULL) = the bytes before the first strip, the strips with their padding, the bytes after (0).
+ * cap = 0 sizes the file and writes nothing; 0 < cap < size is CVHIP_ERR_INVALID with nothing written.  CVHIP_ERR_INVALID too:
+ * width or height 0, channels not 1 to 4, a compression other than 1, 5 or 32773, predictor not 1 or 2, predictor 2 without
+ * LZW.  CVHIP_ERR_UNSUPPORTED: a dimension of 65536 or more, a file of 2^32 bytes or more, a strip of 2^31 bytes or more.
+ * Not here: 16-bit samples, tiles, BigTIFF, Deflate, SEM metadata out, EXIF out. */
+#define CVHIP_TIFF_COMPRESSION_NONE 1u
+#define CVHIP_TIFF_COMPRESSION_LZW 5u
+#define CVHIP_TIFF_COMPRESSION_PACKBITS 32773u
+int cvhip_tiff_encode(cvhip_device *dev, const uint8_t *pixels, uint32_t width, uint32_t height, uint32_t channels,
+                      uint32_t compression, uint32_t predictor, uint32_t rows_per_strip,
+                      uint8_t *out, uint64_t cap, uint64_t *out_size, uint64_t *out_sections);
+/* Of the calling thread's last cvhip_tiff_encode that sized or wrote a file: out_stats[4] = strips, LZW codes written (Clears
+ * and EOIs included), Clear codes written, PackBits packets. */
+int cvhip_tiff_encode_last_stats(uint64_t *out_stats);
+/* Of the same call, for measurements (tests/tools/bench_tiff_out.py): out_ticks[3] = the ticks of the device's 100 MHz clock that
+ * the LZW waves spent loading their strips' bytes, on the serial walk against the table, and packing the codes - each summed
+ * over the strips, which run side by side, so the three give the shares of the LZW kernel's time, not its length.  0 without LZW. */
+int cvhip_tiff_encode_last_phases(uint64_t *out_ticks);
+
+/* ------------------------------------------------------------------------------------------
  * JPEG files in (csrc/jpeg_kernels.hip, csrc/jpeg_common.hpp): what the reference opens with
  * image::open(path)?.into_luma8() / into_rgb8() and crops by databar_height (src/reconstruction.rs:40-60), and the EXIF
  * FocalLengthIn35mmFilm it reads (:138-142).  The host walks the markers; the entropy decode and everything behind it runs on
