@@ -85,6 +85,51 @@ def lzw(data: bytes) -> bytes:
     return lzw_pack(lzw_codes(data))
 
 
+def lzw_stagings(data: bytes, stage):
+    """The strip's codes as they leave an encoder that takes the strip `stage` bytes at a time (tiff_lzw_kernel: LZW_CHUNK),
+    from the code sequence of lzw_codes alone -> per staging a dict of
+      codes   the codes that leave in it: the first Clear in staging 0; a code with the byte behind its string, the byte that
+              did not extend it; a table-full Clear with the same byte; the pending string, a Clear behind it and EOI in the
+              last staging
+      end     the bit position of the stream behind the staging's last code, modulo 32
+      clears  the residues (byte index modulo `stage`) of the bytes with which a table-full Clear left
+      crosses whether the staging's last code lies in two 32-bit words of the stream
+    A code's string is as long as the decoder's: 1 below 256, else one more than the string of the code its entry was made
+    from.  No table of (prefix, byte) pairs and no probe order: the bytes do not depend on how the strings are found."""
+    codes, n = lzw_codes(data), len(data)
+    count = max(1, -(-n // stage))
+    out = [dict(codes=[], end=0, clears=[], crosses=False) for _ in range(count)]
+    assert codes[0] == CLEAR and codes[-1] == EOI
+    at, lengths, where = 0, [], [0]   # the bytes the codes so far stand for; of the codes since the Clear; the staging of each code
+    for code in codes[1:-1]:
+        if code == CLEAR:
+            where.append(where[-1])
+            if at < n:
+                out[where[-1]]["clears"].append(at % stage)
+            lengths = []
+            continue
+        length = 1 if code < 256 else lengths[code - 258] + 1
+        lengths.append(length)
+        at += length
+        where.append(at // stage if at < n else count - 1)
+    where.append(count - 1)
+    assert at == n and where == sorted(where)
+    bit, c = 0, 0
+    for code, k in zip(codes, where):
+        w = ref_tiff.code_width(c)
+        s = out[k]
+        s["codes"].append(code)
+        s["crosses"] = bit // 32 != (bit + w - 1) // 32
+        bit += w
+        c = 0 if code == CLEAR else c + 1
+        s["end"] = bit % 32
+    for before, s in zip(out, out[1:]):   # (a staging without a code ends where the one in front of it ended)
+        if not s["codes"]:
+            s["end"] = before["end"]
+    assert (bit + 7) // 8 == len(lzw_pack(codes))
+    return out
+
+
 # ---- PackBits --------------------------------------------------------------------------------------------------------------
 def packbits_row(row: bytes):
     """The greedy walk of one row (tiff_scenes.packbits on the row alone) -> [(is a run, start, length)]."""

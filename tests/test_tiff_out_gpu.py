@@ -30,7 +30,15 @@ def test_file_is_the_restated_file(gpu_device, name):
     front of EOI; a flat strip; 1 x 1; streams that end 1 to 7 bits into a byte, payloads of odd length; Predictor 2 at 1 to 4
     channels, several rows a strip, width 1, wrapping differences; a 64 KB strip, 64 stagings of the kernel.  PackBits: runs of
     2, 3, 127 .. 131 and 258, literals of 127 .. 129, a triple at a row's end, flat rows, 1-byte rows, widths around 64 and 257.
-    Strips: 1 (inline offset and count), 2, 64, 65, 256, 257, 1025; a short last strip; the default rows per strip."""
+    Strips: 1 (inline offset and count), 2, 64, 65, 256, 257, 1025; a short last strip; the default rows per strip.
+    The LZW kernel's staging (S.LZW_STAGE bytes at a time; tests/test_tiff_out_ref.py holds each scene to its seam): a code a byte
+    in strips of a staging less, equal and more a byte, of two stagings likewise, and of four with the table-full Clear inside -
+    1027 codes in a staging; that Clear with the last two and the first two bytes of a staging; strips of 12 such stagings side by
+    side in the scratch; a flat strip of 640 stagings, seven of them without a code, where the carried word must survive; every
+    carried bit count 0 to 31; Predictor 2 over rows of 1023, 1025 and 1028 bytes, five a strip.  Launches: GRID_LANES / 64 + 6
+    strips, the last six equal to the first six - a wave's second strip; 65535 rows, a row a strip, LZW and PackBits;
+    GRID_LANES / 256 + 6 PackBits rows, seven a strip - the copy kernel's second trip over rows; rows of 65535 x 4 bytes, PackBits
+    and LZW with Predictor 2; PackBits runs of 2 to 4 and 128 to 131 from positions 61 to 66 and 253 to 258 of a row."""
     pixels, compression, predictor, rps = S.scene(name)
     want, stats, want_sections = S.expected(name)
     sections = []
@@ -56,8 +64,10 @@ def _call(device, pixels, w, h, c, compression, predictor, rps, out, cap, sectio
     return rc, size.value
 
 
-@pytest.mark.parametrize("name", ["short_last_strip_lzw", "pb_rgba_sparse", "two_strips_raw_rgb"])
+@pytest.mark.parametrize("name", ["short_last_strip_lzw", "pb_rgba_sparse", "two_strips_raw_rgb", "pb_1_byte_rows", "odd_strips_raw", "raw_1_byte_strips"])
 def test_every_way_in_and_out(gpu_device, name):
+    """The last three: units of the copy kernel of 2 bytes (PackBits rows of a byte), of 5 bytes and of 1 byte (raw strips, a
+    padding byte between them) - shorter than the bytes in front of the first aligned dword - at every alignment of `out`."""
     import torch
 
     pixels, cmp_, pred, rps = S.scene(name)
@@ -107,6 +117,30 @@ def test_every_way_in_and_out(gpu_device, name):
     assert _call(gpu_device, src, w, h, c, cmp_, pred, rps, C.c_void_p(d_out.data_ptr()), size - 1)[0] == INVALID
     torch.cuda.synchronize()
     assert (d_out.cpu().numpy() == 0x5A).all()
+
+
+@pytest.mark.parametrize("name", ["pred_rgb8", "pb_rgba_sparse", "two_strips_raw_rgb"])
+def test_pixels_at_any_address(gpu_device, name):
+    """`pixels` 1, 2 and 3 bytes into a larger device tensor and into a larger host array: the same file.  LZW with Predictor 2
+    (the byte `channels` in front is read too), PackBits, and uncompressed, where the copy kernel reads the pixels themselves."""
+    import torch
+
+    pixels, cmp_, pred, rps = S.scene(name)
+    file = S.expected(name)[0]
+    size = len(file)
+    h, w, c = pixels.shape
+    flat = pixels.reshape(-1)
+    out = np.zeros(size, dtype=np.uint8)
+    for offset in (1, 2, 3):
+        host = np.full(flat.size + 8, 0xA5, dtype=np.uint8)
+        host[offset:offset + flat.size] = flat
+        dev = torch.from_numpy(host).cuda()
+        torch.cuda.synchronize()
+        for src in (C.c_void_p(dev.data_ptr() + offset), C.c_void_p(host.ctypes.data + offset)):
+            out[:] = 0
+            assert _call(gpu_device, src, w, h, c, cmp_, pred, rps, mesh._p(out), size) == (0, size)
+            assert same(out, file), offset
+        assert (dev.cpu().numpy() == host).all()   # (read only)
 
 
 def test_refusals_write_nothing(gpu_device):

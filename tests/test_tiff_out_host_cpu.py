@@ -109,6 +109,10 @@ def test_code_widths(exe, tmp_path):
 def lzw_inputs():
     out = [(n, S.scene(n)[0].tobytes()) for n in ("lzw_last_code_3835", "lzw_last_code_3836", "lzw_last_code_3837", "lzw_flat", "lzw_1x1",
                                                  "lzw_width_254", "lzw_width_766", "lzw_width_1790", "lzw_noise_8192_one_strip", "lzw_strip_64k")]
+    # the kernel's staging seams (the walk is shared): the densest stagings, a table-full Clear at each end of one, strings longer
+    # than a staging, a strip close to its bound
+    out += [(n, S.strip_bytes(n)[0]) for n in ("lzw_dense_4096", "lzw_clear_at_1022", "lzw_clear_at_1023", "lzw_clear_at_0", "lzw_clear_at_1",
+                                                "lzw_dense_strips", "lzw_flat_640k")]
     out.append(("noise_40000", S.noise(40000, 41).tobytes()))
     out.append(("two_letters", np.random.default_rng(42).integers(0, 2, size=30000, dtype=np.uint8).tobytes()))
     return out

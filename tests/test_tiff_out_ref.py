@@ -1,7 +1,8 @@
 """tests/ref_tiff_out.py, the definition of cvhip_tiff_encode, against what can read or write the same file
 on the CPU: ref_tiff.samples and Pillow read every scene's file back to the pixels; every LZW strip equals the strip libtiff
 (through Pillow) writes for the same rows, RowsPerStrip and predictor - the strip whose last code is the 3836th since a
-Clear included, where libtiff puts a Clear in front of EOI; the PackBits closed form equals the greedy walk."""
+Clear included, where libtiff puts a Clear in front of EOI; the PackBits closed form equals the greedy walk; the scenes reach
+the seams they are named for - of the format, of the LZW kernel's staging (ref_tiff_out.lzw_stagings) and of the launches."""
 import io
 
 import numpy as np
@@ -10,6 +11,7 @@ import pytest
 import ref_tiff
 import ref_tiff_out as R
 import tiff_out_scenes as S
+from cybervision_amd import mesh  # (GRID_LANES only: importing it loads no library)
 
 MODES = {1: "L", 2: "LA", 3: "RGB", 4: "RGBA"}
 
@@ -83,6 +85,124 @@ def test_scene_seams():
     lengths = {(run, n) for row in S.scene("pb_seams")[0] for run, _, n in R.packbits_row(row.tobytes())}
     assert {(True, 3), (True, 127), (True, 128), (False, 127), (False, 128)} <= lengths
     assert S.expected("pb_two_flat_rows")[1]["packets"] == 2
+    staging_seams()
+    launch_seams()
+
+
+def stagings(name):
+    """lzw_stagings of every strip of the scene, at the kernel's staging size."""
+    return [R.lzw_stagings(strip, S.LZW_STAGE) for strip in S.strip_bytes(name)]
+
+
+def test_staging_restatement():
+    """lzw_stagings against lzw_codes and lzw_pack: the codes in order, every byte accounted for (asserted inside), a staging a
+    strip when the stage is the strip, and at a stage of 1 byte each code with the byte behind its string."""
+    data = S.noise(5000, 44).tobytes() + bytes(300) + S.noise(3000, 45).tobytes()
+    codes = R.lzw_codes(data)
+    for stage in (1, 7, S.LZW_STAGE, len(data) - 1, len(data), len(data) + 1):
+        st = R.lzw_stagings(data, stage)
+        assert len(st) == -(-len(data) // stage) and [c for s in st for c in s["codes"]] == codes
+        assert st[-1]["end"] == sum(ref_tiff.code_width(c) for c in widths_index(codes)) % 32
+    one = R.lzw_stagings(data, 1)
+    assert one[0]["codes"] == [R.CLEAR] and one[1]["codes"] == [data[0]] and one[-1]["codes"][-1] == R.EOI
+    assert [s["clears"] for s in one if s["clears"]] == [[0]] * (codes.count(R.CLEAR) - 1)
+    assert len(R.lzw_stagings(b"\x05", S.LZW_STAGE)) == 1 and R.lzw_stagings(b"\x05", S.LZW_STAGE)[0]["codes"] == [R.CLEAR, 5, R.EOI]
+
+
+def widths_index(codes):
+    c = 0
+    for code in codes:
+        yield c
+        c = 0 if code == R.CLEAR else c + 1
+
+
+def staging_seams():
+    """The LZW scenes on the seams of the kernel's staging (S.LZW_STAGE bytes at a time), by lzw_stagings."""
+    stage = S.LZW_STAGE
+    D = S.pair_distinct()
+    pairs = list(zip(D[:-1].tolist(), D[1:].tolist()))
+    assert len(D) == 65280 and len(set(pairs)) == len(pairs)   # no two adjacent pairs equal: a code a byte
+    # ---- the codes of a staging, strips beside a multiple of the staging
+    counts = {1023: [1025], 1024: [1026], 1025: [1024, 3], 2047: [1024, 1025], 2048: [1024, 1026], 2049: [1024, 1024, 3],
+              4096: [1024, 1024, 1024, 1027]}
+    for n, want in counts.items():
+        pixels = S.scene("lzw_dense_%d" % n)[0]
+        assert pixels.shape == (1, n, 1) and pixels.tobytes() == D[:n].tobytes()
+        st, = stagings("lzw_dense_%d" % n)
+        assert [len(s["codes"]) for s in st] == want
+    st, = stagings("lzw_dense_4096")
+    assert st[3]["clears"] == [R.CLEAR_AFTER % stage] and R.CLEAR_AFTER // stage == 3   # the Clear leaves with byte 3836
+    # the bound on a staging's codes: a code for each of its bytes, one Clear - the strip's first or one at table-full, which
+    # are CLEAR_AFTER codes apart and so never in one staging -, then the pending string, a Clear behind it and EOI.  The
+    # last two Clears cannot both occur either, so the most that is reached is one less
+    most = stage + 1 + 3
+    assert R.CLEAR_AFTER > most and most < stage + 8   # LZW_CHUNK_CODES of tiff_encode_common.hpp
+    assert max(len(s["codes"]) for n in S.lzw_names() for strip in stagings(n) for s in strip) == most - 1 == 1027
+    # ---- a table-full Clear with the last and the first bytes of a staging
+    for r, k in ((1022, 3), (1023, 3), (0, 4), (1, 4)):
+        pixels = S.scene("lzw_clear_at_%d" % r)[0]
+        assert pixels.shape == (1, 6000, 1)
+        st, = stagings("lzw_clear_at_%d" % r)
+        assert [(j, s["clears"]) for j, s in enumerate(st) if s["clears"]] == [(k, [r % stage])]
+        lead = int(np.argmax(pixels.ravel() != 0x80))
+        assert lead in S.CLEAR_AT_WINDOW and pixels.ravel()[lead:].tobytes() == D[:6000 - lead].tobytes()
+    # ---- strips of 12 stagings close to their scratch stride
+    pixels, _, _, rps = S.scene("lzw_dense_strips")
+    assert pixels.shape == (85, 768, 1) and rps == 16 and pixels.tobytes() == D.tobytes()
+    sizes = [n for _, n in R.strips_of(S.expected("lzw_dense_strips")[0])]
+    assert len(sizes) == 6 and [len(st) for st in stagings("lzw_dense_strips")] == [12] * 5 + [4]
+    # a code a byte at 9 to 12 bits against the bound's 12: 43222 of 46032 bits over the 3836 codes between two Clears
+    assert all(0.93 * R.worst_strip(R.LZW, 16, 768) < n <= R.worst_strip(R.LZW, 16, 768) for n in sizes[:5])
+    # ---- stagings without a code
+    st, = stagings("lzw_flat_640k")
+    assert len(st) == 640 and sum(len(s["codes"]) for s in st) == 1147 == S.expected("lzw_flat_640k")[1]["codes"]
+    empty = [k for k, s in enumerate(st) if not s["codes"]]
+    assert len(empty) == 7 and all(st[k]["end"] == st[k - 1]["end"] != 0 for k in empty)   # (a partial word is carried through)
+    # ---- every carried bit count at a staging's end; a last code of a staging in two words
+    ends, crossing = set(), 0
+    for n in S.lzw_names():
+        for strip in stagings(n):
+            ends |= {s["end"] for s in strip[:-1]}
+            crossing += sum(s["crosses"] and bool(s["codes"]) for s in strip[:-1])
+    assert ends == set(range(32)) and crossing >= 1
+    # ---- Predictor 2 across rows that start in mid-staging
+    for name, row_bytes in (("pred_rows_1023", 1023), ("pred_rows_1028", 1028), ("pred_rows_1025", 1025)):
+        pixels, compression, predictor, rps = S.scene(name)
+        assert (pixels.shape[0], pixels.shape[1] * pixels.shape[2], compression, predictor, rps) == (5, row_bytes, R.LZW, 2, 5)
+        assert all((r * row_bytes) % stage != 0 for r in range(1, 5)) and S.expected(name)[1]["strips"] == 1
+
+
+def launch_seams():
+    """The scenes past one launch of tiff_lzw_kernel (a wave a strip) and of tiff_copy_kernel (a workgroup a unit), the most rows
+    and the widest row, and the PackBits runs on either side of lane 64 and workgroup 256 of a row."""
+    T, U = mesh.GRID_LANES // 64, mesh.GRID_LANES // 256
+    pixels, compression, _, rps = S.scene("strips_lzw_second_trip")
+    assert pixels.shape == (T + 6, 40, 1) and (compression, rps) == (R.LZW, 1) and S.expected("strips_lzw_second_trip")[1]["strips"] == T + 6
+    assert (pixels[T:] == pixels[:6]).all() and len({row.tobytes() for row in pixels[:T]}) == T
+    for name, compression in (("strips_65535_lzw", R.LZW), ("strips_65535_packbits", R.PACKBITS)):
+        assert S.scene(name)[0].shape == (65535, 1, 1) and S.scene(name)[1:] == (compression, 1, 1)
+        assert S.expected(name)[1]["strips"] == 65535 > 15 * T and 65535 > 63 * U
+        with pytest.raises(R.TiffOutError):
+            R.check(1, 65536, 1, compression, 1, 1)
+    assert 65535 < mesh.GRID_LANES   # a lane a row or a strip (tiff_packbits_kernel, tiff_sizes_kernel, tiff_table_kernel): one trip
+    pixels, compression, _, rps = S.scene("pb_rows_second_trip")
+    assert pixels.shape == (U + 6, 37, 1) and (compression, rps) == (R.PACKBITS, 7) and U % 7 != 0 and (U + 6) % 7 != 0
+    assert set(np.unique(pixels)) == {0, 1, 2}
+    for name, compression, predictor in (("widest_rgba_packbits", R.PACKBITS, 1), ("widest_rgba_lzw_pred", R.LZW, 2)):
+        pixels, cmp_, pred, rps = S.scene(name)
+        assert pixels.shape == (2, 65535, 4) and (cmp_, pred, rps) == (compression, predictor, 0)
+        assert R.check(65535, 2, 4, compression, predictor, 0) == (262140, 1, 2)
+        with pytest.raises(R.TiffOutError):
+            R.check(65536, 2, 4, compression, predictor, 0)
+    kinds = {run for row in S.scene("widest_rgba_packbits")[0].reshape(2, -1) for run, _, _ in R.packbits_row(row.tobytes())}
+    assert kinds == {True, False} and S.expected("widest_rgba_lzw_pred")[1]["clears"] > 2
+    rows = S.scene("pb_seam_sweep")[0]
+    assert S.PB_SWEEP == [(n, p) for n in (2, 3, 4, 128, 129, 130, 131) for p in (*range(61, 67), *range(253, 259))]
+    assert rows.shape == (len(S.PB_SWEEP), 700, 1)
+    for (n, p), row in zip(S.PB_SWEEP, rows.reshape(len(rows), -1)):
+        runs = [(at, length) for run, at, length in R.packbits_row(row.tobytes()) if run]
+        assert runs == {2: [], 3: [(p, 3)], 4: [(p, 4)], 128: [(p, 128)], 129: [(p, 128)], 130: [(p, 128)], 131: [(p, 128), (p + 128, 3)]}[n]
+        assert (row[p:p + n] == 255).all() and row[p - 1] != 255 and row[p + n] != 255
 
 
 @pytest.mark.parametrize("name,code", [(k, v[1]) for k, v in S.REFUSED.items()])

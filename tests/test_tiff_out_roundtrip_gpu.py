@@ -13,7 +13,9 @@ from cybervision_amd.mesh import TiffCompression  # (without the encoder every t
 
 pytestmark = pytest.mark.gpu
 NAMES = ["pred_g8", "pred_rgb8", "pred_rgba8", "short_last_strip_lzw", "lzw_noise_8192_one_strip", "lzw_strip_64k", "pb_seams", "pb_rgb",
-         "pb_rgba_sparse", "two_strips_raw_rgb", "strips_257_lzw", "lzw_1x1"]
+         "pb_rgba_sparse", "two_strips_raw_rgb", "strips_257_lzw", "lzw_1x1",
+         # the encoder's staging and launch seams (tests/test_tiff_out_ref.py: test_scene_seams)
+         "lzw_flat_640k", "lzw_dense_4096", "lzw_clear_at_1023", "strips_lzw_second_trip", "pb_rows_second_trip", "widest_rgba_lzw_pred"]
 
 
 @pytest.mark.parametrize("name", NAMES)
