@@ -153,6 +153,10 @@ SIGNATURES = {
     "cvhip_jpeg_info": (C.c_int, [_vp, C.c_uint64, _vp]),
     "cvhip_jpeg_decode": (C.c_int, [_vp, _vp, C.c_uint64, _u32, _u32, _vp, C.c_uint64, C.POINTER(C.c_uint64)]),
     "cvhip_jpeg_last_stats": (C.c_int, [_vp]),
+    # progressive JPEG files in: (file, size, out_info[7]); cvhip_jpeg_decode's arguments; (out_stats[8])
+    "cvhip_jpeg_progressive_info": (C.c_int, [_vp, C.c_uint64, _vp]),
+    "cvhip_jpeg_progressive_decode": (C.c_int, [_vp, _vp, C.c_uint64, _u32, _u32, _vp, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "cvhip_jpeg_progressive_last_stats": (C.c_int, [_vp]),
     # TIFF files in: (file, size, out_info[12], out_scale[3]); (file, size, format, drop_rows, out, cap, out_size); (out_stats[4])
     "cvhip_tiff_info": (C.c_int, [_vp, C.c_uint64, _vp, _vp]),
     "cvhip_tiff_decode": (C.c_int, [_vp, _vp, C.c_uint64, _u32, _u32, _vp, C.c_uint64, C.POINTER(C.c_uint64)]),

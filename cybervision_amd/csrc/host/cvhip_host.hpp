@@ -861,6 +861,30 @@ inline std::vector<uint8_t> jpeg_decode(GpuDevice &dev, const uint8_t *file, uin
     });
 }
 
+// ---- progressive JPEG: the SOF2 files jpeg_decode refuses
+struct JpegProgressiveInfo : JpegInfo {
+    uint32_t scans = 0;
+};
+
+// the frame, the EXIF focal length and the number of scans of a progressive file's bytes (host only; the whole file is walked)
+inline JpegProgressiveInfo jpeg_progressive_info(const uint8_t *file, uint64_t size)
+{
+    uint32_t v[7] = {0, 0, 0, 0, 0, 0, 0};
+    check(cvhip_jpeg_progressive_info(file, size, v), "cvhip_jpeg_progressive_info");
+    JpegProgressiveInfo info;
+    info.width = v[0], info.height = v[1], info.components = v[2], info.h = v[3], info.v = v[4], info.focal_length_35mm = v[5], info.scans = v[6];
+    return info;
+}
+
+// as jpeg_decode, of a progressive file
+inline std::vector<uint8_t> jpeg_progressive_decode(GpuDevice &dev, const uint8_t *file, uint64_t size, Format format = Format::Luma8,
+                                                    uint32_t drop_rows = 0)
+{
+    return mesh::detail::size_then_fill([&](uint8_t *dst, uint64_t cap, uint64_t *out_size) {
+        check(cvhip_jpeg_progressive_decode(dev.handle(), file, size, (uint32_t)format, drop_rows, dst, cap, out_size), "cvhip_jpeg_progressive_decode");
+    });
+}
+
 // ---- TIFF: the SEM pairs of --projection=parallel, with the metadata of reconstruction.rs:80-144
 struct TiffInfo {
     uint32_t width = 0, height = 0, samples = 0, bits = 0, compression = 0, photometric = 0, predictor = 0, strips = 0, rows_per_strip = 0;

@@ -6,7 +6,10 @@ the host walks the IFD and reads the SEM text block of tag 34683 / 34682 - scale
 LZW / PackBits decompression, Predictor 2 and the conversion run on the device.  PNG (cvhip_png_decode):
 the host walks the chunks and reads IHDR, PLTE and the eXIf chunk's focal length, inflate, the IDAT CRCs, the Adler-32, the
 five filters and the conversion run on the device; every colour type and bit depth, alpha and tRNS dropped, the SEM fields
-keep their defaults.  Adam7 PNG, Deflate and tiled TIFF and progressive JPEG are not built."""
+keep their defaults.  Progressive JPEG (cvhip_jpeg_progressive_decode): the host walks the markers of the
+whole file and checks the progression, the entropy decode of every scan accumulates the coefficients on the device, the tail
+is the baseline path's; `load` takes it for a file whose first SOF marker is SOF2.  Adam7 PNG, Deflate and tiled TIFF, and of
+JPEG arithmetic coding, 12 bits, sequential files of several scans and incomplete progressions are not built."""
 from __future__ import annotations
 
 import ctypes as C
@@ -72,6 +75,49 @@ def decode_jpeg(device, data, mode: str = "L", drop_rows: int = 0, out=None):
     out: None - a numpy array; "device" - a torch tensor on the device; or the numpy array / device tensor to fill (its
     first bytes; it is returned as given)."""
     return _decode("cvhip_jpeg_decode", device, data, mode, drop_rows, out, lambda d: jpeg_info(d)["width"])
+
+
+def jpeg_progressive_info(data) -> dict:
+    """cvhip_jpeg_progressive_info of a file's bytes (host only) -> jpeg_info's fields and scans, the number of scans."""
+    p, n, _keep = _file(data)
+    info = np.zeros(7, dtype=np.uint32)
+    _lib.check(_lib.lib().cvhip_jpeg_progressive_info(p, n, C.c_void_p(info.ctypes.data)), "cvhip_jpeg_progressive_info")
+    w, h, comps, hs, vs, focal, scans = (int(v) for v in info)
+    return {"width": w, "height": h, "components": comps, "h": hs, "v": vs, "focal_length_35mm": focal or None, "scans": scans}
+
+
+def decode_jpeg_progressive(device, data, mode: str = "L", drop_rows: int = 0, out=None):
+    """cvhip_jpeg_progressive_decode of a progressive file's bytes, as decode_jpeg."""
+    return _decode("cvhip_jpeg_progressive_decode", device, data, mode, drop_rows, out, lambda d: jpeg_progressive_info(d)["width"])
+
+
+def jpeg_progressive_last_stats() -> dict:
+    """cvhip_jpeg_progressive_last_stats: of this thread's last progressive decode - scans, restart intervals, subsequences,
+    launches of the synchronisation kernel that settles the first scans, the most rounds a workgroup needed within a launch,
+    AC-refinement scans, the launches that hold one, the longest EOB run."""
+    s = np.zeros(8, dtype=np.uint64)
+    _lib.check(_lib.lib().cvhip_jpeg_progressive_last_stats(C.c_void_p(s.ctypes.data)), "cvhip_jpeg_progressive_last_stats")
+    names = ("scans", "intervals", "subsequences", "sync_launches", "workgroup_rounds", "ac_refinement_scans", "ac_refinement_launches", "longest_eob_run")
+    return {k: int(v) for k, v in zip(names, s)}
+
+
+def _first_sof(data) -> int:
+    """The first SOFn marker of a JPEG file's segments (0xC0 .. 0xCF without DHT, JPG and DAC), 0 where the walk finds none."""
+    n, at = len(data), 2
+    if data[:2] != b"\xff\xd8":
+        return 0
+    while at + 4 <= n and data[at] == 0xFF:
+        while at < n and data[at] == 0xFF:
+            at += 1
+        if at + 2 >= n:
+            return 0
+        m = data[at]
+        if 0xC0 <= m <= 0xCF and m not in (0xC4, 0xC8, 0xCC):
+            return m
+        if m == 0xDA or m == 0xD9:
+            return 0
+        at += 1 + (0 if m == 0x01 or 0xD0 <= m <= 0xD7 else data[at + 1] << 8 | data[at + 2])
+    return 0
 
 
 def tiff_info(data) -> dict:
@@ -153,7 +199,7 @@ class SourceImage:
 
 def load(device, path, rgb: bool = False, drop_rows=None, out=None) -> SourceImage:
     """SourceImage::load (and load_rgb with rgb=True) of a TIFF, PNG or JPEG file, told apart by the first four (TIFF) or
-    eight (PNG) bytes (anything else gets the JPEG path and its error).  drop_rows: the rows cut from the bottom; None - the
+    eight (PNG) bytes (anything else gets the JPEG path and its error; a JPEG file whose first SOF marker is SOF2 the progressive one).  drop_rows: the rows cut from the bottom; None - the
     file's own databar_height (the DatabarHeight of a TIFF file's SEM block; 0 for PNG and JPEG).  out: None or "device", as decode_jpeg takes
     it, for img; rgb is a numpy array."""
     data = Path(path).read_bytes()
@@ -168,6 +214,11 @@ def load(device, path, rgb: bool = False, drop_rows=None, out=None) -> SourceIma
         info = png_info(data)
         img = decode_png(device, data, "L", drop_rows, out)
         colour = decode_png(device, data, "RGB", drop_rows) if rgb else None
+        return SourceImage(img, colour, info["focal_length_35mm"], str(path))
+    if _first_sof(data) == 0xC2:   # progressive: every other file goes where it went
+        info = jpeg_progressive_info(data)
+        img = decode_jpeg_progressive(device, data, "L", drop_rows, out)
+        colour = decode_jpeg_progressive(device, data, "RGB", drop_rows) if rgb else None
         return SourceImage(img, colour, info["focal_length_35mm"], str(path))
     info = jpeg_info(data)
     img = decode_jpeg(device, data, "L", drop_rows, out)

@@ -714,6 +714,41 @@ int cvhip_jpeg_decode(cvhip_device *dev, const uint8_t *file, uint64_t size, uin
 int cvhip_jpeg_last_stats(uint64_t *out_stats);
 
 /* ------------------------------------------------------------------------------------------
+ * Progressive JPEG files in (csrc/jpeg_prog_kernels.hip, csrc/jpeg_prog_common.hpp): the SOF2 files that
+ * cvhip_jpeg_decode refuses and image::open decodes - mozjpeg's and jpegtran's output, most of the web's photographs.  The pixels
+ * are DEFINED (tests/ref_jpeg_prog.py is the definition, pinned to Pillow) as libjpeg's default decode of the whole file: the
+ * coefficients accumulate over all scans as jdphuff.c does - DC first and refinement, AC first with EOB runs, AC refinement with
+ * its correction bits - and go through the path above unchanged: dequantisation, jidctint, fancy upsampling, YCbCr -> RGB, luma.
+ * The host walks the markers of the whole file and checks the progression; the cut of the scans at their RSTn markers, the
+ * entropy decode of every scan and everything behind it run on the device.
+ * Supported: SOF2, 8 bits, 1 or 3 components with the sampling factors above; Ss, Se, Ah, Al as T.81 G.1 allows (a DC scan
+ * of 1 to 3 components with Ss = Se = 0, an AC scan of one component with 1 <= Ss <= Se <= 63, Ah = 0 in a first scan, in a
+ * refinement Ah = the Al every coefficient of the band was last sent with and Al = Ah - 1, Al <= 13, a component's AC scans
+ * behind a DC scan of it); any DRI, which may change between scans; DHT and DQT segments anywhere before or between scans (a
+ * component keeps the quantisation table in force at its first scan); at most 256 scans.
+ * CVHIP_ERR_UNSUPPORTED: a frame that is not SOF2 - a baseline file too: that is cvhip_jpeg_decode's, and a sequential file of
+ * several scans is not built -; an incomplete progression, that is one that ends with one of a component's coefficients 0 .. 9
+ * (zig-zag order) unsent or not refined down to Al = 0 (there libjpeg smooths between blocks, differently from version to
+ * version; whatever is missing or unrefined of 10 .. 63 stays as sent); more than 256 scans; a file of 2^31 or more bytes, more
+ * than 2^25 blocks; and what cvhip_jpeg_decode refuses of a frame (12 bits, DNL, 2 or 4 components, other sampling factors).
+ * CVHIP_ERR_INVALID: anything malformed - a scan header outside the rules above, s > 1 in a refinement (libjpeg warns and
+ * reads 1), a run past Se, a code that is not in its table, a missing, surplus or misnumbered RSTn, a scan whose data ends
+ * before its last block, a truncated segment, a missing table; nothing is written then.  What follows a scan's last block is
+ * ignored. */
+/* Host only, no device.  out_info[7] = cvhip_jpeg_info's six words and the number of scans. */
+int cvhip_jpeg_progressive_info(const uint8_t *file, uint64_t size, uint32_t *out_info);
+/* cvhip_jpeg_decode's arguments and contract for a progressive file: cap = 0 sizes and writes nothing (the whole file is
+ * walked and the progression checked, on the host), 0 < cap < size is CVHIP_ERR_INVALID with nothing written, out in host or
+ * device memory at any alignment. */
+int cvhip_jpeg_progressive_decode(cvhip_device *dev, const uint8_t *file, uint64_t size, uint32_t format, uint32_t drop_rows, uint8_t *out,
+                                  uint64_t cap, uint64_t *out_size);
+/* Of the calling thread's last cvhip_jpeg_progressive_decode that reached the device: out_stats[8] = scans, restart intervals
+ * (of all scans), subsequences (the 1024-bit units of all scans' data, counted on the device), launches of the synchronisation
+ * kernel that settles the DC-first and AC-first scans, the most rounds a workgroup needed within a launch, AC-refinement
+ * scans, launches that hold one, the longest EOB run. */
+int cvhip_jpeg_progressive_last_stats(uint64_t *out_stats);
+
+/* ------------------------------------------------------------------------------------------
  * TIFF files in (csrc/tiff_kernels.hip, csrc/tiff_common.hpp): the reference's SEM pairs
  * (--projection=parallel), opened like every input with image::open(path)?.into_luma8() / into_rgb8() and cropped by the
  * DatabarHeight of the microscope's text block in tag 34683 or 34682 (src/reconstruction.rs:40-60, 80-144).  The host walks the
