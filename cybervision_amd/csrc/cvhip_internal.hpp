@@ -156,6 +156,22 @@ void launch_extend_tracks_new(const uint32_t *cells, uint32_t lw, uint32_t lh, u
 // ---- shared by the multi-view entry points (tracks, triangulation, pose, mesh, mesh output, Delaunay) ------------------------
 bool on_device(const void *p); // device or managed memory (anything else is taken as host memory); cvhip_api.hip
 inline int device_error(const char *what, hipError_t e) { return fail(CVHIP_ERR_DEVICE, std::string(what) + ": " + hipGetErrorString(e)); }
+// a file parser's refusal as its entry point's: "what: why", unsupported or invalid
+inline int refused(const char *what, bool is_unsupported, const char *why)
+{
+    return fail(is_unsupported ? CVHIP_ERR_UNSUPPORTED : CVHIP_ERR_INVALID, std::string(what) + ": " + why);
+}
+// One device allocation of a call, carved (an allocation costs more than most of the decoders' kernels): reserve() gives every
+// part its offset, a multiple of 256 bytes; total is what to allocate.
+struct Carver {
+    size_t total = 0;
+    size_t reserve(size_t nbytes)
+    {
+        const size_t at = total;
+        total += (nbytes + 255) / 256 * 256;
+        return at;
+    }
+};
 #define CVHIP_TRY_HIP_AT(what, expr)                              \
     do {                                                          \
         hipError_t _e = (expr);                                   \

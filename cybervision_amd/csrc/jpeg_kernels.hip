@@ -41,32 +41,17 @@ namespace jc = jpeg_common;
 
 #include "jpeg_tail.inc"
 
-constexpr uint32_t KIND_DROP = 0, KIND_DATA = 1, KIND_RST = 2;
+#include "jpeg_entropy.inc"
+
 constexpr uint32_t ERR_RST = 1, ERR_CODE = 2, ERR_RUN = 4, ERR_DATA = 8;
-constexpr uint32_t SHORT_BITS = 10, SHORT_ENTRIES = 1u << SHORT_BITS, MAX_LUTS = 6; // the codes of up to 10 bits, per table, in LDS
+constexpr uint32_t MAX_LUTS = 6; // the tables of a scan, whose short codes lie in LDS
 constexpr uint64_t MAX_SCAN_BYTES = 1ull << 31, MAX_BLOCKS = 1ull << 25;
-
-__device__ const uint8_t d_zigzag[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
-                                         41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
-                                         30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
-
-// What byte i of the scan[0 .. n) is.  One byte back and one ahead decide it (tests/ref_jpeg.py: segments).
-__device__ __forceinline__ uint32_t classify(const uint8_t *__restrict__ scan, unsigned long long n, unsigned long long i)
-{
-    const uint32_t b = scan[i], prev = i ? scan[i - 1] : 0u, next = i + 1 < n ? scan[i + 1] : 0x100u;
-    if (b == 0xFF) return (next == 0x00 || next == 0x100) ? KIND_DATA : KIND_DROP; // stuffed; fill, or a marker's first byte
-    if (prev == 0xFF) {
-        if (b == 0x00) return KIND_DROP;
-        if (b >= 0xD0 && b <= 0xD7) return KIND_RST;
-    }
-    return KIND_DATA;
-}
 
 // counts[i / 64] = data bytes | markers << 32 of bytes 64 (i / 64) .. + 63
 __global__ __launch_bounds__(BLOCK) void jpeg_mark_kernel(const uint8_t *__restrict__ scan, unsigned long long n, unsigned long long *__restrict__ counts)
 {
     const unsigned long long i = (unsigned long long)blockIdx.x * BLOCK + threadIdx.x;
-    const uint32_t kind = i < n ? classify(scan, n, i) : KIND_DROP;
+    const uint32_t kind = i < n ? classify<true>(scan, 0ull, n, i) : KIND_DROP;
     const unsigned long long data = __ballot(kind == KIND_DATA), rst = __ballot(kind == KIND_RST);
     if ((threadIdx.x & 63u) == 0 && i < n) counts[i >> 6] = (unsigned long long)__popcll(data) | (unsigned long long)__popcll(rst) << 32;
 }
@@ -78,7 +63,7 @@ __global__ __launch_bounds__(BLOCK) void jpeg_compact_kernel(const uint8_t *__re
 {
     const unsigned long long i = (unsigned long long)blockIdx.x * BLOCK + threadIdx.x;
     const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t kind = i < n ? classify(scan, n, i) : KIND_DROP;
+    const uint32_t kind = i < n ? classify<true>(scan, 0ull, n, i) : KIND_DROP;
     const unsigned long long data = __ballot(kind == KIND_DATA), rst = __ballot(kind == KIND_RST), below = (1ull << lane) - 1ull;
     if (i >= n) return;
     const unsigned long long off = counts[i >> 6];
@@ -109,32 +94,6 @@ __global__ __launch_bounds__(BLOCK) void jpeg_segments_kernel(unsigned long long
 }
 
 // ---- the entropy decoder of one subsequence ---------------------------------------------------------------------------------------
-// A state: the next bit (of the clean buffer) | the block's slot in its MCU << 40 | the zig-zag index << 44
-__device__ __forceinline__ unsigned long long pack_state(unsigned long long p, uint32_t slot, uint32_t k)
-{
-    return p | (unsigned long long)slot << 40 | (unsigned long long)k << 44;
-}
-
-// the 64 bits of the clean buffer (big-endian) from word wi on, those at and past seg_end_bits read as ones; 32 wi < seg_end_bits
-__device__ __forceinline__ unsigned long long load_window(const uint32_t *__restrict__ words, unsigned long long wi, unsigned long long seg_end_bits)
-{
-    const unsigned long long base = wi << 5;
-    unsigned long long v = (unsigned long long)__builtin_bswap32(words[wi]) << 32 | __builtin_bswap32(words[wi + 1]);
-    if (seg_end_bits < base + 64) v |= ~0ull >> (seg_end_bits - base); // (1 .. 63 valid bits)
-    return v;
-}
-
-// s_short[t][the next SHORT_BITS bits] = table t's entry where the code there has at most SHORT_BITS bits, else 0 (look in the
-// whole table).  Nearly every symbol of a photograph is decoded from LDS; the whole tables stay in global memory.
-__device__ __forceinline__ void load_short_tables(const uint16_t *__restrict__ luts, uint32_t n_luts, uint16_t *s_short)
-{
-    for (uint32_t at = threadIdx.x; at < n_luts * SHORT_ENTRIES; at += BLOCK) {
-        const uint16_t entry = luts[(size_t)(at >> SHORT_BITS) * jc::LUT_ENTRIES + ((at & (SHORT_ENTRIES - 1u)) << (16 - SHORT_BITS))];
-        s_short[at] = (entry >> 8) <= SHORT_BITS ? entry : (uint16_t)0;
-    }
-    __syncthreads();
-}
-
 // Decodes from `state` while the next bit is below end_bit -> the exit state; blocks += the blocks completed.  WRITE: the
 // coefficients of blocks `block` .. below block_limit go to coef (the DC as its difference), and what the file does wrong is
 // flagged.
@@ -194,71 +153,33 @@ __device__ __forceinline__ unsigned long long decode_subsequence(const uint32_t 
     return pack_state(p, slot, k);
 }
 
-// the interval of subsequence i: the last s with sub_first[s] <= i (sub_first[nseg] = the subsequences of the scan > i)
-__device__ __forceinline__ uint32_t interval_of(const unsigned long long *__restrict__ sub_first, uint32_t nseg, unsigned long long i)
-{
-    uint32_t lo = 0, hi = nseg;
-    while (hi - lo > 1) {
-        const uint32_t mid = lo + (hi - lo) / 2;
-        if (sub_first[mid] <= i) lo = mid;
-        else hi = mid;
-    }
-    return lo;
-}
-
-// round 0: every subsequence from its guess, settled within the workgroup.  round > 0: the first lane of a workgroup takes
-// exit_in[i - 1], the launch before's; flags[FLAG_CHANGED] is set when a workgroup's last exit state differs from exit_in's.
+// A lane per subsequence: its interval and bit range, then jpeg_entropy.inc's settle loop from the guess "its first bit, block
+// slot 0, coefficient 0" - the true state of an interval's first subsequence.
 __global__ __launch_bounds__(BLOCK) void jpeg_sync_kernel(const uint32_t *__restrict__ words, const uint16_t *__restrict__ luts, JpegParams P,
                                                           const unsigned long long *__restrict__ seg_start,
                                                           const unsigned long long *__restrict__ sub_first, unsigned long long *__restrict__ entry,
                                                           const unsigned long long *__restrict__ exit_in, unsigned long long *__restrict__ exit_out,
                                                           unsigned long long *__restrict__ counts, uint32_t round, uint32_t *__restrict__ flags)
 {
-    __shared__ unsigned long long s_exit[BLOCK];
     __shared__ uint16_t s_short[MAX_LUTS * SHORT_ENTRIES];
     if (flags[FLAG_ERR]) return; // (set by the kernels before this one only: the same for every lane)
     load_short_tables(luts, P.n_luts, s_short);
     const unsigned long long i = (unsigned long long)blockIdx.x * BLOCK + threadIdx.x, total = sub_first[P.nseg];
     const bool active = i < total;
-    unsigned long long fixed = 0, end_bit = 0, seg_end_bits = 0, cur_entry = 0, cur_exit = 0, blocks = 0, old_exit = 0;
+    unsigned long long first_bit = 0, end_bit = 0, seg_end_bits = 0;
     bool known = false;
     if (active) {
         const uint32_t s = interval_of(sub_first, P.nseg, i);
-        const unsigned long long j = i - sub_first[s], first_bit = seg_start[s] * 8 + j * jc::SUBSEQ_BITS;
-        seg_end_bits = seg_start[s + 1] * 8;
+        const unsigned long long j = i - sub_first[s];
+        first_bit = seg_start[s] * 8 + j * jc::SUBSEQ_BITS, seg_end_bits = seg_start[s + 1] * 8;
         end_bit = first_bit + jc::SUBSEQ_BITS < seg_end_bits ? first_bit + jc::SUBSEQ_BITS : seg_end_bits;
         known = j == 0;
-        fixed = pack_state(first_bit, 0, 0); // the true state of an interval's first subsequence, the guess of the others
-        if (round == 0) {
-            cur_entry = fixed;
-            cur_exit = decode_subsequence<false>(words, luts, s_short, P, cur_entry, end_bit, seg_end_bits, blocks, nullptr, 0, 0, nullptr);
-        } else {
-            cur_entry = entry[i], cur_exit = old_exit = exit_in[i], blocks = counts[i];
-        }
     }
-    s_exit[threadIdx.x] = cur_exit;
-    uint32_t rounds = 0;
-    for (;;) {
-        __syncthreads();
-        unsigned long long want = cur_entry;
-        if (active && !known) {
-            if (threadIdx.x) want = s_exit[threadIdx.x - 1];
-            else if (round) want = exit_in[i - 1];
-        }
-        const bool change = want != cur_entry;
-        if (!__syncthreads_or(change)) break; // (and every lane has read before any lane writes)
-        if (change) {
-            cur_entry = want, blocks = 0;
-            cur_exit = decode_subsequence<false>(words, luts, s_short, P, cur_entry, end_bit, seg_end_bits, blocks, nullptr, 0, 0, nullptr);
-            s_exit[threadIdx.x] = cur_exit;
-        }
-        rounds++;
-    }
-    if (active) {
-        entry[i] = cur_entry, exit_out[i] = cur_exit, counts[i] = blocks;
-        if (threadIdx.x == BLOCK - 1 && (round == 0 || cur_exit != old_exit)) atomicOr(&flags[FLAG_CHANGED], 1u);
-    }
-    if (threadIdx.x == 0 && rounds) atomicMax(&flags[FLAG_ROUNDS], rounds);
+    settle(
+        active, known, i, round, entry, exit_in, exit_out, counts, flags, [&]() { return pack_state(first_bit, 0, 0); },
+        [&](unsigned long long state, unsigned long long &blocks) {
+            return decode_subsequence<false>(words, luts, s_short, P, state, end_bit, seg_end_bits, blocks, nullptr, 0, 0, nullptr);
+        });
 }
 
 // counts: scanned, counts[the launch's lanes] = their total.  coef was zeroed.
@@ -304,8 +225,6 @@ __global__ __launch_bounds__(BLOCK) void jpeg_dc_kernel(const short *__restrict_
 
 thread_local uint64_t t_stats[4] = {0, 0, 0, 0}; // of the thread's last decode: intervals, subsequences, sync launches, rounds within a workgroup
 
-int refused(const char *what, int code, const char *why) { return fail(code == jc::UNSUPPORTED ? CVHIP_ERR_UNSUPPORTED : CVHIP_ERR_INVALID, std::string(what) + ": " + why); }
-
 } // namespace
 } // namespace cvhip
 
@@ -316,7 +235,7 @@ extern "C" int cvhip_jpeg_info(const uint8_t *file, uint64_t size, uint32_t *out
     if (!file || !out_info) return fail(CVHIP_ERR_INVALID, "jpeg_info: null argument");
     jc::Header h;
     const int rc = jc::parse(file, (size_t)size, h);
-    if (rc != jc::OK) return refused("jpeg_info", rc, h.error);
+    if (rc != jc::OK) return refused("jpeg_info", rc == jc::UNSUPPORTED, h.error);
     out_info[0] = h.width, out_info[1] = h.height, out_info[2] = h.components, out_info[3] = h.hmax, out_info[4] = h.vmax;
     out_info[5] = h.focal_length_35mm;
     return CVHIP_OK;
@@ -336,7 +255,7 @@ extern "C" int cvhip_jpeg_decode(cvhip_device *dev, const uint8_t *file, uint64_
     if (format != CVHIP_IMAGE_LUMA8 && format != CVHIP_IMAGE_RGB8) return fail(CVHIP_ERR_INVALID, "jpeg_decode: format is not CVHIP_IMAGE_LUMA8 or CVHIP_IMAGE_RGB8");
     jc::Header h;
     const int rc = jc::parse(file, (size_t)size, h);
-    if (rc != jc::OK) return refused("jpeg_decode", rc, h.error);
+    if (rc != jc::OK) return refused("jpeg_decode", rc == jc::UNSUPPORTED, h.error);
     if (drop_rows >= h.height) return fail(CVHIP_ERR_INVALID, "jpeg_decode: drop_rows leaves no row");
     const uint32_t channels = format == CVHIP_IMAGE_RGB8 ? 3u : 1u;
     const unsigned long long bytes = (unsigned long long)h.width * (h.height - drop_rows) * channels;
@@ -376,35 +295,23 @@ extern "C" int cvhip_jpeg_decode(cvhip_device *dev, const uint8_t *file, uint64_
     CallScratch sc;
     const unsigned long long chunks = (n + 63) / 64, sub_cap = n / (jc::SUBSEQ_BITS / 8) + nseg + 1;
     const uint32_t sync_blocks = (uint32_t)((sub_cap + BLOCK - 1) / BLOCK);
-    uint8_t *d_blob = nullptr, *clean = nullptr, *plane_bytes = nullptr, *d_out = nullptr;
+    uint8_t *d_blob = nullptr, *clean = nullptr, *d_out = nullptr;
     unsigned long long *chunk_counts = nullptr, *seg_start = nullptr, *sub_first = nullptr, *states = nullptr, *counts = nullptr, *sums = nullptr;
     uint32_t *flags = nullptr, h_flags[FLAGS] = {0, 0, 0, 0};
     short *coef = nullptr;
-    Planes planes{};
-    size_t plane_total = 0, plane_at[3] = {0, 0, 0};
-    for (uint32_t c = 0; c < P.ncomp; c++) {
-        planes.stride[c] = h.mcus_x * (c == 0 ? h.hmax : 1u) * 8u;
-        plane_at[c] = plane_total;
-        plane_total += (size_t)planes.stride[c] * h.mcus_y * (c == 0 ? h.vmax : 1u) * 8u; // (a multiple of 64 bytes)
-    }
-    // one allocation, carved: an allocation costs more than most of these kernels
-    size_t arena_bytes = 0;
-    auto reserve = [&](size_t nbytes) {
-        const size_t at = arena_bytes;
-        arena_bytes += (nbytes + 255) / 256 * 256;
-        return at;
-    };
-    const size_t at_blob = reserve(blob.size()), at_clean = reserve((size_t)n + 16); // (window() reads the word behind a position's own)
-    const size_t at_chunks = reserve(((size_t)chunks + 1) * 8), at_seg = reserve(((size_t)nseg + 1) * 8), at_sub = reserve(((size_t)nseg + 1) * 8);
-    const size_t at_states = reserve((size_t)sub_cap * 3 * 8); // entry states, and the exit states of two launches
-    const size_t at_counts = reserve(((size_t)sub_cap + 1) * 8), at_flags = reserve(FLAGS * sizeof(uint32_t));
-    const size_t at_coef = reserve((size_t)n_blocks * 64 * sizeof(short)), at_sums = reserve(((size_t)P.ncomp * P.mcus + 1) * 8);
-    const size_t at_planes = reserve(plane_total);
+    PlaneLayout layout(P);
+    Carver carve; // one allocation, carved: an allocation costs more than most of these kernels
+    const size_t at_blob = carve.reserve(blob.size()), at_clean = carve.reserve((size_t)n + 16); // (window() reads the word behind a position's own)
+    const size_t at_chunks = carve.reserve(((size_t)chunks + 1) * 8), at_seg = carve.reserve(((size_t)nseg + 1) * 8), at_sub = carve.reserve(((size_t)nseg + 1) * 8);
+    const size_t at_states = carve.reserve((size_t)sub_cap * 3 * 8); // entry states, and the exit states of two launches
+    const size_t at_counts = carve.reserve(((size_t)sub_cap + 1) * 8), at_flags = carve.reserve(FLAGS * sizeof(uint32_t));
+    const size_t at_coef = carve.reserve((size_t)n_blocks * 64 * sizeof(short)), at_sums = carve.reserve(((size_t)P.ncomp * P.mcus + 1) * 8);
+    const size_t at_planes = carve.reserve(layout.total);
     uint8_t *arena = nullptr;
-    hipError_t e = sc.alloc(&arena, arena_bytes);
+    hipError_t e = sc.alloc(&arena, carve.total);
     if (e == hipSuccess) e = sc.output(out, (size_t)bytes, &d_out);
     if (e != hipSuccess) return device_error("jpeg_decode", e);
-    d_blob = arena + at_blob, clean = arena + at_clean, plane_bytes = arena + at_planes;
+    d_blob = arena + at_blob, clean = arena + at_clean;
     chunk_counts = reinterpret_cast<unsigned long long *>(arena + at_chunks), seg_start = reinterpret_cast<unsigned long long *>(arena + at_seg);
     sub_first = reinterpret_cast<unsigned long long *>(arena + at_sub), states = reinterpret_cast<unsigned long long *>(arena + at_states);
     counts = reinterpret_cast<unsigned long long *>(arena + at_counts), sums = reinterpret_cast<unsigned long long *>(arena + at_sums);
@@ -415,7 +322,7 @@ extern "C" int cvhip_jpeg_decode(cvhip_device *dev, const uint8_t *file, uint64_
     if (e == hipSuccess) e = hipMemsetAsync(flags, 0, FLAGS * sizeof(uint32_t), s);
     if (e == hipSuccess) e = hipMemsetAsync(coef, 0, (size_t)n_blocks * 64 * sizeof(short), s);
     if (e != hipSuccess) return device_error("jpeg_decode", e);
-    for (uint32_t c = 0; c < P.ncomp; c++) planes.base[c] = plane_bytes + plane_at[c];
+    const Planes &planes = layout.placed(arena + at_planes, P.ncomp);
     const uint16_t *d_quant = reinterpret_cast<const uint16_t *>(d_blob), *d_luts = reinterpret_cast<const uint16_t *>(d_blob + quant_bytes);
     const uint8_t *d_scan = d_blob + quant_bytes + lut_bytes;
     const uint32_t *words = reinterpret_cast<const uint32_t *>(clean);
@@ -428,45 +335,23 @@ extern "C" int cvhip_jpeg_decode(cvhip_device *dev, const uint8_t *file, uint64_
                        flags);
     launch_scan_u64(sub_first, nseg, sub_first + nseg, s);
     // ---- the states settle: within the workgroups, then across them, a launch and one flag back per round
-    hipLaunchKernelGGL(jpeg_sync_kernel, dim3(sync_blocks), block, 0, s, words, d_luts, P, seg_start, sub_first, entry, exits[0], exits[0], counts, 0u,
-                       flags);
-    uint32_t launches = 1;
-    for (uint32_t from = 0; sync_blocks > 1; from ^= 1u, launches++) {
-        if (launches > sync_blocks + 1) return fail(CVHIP_ERR_DEVICE, "jpeg_decode: the decoder's states did not settle");
-        e = hipGetLastError();
-        if (e == hipSuccess) e = hipMemsetAsync(flags + FLAG_CHANGED, 0, sizeof(uint32_t), s);
-        if (e != hipSuccess) return device_error("jpeg_decode", e);
-        hipLaunchKernelGGL(jpeg_sync_kernel, dim3(sync_blocks), block, 0, s, words, d_luts, P, seg_start, sub_first, entry, exits[from], exits[from ^ 1u],
-                           counts, launches, flags);
-        e = hipGetLastError();
-        if (e == hipSuccess) e = hipMemcpyAsync(h_flags, flags, sizeof(h_flags), hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipStreamSynchronize(s);
-        if (e != hipSuccess) return device_error("jpeg_decode", e);
-        if (h_flags[FLAG_ERR] || !h_flags[FLAG_CHANGED]) {
-            launches++;
-            break;
-        }
-    }
+    uint32_t launches = 0;
+    int status = settle_launches("jpeg_decode", sync_blocks, flags, h_flags, FLAGS, s, launches, [&](uint32_t round, uint32_t from, uint32_t to) {
+        hipLaunchKernelGGL(jpeg_sync_kernel, dim3(sync_blocks), block, 0, s, words, d_luts, P, seg_start, sub_first, entry, exits[from], exits[to], counts, round,
+                           flags);
+    });
+    if (status != CVHIP_OK) return status;
     launch_scan_u64(counts, sub_cap, counts + sub_cap, s);
     hipLaunchKernelGGL(jpeg_write_kernel, dim3(sync_blocks), block, 0, s, words, d_luts, P, seg_start, sub_first, entry, counts, coef, flags);
     hipLaunchKernelGGL(jpeg_dc_kernel, dim3((P.mcus + BLOCK - 1) / BLOCK), block, 0, s, coef, P, sums);
     launch_scan_u64(sums, (unsigned long long)P.ncomp * P.mcus, sums + (size_t)P.ncomp * P.mcus, s);
-    hipLaunchKernelGGL(jpeg_idct_kernel, dim3((uint32_t)((n_blocks + WAVE - 1) / WAVE)), dim3(WAVE), 0, s, coef, P, sums, d_quant, planes, n_blocks, flags);
-    const uint32_t lead = (uint32_t)std::min<unsigned long long>(bytes, (4 - (reinterpret_cast<uintptr_t>(d_out) & 3u)) & 3u);
-    const unsigned long long lanes = (bytes - lead) / 4 + lead + (bytes - lead) % 4;
-    hipLaunchKernelGGL(jpeg_pixels_kernel, dim3((uint32_t)((lanes + BLOCK - 1) / BLOCK)), block, 0, s, P, planes, channels, d_out, bytes, lead, flags);
-    e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(h_flags, flags, sizeof(h_flags), hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e != hipSuccess) return device_error("jpeg_decode", e);
+    status = launch_tail("jpeg_decode", P, planes, coef, sums, d_quant, channels, d_out, bytes, flags, h_flags, FLAGS, s);
+    if (status != CVHIP_OK) return status;
     t_stats[0] = nseg, t_stats[1] = h_flags[FLAG_SUBSEQUENCES], t_stats[2] = launches, t_stats[3] = h_flags[FLAG_ROUNDS];
     const uint32_t err = h_flags[FLAG_ERR];
     if (err & ERR_RST) return fail(CVHIP_ERR_INVALID, "jpeg_decode: a missing, surplus or misnumbered RSTn");
     if (err & ERR_CODE) return fail(CVHIP_ERR_INVALID, "jpeg_decode: a code that is not in its table");
     if (err & ERR_RUN) return fail(CVHIP_ERR_INVALID, "jpeg_decode: a run past coefficient 63");
     if (err & ERR_DATA) return fail(CVHIP_ERR_INVALID, "jpeg_decode: the data ends before the last MCU");
-    e = sc.copy_out(out, d_out, (size_t)bytes, s);
-    if (e == hipSuccess) e = sc.drain(s);
-    if (e != hipSuccess) return device_error("jpeg_decode", e);
-    return CVHIP_OK;
+    return deliver("jpeg_decode", sc, out, d_out, bytes, s);
 }

@@ -1,6 +1,6 @@
 // jpeg_prog_common.hpp — the host side of cvhip_jpeg_progressive_decode (jpeg_prog_kernels.hip) as plain C++
 // that also compiles without HIP (tests/cpp/jpeg_prog_host.cpp runs it on the CPU under sanitizers): the marker walk over the
-// whole file, the scan list (components, Ss, Se, Ah, Al, byte range, restart interval, the Huffman tables in force), the
+// whole file (jpeg_common.hpp's walk(), with this file's handling of a scan), the scan list (components, Ss, Se, Ah, Al, byte range, restart interval, the Huffman tables in force), the
 // progression checks with a ledger of the Al every coefficient was last sent with, one 16-bit-prefix lookup per distinct table
 // a scan uses, and the launch order of the scans.  The device cuts the scans at their RSTn markers and decodes them; for the
 // CPU program that checks the walk, parse(.., cut = true) cuts them on the host too and decode_interval is the sequential
@@ -90,65 +90,6 @@ JPEG_PROG_HD inline uint32_t block_index(const Frame &F, const Scan &S, uint32_t
 // ---- the marker walk ---------------------------------------------------------------------------------------------------------------
 namespace detail {
 
-inline int read_dqt(const uint8_t *seg, size_t len, uint16_t (&quant)[4][64], bool (&have)[4])
-{
-    for (size_t k = 0; k < len;) {
-        const uint32_t pq = seg[k] >> 4, tq = seg[k] & 15u;
-        if (pq > 1 || tq > 3 || k + 1 + 64 * (pq + 1) > len) return INVALID;
-        for (int i = 0; i < 64; i++) quant[tq][jc::ZIGZAG[i]] = pq ? (uint16_t)(seg[k + 1 + 2 * i] << 8 | seg[k + 2 + 2 * i]) : seg[k + 1 + i];
-        have[tq] = true;
-        k += 1 + 64 * (pq + 1);
-    }
-    return OK;
-}
-
-inline int read_dht(const uint8_t *seg, size_t len, jc::HuffmanTable (&huff)[2][4], const char *&why)
-{
-    for (size_t k = 0; k < len;) {
-        why = "DHT";
-        if (k + 17 > len) return INVALID;
-        const uint32_t tc = seg[k] >> 4, th = seg[k] & 15u;
-        uint32_t total = 0;
-        for (int i = 0; i < 16; i++) total += seg[k + 1 + i];
-        if (tc > 1 || th > 3 || total > 256 || k + 17 + total > len) return INVALID;
-        uint32_t code = 0, s = 0;
-        for (int bits = 1; bits <= 16; bits++) {
-            for (uint32_t c = 0; c < seg[k + bits]; c++, code++, s++) {
-                why = "DHT: the code space is overfull";
-                if (code >= (1u << bits)) return INVALID;
-                why = "DHT: a DC category above 15";
-                if (tc == 0 && seg[k + 17 + s] > 15) return INVALID;
-            }
-            code <<= 1;
-        }
-        jc::HuffmanTable &t = huff[tc][th];
-        t = jc::HuffmanTable();
-        t.present = true, t.total = total;
-        std::memcpy(t.counts, seg + k + 1, 16);
-        std::memcpy(t.symbols, seg + k + 17, total);
-        k += 17 + total;
-    }
-    return OK;
-}
-
-// the first FF at or behind `start` that is followed by neither 00, FF nor RSTn, or the file's end
-inline size_t scan_end(const uint8_t *data, size_t n, size_t start)
-{
-    size_t end = start;
-    while (end < n) {
-        const void *ff = std::memchr(data + end, 0xFF, n - end);
-        if (!ff || (size_t)((const uint8_t *)ff - data) + 1 >= n) return n;
-        end = (size_t)((const uint8_t *)ff - data);
-        const uint32_t nx = data[end + 1];
-        if (nx == 0 || nx == 0xFF || (nx >= 0xD0 && nx <= 0xD7)) {
-            end += nx == 0xFF ? 1 : 2;
-            continue;
-        }
-        break;
-    }
-    return end;
-}
-
 inline uint32_t table_id(File &f, const jc::HuffmanTable &t)
 {
     for (size_t k = 0; k < f.tables.size(); k++)
@@ -199,166 +140,99 @@ inline int cut_intervals(File &f, const uint8_t *data, size_t s0, size_t s1, uin
 
 } // namespace detail
 
-// The marker walk of data[0 .. n) over every scan -> OK, INVALID or UNSUPPORTED (f.error says why).  cut: also walk every
-// scan's bytes for its RSTn markers (the restart intervals' byte ranges, their numbering and count, the subsequences) - what the
-// device does for the library (jpeg_prog_kernels.hip), restated on the host for the CPU program that checks it.
+// The marker walk of data[0 .. n) over every scan -> OK, INVALID or UNSUPPORTED (f.error says why): jpeg_common.hpp's walk(),
+// carried on behind every scan up to EOI or the file's end.  cut: also walk every scan's bytes for its RSTn markers (the
+// restart intervals' byte ranges, their numbering and count, the subsequences) - what the device does for the library
+// (jpeg_prog_kernels.hip), restated on the host for the CPU program that checks it.
 inline int parse(const uint8_t *data, size_t n, File &f, bool cut = false)
 {
-    if (n < 4 || data[0] != 0xFF || data[1] != 0xD8) return refuse(f, INVALID, "no SOI");
-    if (n >= (1ull << 31)) return refuse(f, UNSUPPORTED, "a file of 2^31 or more bytes");
-    size_t at = 2;
-    bool have_frame = false, have_quant[4] = {false, false, false, false}, latched[3] = {false, false, false};
-    int adobe = -1;
-    uint32_t restart = 0;
-    uint16_t quant[4][64];
-    jc::HuffmanTable huff[2][4];
-    jc::Component comp[3];
+    // (a file without SOI is refused for that, whatever its size)
+    if (n >= (1ull << 31) && data[0] == 0xFF && data[1] == 0xD8) return refuse(f, UNSUPPORTED, "a file of 2^31 or more bytes");
+    const jc::Dialect progressive{0xC2, "a frame that is not progressive (SOF2)", "a marker that cannot stand outside a scan"}; // (a baseline file too: cvhip_jpeg_decode's)
+    jc::Walk w;
+    bool latched[3] = {false, false, false};
     int ledger[3][64];
+    for (auto &row : ledger)
+        for (int &v : row) v = -1;
     Frame &F = f.frame;
-    for (;;) {
-        if (at >= n) {
-            if (!f.scans.empty()) break; // (no EOI: the file's end is the end)
-            return refuse(f, INVALID, "no marker");
+    const int walked = jc::walk(data, n, w, progressive, [&](const uint8_t *seg, size_t len, size_t &at) {
+        if (!w.have_frame) return jc::refuse(w, INVALID, "a scan before the frame");
+        F = Frame{w.width, w.height, w.components, w.hmax, w.vmax, w.mcus_x, w.mcus_y, jc::blocks_per_mcu(w)};
+        if (f.scans.size() >= MAX_SCANS) return jc::refuse(w, UNSUPPORTED, "more than 256 scans");
+        if (len < 1 || len != 4 + 2 * (size_t)seg[0]) return jc::refuse(w, INVALID, "SOS");
+        const uint32_t ns = seg[0];
+        if (ns < 1 || ns > F.ncomp) return jc::refuse(w, INVALID, "SOS");
+        Scan S{};
+        S.ncomp = ns, S.ss = seg[1 + 2 * ns], S.se = seg[2 + 2 * ns], S.ah = seg[3 + 2 * ns] >> 4, S.al = seg[3 + 2 * ns] & 15u;
+        S.ac_lut = NO_LUT;
+        if (S.ss > S.se || S.se > 63 || (S.ss == 0 && S.se != 0) || (S.ss > 0 && ns != 1) || S.al > 13 || S.ah > 13)
+            return jc::refuse(w, INVALID, "SOS: the band or the bit position");
+        if (S.ah && S.al != S.ah - 1) return jc::refuse(w, INVALID, "SOS: a refinement of more than one bit");
+        if (F.ncomp == 3 && w.adobe >= 0 && w.adobe != 1) return jc::refuse(w, UNSUPPORTED, "an Adobe transform that is not YCbCr");
+        for (uint32_t k = 0; k < ns; k++) {
+            uint32_t c = 0;
+            while (c < F.ncomp && w.comp[c].id != seg[1 + 2 * k]) c++;
+            if (c == F.ncomp) return jc::refuse(w, INVALID, "SOS: no such component");
+            if (k && c <= S.comp[k - 1]) return jc::refuse(w, INVALID, "SOS: the components are not in the frame's order");
+            const uint32_t td = seg[2 + 2 * k] >> 4, ta = seg[2 + 2 * k] & 15u;
+            if (td > 3 || ta > 3) return jc::refuse(w, INVALID, "SOS");
+            if (!latched[c]) { // (libjpeg latches a component's table at its first scan)
+                if (!w.have_quant[w.comp[c].tq]) return jc::refuse(w, INVALID, "a missing table");
+                std::memcpy(f.quant[c], w.quant[w.comp[c].tq], sizeof(f.quant[c]));
+                latched[c] = true;
+            }
+            S.comp[k] = c, S.dc_lut[k] = NO_LUT;
+            if (S.ss == 0 && S.ah == 0) {
+                if (!w.huff[0][td].present) return jc::refuse(w, INVALID, "a missing table");
+                S.dc_lut[k] = detail::table_id(f, w.huff[0][td]);
+            }
+            if (S.ss > 0) {
+                if (!w.huff[1][ta].present) return jc::refuse(w, INVALID, "a missing table");
+                S.ac_lut = detail::table_id(f, w.huff[1][ta]);
+                if (ledger[c][0] < 0) return jc::refuse(w, INVALID, "an AC scan before the component's DC scan");
+            }
+            for (uint32_t z = S.ss; z <= S.se; z++) {
+                if (S.ah == 0 && ledger[c][z] >= 0) return jc::refuse(w, INVALID, "a first scan of coefficients that were sent");
+                if (S.ah && ledger[c][z] != (int)S.ah) return jc::refuse(w, INVALID, "Ah is not the Al the coefficients were last sent with");
+                ledger[c][z] = (int)S.al;
+            }
         }
-        if (data[at] != 0xFF) return refuse(f, INVALID, "no marker");
-        while (at < n && data[at] == 0xFF) at++;
-        if (at >= n) {
-            if (!f.scans.empty()) break;
-            return refuse(f, INVALID, "the file ends in a marker");
+        if (ns > 1)
+            S.mcus = F.mcus_x * F.mcus_y, S.across = 0;
+        else {
+            const uint32_t c = S.comp[0], ch = c == 0 ? F.hmax : 1u, cv = c == 0 ? F.vmax : 1u;
+            const uint32_t dw = (F.width * ch + F.hmax - 1) / F.hmax, dh = (F.height * cv + F.vmax - 1) / F.vmax;
+            S.across = (dw + 7) / 8, S.mcus = S.across * ((dh + 7) / 8);
         }
-        const uint32_t m = data[at++];
-        if (m == 0xD9 && !f.scans.empty()) break;
-        if (m == 0xD9 || m == 0xD8 || (m >= 0xD0 && m <= 0xD7) || m == 0x00) return refuse(f, INVALID, "a marker that cannot stand outside a scan");
-        if (m == 0x01) continue;
-        if (at + 2 > n) return refuse(f, INVALID, "truncated segment");
-        const size_t length = (size_t)data[at] << 8 | data[at + 1];
-        if (length < 2 || at + length > n) return refuse(f, INVALID, "truncated segment");
-        const uint8_t *seg = data + at + 2;
-        const size_t len = length - 2;
-        if (m == 0xDB) {
-            if (detail::read_dqt(seg, len, quant, have_quant) != OK) return refuse(f, INVALID, "DQT");
-        } else if (m == 0xC4) {
-            const char *why = "DHT";
-            if (detail::read_dht(seg, len, huff, why) != OK) return refuse(f, INVALID, why);
-        } else if (m == 0xDD) {
-            if (len != 2) return refuse(f, INVALID, "DRI");
-            restart = (uint32_t)seg[0] << 8 | seg[1];
-        } else if (m == 0xC2) {
-            if (have_frame) return refuse(f, INVALID, "two frames");
-            if (len < 6) return refuse(f, INVALID, "SOF");
-            const uint32_t p = seg[0], hh = (uint32_t)seg[1] << 8 | seg[2], w = (uint32_t)seg[3] << 8 | seg[4], nf = seg[5];
-            if (len != 6 + 3 * (size_t)nf) return refuse(f, INVALID, "SOF");
-            if (p == 12) return refuse(f, UNSUPPORTED, "12-bit samples");
-            if (p != 8) return refuse(f, INVALID, "precision");
-            if (hh == 0) return refuse(f, UNSUPPORTED, "DNL");
-            if (w == 0) return refuse(f, INVALID, "width 0");
-            if (nf == 2 || nf == 4) return refuse(f, UNSUPPORTED, "2 or 4 components");
-            if (nf != 1 && nf != 3) return refuse(f, INVALID, "components");
-            for (uint32_t c = 0; c < nf; c++) {
-                jc::Component &k = comp[c];
-                k.id = seg[6 + 3 * c], k.h = seg[7 + 3 * c] >> 4, k.v = seg[7 + 3 * c] & 15u, k.tq = seg[8 + 3 * c];
-                if (k.h < 1 || k.h > 4 || k.v < 1 || k.v > 4 || k.tq > 3) return refuse(f, INVALID, "SOF");
+        S.intervals = w.restart ? (S.mcus + w.restart - 1) / w.restart : 1u;
+        S.restart = w.restart ? w.restart : S.mcus;
+        // the launch it goes in: behind every earlier scan of one of its components whose band overlaps its own, where it
+        // reads what that scan wrote (a refinement); first scans write where nothing was sent
+        S.level = 0;
+        if (S.ah)
+            for (const Scan &before : f.scans) {
+                bool shares = false;
+                for (uint32_t a = 0; a < before.ncomp; a++)
+                    for (uint32_t b = 0; b < ns; b++) shares |= before.comp[a] == S.comp[b];
+                if (shares && before.ss <= S.se && S.ss <= before.se && before.level + 1 > S.level) S.level = before.level + 1;
             }
-            if (nf == 1)
-                comp[0].h = comp[0].v = 1;
-            else {
-                const jc::Component &y = comp[0];
-                const bool luma_ok = (y.h == 1 && y.v == 1) || (y.h == 2 && y.v == 1) || (y.h == 2 && y.v == 2);
-                if (!luma_ok || comp[1].h != 1 || comp[1].v != 1 || comp[2].h != 1 || comp[2].v != 1)
-                    return refuse(f, UNSUPPORTED, "sampling factors other than 1x1, 2x1 or 2x2 luma over 1x1 chroma");
-            }
-            F.width = w, F.height = hh, F.ncomp = nf, F.hmax = comp[0].h, F.vmax = comp[0].v;
-            F.mcus_x = (w + 8 * F.hmax - 1) / (8 * F.hmax), F.mcus_y = (hh + 8 * F.vmax - 1) / (8 * F.vmax);
-            F.bpm = nf == 1 ? 1u : F.hmax * F.vmax + 2u;
-            for (auto &row : ledger)
-                for (int &v : row) v = -1;
-            have_frame = true;
-        } else if (m >= 0xC0 && m <= 0xCF && m != 0xC4 && m != 0xC8 && m != 0xCC) {
-            return refuse(f, UNSUPPORTED, "a frame that is not progressive (SOF2)"); // (a baseline file too: cvhip_jpeg_decode's)
-        } else if (m == 0xCC) {
-            return refuse(f, UNSUPPORTED, "arithmetic conditioning");
-        } else if (m == 0xDC) {
-            return refuse(f, UNSUPPORTED, "DNL");
-        } else if (m == 0xE1 && len >= 6 && std::memcmp(seg, "Exif\0\0", 6) == 0 && f.focal_length_35mm == 0) {
-            f.focal_length_35mm = jc::exif_focal_length_35mm(seg + 6, len - 6);
-        } else if (m == 0xEE && len >= 12 && std::memcmp(seg, "Adobe", 5) == 0) {
-            adobe = seg[11];
-        } else if (m == 0xDA) {
-            if (!have_frame) return refuse(f, INVALID, "a scan before the frame");
-            if (f.scans.size() >= MAX_SCANS) return refuse(f, UNSUPPORTED, "more than 256 scans");
-            if (len < 1 || len != 4 + 2 * (size_t)seg[0]) return refuse(f, INVALID, "SOS");
-            const uint32_t ns = seg[0];
-            if (ns < 1 || ns > F.ncomp) return refuse(f, INVALID, "SOS");
-            Scan S{};
-            S.ncomp = ns, S.ss = seg[1 + 2 * ns], S.se = seg[2 + 2 * ns], S.ah = seg[3 + 2 * ns] >> 4, S.al = seg[3 + 2 * ns] & 15u;
-            S.ac_lut = NO_LUT;
-            if (S.ss > S.se || S.se > 63 || (S.ss == 0 && S.se != 0) || (S.ss > 0 && ns != 1) || S.al > 13 || S.ah > 13)
-                return refuse(f, INVALID, "SOS: the band or the bit position");
-            if (S.ah && S.al != S.ah - 1) return refuse(f, INVALID, "SOS: a refinement of more than one bit");
-            if (F.ncomp == 3 && adobe >= 0 && adobe != 1) return refuse(f, UNSUPPORTED, "an Adobe transform that is not YCbCr");
-            for (uint32_t k = 0; k < ns; k++) {
-                uint32_t c = 0;
-                while (c < F.ncomp && comp[c].id != seg[1 + 2 * k]) c++;
-                if (c == F.ncomp) return refuse(f, INVALID, "SOS: no such component");
-                if (k && c <= S.comp[k - 1]) return refuse(f, INVALID, "SOS: the components are not in the frame's order");
-                const uint32_t td = seg[2 + 2 * k] >> 4, ta = seg[2 + 2 * k] & 15u;
-                if (td > 3 || ta > 3) return refuse(f, INVALID, "SOS");
-                if (!latched[c]) { // (libjpeg latches a component's table at its first scan)
-                    if (!have_quant[comp[c].tq]) return refuse(f, INVALID, "a missing table");
-                    std::memcpy(f.quant[c], quant[comp[c].tq], sizeof(f.quant[c]));
-                    latched[c] = true;
-                }
-                S.comp[k] = c, S.dc_lut[k] = NO_LUT;
-                if (S.ss == 0 && S.ah == 0) {
-                    if (!huff[0][td].present) return refuse(f, INVALID, "a missing table");
-                    S.dc_lut[k] = detail::table_id(f, huff[0][td]);
-                }
-                if (S.ss > 0) {
-                    if (!huff[1][ta].present) return refuse(f, INVALID, "a missing table");
-                    S.ac_lut = detail::table_id(f, huff[1][ta]);
-                    if (ledger[c][0] < 0) return refuse(f, INVALID, "an AC scan before the component's DC scan");
-                }
-                for (uint32_t z = S.ss; z <= S.se; z++) {
-                    if (S.ah == 0 && ledger[c][z] >= 0) return refuse(f, INVALID, "a first scan of coefficients that were sent");
-                    if (S.ah && ledger[c][z] != (int)S.ah) return refuse(f, INVALID, "Ah is not the Al the coefficients were last sent with");
-                    ledger[c][z] = (int)S.al;
-                }
-            }
-            if (ns > 1)
-                S.mcus = F.mcus_x * F.mcus_y, S.across = 0;
-            else {
-                const uint32_t c = S.comp[0], ch = c == 0 ? F.hmax : 1u, cv = c == 0 ? F.vmax : 1u;
-                const uint32_t dw = (F.width * ch + F.hmax - 1) / F.hmax, dh = (F.height * cv + F.vmax - 1) / F.vmax;
-                S.across = (dw + 7) / 8, S.mcus = S.across * ((dh + 7) / 8);
-            }
-            S.intervals = restart ? (S.mcus + restart - 1) / restart : 1u;
-            S.restart = restart ? restart : S.mcus;
-            // the launch it goes in: behind every earlier scan of one of its components whose band overlaps its own, where it
-            // reads what that scan wrote (a refinement); first scans write where nothing was sent
-            S.level = 0;
-            if (S.ah)
-                for (const Scan &before : f.scans) {
-                    bool shares = false;
-                    for (uint32_t a = 0; a < before.ncomp; a++)
-                        for (uint32_t b = 0; b < ns; b++) shares |= before.comp[a] == S.comp[b];
-                    if (shares && before.ss <= S.se && S.ss <= before.se && before.level + 1 > S.level) S.level = before.level + 1;
-                }
-            const size_t start = at + length, end = detail::scan_end(data, n, start);
-            S.first_interval = S.ifirst = (uint32_t)f.intervals.size();
-            S.begin = (uint32_t)start, S.end = (uint32_t)end, S.vfirst = f.virtual_bytes;
-            f.virtual_bytes += end > start ? (uint32_t)((end - start + 63) / 64 * 64) : 64u;
-            if (cut) {
-                const int rc = detail::cut_intervals(f, data, start, end, (uint32_t)f.scans.size(), S.intervals);
-                if (rc != OK) return rc;
-            } else
-                for (uint32_t k = 0; k < S.intervals; k++) f.intervals.push_back(Interval{(uint32_t)f.scans.size(), k, 0u, 0u});
-            f.scan_bytes += end - start;
-            f.scans.push_back(S);
-            at = end;
-            continue;
-        }
-        at += length;
-    }
+        const size_t start = at, end = jc::scan_end(data, n, start);
+        S.first_interval = S.ifirst = (uint32_t)f.intervals.size();
+        S.begin = (uint32_t)start, S.end = (uint32_t)end, S.vfirst = f.virtual_bytes;
+        f.virtual_bytes += end > start ? (uint32_t)((end - start + 63) / 64 * 64) : 64u;
+        if (cut) {
+            const int rc = detail::cut_intervals(f, data, start, end, (uint32_t)f.scans.size(), S.intervals);
+            if (rc != OK) return jc::refuse(w, rc, f.error);
+        } else
+            for (uint32_t k = 0; k < S.intervals; k++) f.intervals.push_back(Interval{(uint32_t)f.scans.size(), k, 0u, 0u});
+        f.scan_bytes += end - start;
+        f.scans.push_back(S);
+        at = end;
+        w.may_end = true; // behind a scan EOI, or the file's end without one, ends the walk
+        return OK;
+    });
+    f.focal_length_35mm = w.focal_length_35mm;
+    if (walked != OK) return refuse(f, walked, w.error);
     for (uint32_t c = 0; c < F.ncomp; c++)
         for (int z = 0; z < 10; z++)
             if (ledger[c][z] != 0) return refuse(f, UNSUPPORTED, "an incomplete progression: a coefficient 0 .. 9 is unsent or unrefined");

@@ -48,51 +48,21 @@ namespace jp = jpeg_prog;
 
 #include "jpeg_tail.inc"
 
+#include "jpeg_entropy.inc"
+
 constexpr uint64_t MAX_BLOCKS = 1ull << 25;
-constexpr uint32_t SHORT_BITS = 10, SHORT_ENTRIES = 1u << SHORT_BITS; // the codes of up to 10 bits of a scan's table, in LDS
 constexpr uint32_t PROG_FLAGS = FLAGS + jp::METS; // flags[FLAG_ERR], and behind the baseline path's words what the decode met
-
-__device__ const uint8_t d_zigzag[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
-                                         41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
-                                         30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
-
-constexpr uint32_t KIND_DROP = 0, KIND_DATA = 1, KIND_RST = 2;
 
 // the scan that virtual byte v lies in: the last with vfirst <= v
 __device__ __forceinline__ uint32_t scan_of_byte(const jp::Scan *__restrict__ scans, uint32_t n_scans, uint32_t v)
 {
-    uint32_t lo = 0, hi = n_scans;
-    while (hi - lo > 1) {
-        const uint32_t mid = lo + (hi - lo) / 2;
-        if (scans[mid].vfirst <= v) lo = mid;
-        else hi = mid;
-    }
-    return lo;
+    return last_not_above(n_scans, v, [&](uint32_t s) { return scans[s].vfirst; });
 }
 
 // the scan that restart interval g (file order) lies in: the last with ifirst <= g
 __device__ __forceinline__ uint32_t scan_of_interval(const jp::Scan *__restrict__ scans, uint32_t n_scans, uint32_t g)
 {
-    uint32_t lo = 0, hi = n_scans;
-    while (hi - lo > 1) {
-        const uint32_t mid = lo + (hi - lo) / 2;
-        if (scans[mid].ifirst <= g) lo = mid;
-        else hi = mid;
-    }
-    return lo;
-}
-
-// What byte i of a scan's file[begin .. end) is: section 4.16's rule (one byte back and one ahead decide it), but an FF that the
-// scan's range ends behind is dropped (tests/ref_jpeg_prog.py: intervals - the data ends there).
-__device__ __forceinline__ uint32_t classify(const uint8_t *__restrict__ file, uint32_t begin, uint32_t end, uint32_t i)
-{
-    const uint32_t b = file[i], prev = i > begin ? file[i - 1] : 0u, next = i + 1 < end ? file[i + 1] : 0x100u;
-    if (b == 0xFF) return next == 0x00 ? KIND_DATA : KIND_DROP; // stuffed; fill, a marker's first byte, or the range's last
-    if (prev == 0xFF) {
-        if (b == 0x00) return KIND_DROP;
-        if (b >= 0xD0 && b <= 0xD7) return KIND_RST;
-    }
-    return KIND_DATA;
+    return last_not_above(n_scans, g, [&](uint32_t s) { return scans[s].ifirst; });
 }
 
 // The bytes of ALL scans, laid end to end with every scan begun at a multiple of 64 (virtual bytes 0 .. n_virtual; those behind
@@ -103,7 +73,7 @@ __device__ __forceinline__ uint32_t kind_of(const uint8_t *__restrict__ file, co
     if (v >= n_virtual) return KIND_DROP;
     s = scan_of_byte(scans, n_scans, v);
     i = scans[s].begin + (v - scans[s].vfirst);
-    return i < scans[s].end ? classify(file, scans[s].begin, scans[s].end, i) : KIND_DROP;
+    return i < scans[s].end ? classify<false>(file, scans[s].begin, scans[s].end, i) : KIND_DROP;
 }
 
 __global__ __launch_bounds__(BLOCK) void jpeg_prog_mark_kernel(const uint8_t *__restrict__ file, const jp::Scan *__restrict__ scans, uint32_t n_scans,
@@ -218,21 +188,6 @@ __global__ __launch_bounds__(BLOCK) void jpeg_prog_subseq_kernel(const jp::Scan 
     sub_count[t] = subs ? subs : 1;
 }
 
-// A state: the next bit (of the clean buffer) | the block's number in its scan MCU << 40 | the zig-zag index << 44
-__device__ __forceinline__ unsigned long long pack_state(unsigned long long p, uint32_t slot, uint32_t k)
-{
-    return p | (unsigned long long)slot << 40 | (unsigned long long)k << 44;
-}
-
-// the 64 bits of the clean buffer (big-endian) from word wi on, those at and past seg_end_bits read as ones; 32 wi < seg_end_bits
-__device__ __forceinline__ unsigned long long load_window(const uint32_t *__restrict__ words, unsigned long long wi, unsigned long long seg_end_bits)
-{
-    const unsigned long long base = wi << 5;
-    unsigned long long v = (unsigned long long)__builtin_bswap32(words[wi]) << 32 | __builtin_bswap32(words[wi + 1]);
-    if (seg_end_bits < base + 64) v |= ~0ull >> (seg_end_bits - base); // (1 .. 63 valid bits)
-    return v;
-}
-
 // the blocks of a scan MCU
 __device__ __forceinline__ uint32_t blocks_per_scan_mcu(const jp::Frame &F, const jp::Scan &S)
 {
@@ -328,22 +283,9 @@ __device__ __forceinline__ unsigned long long decode_first(const uint32_t *__res
     return pack_state(p, slot, k);
 }
 
-// the interval of subsequence i: the last t with sub_first[t] <= i (sub_first[n_first] = the subsequences of the first scans > i)
-__device__ __forceinline__ uint32_t interval_of(const unsigned long long *__restrict__ sub_first, uint32_t n_first, unsigned long long i)
-{
-    uint32_t lo = 0, hi = n_first;
-    while (hi - lo > 1) {
-        const uint32_t mid = lo + (hi - lo) / 2;
-        if (sub_first[mid] <= i) lo = mid;
-        else hi = mid;
-    }
-    return lo;
-}
-
 // Section 4.16's jpeg_sync_kernel over the subsequences of ALL first scans, every lane with its own scan's tables, band and
-// MCU.  round 0: every subsequence from its guess (its first bit, block 0 of the MCU, coefficient Ss), settled within the
-// workgroup.  round > 0: the first lane of a workgroup takes exit_in[i - 1], the launch before's; flags[FLAG_CHANGED] is set
-// when a workgroup's last exit state differs from exit_in's.  An interval's first subsequence starts from the known state.
+// MCU: its interval, scan and bit range, then jpeg_entropy.inc's settle loop from the guess "its first bit, block 0 of the MCU,
+// coefficient Ss" - the true state of an interval's first subsequence.
 __global__ __launch_bounds__(BLOCK) void jpeg_prog_sync_kernel(const uint32_t *__restrict__ words, const uint16_t *__restrict__ luts, jp::Frame F,
                                                                const jp::Scan *__restrict__ scans, const jp::Interval *__restrict__ intervals,
                                                                uint32_t n_first, const unsigned long long *__restrict__ seg_start,
@@ -351,51 +293,26 @@ __global__ __launch_bounds__(BLOCK) void jpeg_prog_sync_kernel(const uint32_t *_
                                                                const unsigned long long *__restrict__ exit_in, unsigned long long *__restrict__ exit_out,
                                                                unsigned long long *__restrict__ counts, uint32_t round, uint32_t *__restrict__ flags)
 {
-    __shared__ unsigned long long s_exit[BLOCK];
     if (flags[FLAG_ERR]) return; // (set by the kernels before this one only: the same for every lane)
     const unsigned long long i = (unsigned long long)blockIdx.x * BLOCK + threadIdx.x, total = sub_first[n_first];
     const bool active = i < total;
-    unsigned long long end_bit = 0, seg_end_bits = 0, cur_entry = 0, cur_exit = 0, blocks = 0, old_exit = 0;
+    unsigned long long first_bit = 0, end_bit = 0, seg_end_bits = 0;
     bool known = false;
     uint32_t scan = 0;
     if (active) {
         const uint32_t t = interval_of(sub_first, n_first, i);
         scan = intervals[t].scan;
         const uint32_t g = scans[scan].ifirst + intervals[t].index;
-        const unsigned long long j = i - sub_first[t], first_bit = seg_start[g] * 8 + j * jc::SUBSEQ_BITS;
-        seg_end_bits = seg_start[g + 1] * 8;
+        const unsigned long long j = i - sub_first[t];
+        first_bit = seg_start[g] * 8 + j * jc::SUBSEQ_BITS, seg_end_bits = seg_start[g + 1] * 8;
         end_bit = first_bit + jc::SUBSEQ_BITS < seg_end_bits ? first_bit + jc::SUBSEQ_BITS : seg_end_bits;
         known = j == 0;
-        if (round == 0) {
-            cur_entry = pack_state(first_bit, 0, scans[scan].ss); // the true state of an interval's first subsequence, the guess of the others
-            cur_exit = decode_first<false>(words, luts, F, scans[scan], cur_entry, end_bit, seg_end_bits, blocks, nullptr, 0, 0, nullptr);
-        } else {
-            cur_entry = entry[i], cur_exit = old_exit = exit_in[i], blocks = counts[i];
-        }
     }
-    s_exit[threadIdx.x] = cur_exit;
-    uint32_t rounds = 0;
-    for (;;) {
-        __syncthreads();
-        unsigned long long want = cur_entry;
-        if (active && !known) {
-            if (threadIdx.x) want = s_exit[threadIdx.x - 1];
-            else if (round) want = exit_in[i - 1];
-        }
-        const bool change = want != cur_entry;
-        if (!__syncthreads_or(change)) break; // (and every lane has read before any lane writes)
-        if (change) {
-            cur_entry = want, blocks = 0;
-            cur_exit = decode_first<false>(words, luts, F, scans[scan], cur_entry, end_bit, seg_end_bits, blocks, nullptr, 0, 0, nullptr);
-            s_exit[threadIdx.x] = cur_exit;
-        }
-        rounds++;
-    }
-    if (active) {
-        entry[i] = cur_entry, exit_out[i] = cur_exit, counts[i] = blocks;
-        if (threadIdx.x == BLOCK - 1 && (round == 0 || cur_exit != old_exit)) atomicOr(&flags[FLAG_CHANGED], 1u);
-    }
-    if (threadIdx.x == 0 && rounds) atomicMax(&flags[FLAG_ROUNDS], rounds);
+    settle(
+        active, known, i, round, entry, exit_in, exit_out, counts, flags, [&]() { return pack_state(first_bit, 0, scans[scan].ss); },
+        [&](unsigned long long state, unsigned long long &blocks) {
+            return decode_first<false>(words, luts, F, scans[scan], state, end_bit, seg_end_bits, blocks, nullptr, 0, 0, nullptr);
+        });
 }
 
 // counts: scanned, counts[the launch's lanes] = their total.  One more decode from the settled states stores the shifted AC
@@ -513,11 +430,7 @@ __global__ __launch_bounds__(WAVE) void jpeg_prog_refine_kernel(const uint8_t *_
     const jp::Scan &S = scans[iv.scan];
     const uint32_t ss = S.ss, se = S.se, al = S.al, c = S.comp[0];
     const uint16_t *lut = luts + (size_t)S.ac_lut * jc::LUT_ENTRIES;
-    // s_short[the next SHORT_BITS bits] = the table's entry where the code there has at most SHORT_BITS bits, else 0
-    for (uint32_t at = lane; at < SHORT_ENTRIES; at += WAVE) {
-        const uint16_t entry = lut[at << (16 - SHORT_BITS)];
-        s_short[at] = (entry >> 8) <= SHORT_BITS ? entry : (uint16_t)0;
-    }
+    for (uint32_t at = lane; at < SHORT_ENTRIES; at += WAVE) s_short[at] = short_entry(lut[at << (16 - SHORT_BITS)]); // (jpeg_entropy.inc: load_short_tables)
     __syncthreads();
     const uint32_t natural = d_zigzag[lane];
     const bool in_band = lane >= ss && lane <= se;
@@ -610,8 +523,6 @@ __global__ __launch_bounds__(BLOCK) void jpeg_prog_dc_kernel(short *__restrict__
 
 thread_local uint64_t t_stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 
-int refused(const char *what, int code, const char *why) { return fail(code == jc::UNSUPPORTED ? CVHIP_ERR_UNSUPPORTED : CVHIP_ERR_INVALID, std::string(what) + ": " + why); }
-
 } // namespace
 } // namespace cvhip
 
@@ -622,7 +533,7 @@ extern "C" int cvhip_jpeg_progressive_info(const uint8_t *file, uint64_t size, u
     if (!file || !out_info) return fail(CVHIP_ERR_INVALID, "jpeg_progressive_info: null argument");
     jp::File f;
     const int rc = jp::parse(file, (size_t)size, f);
-    if (rc != jp::OK) return refused("jpeg_progressive_info", rc, f.error);
+    if (rc != jp::OK) return refused("jpeg_progressive_info", rc == jp::UNSUPPORTED, f.error);
     out_info[0] = f.frame.width, out_info[1] = f.frame.height, out_info[2] = f.frame.ncomp, out_info[3] = f.frame.hmax, out_info[4] = f.frame.vmax;
     out_info[5] = f.focal_length_35mm, out_info[6] = (uint32_t)f.scans.size();
     return CVHIP_OK;
@@ -644,7 +555,7 @@ extern "C" int cvhip_jpeg_progressive_decode(cvhip_device *dev, const uint8_t *f
         return fail(CVHIP_ERR_INVALID, "jpeg_progressive_decode: format is not CVHIP_IMAGE_LUMA8 or CVHIP_IMAGE_RGB8");
     jp::File f;
     const int rc = jp::parse(file, (size_t)size, f);
-    if (rc != jp::OK) return refused(what, rc, f.error);
+    if (rc != jp::OK) return refused(what, rc == jp::UNSUPPORTED, f.error);
     const jp::Frame &F = f.frame;
     if (drop_rows >= F.height) return fail(CVHIP_ERR_INVALID, "jpeg_progressive_decode: drop_rows leaves no row");
     const uint32_t channels = format == CVHIP_IMAGE_RGB8 ? 3u : 1u;
@@ -702,32 +613,20 @@ extern "C" int cvhip_jpeg_progressive_decode(cvhip_device *dev, const uint8_t *f
     CVHIP_TRY_HIP(hipSetDevice(dev->d.ordinal));
     hipStream_t s = dev->d.stream;
     CallScratch sc;
-    Planes planes{};
-    size_t plane_total = 0, plane_at[3] = {0, 0, 0};
-    for (uint32_t c = 0; c < P.ncomp; c++) {
-        planes.stride[c] = F.mcus_x * (c == 0 ? F.hmax : 1u) * 8u;
-        plane_at[c] = plane_total;
-        plane_total += (size_t)planes.stride[c] * F.mcus_y * (c == 0 ? F.vmax : 1u) * 8u; // (a multiple of 64 bytes)
-    }
-    // one allocation, carved: an allocation costs more than most of these kernels
-    size_t arena_bytes = 0;
-    auto reserve = [&](size_t nbytes) {
-        const size_t at = arena_bytes;
-        arena_bytes += (nbytes + 255) / 256 * 256;
-        return at;
-    };
+    PlaneLayout layout(P);
+    Carver carve; // one allocation, carved: an allocation costs more than most of these kernels
     const size_t sums_bytes = ((size_t)P.ncomp * P.mcus + 1) * 8;
     const uint32_t n_virtual = f.virtual_bytes, chunks = n_virtual / 64, n_scans = (uint32_t)f.scans.size(), n_intervals = (uint32_t)f.intervals.size();
-    const size_t at_blob = reserve(blob.size()), at_flags = reserve(PROG_FLAGS * sizeof(uint32_t));
+    const size_t at_blob = carve.reserve(blob.size()), at_flags = carve.reserve(PROG_FLAGS * sizeof(uint32_t));
     const uint32_t n_first = f.level_dc[0]; // the restart intervals of the first scans: intervals[0 .. n_first)
     const unsigned long long sub_cap = n_virtual / (jc::SUBSEQ_BITS / 8) + n_first + 1;
     const uint32_t sync_blocks = (uint32_t)((sub_cap + BLOCK - 1) / BLOCK);
-    const size_t at_sub = reserve(((size_t)n_first + 1) * 8), at_states = reserve((size_t)sub_cap * 3 * 8); // entry states, the exit states of two launches
-    const size_t at_counts = reserve(((size_t)sub_cap + 1) * 8), at_dc_sums = reserve(((size_t)dc_mcus + 1) * 8);
-    const size_t at_clean = reserve((size_t)n_virtual + 16), at_chunks = reserve(((size_t)chunks + 1) * 8), at_seg = reserve(((size_t)n_intervals + 1) * 8);
-    const size_t at_coef = reserve((size_t)n_blocks * 64 * sizeof(short)), at_sums = reserve(sums_bytes), at_planes = reserve(plane_total);
+    const size_t at_sub = carve.reserve(((size_t)n_first + 1) * 8), at_states = carve.reserve((size_t)sub_cap * 3 * 8); // entry states, the exit states of two launches
+    const size_t at_counts = carve.reserve(((size_t)sub_cap + 1) * 8), at_dc_sums = carve.reserve(((size_t)dc_mcus + 1) * 8);
+    const size_t at_clean = carve.reserve((size_t)n_virtual + 16), at_chunks = carve.reserve(((size_t)chunks + 1) * 8), at_seg = carve.reserve(((size_t)n_intervals + 1) * 8);
+    const size_t at_coef = carve.reserve((size_t)n_blocks * 64 * sizeof(short)), at_sums = carve.reserve(sums_bytes), at_planes = carve.reserve(layout.total);
     uint8_t *arena = nullptr, *d_out = nullptr;
-    hipError_t e = sc.alloc(&arena, arena_bytes);
+    hipError_t e = sc.alloc(&arena, carve.total);
     if (e == hipSuccess) e = sc.output(out, (size_t)bytes, &d_out);
     if (e != hipSuccess) return device_error(what, e);
     uint8_t *d_blob = arena + at_blob;
@@ -745,7 +644,7 @@ extern "C" int cvhip_jpeg_progressive_decode(cvhip_device *dev, const uint8_t *f
     unsigned long long *counts = reinterpret_cast<unsigned long long *>(arena + at_counts), *dc_sums = reinterpret_cast<unsigned long long *>(arena + at_dc_sums);
     if (e == hipSuccess) e = hipMemsetAsync(counts, 0, ((size_t)sub_cap + 1) * 8, s);
     if (e != hipSuccess) return device_error(what, e);
-    for (uint32_t c = 0; c < P.ncomp; c++) planes.base[c] = arena + at_planes + plane_at[c];
+    const Planes &planes = layout.placed(arena + at_planes, P.ncomp);
     const uint16_t *d_quant = reinterpret_cast<const uint16_t *>(d_blob), *d_luts = reinterpret_cast<const uint16_t *>(d_blob + at_luts);
     const jp::Scan *d_scans = reinterpret_cast<const jp::Scan *>(d_blob + at_scans);
     const jp::Interval *d_intervals = reinterpret_cast<const jp::Interval *>(d_blob + at_intervals);
@@ -763,25 +662,12 @@ extern "C" int cvhip_jpeg_progressive_decode(cvhip_device *dev, const uint8_t *f
     unsigned long long *entry = states, *exits[2] = {states + sub_cap, states + 2 * sub_cap};
     hipLaunchKernelGGL(jpeg_prog_subseq_kernel, dim3((n_first + BLOCK - 1) / BLOCK), block, 0, s, d_scans, d_intervals, n_first, seg_start, sub_first, flags);
     launch_scan_u64(sub_first, n_first, sub_first + n_first, s);
-    hipLaunchKernelGGL(jpeg_prog_sync_kernel, dim3(sync_blocks), block, 0, s, words, d_luts, F, d_scans, d_intervals, n_first, seg_start, sub_first, entry,
-                       exits[0], exits[0], counts, 0u, flags);
-    uint32_t launches = 1;
-    for (uint32_t from = 0; sync_blocks > 1; from ^= 1u, launches++) {
-        if (launches > sync_blocks + 1) return fail(CVHIP_ERR_DEVICE, "jpeg_progressive_decode: the decoder's states did not settle");
-        e = hipGetLastError();
-        if (e == hipSuccess) e = hipMemsetAsync(flags + FLAG_CHANGED, 0, sizeof(uint32_t), s);
-        if (e != hipSuccess) return device_error(what, e);
+    uint32_t launches = 0;
+    int status = settle_launches(what, sync_blocks, flags, h_flags, PROG_FLAGS, s, launches, [&](uint32_t round, uint32_t from, uint32_t to) {
         hipLaunchKernelGGL(jpeg_prog_sync_kernel, dim3(sync_blocks), block, 0, s, words, d_luts, F, d_scans, d_intervals, n_first, seg_start, sub_first, entry,
-                           exits[from], exits[from ^ 1u], counts, launches, flags);
-        e = hipGetLastError();
-        if (e == hipSuccess) e = hipMemcpyAsync(h_flags, flags, sizeof(h_flags), hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipStreamSynchronize(s);
-        if (e != hipSuccess) return device_error(what, e);
-        if (h_flags[FLAG_ERR] || !h_flags[FLAG_CHANGED]) {
-            launches++;
-            break;
-        }
-    }
+                           exits[from], exits[to], counts, round, flags);
+    });
+    if (status != CVHIP_OK) return status;
     launch_scan_u64(counts, sub_cap, counts + sub_cap, s);
     hipLaunchKernelGGL(jpeg_prog_write_kernel, dim3(sync_blocks), block, 0, s, words, d_luts, F, d_scans, d_intervals, n_first, seg_start, sub_first, entry,
                        counts, coef, flags);
@@ -802,14 +688,8 @@ extern "C" int cvhip_jpeg_progressive_decode(cvhip_device *dev, const uint8_t *f
     }
     // ---- the tail, as the baseline path's
     if (P.luma_blocks > 1) hipLaunchKernelGGL(jpeg_prog_dc_kernel, dim3((P.mcus + BLOCK - 1) / BLOCK), block, 0, s, coef, P, flags);
-    hipLaunchKernelGGL(jpeg_idct_kernel, dim3((uint32_t)((n_blocks + WAVE - 1) / WAVE)), dim3(WAVE), 0, s, coef, P, sums, d_quant, planes, n_blocks, flags);
-    const uint32_t lead = (uint32_t)std::min<unsigned long long>(bytes, (4 - (reinterpret_cast<uintptr_t>(d_out) & 3u)) & 3u);
-    const unsigned long long lanes = (bytes - lead) / 4 + lead + (bytes - lead) % 4;
-    hipLaunchKernelGGL(jpeg_pixels_kernel, dim3((uint32_t)((lanes + BLOCK - 1) / BLOCK)), block, 0, s, P, planes, channels, d_out, bytes, lead, flags);
-    e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(h_flags, flags, sizeof(h_flags), hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e != hipSuccess) return device_error(what, e);
+    status = launch_tail(what, P, planes, coef, sums, d_quant, channels, d_out, bytes, flags, h_flags, PROG_FLAGS, s);
+    if (status != CVHIP_OK) return status;
     t_stats[0] = f.scans.size(), t_stats[1] = f.intervals.size(), t_stats[2] = h_flags[FLAG_SUBSEQUENCES], t_stats[3] = launches, t_stats[4] = h_flags[FLAG_ROUNDS];
     t_stats[5] = f.ac_refinement_scans, t_stats[6] = f.ac_refinement_launches, t_stats[7] = h_flags[FLAGS + jp::MET_EOB_RUN];
     const uint32_t err = h_flags[FLAG_ERR];
@@ -818,8 +698,5 @@ extern "C" int cvhip_jpeg_progressive_decode(cvhip_device *dev, const uint8_t *f
     if (err & jp::ERR_RUN) return fail(CVHIP_ERR_INVALID, "jpeg_progressive_decode: a run past Se");
     if (err & jp::ERR_REFINE) return fail(CVHIP_ERR_INVALID, "jpeg_progressive_decode: a refinement symbol of more than one bit");
     if (err & jp::ERR_DATA) return fail(CVHIP_ERR_INVALID, "jpeg_progressive_decode: the data ends before the scan's last block");
-    e = sc.copy_out(out, d_out, (size_t)bytes, s);
-    if (e == hipSuccess) e = sc.drain(s);
-    if (e != hipSuccess) return device_error(what, e);
-    return CVHIP_OK;
+    return deliver(what, sc, out, d_out, bytes, s);
 }

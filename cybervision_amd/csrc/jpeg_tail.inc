@@ -1,7 +1,8 @@
 // jpeg_tail.inc — what cvhip_jpeg_decode (jpeg_kernels.hip, DESIGN.md 4.16) and cvhip_jpeg_progressive_decode (jpeg_prog_kernels.hip,
 // DESIGN.md 4.22) share behind their entropy decodes: the frame as the kernels take it, and the tail from the block store to the
-// pixels - jpeg_idct_kernel and jpeg_pixels_kernel.  Included inside namespace cvhip { namespace { of each of the two sources: every
-// kernel here is compiled into both, none is called across them.
+// pixels - jpeg_idct_kernel and jpeg_pixels_kernel - with its host side: the planes' layout, the two launches with the flags' way
+// back, the copy into the caller's array.  Included inside namespace cvhip { namespace { of each of the two sources, in front of
+// jpeg_entropy.inc (what they share in front of the block store): every kernel here is compiled into both, none is called across them.
 
 constexpr int WAVE = 64;
 constexpr uint32_t BLOCK = 256;      // lanes of a workgroup; of jpeg_sync_kernel: the subsequences that settle within one launch
@@ -172,4 +173,48 @@ __global__ __launch_bounds__(BLOCK) void jpeg_pixels_kernel(JpegParams P, Planes
     if (single >= singles) return;
     const unsigned long long at = single < lead ? single : 4 * dwords + single;
     out[at] = (uint8_t)result_byte(P, planes, dw, dh, channels, at);
+}
+
+// ---- the host side of the tail ---------------------------------------------------------------------------------------------------
+// the components' planes one behind the other: their strides, where each begins and the bytes of all
+struct PlaneLayout {
+    Planes planes{};
+    size_t at[3] = {0, 0, 0}, total = 0;
+    explicit PlaneLayout(const JpegParams &P)
+    {
+        for (uint32_t c = 0; c < P.ncomp; c++) {
+            planes.stride[c] = P.mcus_x * (c == 0 ? P.hmax : 1u) * 8u;
+            at[c] = total;
+            total += (size_t)planes.stride[c] * P.mcus_y * (c == 0 ? P.vmax : 1u) * 8u; // (a multiple of 64 bytes)
+        }
+    }
+    const Planes &placed(uint8_t *base, uint32_t ncomp)
+    {
+        for (uint32_t c = 0; c < ncomp; c++) planes.base[c] = base + at[c];
+        return planes;
+    }
+};
+
+// The block store to the pixels in d_out[0 .. bytes), and flags[0 .. n_flags) back into h_flags: waits for the stream.
+inline int launch_tail(const char *what, const JpegParams &P, const Planes &planes, const short *coef, const unsigned long long *sums,
+                       const uint16_t *d_quant, uint32_t channels, uint8_t *d_out, unsigned long long bytes, uint32_t *flags, uint32_t *h_flags,
+                       size_t n_flags, hipStream_t s)
+{
+    const unsigned long long n_blocks = (unsigned long long)P.mcus * P.bpm;
+    hipLaunchKernelGGL(jpeg_idct_kernel, dim3((uint32_t)((n_blocks + WAVE - 1) / WAVE)), dim3(WAVE), 0, s, coef, P, sums, d_quant, planes, n_blocks, flags);
+    const uint32_t lead = (uint32_t)std::min<unsigned long long>(bytes, (4 - (reinterpret_cast<uintptr_t>(d_out) & 3u)) & 3u);
+    const unsigned long long lanes = (bytes - lead) / 4 + lead + (bytes - lead) % 4;
+    hipLaunchKernelGGL(jpeg_pixels_kernel, dim3((uint32_t)((lanes + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, s, P, planes, channels, d_out, bytes, lead, flags);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(h_flags, flags, n_flags * sizeof(uint32_t), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    return e == hipSuccess ? CVHIP_OK : device_error(what, e);
+}
+
+// the pixels into the caller's array, once the flags say that they are good
+inline int deliver(const char *what, CallScratch &sc, uint8_t *out, const uint8_t *d_out, unsigned long long bytes, hipStream_t s)
+{
+    hipError_t e = sc.copy_out(out, d_out, (size_t)bytes, s);
+    if (e == hipSuccess) e = sc.drain(s);
+    return e == hipSuccess ? CVHIP_OK : device_error(what, e);
 }

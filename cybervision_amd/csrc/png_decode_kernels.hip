@@ -732,8 +732,6 @@ __global__ __launch_bounds__(BLOCK) void png_convert_kernel(const uint8_t *__res
 
 thread_local uint64_t t_stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 
-int refused(const char *what, int code, const char *why) { return fail(code == pd::UNSUPPORTED ? CVHIP_ERR_UNSUPPORTED : CVHIP_ERR_INVALID, std::string(what) + ": " + why); }
-
 int file_error(uint32_t err)
 {
     const char *why = err & ERR_CRC       ? "an IDAT chunk's CRC"
@@ -760,7 +758,7 @@ extern "C" int cvhip_png_info(const uint8_t *file, uint64_t size, uint32_t *out_
     if (!file || !out_info) return fail(CVHIP_ERR_INVALID, "png_info: null argument");
     pd::Header h;
     const int rc = pd::parse(file, (size_t)size, h);
-    if (rc != pd::OK) return refused("png_info", rc, h.error);
+    if (rc != pd::OK) return refused("png_info", rc == pd::UNSUPPORTED, h.error);
     out_info[0] = h.width, out_info[1] = h.height, out_info[2] = h.colour, out_info[3] = h.depth, out_info[4] = h.interlace;
     out_info[5] = (uint32_t)h.idat.size(), out_info[6] = h.focal_length_35mm, out_info[7] = h.flags;
     return CVHIP_OK;
@@ -780,7 +778,7 @@ extern "C" int cvhip_png_decode(cvhip_device *dev, const uint8_t *file, uint64_t
     if (format != CVHIP_IMAGE_LUMA8 && format != CVHIP_IMAGE_RGB8) return fail(CVHIP_ERR_INVALID, "png_decode: format is not CVHIP_IMAGE_LUMA8 or CVHIP_IMAGE_RGB8");
     pd::Header h;
     const int rc = pd::parse(file, (size_t)size, h);
-    if (rc != pd::OK) return refused("png_decode", rc, h.error);
+    if (rc != pd::OK) return refused("png_decode", rc == pd::UNSUPPORTED, h.error);
     if (drop_rows >= h.height) return fail(CVHIP_ERR_INVALID, "png_decode: drop_rows leaves no row");
     const uint32_t channels = format == CVHIP_IMAGE_RGB8 ? 3u : 1u;
     const unsigned long long bytes = (unsigned long long)h.width * (h.height - drop_rows) * channels;
@@ -812,18 +810,13 @@ extern "C" int cvhip_png_decode(cvhip_device *dev, const uint8_t *file, uint64_t
     CVHIP_TRY_HIP(hipSetDevice(dev->d.ordinal));
     hipStream_t s = dev->d.stream;
     CallScratch sc;
-    size_t arena_bytes = 0; // one allocation, carved
-    auto reserve = [&](size_t nbytes) {
-        const size_t at = arena_bytes;
-        arena_bytes += (nbytes + 255) / 256 * 256;
-        return at;
-    };
+    Carver carve; // one allocation, carved
     const size_t pad = 32;
-    const size_t at_blob = reserve(blob.size() + pad), at_status = reserve(sizeof(Status)), at_win = reserve((size_t)max_windows * WIN_WORDS * 8);
-    const size_t at_entry = reserve((size_t)max_records * 8), at_count = reserve(((size_t)max_records + 1) * 8);
-    const size_t at_raw = reserve((size_t)P.filtered), at_src = reserve((size_t)P.filtered * 4 * 2);
+    const size_t at_blob = carve.reserve(blob.size() + pad), at_status = carve.reserve(sizeof(Status)), at_win = carve.reserve((size_t)max_windows * WIN_WORDS * 8);
+    const size_t at_entry = carve.reserve((size_t)max_records * 8), at_count = carve.reserve(((size_t)max_records + 1) * 8);
+    const size_t at_raw = carve.reserve((size_t)P.filtered), at_src = carve.reserve((size_t)P.filtered * 4 * 2);
     uint8_t *arena = nullptr, *d_out = nullptr;
-    hipError_t e = sc.alloc(&arena, arena_bytes);
+    hipError_t e = sc.alloc(&arena, carve.total);
     if (e == hipSuccess) e = sc.output(out, (size_t)bytes, &d_out);
     if (e != hipSuccess) return device_error("png_decode", e);
     uint8_t *d_blob = arena + at_blob, *raw = arena + at_raw;

@@ -322,8 +322,6 @@ __global__ __launch_bounds__(BLOCK) void tiff_convert_kernel(const uint8_t *__re
 
 thread_local uint64_t t_stats[4] = {0, 0, 0, 0}; // of the thread's last decode: strips, LZW codes read, Clears met, the longest string
 
-int refused(const char *what, int code, const char *why) { return fail(code == tc::UNSUPPORTED ? CVHIP_ERR_UNSUPPORTED : CVHIP_ERR_INVALID, std::string(what) + ": " + why); }
-
 } // namespace
 } // namespace cvhip
 
@@ -334,7 +332,7 @@ extern "C" int cvhip_tiff_info(const uint8_t *file, uint64_t size, uint32_t *out
     if (!file || !out_info || !out_scale) return fail(CVHIP_ERR_INVALID, "tiff_info: null argument");
     tc::Header h;
     const int rc = tc::parse(file, (size_t)size, h);
-    if (rc != tc::OK) return refused("tiff_info", rc, h.error);
+    if (rc != tc::OK) return refused("tiff_info", rc == tc::UNSUPPORTED, h.error);
     out_info[0] = h.width, out_info[1] = h.height, out_info[2] = h.samples, out_info[3] = h.bits, out_info[4] = h.compression;
     out_info[5] = h.photometric, out_info[6] = h.predictor, out_info[7] = (uint32_t)h.strips.size(), out_info[8] = h.rows_per_strip;
     out_info[9] = h.focal_length_35mm, out_info[10] = h.databar_height, out_info[11] = (h.sem ? 1u : 0u) | (h.have_tilt ? 2u : 0u);
@@ -356,7 +354,7 @@ extern "C" int cvhip_tiff_decode(cvhip_device *dev, const uint8_t *file, uint64_
     if (format != CVHIP_IMAGE_LUMA8 && format != CVHIP_IMAGE_RGB8) return fail(CVHIP_ERR_INVALID, "tiff_decode: format is not CVHIP_IMAGE_LUMA8 or CVHIP_IMAGE_RGB8");
     tc::Header h;
     const int rc = tc::parse(file, (size_t)size, h);
-    if (rc != tc::OK) return refused("tiff_decode", rc, h.error);
+    if (rc != tc::OK) return refused("tiff_decode", rc == tc::UNSUPPORTED, h.error);
     if (drop_rows == CVHIP_TIFF_DROP_DATABAR) drop_rows = h.databar_height;
     if (drop_rows >= h.height) return fail(CVHIP_ERR_INVALID, "tiff_decode: drop_rows leaves no row");
     const uint32_t channels = format == CVHIP_IMAGE_RGB8 ? 3u : 1u;
@@ -384,15 +382,10 @@ extern "C" int cvhip_tiff_decode(cvhip_device *dev, const uint8_t *file, uint64_
     CallScratch sc;
     const size_t raw_bytes = (size_t)h.row_bytes * h.height; // the decompressed rows, or the rows with Predictor 2 undone
     const bool need_raw = P.compressed || P.predictor == 2;
-    size_t arena_bytes = 0;
-    auto reserve = [&](size_t nbytes) {
-        const size_t at = arena_bytes;
-        arena_bytes += (nbytes + 255) / 256 * 256;
-        return at;
-    };
-    const size_t at_blob = reserve(blob.size()), at_flags = reserve(FLAGS * sizeof(uint32_t)), at_raw = reserve(need_raw ? raw_bytes : 0);
+    Carver carve;
+    const size_t at_blob = carve.reserve(blob.size()), at_flags = carve.reserve(FLAGS * sizeof(uint32_t)), at_raw = carve.reserve(need_raw ? raw_bytes : 0);
     uint8_t *arena = nullptr, *d_out = nullptr;
-    hipError_t e = sc.alloc(&arena, arena_bytes);
+    hipError_t e = sc.alloc(&arena, carve.total);
     if (e == hipSuccess) e = sc.output(out, (size_t)bytes, &d_out);
     if (e != hipSuccess) return device_error("tiff_decode", e);
     uint32_t *flags = reinterpret_cast<uint32_t *>(arena + at_flags), h_flags[FLAGS] = {0, 0, 0, 0};

@@ -1,7 +1,8 @@
 // cybervision_amd/csrc/jpeg_common.hpp on the CPU, built with AddressSanitizer and UBSan by tests/test_jpeg_host_cpu.py:
-//   jpeg_host parse FILE            one line of JSON: the return code and, when it is 0, what the parser found
+//   jpeg_host parse FILE            one line of JSON: the return code and, when it is 0, what the parser found, else the reason
 //   jpeg_host fuzz FILE SEED FLIPS  the parser over every truncation of the file and over FLIPS seeded corruptions of
-//                                   it; prints how often each code came back
+//                                   it; prints a CRC over every case's code and reason in order, then on the last line
+//                                   how often each code came back
 #include <cstdio>
 #include <cstdlib>
 #include <fstream>
@@ -54,7 +55,7 @@ int main(int argc, char **argv)
         jc::Header h;
         const int rc = run(data, h, lut);
         if (rc != jc::OK) {
-            std::printf("{\"code\": %d}\n", rc);
+            std::printf("{\"code\": %d, \"reason\": \"%s\"}\n", rc, h.error);
             return 0;
         }
         std::printf("{\"code\": 0, \"width\": %u, \"height\": %u, \"components\": %u, \"hmax\": %u, \"vmax\": %u, \"mcus_x\": %u, \"mcus_y\": %u, "
@@ -81,10 +82,12 @@ int main(int argc, char **argv)
             return (uint32_t)(state >> 33);
         };
         int counts[3] = {0, 0, 0};
+        std::string reasons; // "code:reason\n" of every case
         auto tally = [&](const std::vector<uint8_t> &bytes) {
             jc::Header h;
             const int rc = run(bytes, h, lut);
             if (rc != jc::OK && rc != jc::INVALID && rc != jc::UNSUPPORTED) std::abort();
+            reasons += std::to_string(rc) + ":" + h.error + "\n";
             counts[rc == jc::OK ? 0 : rc == jc::INVALID ? 1 : 2]++;
         };
         for (size_t cut = 0; cut < data.size(); cut++) tally(std::vector<uint8_t>(data.begin(), data.begin() + (long)cut));
@@ -98,7 +101,7 @@ int main(int argc, char **argv)
             }
             tally(bytes);
         }
-        std::printf("%d %d %d\n", counts[0], counts[1], counts[2]);
+        std::printf("reasons %u\n%d %d %d\n", crc32(reinterpret_cast<const uint8_t *>(reasons.data()), reasons.size()), counts[0], counts[1], counts[2]);
         return 0;
     }
     return 2;

@@ -1,9 +1,11 @@
 // cybervision_amd/csrc/jpeg_prog_common.hpp on the CPU, built with AddressSanitizer and UBSan by tests/test_jpeg_prog_host_cpu.py:
 //   jpeg_prog_host parse FILE            one line of JSON: the return code and, when the walk accepts the file, the frame, the
 //                                        scan list with its lookups and intervals, and the entropy decode of every interval in
-//                                        launch order (decode_interval, the device lane's text): its code and the block store
+//                                        launch order (decode_interval, the device lane's text): its code and the block store;
+//                                        else the walk's reason
 //   jpeg_prog_host fuzz FILE SEED FLIPS  the same over every truncation of the file and over FLIPS seeded corruptions of it;
-//                                        prints how often each code came back
+//                                        prints a CRC over every case's code and reason in order, then on the last line how
+//                                        often each code came back
 #include <cstdio>
 #include <cstdlib>
 #include <fstream>
@@ -95,7 +97,7 @@ int main(int argc, char **argv)
         Result r;
         const int rc = run(data, r, (size_t)1 << 25);
         if (rc != jp::OK) {
-            std::printf("{\"code\": %d}\n", rc);
+            std::printf("{\"code\": %d, \"reason\": \"%s\"}\n", rc, r.f.error);
             return 0;
         }
         const jp::Frame &F = r.f.frame;
@@ -142,11 +144,13 @@ int main(int argc, char **argv)
             return (uint32_t)(state >> 33);
         };
         int counts[3] = {0, 0, 0};
+        std::string reasons; // "code:reason\n" of every case (the walk's reason: none where only the entropy decode refuses)
         auto tally = [&](const std::vector<uint8_t> &bytes) {
             Result r;
             int rc = run(bytes, r, (size_t)1 << 16);
             if (rc == jp::OK) rc = r.decode;
             if (rc != jp::OK && rc != jp::INVALID && rc != jp::UNSUPPORTED) std::abort();
+            reasons += std::to_string(rc) + ":" + r.f.error + "\n";
             counts[rc == jp::OK ? 0 : rc == jp::INVALID ? 1 : 2]++;
         };
         for (size_t cut = 0; cut < data.size(); cut++) tally(std::vector<uint8_t>(data.begin(), data.begin() + (long)cut));
@@ -160,7 +164,7 @@ int main(int argc, char **argv)
             }
             tally(bytes);
         }
-        std::printf("%d %d %d\n", counts[0], counts[1], counts[2]);
+        std::printf("reasons %u\n%d %d %d\n", crc32(reinterpret_cast<const uint8_t *>(reasons.data()), reasons.size()), counts[0], counts[1], counts[2]);
         return 0;
     }
     return 2;

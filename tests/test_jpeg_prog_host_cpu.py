@@ -91,3 +91,21 @@ def test_truncations_and_corruptions(exe, tmp_path, name):
     assert invalid >= data.index(b"\xff\xda") - 1   # every cut in front of the first scan
     assert unsupported > 0                          # a cut behind a whole scan leaves an incomplete progression
     assert ok > 0
+
+
+def test_refusals_are_the_recorded_ones(exe, tmp_path):
+    """Code and reason of every refused scene, and a CRC over the code and reason of every truncation and corruption in order,
+    are those the walk gave before the two decoders shared it (tests/golden/jpeg_walk_reasons.json): a file with several
+    defects is still refused for the same one."""
+    golden = json.loads((ROOT / "tests" / "golden" / "jpeg_walk_reasons.json").read_text())["progressive"]
+    scenes = jpeg_prog_scenes.refused()
+    assert sorted(scenes) == sorted(golden["refused"])
+    for name, (data, _) in sorted(scenes.items()):
+        (tmp_path / "in.jpg").write_bytes(data)
+        got = json.loads(_run(exe, "parse", tmp_path / "in.jpg"))
+        assert [got["code"], got.get("reason", "")] == golden["refused"][name], name
+    for name, crc in sorted(golden["fuzz"].items()):
+        (tmp_path / "in.jpg").write_bytes(jpeg_prog_scenes.scene(name))
+        res = subprocess.run([str(exe), "fuzz", str(tmp_path / "in.jpg"), "7", "400"], capture_output=True, text=True, timeout=300)
+        assert res.returncode == 0, (res.stdout + res.stderr)[-4000:]
+        assert res.stdout.strip().splitlines()[-2] == "reasons %d" % crc, name
