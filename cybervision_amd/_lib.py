@@ -161,6 +161,10 @@ SIGNATURES = {
     "cvhip_tiff_info": (C.c_int, [_vp, C.c_uint64, _vp, _vp]),
     "cvhip_tiff_decode": (C.c_int, [_vp, _vp, C.c_uint64, _u32, _u32, _vp, C.c_uint64, C.POINTER(C.c_uint64)]),
     "cvhip_tiff_last_stats": (C.c_int, [_vp]),
+    # Deflate and tiled TIFF files in: (file, size, out_info[16], out_scale[3]); cvhip_tiff_decode's arguments; (out_stats[12])
+    "cvhip_tiff_ext_info": (C.c_int, [_vp, C.c_uint64, _vp, _vp]),
+    "cvhip_tiff_ext_decode": (C.c_int, [_vp, _vp, C.c_uint64, _u32, _u32, _vp, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "cvhip_tiff_ext_last_stats": (C.c_int, [_vp]),
     # PNG files in: (file, size, out_info[8]); (file, size, format, drop_rows, out, cap, out_size); (out_stats[8])
     "cvhip_png_info": (C.c_int, [_vp, C.c_uint64, _vp]),
     "cvhip_png_decode": (C.c_int, [_vp, _vp, C.c_uint64, _u32, _u32, _vp, C.c_uint64, C.POINTER(C.c_uint64)]),

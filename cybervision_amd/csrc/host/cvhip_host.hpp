@@ -918,6 +918,33 @@ inline std::vector<uint8_t> tiff_decode(GpuDevice &dev, const uint8_t *file, uin
     });
 }
 
+// ---- TIFF, Deflate strips and tiled layout: a superset of tiff_info / tiff_decode, which answer as they always did
+struct TiffExtInfo : TiffInfo {                                 // of a tiled file strips is the number of tiles, rows_per_strip TileLength
+    uint32_t tile_width = 0, tile_length = 0, tiles_across = 0; // all 0: strips
+};
+
+inline TiffExtInfo tiff_ext_info(const uint8_t *file, uint64_t size)
+{
+    uint32_t v[16] = {0};
+    float s[3] = {0.0f, 0.0f, 0.0f};
+    check(cvhip_tiff_ext_info(file, size, v, s), "cvhip_tiff_ext_info");
+    TiffExtInfo info;
+    info.width = v[0], info.height = v[1], info.samples = v[2], info.bits = v[3], info.compression = v[4], info.photometric = v[5];
+    info.predictor = v[6], info.strips = v[7], info.rows_per_strip = v[8], info.focal_length_35mm = v[9], info.databar_height = v[10];
+    info.sem = (v[11] & 1u) != 0, info.has_tilt_angle = (v[11] & 2u) != 0;
+    info.scale[0] = s[0], info.scale[1] = s[1], info.tilt_angle = s[2];
+    info.tile_width = v[12], info.tile_length = v[13], info.tiles_across = v[14];
+    return info;
+}
+
+// as tiff_decode, of a file that may hold Deflate streams or tiles
+inline std::vector<uint8_t> tiff_ext_decode(GpuDevice &dev, const uint8_t *file, uint64_t size, Format format = Format::Luma8, uint32_t drop_rows = DROP_DATABAR)
+{
+    return mesh::detail::size_then_fill([&](uint8_t *dst, uint64_t cap, uint64_t *out_size) {
+        check(cvhip_tiff_ext_decode(dev.handle(), file, size, (uint32_t)format, drop_rows, dst, cap, out_size), "cvhip_tiff_ext_decode");
+    });
+}
+
 // ---- PNG: every colour type and bit depth, not interlaced; the SEM fields keep their defaults
 struct PngInfo {
     uint32_t width = 0, height = 0, colour_type = 0, bit_depth = 0, interlace = 0, idat_chunks = 0;

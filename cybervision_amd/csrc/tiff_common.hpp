@@ -2,7 +2,9 @@
 // also compiles without HIP (tests/cpp/tiff_host.cpp runs it on the CPU under sanitizers): the walk of a classic TIFF file's
 // first IFD, the strip table, EXIF's FocalLengthIn35mmFilm and the SEM text block of tag 34683 / 34682
 // (src/reconstruction.rs:80-144).  tests/ref_tiff.py is the definition, check for check in the same order; every read is
-// bounded by the file's size.
+// bounded by the file's size.  parse(.., extended = true) is the walk of cvhip_tiff_ext_info / cvhip_tiff_ext_decode (tiff_ext_kernels.hip,
+// DESIGN.md 4.23; tests/ref_tiff_ext.py is its definition): Deflate (8 and 32946) and tiles (tags 322 to 325) are taken too, a
+// tile being a stream of TileLength rows of TileWidth pixels; without the flag every file gets the answer it always got.
 #pragma once
 
 #include <cstddef>
@@ -15,16 +17,18 @@
 namespace tiff_common {
 
 constexpr int OK = 0, INVALID = -1, UNSUPPORTED = -3; // (CVHIP_OK, CVHIP_ERR_INVALID, CVHIP_ERR_UNSUPPORTED)
-constexpr uint32_t COMPRESSION_NONE = 1, COMPRESSION_LZW = 5, COMPRESSION_PACKBITS = 32773;
+constexpr uint32_t COMPRESSION_NONE = 1, COMPRESSION_LZW = 5, COMPRESSION_PACKBITS = 32773, COMPRESSION_DEFLATE = 8, COMPRESSION_DEFLATE_OLD = 32946;
 
 struct Strip {
     uint32_t offset = 0, count = 0, rows = 0; // the bytes file[offset .. offset + count) hold `rows` rows
+    uint32_t row_bytes = 0, x = 0, y = 0;     // of `row_bytes` bytes each (a tile's rows are whole); its top-left sample is pixel (x, y)
 };
 struct Header {
     uint32_t width = 0, height = 0, samples = 0, bits = 0, compression = 1, photometric = 0, predictor = 1, rows_per_strip = 0;
     uint32_t focal_length_35mm = 0; // 0 = none
     uint32_t databar_height = 0;
     uint64_t row_bytes = 0;
+    uint32_t tile_width = 0, tile_length = 0, tiles_across = 0, tiles_down = 0; // all 0: strips
     bool little = true, sem = false, have_tilt = false;
     float scale[2] = {1.0f, 1.0f}, tilt_angle = 0.0f;
     std::vector<Strip> strips;
@@ -169,7 +173,7 @@ inline int refuse(Header &h, int code, const char *why)
 }
 
 // The first IFD of data[0 .. n) -> OK, INVALID or UNSUPPORTED (h.error says why).
-inline int parse(const uint8_t *data, size_t n, Header &h)
+inline int parse(const uint8_t *data, size_t n, Header &h, bool extended = false)
 {
     if (n < 8) return refuse(h, INVALID, "truncated header");
     const bool little = data[0] == 'I' && data[1] == 'I', big = data[0] == 'M' && data[1] == 'M';
@@ -191,7 +195,7 @@ inline int parse(const uint8_t *data, size_t n, Header &h)
         uint32_t kind = 0, count = 0;
         size_t where = 0;
     };
-    Value scalars[9], arrays[5], sem[2]; // sem: 34682, 34683
+    Value scalars[9], arrays[5], sem[2], tile[4]; // sem: 34682, 34683; tile: 322 .. 325, read by the extended walk only
     bool tiles = false;
     for (uint32_t k = 0; k < entries; k++) {
         const size_t at = (size_t)ifd + 2 + 12 * (size_t)k;
@@ -207,6 +211,7 @@ inline int parse(const uint8_t *data, size_t n, Header &h)
             if (SCALARS[i] == tag) slot = &scalars[i], scalar = true;
         for (int i = 0; i < 5; i++)
             if (ARRAYS[i] == tag) slot = &arrays[i];
+        if (extended && tag >= 322 && tag <= 325) slot = &tile[tag - 322], scalar = tag <= 323;
         if (!slot || slot->present) continue;
         if ((kind != 3 && kind != 4) || count == 0 || (scalar && count != 1)) return refuse(h, INVALID, "a tag's type or count");
         const uint64_t total = (uint64_t)(kind == 3 ? 2 : 4) * count;
@@ -226,8 +231,10 @@ inline int parse(const uint8_t *data, size_t n, Header &h)
         return false;
     };
     const Value &bits = arrays[0], &offsets = arrays[1], &counts = arrays[2], &formats = arrays[4];
-    if (tiles) return refuse(h, UNSUPPORTED, "tiles");
-    if (!has(256) || !has(257) || !has(262) || !offsets.present) return refuse(h, INVALID, "a required tag is missing");
+    if (tiles && !extended) return refuse(h, UNSUPPORTED, "tiles");
+    if (tiles && (offsets.present || counts.present)) return refuse(h, INVALID, "strip tags and tile tags");
+    if (!has(256) || !has(257) || !has(262) || !(tiles ? tile[0].present && tile[1].present && tile[2].present : offsets.present))
+        return refuse(h, INVALID, "a required tag is missing");
     const uint32_t width = scalar_of(256, 0), height = scalar_of(257, 0);
     if (width == 0 || height == 0) return refuse(h, INVALID, "width or height 0");
     if (width >= 65536 || height >= 65536) return refuse(h, UNSUPPORTED, "a dimension of 65536 or more");
@@ -252,34 +259,60 @@ inline int parse(const uint8_t *data, size_t n, Header &h)
     if (planar == 2) return refuse(h, UNSUPPORTED, "PlanarConfiguration 2");
     if (planar != 1) return refuse(h, INVALID, "PlanarConfiguration");
     const uint32_t compression = scalar_of(259, 1);
-    if (compression != COMPRESSION_NONE && compression != COMPRESSION_LZW && compression != COMPRESSION_PACKBITS) return refuse(h, UNSUPPORTED, "compression");
+    const bool deflate = extended && (compression == COMPRESSION_DEFLATE || compression == COMPRESSION_DEFLATE_OLD);
+    if (compression != COMPRESSION_NONE && compression != COMPRESSION_LZW && compression != COMPRESSION_PACKBITS && !deflate)
+        return refuse(h, UNSUPPORTED, "compression");
     const uint32_t predictor = scalar_of(317, 1);
     if (predictor == 3) return refuse(h, UNSUPPORTED, "Predictor 3");
     if (predictor != 1 && predictor != 2) return refuse(h, INVALID, "Predictor");
     const uint32_t photometric = scalar_of(262, 0);
     if (!((spp == 1 && photometric <= 1) || (spp >= 3 && photometric == 2))) return refuse(h, UNSUPPORTED, "photometric interpretation and samples");
-    uint32_t rps = scalar_of(278, 0xFFFFFFFFu);
-    if (rps == 0) return refuse(h, INVALID, "RowsPerStrip 0");
-    if (rps > height) rps = height;
-    const uint32_t nstrips = (height + rps - 1) / rps;
     const uint64_t row_bytes = (uint64_t)width * spp * (bps / 8);
-    if ((uint64_t)rps * row_bytes >= (1ull << 31)) return refuse(h, UNSUPPORTED, "a strip of 2^31 bytes or more");
-    if (offsets.count != nstrips) return refuse(h, INVALID, "StripOffsets count");
-    if (!counts.present && compression != COMPRESSION_NONE) return refuse(h, INVALID, "StripByteCounts is missing");
-    if (counts.present && counts.count != nstrips) return refuse(h, INVALID, "StripByteCounts count");
+    // the streams: strips of rps rows of the image's width, or tiles - strips of TileLength rows of TileWidth pixels, the edge
+    // tiles whole - in rows of tiles_across
+    uint32_t rps, nstrips, tile_w = 0, tile_l = 0, across = 0, down = 0;
+    uint64_t stream_row_bytes = row_bytes;
+    const Value &stream_offsets = tiles ? tile[2] : offsets, &stream_counts = tiles ? tile[3] : counts;
+    if (tiles) {
+        tile_w = item(tile[0], 0), tile_l = item(tile[1], 0);
+        if (tile_w == 0 || tile_l == 0 || tile_w % 16 || tile_l % 16) return refuse(h, UNSUPPORTED, "a tile width or length that is no multiple of 16");
+        // (the tags are LONGs: a row and a length are bounded before anything is multiplied, so that no product below wraps)
+        stream_row_bytes = (uint64_t)tile_w * spp * (bps / 8);
+        if (stream_row_bytes >= (1ull << 31) || tile_l >= (1u << 31)) return refuse(h, UNSUPPORTED, "a strip of 2^31 bytes or more");
+        across = (width + tile_w - 1) / tile_w, down = (height + tile_l - 1) / tile_l;
+        rps = tile_l, nstrips = across * down;
+    } else {
+        rps = scalar_of(278, 0xFFFFFFFFu);
+        if (rps == 0) return refuse(h, INVALID, "RowsPerStrip 0");
+        if (rps > height) rps = height;
+        nstrips = (height + rps - 1) / rps;
+    }
+    if ((uint64_t)rps * stream_row_bytes >= (1ull << 31)) return refuse(h, UNSUPPORTED, "a strip of 2^31 bytes or more");
+    if (stream_offsets.count != nstrips) return refuse(h, INVALID, "StripOffsets count");
+    if (!stream_counts.present && compression != COMPRESSION_NONE) return refuse(h, INVALID, "StripByteCounts is missing");
+    if (stream_counts.present && stream_counts.count != nstrips) return refuse(h, INVALID, "StripByteCounts count");
     h.strips.resize(nstrips);
+    uint64_t compressed = 0;
     for (uint32_t s = 0; s < nstrips; s++) {
         Strip &strip = h.strips[s];
-        strip.rows = rps < height - s * rps ? rps : height - s * rps;
-        strip.offset = item(offsets, s);
-        const uint64_t need = strip.rows * row_bytes, count = counts.present ? item(counts, s) : need;
+        if (tiles) strip.rows = rps, strip.x = s % across * tile_w, strip.y = s / across * tile_l;
+        else strip.rows = rps < height - s * rps ? rps : height - s * rps, strip.y = s * rps;
+        strip.row_bytes = (uint32_t)stream_row_bytes;
+        strip.offset = item(stream_offsets, s);
+        const uint64_t need = strip.rows * stream_row_bytes, count = stream_counts.present ? item(stream_counts, s) : need;
         if (count >= (1ull << 31)) return refuse(h, UNSUPPORTED, "a strip of 2^31 bytes or more");
         if ((uint64_t)strip.offset + count > n) return refuse(h, INVALID, "a strip reaches past the file");
         if (compression == COMPRESSION_NONE && count < need) return refuse(h, INVALID, "a strip shorter than its rows");
         if (compression == COMPRESSION_LZW && count >= 2 && data[strip.offset] == 0 && (data[strip.offset + 1] & 1u))
             return refuse(h, UNSUPPORTED, "old-style LZW");
         strip.count = (uint32_t)count;
+        compressed += count;
     }
+    // every Deflate stream is copied to an aligned place of its own: streams that share bytes could ask for any multiple of the file
+    if (deflate && compressed > n) return refuse(h, UNSUPPORTED, "Deflate: streams that overlap");
+    // inflate's source indices are 32-bit, as the PNG path's
+    if (deflate && (uint64_t)nstrips * rps * stream_row_bytes >= (1ull << 31)) return refuse(h, UNSUPPORTED, "Deflate: 2^31 decompressed bytes or more");
+    h.tile_width = tile_w, h.tile_length = tile_l, h.tiles_across = across, h.tiles_down = down;
     h.width = width, h.height = height, h.samples = spp, h.bits = bps, h.compression = compression, h.photometric = photometric;
     h.predictor = predictor, h.rows_per_strip = rps, h.row_bytes = row_bytes;
 

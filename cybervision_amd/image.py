@@ -8,8 +8,11 @@ the host walks the chunks and reads IHDR, PLTE and the eXIf chunk's focal length
 five filters and the conversion run on the device; every colour type and bit depth, alpha and tRNS dropped, the SEM fields
 keep their defaults.  Progressive JPEG (cvhip_jpeg_progressive_decode): the host walks the markers of the
 whole file and checks the progression, the entropy decode of every scan accumulates the coefficients on the device, the tail
-is the baseline path's; `load` takes it for a file whose first SOF marker is SOF2.  Adam7 PNG, Deflate and tiled TIFF, and of
-JPEG arithmetic coding, 12 bits, sequential files of several scans and incomplete progressions are not built."""
+is the baseline path's; `load` takes it for a file whose first SOF marker is SOF2.  Deflate and tiled TIFF (DESIGN.md 4.23;
+cvhip_tiff_ext_decode): the host walk also reads the tile tags, inflate runs a workgroup per strip or tile, the tiles go through
+the strip decompressors, the conversion gathers a row from its tiles; `load` takes it for a TIFF file with a tile tag or
+compression 8 / 32946.  Adam7 PNG, and of JPEG arithmetic coding, 12 bits, sequential files of several scans and incomplete
+progressions are not built."""
 from __future__ import annotations
 
 import ctypes as C
@@ -146,6 +149,53 @@ def tiff_last_stats() -> dict:
     return {"strips": int(s[0]), "codes": int(s[1]), "clears": int(s[2]), "longest": int(s[3])}
 
 
+def tiff_ext_info(data) -> dict:
+    """cvhip_tiff_ext_info of a file's bytes (host only) -> tiff_info's fields - of a tiled file strips is the number of tiles
+    and rows_per_strip TileLength - and tile_width, tile_length, tiles_across (all 0 for a strip file)."""
+    p, n, _keep = _file(data)
+    info, scale = np.zeros(16, dtype=np.uint32), np.zeros(3, dtype=np.float32)
+    _lib.check(_lib.lib().cvhip_tiff_ext_info(p, n, C.c_void_p(info.ctypes.data), C.c_void_p(scale.ctypes.data)), "cvhip_tiff_ext_info")
+    names = ("width", "height", "samples", "bits", "compression", "photometric", "predictor", "strips", "rows_per_strip")
+    out = {k: int(v) for k, v in zip(names, info)}
+    out.update(focal_length_35mm=int(info[9]) or None, databar_height=int(info[10]), sem=bool(info[11] & 1), scale=(float(scale[0]), float(scale[1])),
+               tilt_angle=float(scale[2]) if info[11] & 2 else None, tile_width=int(info[12]), tile_length=int(info[13]), tiles_across=int(info[14]))
+    return out
+
+
+def decode_tiff_ext(device, data, mode: str = "L", drop_rows=None, out=None):
+    """cvhip_tiff_ext_decode of a file's bytes, as decode_tiff: what that takes, and Deflate and tiled files."""
+    return _decode("cvhip_tiff_ext_decode", device, data, mode, TIFF_DROP_DATABAR if drop_rows is None else drop_rows, out, lambda d: tiff_ext_info(d)["width"])
+
+
+def tiff_ext_last_stats() -> dict:
+    """cvhip_tiff_ext_last_stats: of this thread's last decode - streams (strips or tiles), LZW codes read, Clear codes met, the
+    longest string; stored, fixed and dynamic deflate blocks over all streams, subsequences, the most settle rounds one window
+    needed, settle windows, rounds of the copy resolution."""
+    s = np.zeros(12, dtype=np.uint64)
+    _lib.check(_lib.lib().cvhip_tiff_ext_last_stats(C.c_void_p(s.ctypes.data)), "cvhip_tiff_ext_last_stats")
+    names = ("streams", "codes", "clears", "longest", "stored_blocks", "fixed_blocks", "dynamic_blocks", "subsequences", "settle_rounds", "settle_windows",
+             "copy_rounds")
+    return {k: int(v) for k, v in zip(names, s)}
+
+
+def _tiff_is_ext(data) -> bool:
+    """A classic TIFF file whose first IFD holds a tile tag (322 .. 325) or Compression 8 / 32946; False where the walk ends early."""
+    order = "little" if data[:2] == b"II" else "big"
+    ifd = int.from_bytes(data[4:8], order)
+    if ifd + 2 > len(data):
+        return False
+    for k in range(int.from_bytes(data[ifd:ifd + 2], order)):
+        entry = data[ifd + 2 + 12 * k:ifd + 14 + 12 * k]
+        if len(entry) < 12:
+            return False
+        tag, kind = int.from_bytes(entry[:2], order), int.from_bytes(entry[2:4], order)
+        if 322 <= tag <= 325:
+            return True
+        if tag == 259 and kind in (3, 4) and int.from_bytes(entry[8:10] if kind == 3 else entry[8:12], order) in (8, 32946):
+            return True
+    return False
+
+
 def png_info(data) -> dict:
     """cvhip_png_info of a file's bytes (host only) -> width, height, colour_type, bit_depth, interlace, idat_chunks,
     focal_length_35mm (the eXIf chunk's; None when the file has none), plte and trns (such a chunk was read)."""
@@ -199,14 +249,15 @@ class SourceImage:
 
 def load(device, path, rgb: bool = False, drop_rows=None, out=None) -> SourceImage:
     """SourceImage::load (and load_rgb with rgb=True) of a TIFF, PNG or JPEG file, told apart by the first four (TIFF) or
-    eight (PNG) bytes (anything else gets the JPEG path and its error; a JPEG file whose first SOF marker is SOF2 the progressive one).  drop_rows: the rows cut from the bottom; None - the
+    eight (PNG) bytes (a TIFF file with a tile tag or Compression 8 / 32946 gets the Deflate-and-tiles path; anything else gets the JPEG path and its error; a JPEG file whose first SOF marker is SOF2 the progressive one).  drop_rows: the rows cut from the bottom; None - the
     file's own databar_height (the DatabarHeight of a TIFF file's SEM block; 0 for PNG and JPEG).  out: None or "device", as decode_jpeg takes
     it, for img; rgb is a numpy array."""
     data = Path(path).read_bytes()
     if data[:4] in (b"II*\0", b"MM\0*"):
-        info = tiff_info(data)
-        img = decode_tiff(device, data, "L", drop_rows, out)
-        colour = decode_tiff(device, data, "RGB", drop_rows) if rgb else None
+        info_of, decode = (tiff_ext_info, decode_tiff_ext) if _tiff_is_ext(data) else (tiff_info, decode_tiff)   # every other file goes where it went
+        info = info_of(data)
+        img = decode(device, data, "L", drop_rows, out)
+        colour = decode(device, data, "RGB", drop_rows) if rgb else None
         return SourceImage(img, colour, info["focal_length_35mm"], str(path), info["scale"], info["tilt_angle"],
                            info["databar_height"] if drop_rows is None else int(drop_rows))
     drop_rows = 0 if drop_rows is None else drop_rows

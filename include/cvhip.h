@@ -781,6 +781,37 @@ int cvhip_tiff_decode(cvhip_device *dev, const uint8_t *file, uint64_t size, uin
 int cvhip_tiff_last_stats(uint64_t *out_stats);
 
 /* ------------------------------------------------------------------------------------------
+ * TIFF files in, Deflate strips and tiled layout (csrc/tiff_ext_kernels.hip, csrc/tiff_common.hpp with
+ * extended = true): the `image` crate behind image::open(path)?.into_luma8() / into_rgb8() (src/reconstruction.rs:40-60) also
+ * reads Deflate and tiled TIFF files.  These entry points take a superset of what cvhip_tiff_info / cvhip_tiff_decode take -
+ * those answer every file as they always did - and return the same pixels for a file both accept.  The pixels are DEFINED by
+ * tests/ref_tiff_ext.py.  Newly accepted: compression 8 and 32946 (every strip or tile a whole zlib stream: header, stored,
+ * fixed and dynamic blocks in any mix, the Adler-32 checked against the stream's own output; a workgroup per stream), and
+ * tiles (tags 322 to 325) with compression 1, 5, 32773, 8 and 32946, Predictor 1 or 2 (it restarts at every tile's left
+ * edge); edge tiles are stored whole, their padding is decoded and dropped.
+ * CVHIP_ERR_UNSUPPORTED, beyond cvhip_tiff_decode's list without tiles and these two compressions: a tile width or length
+ * that is 0 or no multiple of 16; a tile row, length or tile of 2^31 bytes or more; Deflate whose streams decompress (tiles
+ * padded) to 2^31 bytes or more, or whose byte counts add up to more than the file (streams that share bytes).  CVHIP_ERR_INVALID: strip tags (273, 279) beside tile tags; TileOffsets or TileByteCounts that do not hold
+ * tiles_across x tiles_down entries; a Deflate stream with a bad zlib header, block type 3, a stored block whose NLEN is not
+ * ~LEN, bad code lengths, a code that does not exist, a copy that reaches in front of its own stream's first byte, an end
+ * before the final block's end-of-block or inside the Adler-32, a wrong Adler-32, or output that is not exactly the bytes of
+ * its strip or tile - fewer or more (libtiff stops when the rows are full and reads such a file; here the checksum is
+ * always checked, so the stream has to end where the rows do).  Nothing is written on any refusal. */
+/* Host only, as cvhip_tiff_info (src/reconstruction.rs:40-60, 80-144).  out_info[16]: slots 0 .. 11 as cvhip_tiff_info's - of a
+ * tiled file slot 7 is the number of tiles and slot 8 TileLength -; 12 tile width, 13 tile length (both 0: strips), 14 tiles
+ * across, 15 zero.  out_scale[3] as cvhip_tiff_info's. */
+int cvhip_tiff_ext_info(const uint8_t *file, uint64_t size, uint32_t *out_info, float *out_scale);
+/* cvhip_tiff_decode's arguments and contract, to the letter (src/reconstruction.rs:40-60): cap = 0 sizes without writing,
+ * drop_rows = CVHIP_TIFF_DROP_DATABAR cuts the file's own DatabarHeight, out in host or device memory at any alignment. */
+int cvhip_tiff_ext_decode(cvhip_device *dev, const uint8_t *file, uint64_t size, uint32_t format, uint32_t drop_rows, uint8_t *out,
+                          uint64_t cap, uint64_t *out_size);
+/* Of the calling thread's last cvhip_tiff_ext_decode that reached the device (the streams of src/reconstruction.rs:40-60's
+ * image::open): out_stats[12] = streams (strips or tiles), LZW codes read, Clear codes met, the longest string copied, stored,
+ * fixed and dynamic deflate blocks summed over the streams, subsequences, the most settle rounds one window needed, settle
+ * windows, rounds of the copy resolution, zero. */
+int cvhip_tiff_ext_last_stats(uint64_t *out_stats);
+
+/* ------------------------------------------------------------------------------------------
  * PNG files in (csrc/png_decode_kernels.hip, csrc/png_decode_common.hpp): the third format the reference's
  * `image` crate is built with, and the one this library writes (cvhip_png_encode).  The host walks the chunks, checks the CRC
  * of every chunk that is not an IDAT and reads IHDR, PLTE and eXIf; inflate, the IDAT CRCs, the Adler-32, the five filters
