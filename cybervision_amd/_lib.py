@@ -68,6 +68,8 @@ SIGNATURES = {
     "cvhip_ctx_get_box_counters": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.c_int]),
     "cvhip_ctx_set_box_fold": (C.c_int, [_vp, C.c_int]),
     "cvhip_ctx_get_box_fold_counters": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.c_int]),
+    "cvhip_ctx_set_row_lines": (C.c_int, [_vp, C.c_int]),
+    "cvhip_ctx_get_row_lines_used": (C.c_int, [_vp, C.POINTER(C.c_int)]),
     "cvhip_ctx_set_range_mode": (C.c_int, [_vp, C.c_int]),
     "cvhip_ctx_set_exact_scores": (C.c_int, [_vp, C.c_int]),
     "cvhip_ctx_set_async_readback": (C.c_int, [_vp, C.c_int]),

@@ -264,6 +264,17 @@ class PointCorrelations:
         _lib.check(_lib.lib().cvhip_ctx_get_box_fold_counters(self._h, arr, int(reset)), "cvhip_ctx_get_box_fold_counters")
         return {"union_steps": arr[0], "folded_steps": arr[1], "pairs_ascending": arr[2], "pairs_descending": arr[3]}
 
+    def set_row_lines(self, on: bool):
+        """cvhip_ctx_set_row_lines: the lean box walk along x takes its epipolar lines from a per-row table where they
+        cannot differ along a row (default on; results are identical either way)."""
+        _lib.check(_lib.lib().cvhip_ctx_set_row_lines(self._h, int(on)), "cvhip_ctx_set_row_lines")
+
+    def get_row_lines_used(self):
+        """cvhip_ctx_get_row_lines_used: (forward, reverse) - whether the direction's last box launch used the row table."""
+        arr = (C.c_int * 2)()
+        _lib.check(_lib.lib().cvhip_ctx_get_row_lines_used(self._h, arr), "cvhip_ctx_get_row_lines_used")
+        return bool(arr[0]), bool(arr[1])
+
     def set_borrow_inputs(self, borrow: bool):
         """Device-resident level images are used in place (no copy): the caller guarantees 64 readable bytes after
         the last pixel of each and keeps them unchanged until the call's work has completed (include/cvhip.h)."""

@@ -293,11 +293,38 @@
     ps.e.cx = ps.e.cy = ps.e.ax = ps.e.ay = 0.0;
     ps.e.ox = ps.e.oy = 0;
     ps.r0 = ps.r1 = 0;
-    const bool active = is_out && pixel_setup(p, x, y, stats1, range, ps);
+    // Lean plan, lanes along x, CorrParams::row_lines: a wave is one image row, and everything the setup below derives from
+    // the epipolar line is the row's - it arrives as the row's table entry (RowLine; written by this pass's
+    // search_range_kernel with row_line_of), wave-uniform, and no lane evaluates a line.  Per pixel: the interval, the
+    // statistics word and the validity tests.
+    constexpr bool ROWS = !STEP && !TR;
+    const bool rows = ROWS && p.row_lines != 0;
+    [[maybe_unused]] uint32_t row_m0 = 0u, row_flags = 0u; // (y is the wave's: scalar loads)
+    [[maybe_unused]] bool row_mismatch = false; // (counting instantiations: a lane's own evaluation differs from the table)
+    bool active;
+    if (rows) {
+        if (y < p.row1) {
+            row_m0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)row_table[y].m0);
+            row_flags = (uint32_t)__builtin_amdgcn_readfirstlane((int)row_table[y].flags);
+        }
+        active = is_out && pixel_setup_row(p, x, y, stats1, range, (row_flags & RL_FINITE) != 0u, ps);
+        if constexpr (COUNT && ROWS) {
+            // every lane re-derives its row's entry from ITS pixel's line and interval: any difference poisons the candidate
+            // count (as a missed bracket of the stepped walk does), so every test that compares counts checks the table
+            if (x < p.w1 && y < p.row1) {
+                const RowLine own = row_line_of(p, epipolar_line(p, x, y), active ? ps.r0 : (uint32_t)KERNEL_SIZE);
+                const RowLine tab = row_table[y];
+                row_mismatch = own.m0 != tab.m0 || own.flags != tab.flags || __double_as_longlong(own.ay) != __double_as_longlong(tab.ay);
+            }
+            if (counters && __any(row_mismatch) && lane == 0) atomicAdd(&counters[0], 1ull << 44);
+        }
+    } else {
+        active = is_out && pixel_setup(p, x, y, stats1, range, ps);
+    }
     const Line &e = ps.e;
     const uint32_t r0 = ps.r0, r1 = ps.r1;
     const int cs = p.corridor_size;
-    const bool major_x = e.ox == 0; // candidates advance along x (x2 == i exactly), stripes shift y
+    const bool major_x = rows || e.ox == 0; // candidates advance along x (x2 == i exactly), stripes shift y
 
     // ---- this pixel's candidate set in displacement space ---------------------------------------------------
     // rectangle [lox, lox+wx) x [loy, loy+wy): every stripe keeps its minor coordinate over the interval; or, for
@@ -312,33 +339,29 @@
     bool loose = false;
     int lox = 0, loy = 0, lox_hi = 0, loy_hi = 0;
     uint32_t wx = 0, wy = 0;
-    if (active) {
-        uint32_t m0 = 0, m0l = 0;
-        bool constant = true, consecutive = true, near = true;
+    if (rows) {
+        // the row's entry stands for the evaluation below: RL_SIMPLE is `constant && consecutive && m0 < 2^30 && cy == 0`
+        // of this row's line (one m0 - the lean plan never looks at the far end), and what is left of `sane` is the pixel's
+        // own interval (ilo <= r0 < 2^16 needs no test)
+        if (active) {
+            const uint32_t ilo = max(r0, (uint32_t)KERNEL_SIZE), ihi = min(r1, sat_sub_u32(p.w2, KERNEL_SIZE));
+            simple = (row_flags & RL_SIMPLE) != 0u && (r1 - r0) <= CW_MAX_LEN;
+            lox = (int)ilo - xi;
+            lox_hi = lox;
+            wx = ihi > ilo ? ihi - ilo : 0u;
+            loy = (int)row_m0 - (int)y;
+            loy_hi = loy;
+            wy = (uint32_t)(2 * cs + 1);
+        }
+    } else if (active) {
         // (only the minor coordinate of candidate_xy is needed: the same operations on the selected coefficients)
         const double cmn = major_x ? e.cy : e.cx, amn = major_x ? e.ay : e.ax;
         const int omn = major_x ? e.oy : e.ox;
         const double vf = cmn * (double)r0 + amn, vl = STEP ? cmn * (double)(r1 - 1) + amn : vf;
-        // Lean plan: where v - cs and v + cs share a binade (8 < v - cs, v + cs < 1e9) every v + off is exact (an integer
-        // added inside one binade), so with stripes that advance by +1 the loop below would find them consecutive from
-        // floor(v - cs), which it computes first.  All lines but those within cs rows of 16, 32, ... 2^k skip it.
-        const double vlo0 = vf - (double)cs, vhi0 = vf + (double)cs;
-        const bool closed = !STEP && omn == 1 && vlo0 > 8.0 && vhi0 < 1.0e9 && (__double2hiint(vlo0) ^ __double2hiint(vhi0)) < (1 << 20);
-        if (closed) m0 = m0l = (uint32_t)floor(vlo0);
-        else
-        for (int off = -cs; off <= cs; off++) {
-            // The lean instantiation is only launched for exactly axis-parallel lines (minor coefficient +-0): the
-            // minor coordinate (+-0 * i + add) + off then does not depend on i, so the far end need not be evaluated.
-            const double so = (double)(off * omn);
-            const uint32_t mf = f64_to_u32_sat(floor(vf + so)), ml = STEP ? f64_to_u32_sat(floor(vl + so)) : mf;
-            if (off == -cs) {
-                m0 = mf;
-                m0l = ml;
-            }
-            constant = constant && mf == ml;
-            consecutive = consecutive && mf == m0 + (uint32_t)(off + cs) && ml == m0l + (uint32_t)(off + cs);
-            near = near && mf - (m0 + (uint32_t)(off + cs)) <= 1u && ml - (m0l + (uint32_t)(off + cs)) <= 1u;
-        }
+        // (the lean plan: one floor where v - cs and v + cs share a binade, and never the far end - minor_rows)
+        const MinorRows mr = minor_rows<STEP>(vf, vl, omn, cs);
+        const uint32_t m0 = mr.m0, m0l = mr.m0l;
+        const bool constant = mr.constant, consecutive = mr.consecutive, near = mr.near;
         const uint32_t lim2 = major_x ? p.w2 : p.h2;
         const uint32_t ilo = max(r0, (uint32_t)KERNEL_SIZE), ihi = min(r1, sat_sub_u32(lim2, KERNEL_SIZE));
         const uint32_t nmaj = ihi > ilo ? ihi - ilo : 0u;
@@ -952,6 +975,22 @@
     }
     uint32_t ecount = 0;
     Line ex = e;
+    // The candidate (x | y << 16) that a contender code (stripe << 11 | i - r0) names: candidate_xy of the pixel's line.  With
+    // the row table no line is evaluated: the lane is `simple` on a row-major line with cx = 1, ax = 0, cy = +-0 - so
+    // x2 = floor(1.0 * i + 0.0) = i, and y2 = floor((+-0 * i + ay) + off) is the row of stripe off + cs at ANY i, which setup
+    // found `constant` and `consecutive` from m0 for exactly this: y2 = m0 + stripe.  Both as integers.
+    const auto cand_of = [&](uint32_t code) -> uint32_t {
+        if (rows) {
+            const uint32_t cxy = (r0 + (code & 0x7FFu)) | ((row_m0 + (code >> 11)) << 16);
+            if constexpr (COUNT && ROWS) { // (the counting instantiations evaluate the line all the same, and compare)
+                const CandXY c = candidate_xy(epipolar_line(p, x, y), r0 + (code & 0x7FFu), (int)(code >> 11) - cs);
+                if (cxy != (c.x | (c.y << 16))) row_mismatch = true;
+            }
+            return cxy;
+        }
+        const CandXY c = candidate_xy(ex, r0 + (code & 0x7FFu), (int)(code >> 11) - cs);
+        return c.x | (c.y << 16);
+    };
     if (has) {
         if (count > (uint32_t)S2_K) {
             word = CW_WHOLE << 60;
@@ -960,7 +999,7 @@
         } else if (count > 0u && !(dbg & (16 | 512))) { // (512: the contenders come from unstaged LDS)
             // Rectified instantiation: the epipolar line is not needed during the walk, so it is re-derived here (same
             // expressions, same bits) instead of living in 8 registers across it.
-            if (!STEP) {
+            if (!STEP && !rows) {
                 uint32_t xo = x, yo = y;
                 asm volatile("" : "+v"(xo), "+v"(yo));
                 ex = epipolar_line(p, xo, yo);
@@ -971,9 +1010,7 @@
             // the cell keeps is that g* to within them - a pass without scores never writes it)
             const float T0 = start_of();
             if (!p.need_scores && count == 1u && T > T0 && T - D >= (p.threshold + S2_DELTA + 3.814697265625e-6f) * k1) {
-                const uint32_t code = (uint32_t)clist & 0x7FFFu;
-                const CandXY c = candidate_xy(ex, r0 + (code & 0x7FFu), (int)(code >> 11) - cs);
-                cell = make_uint2(c.x | (c.y << 16), __float_as_uint((T - D) * __builtin_amdgcn_rcpf(k1)));
+                cell = make_uint2(cand_of((uint32_t)clist & 0x7FFFu), __float_as_uint((T - D) * __builtin_amdgcn_rcpf(k1)));
                 ecount = 0u;
             }
         }
@@ -1048,17 +1085,11 @@
     }
     const uint32_t q_base = q_incl - extras;
     for (uint32_t j = 1; j < ecount; j++) {
-        const uint32_t code = (uint32_t)(clist >> (15u * j)) & 0x7FFFu;
-        const CandXY c = candidate_xy(ex, r0 + (code & 0x7FFu), (int)(code >> 11) - cs);
         q_pix[q_base + j - 1u] = x | (y << 16);
-        q_cand[q_base + j - 1u] = c.x | (c.y << 16);
+        q_cand[q_base + j - 1u] = cand_of((uint32_t)(clist >> (15u * j)) & 0x7FFFu);
     }
     uint32_t own_cxy = 0;
-    if (ecount >= 1u) {
-        const uint32_t code = (uint32_t)clist & 0x7FFFu;
-        const CandXY c = candidate_xy(ex, r0 + (code & 0x7FFu), (int)(code >> 11) - cs);
-        own_cxy = c.x | (c.y << 16);
-    }
+    if (ecount >= 1u) own_cxy = cand_of((uint32_t)clist & 0x7FFFu);
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
@@ -1112,6 +1143,7 @@
             v3 += __shfl_down(v3, sft, 64);
         }
         if (COUNT && STEP && __any(bracket_missed) && lane == 0) atomicAdd(&counters[0], 1ull << 44);
+        if (COUNT && ROWS && __any(row_mismatch) && lane == 0) atomicAdd(&counters[0], 1ull << 44); // (a candidate off the table's row)
         if (lane == 0) {
             if (v0) atomicAdd(&counters[0], (unsigned long long)v0);
             if (v1) atomicAdd(&counters[1], (unsigned long long)v1);

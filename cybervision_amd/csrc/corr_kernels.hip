@@ -191,6 +191,62 @@ __device__ __forceinline__ uint32_t corridor_end_of(const CorrParams &p, const L
     return fabs(e.cx) > fabs(e.cy) ? sat_sub_u32(p.w2, KERNEL_SIZE) : sat_sub_u32(p.h2, KERNEL_SIZE);
 }
 
+// The minor coordinates of a pixel's 2 cs + 1 stripes at the two ends of its interval (box_body.inc's setup; mod.rs:424-429
+// with only the minor coordinate evaluated): vf, vl = (minor coefficient * i + add) at i = r0 and r1 - 1, omn = the stripes'
+// offset along the minor axis.  m0, m0l: the row (column) of stripe -cs at either end; constant: every stripe keeps its row
+// over the interval; consecutive: the stripes are the rows m0 .. m0 + 2 cs at both ends; near: or one row further.
+// closed (lean plan only): where v - cs and v + cs share a binade (8 < v - cs, v + cs < 1e9) every v + off is exact (an integer
+// added inside one binade), so with stripes that advance by +1 the loop would find them consecutive from floor(v - cs), which
+// is all that is computed then.  All lines but those within cs rows of 16, 32, ... 2^k skip the loop.
+struct MinorRows {
+    uint32_t m0, m0l;
+    bool constant, consecutive, near, closed;
+};
+template <bool STEP> __device__ __forceinline__ MinorRows minor_rows(double vf, double vl, int omn, int cs)
+{
+    MinorRows r;
+    r.m0 = r.m0l = 0u;
+    r.constant = r.consecutive = r.near = true;
+    const double vlo0 = vf - (double)cs, vhi0 = vf + (double)cs;
+    r.closed = !STEP && omn == 1 && vlo0 > 8.0 && vhi0 < 1.0e9 && (__double2hiint(vlo0) ^ __double2hiint(vhi0)) < (1 << 20);
+    if (r.closed) r.m0 = r.m0l = (uint32_t)floor(vlo0);
+    else
+    for (int off = -cs; off <= cs; off++) {
+        // The lean instantiation is only launched for exactly axis-parallel lines (minor coefficient +-0): the
+        // minor coordinate (+-0 * i + add) + off then does not depend on i, so the far end need not be evaluated.
+        const double so = (double)(off * omn);
+        const uint32_t mf = f64_to_u32_sat(floor(vf + so)), ml = STEP ? f64_to_u32_sat(floor(vl + so)) : mf;
+        if (off == -cs) {
+            r.m0 = mf;
+            r.m0l = ml;
+        }
+        r.constant = r.constant && mf == ml;
+        r.consecutive = r.consecutive && mf == r.m0 + (uint32_t)(off + cs) && ml == r.m0l + (uint32_t)(off + cs);
+        r.near = r.near && mf - (r.m0 + (uint32_t)(off + cs)) <= 1u && ml - (r.m0l + (uint32_t)(off + cs)) <= 1u;
+    }
+    return r;
+}
+
+// A row's entry of the lean box walk's row table (RowLine, CorrParams::row_lines) from the line of ONE of its pixels - the
+// host sets row_lines only where every pixel of a row gives the same entry: the pass is affine with row-major lines
+// (p.affine == 2: cx = 1, ax = 0, ox = 0, oy = 1), aff_c = +-0 and F[6] = +-0, so the line's only varying member is
+// ay = -scale (F[8] + F[7] y / scale + F[6] x / scale) / aff_div with F[6] x / scale the same signed zero for every x >= 0, and
+// the minor coordinate +-0 * i + ay is the same double (a zero of either sign aside, which no floor tells apart) for every i.
+// search_range_kernel writes the table with x = 0, r0 = KERNEL_SIZE; the counting box instantiations call this per lane, with
+// the lane's own x and r0, and compare.
+__device__ __forceinline__ RowLine row_line_of(const CorrParams &p, const Line &e, uint32_t r0)
+{
+    const int cs = p.corridor_size;
+    const double vf = e.cy * (double)r0 + e.ay;
+    const MinorRows mr = minor_rows<false>(vf, vf, e.oy, cs);
+    RowLine rl;
+    rl.ay = e.ay;
+    rl.m0 = mr.m0;
+    rl.flags = (line_finite(e) ? RL_FINITE : 0u) | (mr.constant && mr.consecutive && mr.m0 < 0x40000000u && e.cy == 0.0 ? RL_SIMPLE : 0u) |
+               (mr.closed ? RL_CLOSED : 0u) | (mr.m0 >= 1u && mr.m0 < 0x40000000u ? RL_SANE : 0u);
+    return rl;
+}
+
 // ---------------------------------------------------------------------------------------------
 // window_stats: compute_image_point_data (mod.rs:632-694) == the avg/stdev half of
 // compute_point_data (mod.rs:702-735).  stats[i] = (avg, stdev), NaN outside the 5-px border.
@@ -408,7 +464,7 @@ __device__ __forceinline__ void neighbor_window(const CorrParams &p, uint32_t x,
 // its own validity tests and corridor bounds.  (Pixels of one block on different corridor axes, possible
 // only for perspective geometry, each get their own axis' statistics.)
 __device__ __forceinline__ void search_range_body(const CorrParams &p, const uint32_t *__restrict__ prev,
-                                                  uint32_t *__restrict__ range, int mode)
+                                                  uint32_t *__restrict__ range, int mode, RowLine *__restrict__ row_table)
 {
     // chain path: raw cells of the tile's window (+ slack for the predicated row reads);
     // sum path: the same words hold FA | FB | HA | HB (see below)
@@ -422,6 +478,13 @@ __device__ __forceinline__ void search_range_body(const CorrParams &p, const uin
     const uint32_t byi = (p.row0 >> 1) + tid.y * 4 + (threadIdx.x >> 6);
     const uint32_t tile_x0 = tid.x * 128, tile_y0 = ((p.row0 >> 1) + tid.y * 4) * 2;
     if (threadIdx.x == 0) axis_vote = 0u;
+    // The row table of the box launch behind this kernel (CorrParams::row_lines): the workgroups of the first tile column
+    // write the entries of their eight rows, from the line of the row's pixel x = 0 - F[6] * x / scale is the same signed
+    // zero for every x >= 0, so every pixel of the row has this line (row_line_of).
+    if (p.row_lines && tid.x == 0 && threadIdx.x < 8u) {
+        const uint32_t y = tile_y0 + threadIdx.x - 1u; // (wraps for the row above the image: rejected)
+        if (y >= p.row0 && y < p.row1 && y < p.h1) row_table[y] = row_line_of(p, epipolar_line(p, 0u, y), (uint32_t)KERNEL_SIZE);
+    }
 
     // the (up to) four pixels of this block and their per-pixel tests (mod.rs:334-345)
     uint32_t px[4], py[4];
@@ -760,7 +823,7 @@ __device__ __forceinline__ void search_range_body(const CorrParams &p, const uin
 __global__ __launch_bounds__(256) void search_range_kernel(SearchJob ja, SearchJob jb, int mode)
 {
     const SearchJob &j = this_job();
-    search_range_body(j.p, j.prev, j.range, mode);
+    search_range_body(j.p, j.prev, j.range, mode, j.row_table);
 }
 
 static bool job_active(const SearchJob &j) { return j.p.row1 > j.p.row0; }
@@ -1011,6 +1074,24 @@ __device__ __forceinline__ bool pixel_setup(const CorrParams &p, uint32_t x, uin
     if (!(finite_f32(ps.st1.y) && !(fabsf(ps.st1.y) < p.min_stdev) && line_finite(ps.e))) return false; // :334-345
     ps.r0 = KERNEL_SIZE;
     ps.r1 = corridor_end_of(p, ps.e);
+    if (!p.first_pass) { // mod.rs:351-364
+        const uint32_t rg = range[(size_t)y * p.w1 + x];
+        if (rg == RANGE_NONE) return false;
+        ps.r0 = rg & 0xFFFFu;
+        ps.r1 = rg >> 16;
+    }
+    return ps.r0 < ps.r1;
+}
+// The same for a pass with CorrParams::row_lines, without the line (ps.e stays as it is): whether it is finite is the row's
+// (RL_FINITE of its table entry), and the corridor's end is corridor_end_of of the pass's constants - |cx| = 1 > |cy| = 0.
+__device__ __forceinline__ bool pixel_setup_row(const CorrParams &p, uint32_t x, uint32_t y, const uint2 *__restrict__ stats1,
+                                                const uint32_t *__restrict__ range, bool row_finite, PixelSetup &ps)
+{
+    if (!(x >= KERNEL_SIZE && y >= KERNEL_SIZE && x + KERNEL_SIZE < p.w1 && y + KERNEL_SIZE < p.h1)) return false;
+    ps.st1 = stats_of(stats1[(size_t)y * p.w1 + x]);
+    if (!(finite_f32(ps.st1.y) && !(fabsf(ps.st1.y) < p.min_stdev) && row_finite)) return false; // :334-345
+    ps.r0 = KERNEL_SIZE;
+    ps.r1 = sat_sub_u32(p.w2, KERNEL_SIZE);
     if (!p.first_pass) { // mod.rs:351-364
         const uint32_t rg = range[(size_t)y * p.w1 + x];
         if (rg == RANGE_NONE) return false;
@@ -1630,6 +1711,7 @@ __global__ __launch_bounds__(256, STEP ? (COUNT ? 4 : CVHIP_STEP_WAVES) : (COUNT
     uint32_t *__restrict__ const out = j.out;
     float *__restrict__ const out_score = j.out_score;
     const WorkList declined = j.declined, whole_list = j.whole;
+    [[maybe_unused]] const RowLine *__restrict__ const row_table = j.row_table;
     constexpr bool WIDE = true;
 #include "box_body.inc"
 }
@@ -1644,6 +1726,7 @@ __global__ __launch_bounds__(256, STEP ? (COUNT ? 4 : CVHIP_STEP_WAVES) : (TR ? 
     unsigned long long *__restrict__ contenders, uint32_t *__restrict__ out, float *__restrict__ out_score,
     unsigned long long *__restrict__ counters, WorkList declined, WorkList whole_list)
 {
+    [[maybe_unused]] constexpr const RowLine *row_table = nullptr; // (the stepped plans evaluate their lines per lane)
 #include "box_body.inc"
 }
 

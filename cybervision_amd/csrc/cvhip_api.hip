@@ -191,6 +191,19 @@ static size_t stats_level_offset(size_t max_px, int k)
 }
 static size_t stats_pool_elems(size_t max_px) { return stats_level_offset(max_px, 16) + 64; }
 
+// The row tables of the lean box walk (CorrParams::row_lines) live behind the work lists in cvhip_ctx::work: per direction
+// one entry per row of every level - level j has at most max_h >> j rows, below 2 max_h in all - so that a level's table
+// is never rewritten while another level's or direction's kernels may still read theirs.
+static size_t row_tables_offset_u32(size_t work_cap) { return (8 + 4 * work_cap + 3) & ~(size_t)3; } // (16-byte entries)
+static size_t row_tables_bytes(uint32_t max_h) { return 2 * (2 * (size_t)max_h + 16) * sizeof(RowLine); }
+static RowLine *row_table_of(const cvhip_ctx *c, int dir, int k)
+{
+    const uint32_t max_h = std::max(c->h1, c->h2);
+    size_t off = (size_t)dir * (2 * (size_t)max_h + 16);
+    for (int j = 0; j < k; j++) off += max_h >> j;
+    return reinterpret_cast<RowLine *>(c->work + row_tables_offset_u32(c->work_cap)) + off;
+}
+
 // The staged image of level k lives at its own offset of the per-image pool, like the statistics: a host image of level
 // k - 1 can then be uploaded (copy stream) while level k is still being searched.
 static size_t img_level_offset(size_t max_px, int k)
@@ -476,6 +489,7 @@ static int plan_pass(cvhip_ctx *c, int a, int b, uint32_t lw1, uint32_t lh1, uin
     j.whole = WorkList{wc + 1, items + c->work_cap};
     // The first pass as one workgroup per (tile, stripe): its scratch is the tail of the contender words - the level
     // uses the first lw1 x lh1 of them - where the buffer is large enough for both (any context beyond ~300^2 pixels).
+    j.row_table = row_table_of(c, dir, k);
     j.split = nullptr;
     if (first_pass) {
         const size_t own = (size_t)lw1 * lh1, need = search2_split_words(lw1, lh1, 2u * (uint32_t)c->corridor_size + 1u);
@@ -550,6 +564,12 @@ static int plan_pass(cvhip_ctx *c, int a, int b, uint32_t lw1, uint32_t lh1, uin
             // boxes up to 65 steps wide where that still leaves five workgroups per CU (160 KB of LDS), else up to 33
             p.box_wide = 128u * p.box_pd * 4u + p.box_sh * 128u * 8u <= 32u * 1024u ? 1u : 0u;
         }
+        // The lean launch with lanes along x takes its lines from the row table where they cannot depend on x: an affine F
+        // whose F[6] is a zero of either sign (F[6] * x is then that zero for every x >= 0; anything else, however small,
+        // shifts the offset along a row).  The table is written by the search range kernel in front of the launch, so a pass
+        // without one - a first pass sent here by force_box - evaluates its lines per lane.
+        if (c->row_lines && !plan.stepped && !plan.transposed && !plan.mfma && !plan.pair && !first_pass && p.affine == 2 && F[6] == 0.0)
+            p.row_lines = 1;
     }
     return CVHIP_OK;
 }
@@ -590,6 +610,7 @@ static int launch_passes(cvhip_ctx *c, PassPlan *plans, int n, bool zero_counts,
                         if (!ev) CVHIP_TRY_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
                     CVHIP_TRY_HIP(aux_stream(d, 1, &side));
                 }
+                for (int q = 0; q < m; q++) c->row_lines_used[plans[i + q].dir] = jobs[q].p.row_lines != 0;
                 bool fallbacks_out = false; // (on two streams each direction's fallback kernel follows its own box kernel)
                 CVHIP_TRY(timed(c, cvhip_ctx::K_SEARCH, [&] {
                     fallbacks_out = launch_search3_box(jobs, m, pl.stepped, pl.transposed, pl.mfma ? 1 : (pl.pair ? 2 : 0), s, side, d.box_ev[0],
@@ -953,7 +974,8 @@ int cvhip_ctx_create(cvhip_device *dev, uint32_t w1, uint32_t h1, uint32_t w2, u
         if (e == hipSuccess) e = hipMalloc(&c->range_rev, c->max_px * sizeof(uint32_t));
         if (e == hipSuccess) e = hipMalloc(&c->contenders, c->max_px * sizeof(unsigned long long));
         if (e == hipSuccess) e = hipMalloc(&c->contenders_rev, c->max_px * sizeof(unsigned long long));
-        if (e == hipSuccess) e = hipMalloc(&c->work, (8 + 4 * c->work_cap) * sizeof(uint32_t));
+        if (e == hipSuccess)
+            e = hipMalloc(&c->work, row_tables_offset_u32(c->work_cap) * sizeof(uint32_t) + row_tables_bytes(std::max(h1, h2)));
         if (e == hipSuccess) e = hipMalloc(&c->d_cand, cvhip_ctx::N_COUNTERS * sizeof(unsigned long long));
     }
     if (e == hipSuccess) e = hipMemsetAsync(c->d_cand, 0, cvhip_ctx::N_COUNTERS * sizeof(unsigned long long), dev->d.stream);
@@ -1830,6 +1852,22 @@ int cvhip_ctx_set_box_fold(cvhip_ctx *ctx, int on)
     if (!ctx) return fail(CVHIP_ERR_INVALID, "ctx is null");
     CVHIP_TRY(flush_level_calls(ctx));
     ctx->box_fold = on != 0;
+    return CVHIP_OK;
+}
+
+int cvhip_ctx_set_row_lines(cvhip_ctx *ctx, int on)
+{
+    if (!ctx) return fail(CVHIP_ERR_INVALID, "ctx is null");
+    CVHIP_TRY(flush_level_calls(ctx));
+    ctx->row_lines = on != 0;
+    return CVHIP_OK;
+}
+
+int cvhip_ctx_get_row_lines_used(cvhip_ctx *ctx, int out[2])
+{
+    if (!ctx || !out) return fail(CVHIP_ERR_INVALID, "null argument");
+    CVHIP_TRY(flush_level_calls(ctx));
+    for (int d = 0; d < 2; d++) out[d] = ctx->row_lines_used[d] ? 1 : 0;
     return CVHIP_OK;
 }
 

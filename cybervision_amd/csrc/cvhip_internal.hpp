@@ -84,7 +84,24 @@ struct CorrParams {
     // lean box walk: fold the two ends of a wave's union of displacement ranges into shared steps (box_body.inc;
     // cvhip_ctx_set_box_fold).  0: every wave walks its whole union, one step at a time.
     int box_fold;
+    // lean box walk, lanes along x (search3_box_kernel<., false, false>): 1 = the epipolar line comes from the row table that
+    // this pass's search_range_kernel wrote (SearchJob::row_table, RowLine) instead of being evaluated by every lane.  Set on
+    // the host only where the line cannot depend on x: p.affine is set and F[6] is +0.0 or -0.0 (DESIGN.md section 4.2;
+    // cvhip_ctx_set_row_lines).  0: every lane evaluates its own line.
+    int row_lines;
 };
+
+// One image row of a pass with CorrParams::row_lines: what box_body.inc's per-pixel setup derives from the epipolar line of
+// any pixel of that row.  Written by search_range_kernel with the kernels' own functions (row_line_of, corr_kernels.hip).
+struct RowLine {
+    double ay;      // Line::ay of the row's pixels (cx = 1, cy = aff_c = +-0, ax = 0, ox = 0, oy = 1 are the pass's constants)
+    uint32_t m0;    // image row of stripe -cs
+    uint32_t flags; // RL_*
+};
+constexpr uint32_t RL_FINITE = 1u; // line_finite (mod.rs:338-345)
+constexpr uint32_t RL_SIMPLE = 2u; // the stripes are the rows m0 .. m0 + 2 cs at every candidate, m0 < 2^30
+constexpr uint32_t RL_CLOSED = 4u; // ... known from the binade of v - cs and v + cs alone
+constexpr uint32_t RL_SANE = 8u;   // 1 <= m0 < 2^30: no cast of mod.rs:427-428 saturated
 
 // ---- kernel launchers (corr_kernels.hip) ----------------------------------------------------
 // tile work list shared by the kernels of one search pass (search version 3)
@@ -111,6 +128,8 @@ struct SearchJob {
     WorkList declined, whole;
     // first pass, one workgroup per (tile, stripe): search2_split_words(...) 8-byte words of scratch, or nullptr
     unsigned long long *split;
+    // this level's and direction's row table, indexed by the absolute row of the searched image (CorrParams::row_lines)
+    RowLine *row_table;
 };
 // scratch of the split first pass for a level of w x rows pixels with `stripes` stripes, in 8-byte words
 size_t search2_split_words(uint32_t w, uint32_t rows, uint32_t stripes);
@@ -583,6 +602,8 @@ struct cvhip_ctx {
     bool async_readback = false; // cvhip_ctx_set_async_readback
     bool exact_scores = false; // cvhip_ctx_set_exact_scores: every pass writes the reference's scores (tests)
     bool box_fold = true;      // cvhip_ctx_set_box_fold: the lean box walk folds the ends of a wave's union (CorrParams::box_fold)
+    bool row_lines = true;     // cvhip_ctx_set_row_lines: the lean box walk takes its epipolar lines from a row table (CorrParams::row_lines)
+    bool row_lines_used[2] = {false, false}; // per direction: the last box launch had CorrParams::row_lines (cvhip_ctx_get_row_lines_used)
     int search_version = 3; // (5: version 3 with the rectified box launches on the matrix pipe, search4_mfma_kernel - measured slower;
                             //  6: version 3 with the rectified box launches on two columns per lane, search3_box2_kernel)
     int range_mode = 0; // search_range_kernel: 0 = integer box sums + chain where needed, 1 = chain only, 2 / 3 = test hooks
@@ -590,7 +611,8 @@ struct cvhip_ctx {
     // per-direction scratch of a search pass (the two passes of a level are independent: one launch, blockIdx.z picks one)
     uint32_t *range = nullptr, *range_rev = nullptr;
     unsigned long long *contenders = nullptr, *contenders_rev = nullptr; // filter -> exact kernel hand-off, one word per searched pixel
-    uint32_t *work = nullptr;                 // tile work lists: per direction {declined n, whole n, declined scan, whole scan}, then two item arrays
+    uint32_t *work = nullptr;                 // tile work lists: per direction {declined n, whole n, declined scan, whole scan}, then two item arrays;
+                                              // behind them the row tables (row_table_of, cvhip_api.hip)
     size_t work_cap = 0;                      // items per list
     size_t max_px = 0;
 

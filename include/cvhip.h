@@ -974,6 +974,13 @@ int cvhip_ctx_set_box_fold(cvhip_ctx *ctx, int on);
  * folded with the low steps at the low lanes (ascending), out[3] pairs folded the other way (descending);
  * out[0] - out[1] == out[2] + out[3].  reset clears these four only.  Synchronises. */
 int cvhip_ctx_get_box_fold_counters(cvhip_ctx *ctx, uint64_t out[4], int reset);
+/* The lean box walk with lanes along x (exactly horizontal epipolar lines) takes its lines from a table with one entry per
+ * image row, written by the search range kernel in front of it, where the line cannot differ along a row: an affine F whose
+ * F[6] is +0.0 or -0.0.  Every other pass evaluates the line in every lane, as before; results are
+ * identical either way.  on = 1 (default) / 0: never use the table.  Takes effect with the next pass. */
+int cvhip_ctx_set_row_lines(cvhip_ctx *ctx, int on);
+/* out[0] / out[1]: 1 if the last box launch of the forward / reverse direction took its lines from the row table. */
+int cvhip_ctx_get_row_lines_used(cvhip_ctx *ctx, int out[2]);
 /* Select the search kernel: 1 = every candidate through the exact serial f32 chain, 2 = exact-integer
  * filter per candidate + exact re-evaluation of the contenders, 3 (default) = the same filter evaluated
  * as displacement-plane box sums for whole row segments where the epipolar lines keep one major axis, with 2 for
