@@ -171,6 +171,9 @@ SIGNATURES = {
     "cvhip_png_info": (C.c_int, [_vp, C.c_uint64, _vp]),
     "cvhip_png_decode": (C.c_int, [_vp, _vp, C.c_uint64, _u32, _u32, _vp, C.c_uint64, C.POINTER(C.c_uint64)]),
     "cvhip_png_last_stats": (C.c_int, [_vp]),
+    "cvhip_png_ext_info": (C.c_int, [_vp, C.c_uint64, _vp]),
+    "cvhip_png_ext_decode": (C.c_int, [_vp, _vp, C.c_uint64, _u32, _u32, _vp, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "cvhip_png_ext_last_stats": (C.c_int, [_vp]),
     # the Delaunay triangulation of a camera's points: (xy, k, out_faces, cap_faces, out_n_faces, out_stats)
     "cvhip_mesh_delaunay": (C.c_int, [_vp, _vp, C.c_uint64, _vp, C.c_uint64, C.POINTER(C.c_uint64), _vp]),
     "cvhip_mesh_delaunay_set_lane_cells": (C.c_int, [_vp, _u32]),

@@ -971,6 +971,25 @@ inline std::vector<uint8_t> png_decode(GpuDevice &dev, const uint8_t *file, uint
     });
 }
 
+// ---- PNG, Adam7 interlaced files too: what png_info / png_decode take, and interlace method 1
+inline PngInfo png_ext_info(const uint8_t *file, uint64_t size)
+{
+    uint32_t v[8] = {0};
+    check(cvhip_png_ext_info(file, size, v), "cvhip_png_ext_info");
+    PngInfo info;
+    info.width = v[0], info.height = v[1], info.colour_type = v[2], info.bit_depth = v[3], info.interlace = v[4], info.idat_chunks = v[5];
+    info.focal_length_35mm = v[6], info.plte = (v[7] & 1u) != 0, info.trns = (v[7] & 2u) != 0;
+    return info;
+}
+
+// as png_decode
+inline std::vector<uint8_t> png_ext_decode(GpuDevice &dev, const uint8_t *file, uint64_t size, Format format = Format::Luma8, uint32_t drop_rows = 0)
+{
+    return mesh::detail::size_then_fill([&](uint8_t *dst, uint64_t cap, uint64_t *out_size) {
+        check(cvhip_png_ext_decode(dev.handle(), file, size, (uint32_t)format, drop_rows, dst, cap, out_size), "cvhip_png_ext_decode");
+    });
+}
+
 // SourceImage::calibration_matrix (:164-185), row-major; focal_length_35mm 0 = none: 1
 inline std::array<double, 9> calibration_matrix(uint32_t width, uint32_t height, uint32_t focal_length_35mm)
 {

@@ -26,6 +26,11 @@
 //                        the first wave per row, skewed by one pixel per lane, `up` and `up-left` by a shuffle from the lane above
 //   png_index_kernel     colour type 3: no index beyond the PLTE
 //   png_convert_kernel   a lane per aligned dword of `out`: samples to 8 bits, palette, luma, drop_rows
+// cvhip_png_ext_decode (tests/ref_png_adam7.py) is the same body for a superset of the files: Adam7
+// interlaced ones too.  Their stream is the seven reduced images one behind the other; the last three kernels are templates
+// on ADAM7 - the unfilter launch covers the rows of all passes and a workgroup finds its pass in a table passed by value,
+// the index and convert kernels map a pixel to its pass, row and sample - and a file that is not interlaced runs the
+// <false> instantiations, which are what these kernels were before.
 // A decode from a wrong state is harmless: every read is bounded by the stream's end (32 zero bytes follow it), every step
 // consumes at least one bit, and a code that does not exist consumes one.  In the write pass, whose states are the true
 // ones, the same events are the file's errors.  Once flags[F_ERR] is set no kernel writes to `out`.
@@ -56,8 +61,29 @@ struct IdatEntry {
 
 struct PngParams {
     uint32_t width, height, colour, depth, channels, bpp, palette_entries;
-    unsigned long long row_bytes, filtered; // filtered = height x (1 + row_bytes)
+    unsigned long long row_bytes, filtered; // filtered = height x (1 + row_bytes), or the sum of that over the passes
 };
+
+// The reduced images of an Adam7 file (png_decode_common.hpp's Pass), by value in the kernel arguments: the
+// kernels of cvhip_png_ext_decode read it where the file is interlaced.  An empty pass has no rows.
+struct PassEntry {
+    uint32_t height, row_bytes, first_row, offset; // rows; bytes of one without its filter byte; first row among all passes' rows; first byte in `raw`
+};
+struct PassTable {
+    PassEntry pass[pd::ADAM7_PASSES];
+};
+// x0, y0, log2 dx and log2 dy of pass p, a nibble each (png_decode_common.hpp's ADAM7_* tables)
+constexpr uint32_t ADAM7_X0 = 0x0102040u, ADAM7_Y0 = 0x1020400u, ADAM7_LOG_DX = 0x0112233u, ADAM7_LOG_DY = 0x1122333u;
+__host__ __device__ constexpr uint32_t nibble(uint32_t table, uint32_t p) { return (table >> (4u * p)) & 15u; }
+constexpr bool nibbles_match(uint32_t table, const uint32_t (&values)[7])
+{
+    for (uint32_t p = 0; p < 7; p++)
+        if (nibble(table, p) != values[p]) return false;
+    return true;
+}
+static_assert(nibbles_match(ADAM7_X0, pd::ADAM7_X0) && nibbles_match(ADAM7_Y0, pd::ADAM7_Y0) && nibbles_match(ADAM7_LOG_DX, pd::ADAM7_LOG_DX) &&
+                  nibbles_match(ADAM7_LOG_DY, pd::ADAM7_LOG_DY),
+              "the packed Adam7 tables are png_decode_common.hpp's");
 
 // ---- the IDAT chunks' CRCs -----------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(BLOCK) void png_crc_kernel(const uint8_t *__restrict__ stream, const IdatEntry *__restrict__ table, uint32_t type_crc,
@@ -366,11 +392,23 @@ __device__ __forceinline__ void unfilter_tile(uint8_t *s_tile, uint32_t lane, bo
     }
 }
 
+// ADAM7: the grid is the rows of all passes; a workgroup finds its pass in the table (uniform: scalar compares and selects)
+// and from there on `raw`, `height` and `row_bytes` are its pass's, `first_row` counts from its pass's first row - which
+// starts a segment whatever its type, as the last row ends one: the passes' segments run side by side in the one launch.
+template <bool ADAM7>
 __global__ __launch_bounds__(UNFILTER_LANES) void png_unfilter_kernel(uint8_t *__restrict__ raw, uint32_t height, unsigned long long row_bytes, uint32_t bpp,
-                                                                      uint32_t *__restrict__ flags)
+                                                                      PassTable T, uint32_t *__restrict__ flags)
 {
     __shared__ uint8_t s_tile[(WAVE + 1) * TILE_BYTES]; // row 0: the row above the batch
-    const uint32_t first_row = blockIdx.x, tid = threadIdx.x, lane = tid & (WAVE - 1u);
+    uint32_t first_row = blockIdx.x;
+    if constexpr (ADAM7) {
+        PassEntry e = T.pass[0]; // (never empty)
+#pragma unroll
+        for (uint32_t p = 1; p < pd::ADAM7_PASSES; p++)
+            if (T.pass[p].height && blockIdx.x >= T.pass[p].first_row) e = T.pass[p];
+        raw += e.offset, height = e.height, row_bytes = e.row_bytes, first_row -= e.first_row;
+    }
+    const uint32_t tid = threadIdx.x, lane = tid & (WAVE - 1u);
     const bool worker = tid < WAVE;
     const unsigned long long stride = row_bytes + 1;
     if (flags[F_ERR] & ~ERR_FILTER) return; // (set by the kernels before this one only: the same for every lane)
@@ -434,19 +472,40 @@ __device__ __forceinline__ uint32_t sample_at(const uint8_t *__restrict__ row, u
 }
 __device__ __forceinline__ uint32_t reduce16(uint32_t v) { return (v + 128u) / 257u; }
 
-__global__ __launch_bounds__(BLOCK) void png_index_kernel(const uint8_t *__restrict__ raw, PngParams P, uint32_t *__restrict__ flags)
+// The unfiltered row (the bytes behind its filter byte) that holds pixel `pix`, and in x the pixel's place in that row.
+// ADAM7: the pass of pixel (x, y) is read off the low bits of x and y; its row and place follow from the pass's origin and steps.
+template <bool ADAM7>
+__device__ __forceinline__ const uint8_t *row_of(const uint8_t *__restrict__ raw, const PngParams &P, const PassTable &T, unsigned long long pix,
+                                                 unsigned long long &x)
+{
+    x = pix % P.width;
+    const unsigned long long y = pix / P.width;
+    if constexpr (!ADAM7) return raw + y * (P.row_bytes + 1) + 1;
+    const uint32_t xl = (uint32_t)x, yl = (uint32_t)y;
+    const uint32_t p = yl & 1u ? 6u : xl & 1u ? 5u : yl & 2u ? 4u : xl & 2u ? 3u : yl & 4u ? 2u : xl & 4u ? 1u : 0u;
+    const PassEntry e = T.pass[p];
+    x = (xl - nibble(ADAM7_X0, p)) >> nibble(ADAM7_LOG_DX, p);
+    return raw + e.offset + (unsigned long long)((yl - nibble(ADAM7_Y0, p)) >> nibble(ADAM7_LOG_DY, p)) * (e.row_bytes + 1ull) + 1;
+}
+
+// every pixel's index, of every pass: the padding bits at a row's end are no pixel's
+template <bool ADAM7>
+__global__ __launch_bounds__(BLOCK) void png_index_kernel(const uint8_t *__restrict__ raw, PngParams P, PassTable T, uint32_t *__restrict__ flags)
 {
     const unsigned long long i = (unsigned long long)blockIdx.x * BLOCK + threadIdx.x;
     if (i >= (unsigned long long)P.width * P.height) return;
-    const uint8_t *row = raw + (i / P.width) * (P.row_bytes + 1) + 1;
-    if (sample_at(row, P.depth, i % P.width) >= P.palette_entries) atomicOr(&flags[F_ERR], ERR_INDEX);
+    unsigned long long x;
+    const uint8_t *row = row_of<ADAM7>(raw, P, T, i, x);
+    if (sample_at(row, P.depth, x) >= P.palette_entries) atomicOr(&flags[F_ERR], ERR_INDEX);
 }
 
 // pixel `pix`: r | g << 8 | b << 16 | luma << 24
-__device__ __forceinline__ uint32_t pixel_at(const uint8_t *__restrict__ raw, const uint8_t *__restrict__ palette, const PngParams &P, unsigned long long pix)
+template <bool ADAM7>
+__device__ __forceinline__ uint32_t pixel_at(const uint8_t *__restrict__ raw, const uint8_t *__restrict__ palette, const PngParams &P, const PassTable &T,
+                                             unsigned long long pix)
 {
-    const unsigned long long x = pix % P.width;
-    const uint8_t *row = raw + (pix / P.width) * (P.row_bytes + 1) + 1;
+    unsigned long long x;
+    const uint8_t *row = row_of<ADAM7>(raw, P, T, pix, x);
     if (P.colour == 0 || P.colour == 4) {
         const uint32_t v = sample_at(row, P.depth, x * P.channels);
         const uint32_t g = P.depth == 16 ? reduce16(v) : P.depth == 8 ? v : v * (255u / ((1u << P.depth) - 1u));
@@ -463,17 +522,19 @@ __device__ __forceinline__ uint32_t pixel_at(const uint8_t *__restrict__ raw, co
     if (P.depth == 16 && P.colour != 3) r = reduce16(r), g = reduce16(g), b = reduce16(b), luma = reduce16(luma);
     return r | g << 8 | b << 16 | luma << 24;
 }
-__device__ __forceinline__ uint32_t result_byte(const uint8_t *__restrict__ raw, const uint8_t *__restrict__ palette, const PngParams &P, uint32_t channels,
-                                                unsigned long long at)
+template <bool ADAM7>
+__device__ __forceinline__ uint32_t result_byte(const uint8_t *__restrict__ raw, const uint8_t *__restrict__ palette, const PngParams &P, const PassTable &T,
+                                                uint32_t channels, unsigned long long at)
 {
-    if (channels == 3) return (pixel_at(raw, palette, P, at / 3) >> (8 * (uint32_t)(at % 3))) & 255u;
-    return pixel_at(raw, palette, P, at) >> 24;
+    if (channels == 3) return (pixel_at<ADAM7>(raw, palette, P, T, at / 3) >> (8 * (uint32_t)(at % 3))) & 255u;
+    return pixel_at<ADAM7>(raw, palette, P, T, at) >> 24;
 }
 
 // out[0 .. bytes): `lead` single bytes up to the first 4-byte aligned address, whole dwords, the rest single bytes - a lane
 // per dword and a lane per single byte (jpeg_pixels_kernel's layout)
-__global__ __launch_bounds__(BLOCK) void png_convert_kernel(const uint8_t *__restrict__ raw, const uint8_t *__restrict__ palette, PngParams P, uint32_t channels,
-                                                            uint8_t *__restrict__ out, unsigned long long bytes, uint32_t lead,
+template <bool ADAM7>
+__global__ __launch_bounds__(BLOCK) void png_convert_kernel(const uint8_t *__restrict__ raw, const uint8_t *__restrict__ palette, PngParams P, PassTable T,
+                                                            uint32_t channels, uint8_t *__restrict__ out, unsigned long long bytes, uint32_t lead,
                                                             const uint32_t *__restrict__ flags)
 {
     if (flags[F_ERR]) return;
@@ -482,19 +543,20 @@ __global__ __launch_bounds__(BLOCK) void png_convert_kernel(const uint8_t *__res
         const unsigned long long at = lead + 4 * t;
         uint32_t word = 0;
 #pragma unroll
-        for (uint32_t k = 0; k < 4; k++) word |= result_byte(raw, palette, P, channels, at + k) << (8 * k);
+        for (uint32_t k = 0; k < 4; k++) word |= result_byte<ADAM7>(raw, palette, P, T, channels, at + k) << (8 * k);
         *reinterpret_cast<uint32_t *>(out + at) = word;
         return;
     }
     const unsigned long long single = t - dwords, singles = bytes - 4 * dwords;
     if (single >= singles) return;
     const unsigned long long at = single < lead ? single : 4 * dwords + single;
-    out[at] = (uint8_t)result_byte(raw, palette, P, channels, at);
+    out[at] = (uint8_t)result_byte<ADAM7>(raw, palette, P, T, channels, at);
 }
 
-thread_local uint64_t t_stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+thread_local uint64_t t_stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};      // of cvhip_png_decode
+thread_local uint64_t t_ext_stats[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0}; // of cvhip_png_ext_decode: and the non-empty passes, zero
 
-int file_error(uint32_t err)
+int file_error(const std::string &name, uint32_t err, bool passes = false)
 {
     const char *why = err & ERR_CRC       ? "an IDAT chunk's CRC"
                       : err & ERR_ZLIB    ? "the zlib header"
@@ -502,56 +564,51 @@ int file_error(uint32_t err)
                       : err & ERR_LENGTHS ? "a block's code lengths"
                       : err & ERR_END     ? "the stream ends before the final block's end-of-block or inside the Adler-32"
                       : err & ERR_TOKEN   ? "a code that is not in its table, an unused symbol, or a distance before the first byte"
-                      : err & ERR_SIZE    ? "the stream does not inflate to height x (1 + row bytes) bytes"
+                      : err & ERR_SIZE    ? (passes ? "the stream does not inflate to the passes' bytes" : "the stream does not inflate to height x (1 + row bytes) bytes")
                       : err & ERR_ADLER   ? "the Adler-32"
                       : err & ERR_FILTER  ? "a filter type above 4"
                       : err & ERR_INDEX   ? "a palette index beyond the PLTE"
                                           : "more blocks than the stream has room for";
-    return fail(CVHIP_ERR_INVALID, std::string("png_decode: ") + why);
+    return fail(CVHIP_ERR_INVALID, name + ": " + why);
 }
 
-} // namespace
-} // namespace cvhip
-
-using namespace cvhip;
-
-extern "C" int cvhip_png_info(const uint8_t *file, uint64_t size, uint32_t *out_info)
+int info(const char *name, bool adam7, const uint8_t *file, uint64_t size, uint32_t *out_info)
 {
-    if (!file || !out_info) return fail(CVHIP_ERR_INVALID, "png_info: null argument");
+    if (!file || !out_info) return fail(CVHIP_ERR_INVALID, std::string(name) + ": null argument");
     pd::Header h;
-    const int rc = pd::parse(file, (size_t)size, h);
-    if (rc != pd::OK) return refused("png_info", rc == pd::UNSUPPORTED, h.error);
+    const int rc = pd::parse(file, (size_t)size, h, adam7);
+    if (rc != pd::OK) return refused(name, rc == pd::UNSUPPORTED, h.error);
     out_info[0] = h.width, out_info[1] = h.height, out_info[2] = h.colour, out_info[3] = h.depth, out_info[4] = h.interlace;
     out_info[5] = (uint32_t)h.idat.size(), out_info[6] = h.focal_length_35mm, out_info[7] = h.flags;
     return CVHIP_OK;
 }
 
-extern "C" int cvhip_png_last_stats(uint64_t *out_stats)
+// The body of cvhip_png_decode (adam7 = false, stats = t_stats) and of cvhip_png_ext_decode (adam7 = true, stats = t_ext_stats, whose slot
+// 8 is the non-empty passes).  A file that is not interlaced runs the same instantiations of the kernels through either.
+int decode(const char *name_, bool adam7, uint64_t *stats, cvhip_device *dev, const uint8_t *file, uint64_t size, uint32_t format, uint32_t drop_rows,
+           uint8_t *out, uint64_t cap, uint64_t *out_size)
 {
-    if (!out_stats) return fail(CVHIP_ERR_INVALID, "png_last_stats: null argument");
-    for (int k = 0; k < 8; k++) out_stats[k] = t_stats[k];
-    return CVHIP_OK;
-}
-
-extern "C" int cvhip_png_decode(cvhip_device *dev, const uint8_t *file, uint64_t size, uint32_t format, uint32_t drop_rows, uint8_t *out,
-                                uint64_t cap, uint64_t *out_size)
-{
-    if (!dev || !file || !out_size || (cap && !out)) return fail(CVHIP_ERR_INVALID, "png_decode: null argument");
-    if (format != CVHIP_IMAGE_LUMA8 && format != CVHIP_IMAGE_RGB8) return fail(CVHIP_ERR_INVALID, "png_decode: format is not CVHIP_IMAGE_LUMA8 or CVHIP_IMAGE_RGB8");
+    const std::string name = name_;
+    if (!dev || !file || !out_size || (cap && !out)) return fail(CVHIP_ERR_INVALID, name + ": null argument");
+    if (format != CVHIP_IMAGE_LUMA8 && format != CVHIP_IMAGE_RGB8) return fail(CVHIP_ERR_INVALID, name + ": format is not CVHIP_IMAGE_LUMA8 or CVHIP_IMAGE_RGB8");
     pd::Header h;
-    const int rc = pd::parse(file, (size_t)size, h);
-    if (rc != pd::OK) return refused("png_decode", rc == pd::UNSUPPORTED, h.error);
-    if (drop_rows >= h.height) return fail(CVHIP_ERR_INVALID, "png_decode: drop_rows leaves no row");
+    const int rc = pd::parse(file, (size_t)size, h, adam7);
+    if (rc != pd::OK) return refused(name_, rc == pd::UNSUPPORTED, h.error);
+    if (drop_rows >= h.height) return fail(CVHIP_ERR_INVALID, name + ": drop_rows leaves no row");
     const uint32_t channels = format == CVHIP_IMAGE_RGB8 ? 3u : 1u;
     const unsigned long long bytes = (unsigned long long)h.width * (h.height - drop_rows) * channels;
     *out_size = bytes;
     if (!cap) return CVHIP_OK;
-    if (cap < bytes) return fail(CVHIP_ERR_INVALID, "png_decode: the buffer is smaller than the image");
+    if (cap < bytes) return fail(CVHIP_ERR_INVALID, name + ": the buffer is smaller than the image");
     const unsigned long long n = h.idat_bytes, total_bits = n * 8, n_idat = h.idat.size();
-    if (n >= (1ull << 31)) return fail(CVHIP_ERR_UNSUPPORTED, "png_decode: IDAT data of 2^31 or more bytes");
+    if (n >= (1ull << 31)) return fail(CVHIP_ERR_UNSUPPORTED, name + ": IDAT data of 2^31 or more bytes");
     PngParams P{};
     P.width = h.width, P.height = h.height, P.colour = h.colour, P.depth = h.depth, P.channels = h.channels, P.bpp = h.bpp;
-    P.palette_entries = h.palette_entries, P.row_bytes = h.row_bytes, P.filtered = (h.row_bytes + 1) * h.height;
+    P.palette_entries = h.palette_entries, P.row_bytes = h.row_bytes, P.filtered = h.filtered;
+    const bool laced = h.interlace != 0;
+    PassTable T{}; // (all below 2^31: parse has checked the sum)
+    for (uint32_t p = 0; p < h.pass_entries; p++)
+        T.pass[p] = {h.pass[p].height, (uint32_t)h.pass[p].row_bytes, h.pass[p].first_row, (uint32_t)h.pass[p].offset};
     // ---- the one upload: the palette, the IDAT table, the IDAT payloads end to end
     const size_t table_at = sizeof(h.palette), stream_at = table_at + (size_t)n_idat * sizeof(IdatEntry);
     std::vector<uint8_t> blob(stream_at + (size_t)n);
@@ -580,7 +637,7 @@ extern "C" int cvhip_png_decode(cvhip_device *dev, const uint8_t *file, uint64_t
     uint8_t *arena = nullptr, *d_out = nullptr;
     hipError_t e = sc.alloc(&arena, carve.total);
     if (e == hipSuccess) e = sc.output(out, (size_t)bytes, &d_out);
-    if (e != hipSuccess) return device_error("png_decode", e);
+    if (e != hipSuccess) return device_error(name_, e);
     uint8_t *d_blob = arena + at_blob, *raw = arena + at_raw;
     Status *status = reinterpret_cast<Status *>(arena + at_status), h_status{};
     uint32_t *flags = status->flags, *srcs[2] = {reinterpret_cast<uint32_t *>(arena + at_src), reinterpret_cast<uint32_t *>(arena + at_src) + P.filtered};
@@ -592,7 +649,7 @@ extern "C" int cvhip_png_decode(cvhip_device *dev, const uint8_t *file, uint64_t
     e = hipMemcpyAsync(d_blob, blob.data(), blob.size(), hipMemcpyHostToDevice, s);
     if (e == hipSuccess) e = hipMemsetAsync(d_blob + blob.size(), 0, pad, s);
     if (e == hipSuccess) e = hipMemsetAsync(status, 0, sizeof(Status), s);
-    if (e != hipSuccess) return device_error("png_decode", e);
+    if (e != hipSuccess) return device_error(name_, e);
     auto read_status = [&]() {
         hipError_t r = hipGetLastError();
         if (r == hipSuccess) r = hipMemcpyAsync(&h_status, status, sizeof(Status), hipMemcpyDeviceToHost, s);
@@ -603,45 +660,87 @@ extern "C" int cvhip_png_decode(cvhip_device *dev, const uint8_t *file, uint64_t
     const uint8_t idat_name[4] = {'I', 'D', 'A', 'T'};
     hipLaunchKernelGGL(png_crc_kernel, dim3((uint32_t)n_idat), block, 0, s, d_stream, d_table, pc::crc32(idat_name, 4), flags);
     hipLaunchKernelGGL(png_chain_kernel, dim3(1), block, 0, s, words, n, win, max_windows, rec_entry, rec_count, max_records, flags, values);
-    if ((e = read_status()) != hipSuccess) return device_error("png_decode", e);
+    if ((e = read_status()) != hipSuccess) return device_error(name_, e);
     auto keep_stats = [&](uint64_t copy_rounds) {
         const uint32_t *f = h_status.flags;
-        t_stats[0] = f[F_STORED], t_stats[1] = f[F_FIXED], t_stats[2] = f[F_DYNAMIC], t_stats[3] = f[F_SUBSEQUENCES], t_stats[4] = f[F_ROUNDS];
-        t_stats[5] = f[F_WINDOWS], t_stats[6] = copy_rounds, t_stats[7] = f[F_SEGMENTS];
+        stats[0] = f[F_STORED], stats[1] = f[F_FIXED], stats[2] = f[F_DYNAMIC], stats[3] = f[F_SUBSEQUENCES], stats[4] = f[F_ROUNDS];
+        stats[5] = f[F_WINDOWS], stats[6] = copy_rounds, stats[7] = f[F_SEGMENTS];
+        if (adam7) stats[8] = h.passes, stats[9] = 0;
     };
     keep_stats(0);
-    if (h_status.flags[F_ERR]) return file_error(h_status.flags[F_ERR]);
+    if (h_status.flags[F_ERR]) return file_error(name, h_status.flags[F_ERR], laced);
     const unsigned long long n_win = h_status.flags[F_EMITTED], n_rec = h_status.flags[F_RECORDS];
-    if (n_win == 0) return file_error(ERR_SIZE); // no output at all
+    if (n_win == 0) return file_error(name, ERR_SIZE, laced); // no output at all
     launch_scan_u64(rec_count, n_rec, rec_count + n_rec, s);
     hipLaunchKernelGGL(png_write_kernel, dim3((uint32_t)n_win), block, 0, s, words, n, win, rec_entry, rec_count, n_rec, raw, srcs[0], P.filtered, flags);
     // ---- the copies: pointer doubling, a launch and one flag back per round (a chain of 2^31 copies takes 31 rounds and the one that changes nothing)
     const dim3 byte_grid((uint32_t)((P.filtered + BLOCK - 1) / BLOCK));
     uint32_t rounds = 0, from = 0;
     for (;; from ^= 1u) {
-        if (rounds > 33) return fail(CVHIP_ERR_DEVICE, "png_decode: the copies did not resolve");
+        if (rounds > 33) return fail(CVHIP_ERR_DEVICE, name + ": the copies did not resolve");
         e = hipMemsetAsync(flags + F_CHANGED, 0, sizeof(uint32_t), s);
-        if (e != hipSuccess) return device_error("png_decode", e);
+        if (e != hipSuccess) return device_error(name_, e);
         hipLaunchKernelGGL(png_resolve_kernel, byte_grid, block, 0, s, srcs[from], srcs[from ^ 1u], P.filtered, flags);
         rounds++;
-        if ((e = read_status()) != hipSuccess) return device_error("png_decode", e);
+        if ((e = read_status()) != hipSuccess) return device_error(name_, e);
         if (h_status.flags[F_ERR] || !h_status.flags[F_CHANGED]) break;
     }
     keep_stats(rounds);
-    if (h_status.flags[F_ERR]) return file_error(h_status.flags[F_ERR]);
+    if (h_status.flags[F_ERR]) return file_error(name, h_status.flags[F_ERR], laced);
     hipLaunchKernelGGL(png_gather_kernel, byte_grid, block, 0, s, raw, srcs[from ^ 1u], P.filtered, values);
     hipLaunchKernelGGL(png_finish_kernel, dim3(1), dim3(1), 0, s, d_stream, P.filtered, values, flags);
-    hipLaunchKernelGGL(png_unfilter_kernel, dim3(P.height), dim3(UNFILTER_LANES), 0, s, raw, P.height, P.row_bytes, P.bpp, flags);
-    if (P.colour == 3)
-        hipLaunchKernelGGL(png_index_kernel, dim3((uint32_t)(((unsigned long long)P.width * P.height + BLOCK - 1) / BLOCK)), block, 0, s, raw, P, flags);
+    // the grid: a workgroup per row, of every pass
+    if (laced) hipLaunchKernelGGL(png_unfilter_kernel<true>, dim3(h.pass_rows), dim3(UNFILTER_LANES), 0, s, raw, P.height, P.row_bytes, P.bpp, T, flags);
+    else hipLaunchKernelGGL(png_unfilter_kernel<false>, dim3(P.height), dim3(UNFILTER_LANES), 0, s, raw, P.height, P.row_bytes, P.bpp, T, flags);
+    const dim3 pixel_grid((uint32_t)(((unsigned long long)P.width * P.height + BLOCK - 1) / BLOCK));
+    if (P.colour == 3 && laced) hipLaunchKernelGGL(png_index_kernel<true>, pixel_grid, block, 0, s, raw, P, T, flags);
+    else if (P.colour == 3) hipLaunchKernelGGL(png_index_kernel<false>, pixel_grid, block, 0, s, raw, P, T, flags);
     const uint32_t lead = (uint32_t)std::min<unsigned long long>(bytes, (4 - (reinterpret_cast<uintptr_t>(d_out) & 3u)) & 3u);
     const unsigned long long lanes = (bytes - lead) / 4 + lead + (bytes - lead) % 4;
-    hipLaunchKernelGGL(png_convert_kernel, dim3((uint32_t)((lanes + BLOCK - 1) / BLOCK)), block, 0, s, raw, d_palette, P, channels, d_out, bytes, lead, flags);
-    if ((e = read_status()) != hipSuccess) return device_error("png_decode", e);
+    const dim3 out_grid((uint32_t)((lanes + BLOCK - 1) / BLOCK));
+    if (laced) hipLaunchKernelGGL(png_convert_kernel<true>, out_grid, block, 0, s, raw, d_palette, P, T, channels, d_out, bytes, lead, flags);
+    else hipLaunchKernelGGL(png_convert_kernel<false>, out_grid, block, 0, s, raw, d_palette, P, T, channels, d_out, bytes, lead, flags);
+    if ((e = read_status()) != hipSuccess) return device_error(name_, e);
     keep_stats(rounds);
-    if (h_status.flags[F_ERR]) return file_error(h_status.flags[F_ERR]);
+    if (h_status.flags[F_ERR]) return file_error(name, h_status.flags[F_ERR], laced);
     e = sc.copy_out(out, d_out, (size_t)bytes, s);
     if (e == hipSuccess) e = sc.drain(s);
-    if (e != hipSuccess) return device_error("png_decode", e);
+    if (e != hipSuccess) return device_error(name_, e);
     return CVHIP_OK;
+}
+
+} // namespace
+} // namespace cvhip
+
+using namespace cvhip;
+
+extern "C" int cvhip_png_info(const uint8_t *file, uint64_t size, uint32_t *out_info) { return info("png_info", false, file, size, out_info); }
+
+extern "C" int cvhip_png_last_stats(uint64_t *out_stats)
+{
+    if (!out_stats) return fail(CVHIP_ERR_INVALID, "png_last_stats: null argument");
+    for (int k = 0; k < 8; k++) out_stats[k] = t_stats[k];
+    return CVHIP_OK;
+}
+
+extern "C" int cvhip_png_decode(cvhip_device *dev, const uint8_t *file, uint64_t size, uint32_t format, uint32_t drop_rows, uint8_t *out,
+                                uint64_t cap, uint64_t *out_size)
+{
+    return decode("png_decode", false, t_stats, dev, file, size, format, drop_rows, out, cap, out_size);
+}
+
+// ---- the superset: Adam7 files too ------------------------------------------------------------------------------------
+extern "C" int cvhip_png_ext_info(const uint8_t *file, uint64_t size, uint32_t *out_info) { return info("png_ext_info", true, file, size, out_info); }
+
+extern "C" int cvhip_png_ext_last_stats(uint64_t *out_stats)
+{
+    if (!out_stats) return fail(CVHIP_ERR_INVALID, "png_ext_last_stats: null argument");
+    for (int k = 0; k < 10; k++) out_stats[k] = t_ext_stats[k];
+    return CVHIP_OK;
+}
+
+extern "C" int cvhip_png_ext_decode(cvhip_device *dev, const uint8_t *file, uint64_t size, uint32_t format, uint32_t drop_rows, uint8_t *out,
+                                    uint64_t cap, uint64_t *out_size)
+{
+    return decode("png_ext_decode", true, t_ext_stats, dev, file, size, format, drop_rows, out, cap, out_size);
 }

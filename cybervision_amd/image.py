@@ -11,8 +11,9 @@ whole file and checks the progression, the entropy decode of every scan accumula
 is the baseline path's; `load` takes it for a file whose first SOF marker is SOF2.  Deflate and tiled TIFF (DESIGN.md 4.23;
 cvhip_tiff_ext_decode): the host walk also reads the tile tags, inflate runs a workgroup per strip or tile, the tiles go through
 the strip decompressors, the conversion gathers a row from its tiles; `load` takes it for a TIFF file with a tile tag or
-compression 8 / 32946.  Adam7 PNG, and of JPEG arithmetic coding, 12 bits, sequential files of several scans and incomplete
-progressions are not built."""
+compression 8 / 32946.  Adam7 interlaced PNG (cvhip_png_ext_decode): the stream's seven reduced images are
+unfiltered side by side and interleaved by the conversion; `load` takes it for a PNG file whose IHDR says interlace method 1.
+Of JPEG arithmetic coding, 12 bits, sequential files of several scans and incomplete progressions are not built."""
 from __future__ import annotations
 
 import ctypes as C
@@ -222,6 +223,31 @@ def png_last_stats() -> dict:
     return {k: int(v) for k, v in zip(names, s)}
 
 
+def png_ext_info(data) -> dict:
+    """cvhip_png_ext_info of a file's bytes (host only) -> png_info's fields; interlace is 0 or 1 (Adam7)."""
+    p, n, _keep = _file(data)
+    info = np.zeros(8, dtype=np.uint32)
+    _lib.check(_lib.lib().cvhip_png_ext_info(p, n, C.c_void_p(info.ctypes.data)), "cvhip_png_ext_info")
+    names = ("width", "height", "colour_type", "bit_depth", "interlace", "idat_chunks")
+    out = {k: int(v) for k, v in zip(names, info)}
+    out.update(focal_length_35mm=int(info[6]) or None, plte=bool(info[7] & 1), trns=bool(info[7] & 2))
+    return out
+
+
+def decode_png_ext(device, data, mode: str = "L", drop_rows: int = 0, out=None):
+    """cvhip_png_ext_decode of a file's bytes, as decode_png: what that takes, and Adam7 interlaced files."""
+    return _decode("cvhip_png_ext_decode", device, data, mode, drop_rows, out, lambda d: png_ext_info(d)["width"])
+
+
+def png_ext_last_stats() -> dict:
+    """cvhip_png_ext_last_stats: of this thread's last decode - png_last_stats' fields, the row segments counted over all
+    passes, and passes, the non-empty ones (1 for a file that is not interlaced)."""
+    s = np.zeros(10, dtype=np.uint64)
+    _lib.check(_lib.lib().cvhip_png_ext_last_stats(C.c_void_p(s.ctypes.data)), "cvhip_png_ext_last_stats")
+    names = ("stored_blocks", "fixed_blocks", "dynamic_blocks", "subsequences", "settle_rounds", "settle_windows", "copy_rounds", "row_segments", "passes")
+    return {k: int(v) for k, v in zip(names, s)}
+
+
 def jpeg_last_stats() -> dict:
     """cvhip_jpeg_last_stats: of this thread's last decode - restart intervals, subsequences, launches of the synchronisation
     kernel, the most rounds a workgroup needed within a launch."""
@@ -249,7 +275,7 @@ class SourceImage:
 
 def load(device, path, rgb: bool = False, drop_rows=None, out=None) -> SourceImage:
     """SourceImage::load (and load_rgb with rgb=True) of a TIFF, PNG or JPEG file, told apart by the first four (TIFF) or
-    eight (PNG) bytes (a TIFF file with a tile tag or Compression 8 / 32946 gets the Deflate-and-tiles path; anything else gets the JPEG path and its error; a JPEG file whose first SOF marker is SOF2 the progressive one).  drop_rows: the rows cut from the bottom; None - the
+    eight (PNG) bytes (a PNG file whose IHDR says Adam7 gets the interlaced path; a TIFF file with a tile tag or Compression 8 / 32946 gets the Deflate-and-tiles path; anything else gets the JPEG path and its error; a JPEG file whose first SOF marker is SOF2 the progressive one).  drop_rows: the rows cut from the bottom; None - the
     file's own databar_height (the DatabarHeight of a TIFF file's SEM block; 0 for PNG and JPEG).  out: None or "device", as decode_jpeg takes
     it, for img; rgb is a numpy array."""
     data = Path(path).read_bytes()
@@ -262,9 +288,11 @@ def load(device, path, rgb: bool = False, drop_rows=None, out=None) -> SourceIma
                            info["databar_height"] if drop_rows is None else int(drop_rows))
     drop_rows = 0 if drop_rows is None else drop_rows
     if data[:8] == b"\x89PNG\r\n\x1a\n":
-        info = png_info(data)
-        img = decode_png(device, data, "L", drop_rows, out)
-        colour = decode_png(device, data, "RGB", drop_rows) if rgb else None
+        adam7 = len(data) > 28 and data[28] == 1   # IHDR's interlace byte: every other file goes where it went
+        info_of, decode = (png_ext_info, decode_png_ext) if adam7 else (png_info, decode_png)
+        info = info_of(data)
+        img = decode(device, data, "L", drop_rows, out)
+        colour = decode(device, data, "RGB", drop_rows) if rgb else None
         return SourceImage(img, colour, info["focal_length_35mm"], str(path))
     if _first_sof(data) == 0xC2:   # progressive: every other file goes where it went
         info = jpeg_progressive_info(data)

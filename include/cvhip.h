@@ -824,7 +824,7 @@ int cvhip_tiff_ext_last_stats(uint64_t *out_stats);
  * Supported: colour types 0, 2, 3, 4, 6 at every legal bit depth, no interlacing, any number of IDAT chunks split anywhere,
  * stored, fixed and dynamic deflate blocks in any mix; bytes behind the Adler-32 are ignored, distances up to 32 768 are
  * accepted whatever CINFO says; ancillary chunks (APNG's among them: the default image is decoded) are skipped.
- * CVHIP_ERR_UNSUPPORTED: Adam7, a dimension of 65 536 or more, a filtered image or IDAT data of 2^31 or more bytes.
+ * CVHIP_ERR_UNSUPPORTED: Adam7 (cvhip_png_ext_decode below reads it), a dimension of 65 536 or more, a filtered image or IDAT data of 2^31 or more bytes.
  * CVHIP_ERR_INVALID: anything malformed - a bad signature, a first chunk that is not a 13-byte IHDR, a zero dimension, an
  * illegal colour type / bit depth pair, compression or filter method other than 0, interlace above 1, colour type 3 without
  * PLTE, a PLTE of a wrong length or out of place, a palette index beyond it, no IDAT, IDAT chunks that are not consecutive, a
@@ -845,6 +845,30 @@ int cvhip_png_decode(cvhip_device *dev, const uint8_t *file, uint64_t size, uint
  * subsequences; a stored block's 256 records count as one), rounds of the copy resolution (the one that changed nothing
  * included), row segments of the unfilter pass. */
 int cvhip_png_last_stats(uint64_t *out_stats);
+
+/* ------------------------------------------------------------------------------------------
+ * PNG files in, Adam7 interlaced files too (csrc/png_decode_kernels.hip, csrc/png_decode_common.hpp with
+ * adam7 = true): the `image` crate behind image::open(path)?.into_luma8() / into_rgb8() (src/reconstruction.rs:40-60) also
+ * reads interlaced PNG files.  These entry points take a superset of what cvhip_png_info / cvhip_png_decode take - those
+ * answer every file as they always did, an Adam7 file with CVHIP_ERR_UNSUPPORTED - and return the same bytes for a file both
+ * accept.  The pixels are DEFINED by tests/ref_png_adam7.py: the stream holds seven reduced images one behind the other,
+ * pass p = 0 .. 6 with x0 = 0,4,0,2,0,1,0, y0 = 0,0,4,0,2,0,1, dx = 8,8,4,4,2,2,1, dy = 8,8,8,4,4,2,2, of
+ * ceil((W - x0) / dx) x ceil((H - y0) / dy) samples (a pass with no column or no row has no bytes at all); each is
+ * filtered on its own with zeros above its first row and the image's bpp; sample (px, py) of pass p is pixel
+ * (x0 + px dx, y0 + py dy); the padding bits at the end of a sub-byte row are nothing.  Conversion, eXIf and drop_rows are
+ * cvhip_png_decode's.  CVHIP_ERR_UNSUPPORTED: a dimension of 65 536 or more, passes (rows with their filter bytes) or IDAT
+ * data of 2^31 bytes or more.  CVHIP_ERR_INVALID: cvhip_png_decode's list, with "output that is not the passes' bytes" for
+ * an interlaced file.  Nothing is written on any refusal. */
+/* Host only, as cvhip_png_info (src/reconstruction.rs:40-60): out_info[8] has its slots; slot 4, the interlace method, is 0 or 1. */
+int cvhip_png_ext_info(const uint8_t *file, uint64_t size, uint32_t *out_info);
+/* cvhip_png_decode's arguments and contract, to the letter (src/reconstruction.rs:40-60): cap = 0 sizes without writing, out
+ * in host or device memory at any alignment. */
+int cvhip_png_ext_decode(cvhip_device *dev, const uint8_t *file, uint64_t size, uint32_t format, uint32_t drop_rows, uint8_t *out,
+                         uint64_t cap, uint64_t *out_size);
+/* Of the calling thread's last cvhip_png_ext_decode that reached the device (the files of src/reconstruction.rs:40-60's
+ * image::open): out_stats[10] = slots 0 .. 7 as cvhip_png_last_stats' - the row segments counted over all passes, each of
+ * which starts one -, 8 the non-empty passes (1 for a file that is not interlaced), 9 zero. */
+int cvhip_png_ext_last_stats(uint64_t *out_stats);
 
 /* Row sharding (multi-GPU): restrict the SEARCH passes of this context to shard `num` of `den`
  * equal row chunks of the searched level image: rows [num*rps, min((num+1)*rps, h_level)) with
