@@ -1,19 +1,18 @@
-// inflate_device.inc — the device side of inflate that the PNG reader (png_decode_kernels.hip, DESIGN.md 4.18) and the
-// TIFF reader's Deflate strips and tiles (tiff_ext_kernels.hip, DESIGN.md 4.23) share: the constants, the tables in LDS, peek,
-// the symbol decode, the code build, a dynamic block's header and the decode of one subsequence.  Included inside the
-// including file's namespace, behind png_decode_common.hpp and `namespace pd = png_decode_common`.
+// inflate_device.inc — the device functions of inflate under the stage that the PNG reader (png_decode_kernels.hip, DESIGN.md
+// 4.18) and the TIFF reader's Deflate strips and tiles (tiff_ext_kernels.hip, DESIGN.md 4.23) share (inflate_stage.inc, which
+// is included behind this file): the constants, the tables in LDS, peek, the symbol decode, the code build, a dynamic block's
+// header and the decode of one subsequence.  Included inside the including file's namespace, behind png_decode_common.hpp and
+// `namespace pd = png_decode_common`.
 constexpr uint32_t WAVE = 64, BLOCK = 256; // BLOCK: lanes of a workgroup; of the chain kernel: the subsequences of a settle window
 constexpr uint32_t SHORT_BITS = 10, SHORT_ENTRIES = 1u << SHORT_BITS; // codes of up to 10 bits: one LDS lookup; longer ones: the canonical walk
 constexpr unsigned long long ENDED = ~0ull;                           // the state behind an end-of-block
 constexpr uint32_t LIT_SYMBOLS = 288, DIST_SYMBOLS = 32, PIECE = 1024; // PIECE: bytes of a stored block's record
 constexpr uint32_t F_ERR = 0, F_CHANGED = 1, F_STORED = 2, F_FIXED = 3, F_DYNAMIC = 4, F_SUBSEQUENCES = 5, F_ROUNDS = 6, F_WINDOWS = 7,
                    F_RECORDS = 8, F_SEGMENTS = 9, F_EMITTED = 10, FLAGS = 12;
-constexpr uint32_t V_END_BIT = 0, V_ADLER_A = 1, V_ADLER_B = 2, VALUES = 4;
 constexpr uint32_t ERR_CRC = 1, ERR_ZLIB = 2, ERR_BLOCK = 4, ERR_LENGTHS = 8, ERR_TOKEN = 16, ERR_END = 32, ERR_SIZE = 64, ERR_ADLER = 128,
                    ERR_FILTER = 256, ERR_INDEX = 512, ERR_ROOM = 1024;
 constexpr uint32_t WINDOW_WORDS = BLOCK * pd::SUBSEQ_BITS / 32 + 8; // a settle window's words of the stream, and those its last token may reach into
 constexpr uint32_t HEADER_WORDS = 168; // 3 + 14 + 57 bits and 316 code lengths of at most 14 bits: 4 498 bits, and what a read reaches beyond
-constexpr uint32_t WIN_WORDS = 3; // a window: header bit | BTYPE << 40 | records << 44; the first subsequence's first bit; the first record
 
 __device__ const uint8_t d_cl_order[19] = {16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15};
 

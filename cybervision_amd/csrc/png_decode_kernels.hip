@@ -5,23 +5,10 @@
 // payloads, end to end, go up in one copy.
 //
 //   png_crc_kernel       a workgroup per IDAT chunk: the CRC-32 of 256 pieces, combined with png_common.hpp's arithmetic
-//   png_chain_kernel     one workgroup walks the chain of deflate blocks, whose headers can only be found in order.  A
-//                        dynamic block's code lengths are read by one lane, the tables are built in LDS; inside the block
-//                        the decode is the self-synchronising one of jpeg_sync_kernel: a lane per subsequence of
-//                        SUBSEQ_BITS bits, the state is the bit offset of a whole token, lanes decode again from their left
-//                        neighbour's exit until nothing changes.  A window of 256 subsequences, its part of the stream in
-//                        LDS, settles completely before the next one starts from its last exit, so nothing waits for
-//                        another workgroup.  A lane does not take over "ended" from its left (a false end-of-block would
-//                        be handed down the window a lane a round); only the first end-of-block of the settled chain, in
-//                        front of which every lane holds its true state, ends the block.  Out come records (entry state, output bytes) per
-//                        subsequence, and per 1024 bytes of a stored block a (source, length) record
-//   launch_scan_u64      the output position of every record
-//   png_write_kernel     a workgroup per window: the block's tables again (from its header), one more decode from the
-//                        settled states: literals to the filtered image, and per output byte its source index (itself
-//                        for a literal, o - distance for a copy)
-//   png_resolve_kernel   pointer doubling over the source indices, two buffers, until a launch changes nothing
-//   png_gather_kernel    every byte from its literal; the Adler-32 sums of the whole
-//   png_finish_kernel    the Adler-32 behind the last block against those sums
+//   inflate_streams      inflate_stage.inc, the stage the TIFF reader runs on its Deflate strips and tiles, on a table of one
+//                        stream: one workgroup walks the chain of deflate blocks and settles it window by window, a workgroup
+//                        per window writes literals and source indices to the filtered image, the copies resolve by pointer
+//                        doubling, and the Adler-32 is checked.  The stage's head comment says how and why
 //   png_unfilter_kernel  a workgroup per row segment - None and Sub rows start one -: tiles of 64 rows through LDS, a lane of
 //                        the first wave per row, skewed by one pixel per lane, `up` and `up-left` by a shuffle from the lane above
 //   png_index_kernel     colour type 3: no index beyond the PLTE
@@ -31,9 +18,7 @@
 // on ADAM7 - the unfilter launch covers the rows of all passes and a workgroup finds its pass in a table passed by value,
 // the index and convert kernels map a pixel to its pass, row and sample - and a file that is not interlaced runs the
 // <false> instantiations, which are what these kernels were before.
-// A decode from a wrong state is harmless: every read is bounded by the stream's end (32 zero bytes follow it), every step
-// consumes at least one bit, and a code that does not exist consumes one.  In the write pass, whose states are the true
-// ones, the same events are the file's errors.  Once flags[F_ERR] is set no kernel writes to `out`.
+// Once flags[F_ERR] is set no kernel writes to `out`.
 #include <cstring>
 #include <vector>
 
@@ -48,11 +33,7 @@ namespace pd = png_decode_common;
 namespace pc = png_common;
 
 #include "inflate_device.inc"
-
-struct Status { // read back in one copy
-    unsigned long long values[VALUES];
-    uint32_t flags[FLAGS];
-};
+#include "inflate_stage.inc"
 
 struct IdatEntry {
     unsigned long long offset; // in the stream
@@ -110,241 +91,6 @@ __global__ __launch_bounds__(BLOCK) void png_crc_kernel(const uint8_t *__restric
         else if (n) total = pc::crc_combine(total, s_crc[t], n);
     }
     if (total != chunk.crc) atomicOr(&flags[F_ERR], ERR_CRC);
-}
-
-// ---- the chain of blocks ---------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(BLOCK) void png_chain_kernel(const uint32_t *__restrict__ words, unsigned long long n_bytes, unsigned long long *__restrict__ win,
-                                                          unsigned long long max_windows, unsigned long long *__restrict__ rec_entry,
-                                                          unsigned long long *__restrict__ rec_count, unsigned long long max_records,
-                                                          uint32_t *__restrict__ flags, unsigned long long *__restrict__ values)
-{
-    __shared__ Tables T;
-    __shared__ uint32_t s_stream[WINDOW_WORDS];
-    __shared__ unsigned long long s_exit[BLOCK], s_p, s_eob;
-    __shared__ uint32_t s_err, s_btype, s_final, s_first, s_len;
-    const uint32_t tid = threadIdx.x;
-    const unsigned long long total_bits = n_bytes * 8;
-    if (tid == 0) { // the zlib header
-        uint32_t err = 0;
-        if (n_bytes < 2) err = ERR_END;
-        else {
-            const uint32_t cmf = words[0] & 255u, flg = (words[0] >> 8) & 255u;
-            if ((cmf & 15u) != 8 || (cmf >> 4) > 7 || (flg & 32u) || ((cmf << 8 | flg) % 31u)) err = ERR_ZLIB;
-        }
-        s_err = err;
-    }
-    __syncthreads();
-    uint32_t err = s_err, stored = 0, fixed = 0, dynamic = 0, most_rounds = 0, subsequences = 0;
-    unsigned long long p = 16, n_win = 0, n_rec = 0, windows = 0;
-    bool final_seen = false;
-    // (every block takes at least three bits: the bound holds whatever the file says)
-    for (unsigned long long blocks = 0; !err && !final_seen && blocks <= total_bits; blocks++) {
-        const unsigned long long header = p;
-        __syncthreads(); // (the shared words of the block before are read)
-        if (tid == 0) {
-            uint32_t e = 0;
-            unsigned long long q = p + 3;
-            if (q > total_bits) e = ERR_END;
-            else {
-                const uint32_t b = peek(words, p);
-                s_final = b & 1u, s_btype = (b >> 1) & 3u;
-                if (s_btype == 3) e = ERR_BLOCK;
-                else if (s_btype == 0) {
-                    q = (q + 7) & ~7ull;
-                    if (q + 32 > total_bits) e = ERR_END;
-                    else {
-                        const uint32_t v = peek(words, q);
-                        s_len = v & 0xFFFFu;
-                        if ((s_len ^ 0xFFFFu) != (v >> 16)) e = ERR_BLOCK;
-                        q += 32;
-                        if (!e && q + 8ull * s_len > total_bits) e = ERR_END;
-                    }
-                }
-            }
-            s_err = e, s_p = q;
-        }
-        __syncthreads();
-        err = s_err;
-        if (err) break;
-        const uint32_t btype = s_btype;
-        final_seen = s_final != 0;
-        if (btype == 0) { // a stored block: a record per PIECE bytes
-            stored++;
-            const unsigned long long first_byte = s_p >> 3, length = s_len;
-            for (unsigned long long done = 0; done < length; done += (unsigned long long)BLOCK * PIECE) {
-                const unsigned long long pieces = min((unsigned long long)BLOCK, (length - done + PIECE - 1) / PIECE);
-                if (n_win + 1 > max_windows || n_rec + pieces > max_records) {
-                    err = ERR_ROOM;
-                    break;
-                }
-                if (tid < pieces) {
-                    const unsigned long long at = done + (unsigned long long)tid * PIECE;
-                    rec_entry[n_rec + tid] = first_byte + at, rec_count[n_rec + tid] = min((unsigned long long)PIECE, length - at);
-                }
-                if (tid == 0) win[WIN_WORDS * n_win] = header | pieces << 44, win[WIN_WORDS * n_win + 1] = 0, win[WIN_WORDS * n_win + 2] = n_rec;
-                n_win++, n_rec += pieces, windows++;
-            }
-            p = s_p + 8 * length;
-            continue;
-        }
-        if (btype == 1) fixed++;
-        else dynamic++;
-        // the header's words to LDS first (HEADER_WORDS hold the longest one): one lane reads them, a load from memory each time otherwise
-        const unsigned long long header_word = p >> 5;
-        for (uint32_t k = tid; k < HEADER_WORDS; k += BLOCK) s_stream[k] = header_word + k < (n_bytes + 32) / 4 ? words[header_word + k] : 0u;
-        __syncthreads();
-        err = load_tables(s_stream, header_word, p + 3, total_bits, btype, T, &s_err, &s_p);
-        if (err) break;
-        unsigned long long base = s_p, entry0 = s_p;
-        bool block_done = false;
-        while (!err && !block_done) { // a window of BLOCK subsequences; each takes BLOCK x SUBSEQ_BITS bits of the stream
-            if (base >= total_bits) {
-                err = ERR_END; // the stream ends before the block's end-of-block
-                break;
-            }
-            windows++;
-            const unsigned long long first_bit = base + (unsigned long long)tid * pd::SUBSEQ_BITS;
-            const bool active = first_bit < total_bits;
-            const unsigned long long end_bit = min(first_bit + pd::SUBSEQ_BITS, total_bits);
-            const unsigned long long n_active = min((unsigned long long)BLOCK, (total_bits - base + pd::SUBSEQ_BITS - 1) / pd::SUBSEQ_BITS);
-            // the window's part of the stream to LDS: in this one workgroup every load from memory would be waited for
-            const unsigned long long word_base = base >> 5, stream_words = (n_bytes + 32) / 4;
-#pragma unroll 8
-            for (uint32_t k = tid; k < WINDOW_WORDS; k += BLOCK) s_stream[k] = word_base + k < stream_words ? words[word_base + k] : 0u;
-            __syncthreads();
-            unsigned long long cur_entry = tid == 0 ? entry0 : first_bit, cur_exit = ENDED, count = 0, eob_after = 0;
-            if (active) cur_exit = cur_entry >= end_bit ? cur_entry : decode_subsequence<false>(s_stream, word_base, T, cur_entry, end_bit, count, eob_after, nullptr, nullptr, 0, 0, nullptr);
-            s_exit[tid] = cur_exit;
-            if (tid == 0) s_first = BLOCK;
-            uint32_t rounds = 0;
-            for (uint32_t r = 0; r <= BLOCK; r++) { // lane k holds its true state after k rounds
-                __syncthreads();
-                // (a left neighbour that met an end-of-block says nothing about this lane: were it the block's end, this lane
-                // would not count; were it a false one, adopting it would hand "ended" down the window a lane a round)
-                unsigned long long want = (tid && active) ? s_exit[tid - 1] : cur_entry;
-                if (want == ENDED) want = cur_entry;
-                const bool change = want != cur_entry;
-                if (!__syncthreads_or(change)) break; // (and every lane has read before any lane writes)
-                if (change) {
-                    cur_entry = want, count = 0, eob_after = 0;
-                    cur_exit = cur_entry >= end_bit ? cur_entry
-                                                                             : decode_subsequence<false>(s_stream, word_base, T, cur_entry, end_bit, count, eob_after, nullptr, nullptr, 0, 0, nullptr);
-                    s_exit[tid] = cur_exit;
-                }
-                rounds++;
-            }
-            most_rounds = max(most_rounds, rounds);
-            const bool ends_here = active && cur_exit == ENDED; // the first such lane: every lane before it holds its true state
-            if (ends_here) atomicMin(&s_first, tid);
-            __syncthreads();
-            const uint32_t jend = s_first;
-            const unsigned long long emit = jend < BLOCK ? jend + 1 : n_active;
-            subsequences += (uint32_t)emit;
-            if (__syncthreads_or(tid < emit && count != 0)) { // (a window without output needs no write pass)
-                if (n_win + 1 > max_windows || n_rec + emit > max_records) {
-                    err = ERR_ROOM;
-                    break;
-                }
-                if (tid < emit) rec_entry[n_rec + tid] = cur_entry, rec_count[n_rec + tid] = count;
-                if (tid == 0)
-                    win[WIN_WORDS * n_win] = header | (unsigned long long)btype << 40 | emit << 44, win[WIN_WORDS * n_win + 1] = base,
-                                        win[WIN_WORDS * n_win + 2] = n_rec;
-                n_win++, n_rec += emit;
-            }
-            if (jend < BLOCK) {
-                if (tid == jend) s_eob = eob_after;
-                __syncthreads();
-                p = s_eob;
-                if (p > total_bits) err = ERR_END;
-                block_done = true;
-            } else if (n_active < BLOCK) {
-                err = ERR_END;
-            } else {
-                entry0 = s_exit[BLOCK - 1];
-                base += (unsigned long long)BLOCK * pd::SUBSEQ_BITS;
-                __syncthreads();
-            }
-        }
-    }
-    if (!err && !final_seen) err = ERR_END;
-    if (!err && (p + 7) / 8 + 4 > n_bytes) err = ERR_END; // the stream ends inside the Adler-32
-    if (tid == 0) {
-        if (err) atomicOr(&flags[F_ERR], err);
-        flags[F_STORED] = stored, flags[F_FIXED] = fixed, flags[F_DYNAMIC] = dynamic, flags[F_SUBSEQUENCES] = subsequences;
-        flags[F_ROUNDS] = most_rounds, flags[F_WINDOWS] = (uint32_t)windows, flags[F_EMITTED] = (uint32_t)n_win, flags[F_RECORDS] = (uint32_t)n_rec;
-        values[V_END_BIT] = p;
-    }
-}
-
-// rec_out: the records' counts, scanned; rec_out[n_rec] = their total
-__global__ __launch_bounds__(BLOCK) void png_write_kernel(const uint32_t *__restrict__ words, unsigned long long n_bytes, const unsigned long long *__restrict__ win,
-                                                          const unsigned long long *__restrict__ rec_entry, const unsigned long long *__restrict__ rec_out,
-                                                          unsigned long long n_rec, uint8_t *__restrict__ raw, uint32_t *__restrict__ src,
-                                                          unsigned long long filtered, uint32_t *__restrict__ flags)
-{
-    __shared__ Tables T;
-    __shared__ unsigned long long s_p;
-    __shared__ uint32_t s_err;
-    const uint32_t tid = threadIdx.x;
-    const unsigned long long total_bits = n_bytes * 8;
-    const unsigned long long w0 = win[WIN_WORDS * (unsigned long long)blockIdx.x], base = win[WIN_WORDS * (unsigned long long)blockIdx.x + 1];
-    const unsigned long long first = win[WIN_WORDS * (unsigned long long)blockIdx.x + 2];
-    const unsigned long long header = w0 & ((1ull << 40) - 1ull), emit = w0 >> 44;
-    const uint32_t btype = (uint32_t)(w0 >> 40) & 3u;
-    if (blockIdx.x == 0 && tid == 0 && rec_out[n_rec] != filtered) atomicOr(&flags[F_ERR], ERR_SIZE); // not height x (1 + row bytes)
-    if (btype == 0) {
-        if (tid >= emit) return;
-        const uint8_t *from = reinterpret_cast<const uint8_t *>(words) + rec_entry[first + tid];
-        const unsigned long long o = rec_out[first + tid], n = rec_out[first + tid + 1] - o;
-        for (unsigned long long k = 0; k < n && k < PIECE && o + k < filtered; k++) raw[o + k] = from[k], src[o + k] = (uint32_t)(o + k);
-        return;
-    }
-    if (load_tables(words, 0, header + 3, total_bits, btype, T, &s_err, &s_p)) return; // (the chain kernel has accepted the header)
-    if (tid >= emit) return;
-    const unsigned long long entry = rec_entry[first + tid];
-    const unsigned long long end_bit = min(base + (unsigned long long)(tid + 1) * pd::SUBSEQ_BITS, total_bits);
-    if (entry == ENDED || entry >= end_bit) return;
-    unsigned long long count = 0, eob_after = 0;
-    decode_subsequence<true>(words, 0, T, entry, end_bit, count, eob_after, raw, src, rec_out[first + tid], filtered, flags);
-}
-
-// out[o] = in[in[o]] where that is another step back (in[o] < o for a copy, = o for a literal; anything else is left alone)
-__global__ __launch_bounds__(BLOCK) void png_resolve_kernel(const uint32_t *__restrict__ in, uint32_t *__restrict__ out, unsigned long long n,
-                                                            uint32_t *__restrict__ flags)
-{
-    const unsigned long long o = (unsigned long long)blockIdx.x * BLOCK + threadIdx.x;
-    if (o >= n) return;
-    uint32_t s = in[o];
-    if (s < o) {
-        const uint32_t t = in[s];
-        if (t < s) s = t, flags[F_CHANGED] = 1u;
-    }
-    out[o] = s;
-}
-
-// raw[o] = its literal; values[V_ADLER_A] += sum d[o], values[V_ADLER_B] += sum ((n - o) mod 65521) d[o] (png_common.hpp: AdlerSums)
-__global__ __launch_bounds__(BLOCK) void png_gather_kernel(uint8_t *__restrict__ raw, const uint32_t *__restrict__ src, unsigned long long n,
-                                                           unsigned long long *__restrict__ values)
-{
-    const unsigned long long o = (unsigned long long)blockIdx.x * BLOCK + threadIdx.x;
-    unsigned long long a = 0, b = 0;
-    if (o < n) {
-        const uint32_t s = src[o];
-        const uint8_t d = raw[s < o ? s : o]; // (a literal's position holds its own byte: reading it while its lane rewrites it is harmless)
-        if (s < o) raw[o] = d;
-        a = d, b = ((n - o) % pc::ADLER_MOD) * d;
-    }
-    for (int step = WAVE / 2; step; step >>= 1) a += __shfl_down(a, step), b += __shfl_down(b, step);
-    if ((threadIdx.x & (WAVE - 1u)) == 0 && (a | b)) atomicAdd(&values[V_ADLER_A], a), atomicAdd(&values[V_ADLER_B], b);
-}
-
-__global__ void png_finish_kernel(const uint8_t *__restrict__ stream, unsigned long long n, const unsigned long long *__restrict__ values,
-                                  uint32_t *__restrict__ flags)
-{
-    const unsigned long long at = (values[V_END_BIT] + 7) / 8; // (the chain kernel has checked that four bytes follow)
-    const uint32_t want = (uint32_t)stream[at] << 24 | (uint32_t)stream[at + 1] << 16 | (uint32_t)stream[at + 2] << 8 | stream[at + 3];
-    const pc::AdlerSums sums = {(uint32_t)(values[V_ADLER_A] % pc::ADLER_MOD), (uint32_t)(values[V_ADLER_B] % pc::ADLER_MOD)};
-    if (pc::adler_value(sums, n) != want) atomicOr(&flags[F_ERR], ERR_ADLER);
 }
 
 // ---- the filters --------------------------------------------------------------------------------------------------------------------
@@ -609,10 +355,13 @@ int decode(const char *name_, bool adam7, uint64_t *stats, cvhip_device *dev, co
     PassTable T{}; // (all below 2^31: parse has checked the sum)
     for (uint32_t p = 0; p < h.pass_entries; p++)
         T.pass[p] = {h.pass[p].height, (uint32_t)h.pass[p].row_bytes, h.pass[p].first_row, (uint32_t)h.pass[p].offset};
-    // ---- the one upload: the palette, the IDAT table, the IDAT payloads end to end
-    const size_t table_at = sizeof(h.palette), stream_at = table_at + (size_t)n_idat * sizeof(IdatEntry);
+    // ---- the one upload: the palette, the IDAT table, the stage's table of the one stream (its offset and its byte count, in
+    // sixteen bytes: the stream stays at a multiple of 16), the IDAT payloads end to end
+    const size_t table_at = sizeof(h.palette), streams_at = table_at + (size_t)n_idat * sizeof(IdatEntry), stream_at = streams_at + 16;
     std::vector<uint8_t> blob(stream_at + (size_t)n);
     std::memcpy(blob.data(), h.palette, sizeof(h.palette));
+    const uint32_t stream_table[2] = {0u, (uint32_t)n};
+    std::memcpy(blob.data() + streams_at, stream_table, sizeof(stream_table));
     unsigned long long placed = 0;
     for (size_t k = 0; k < n_idat; k++) {
         const IdatEntry entry = {placed, h.idat[k].length, h.idat[k].crc};
@@ -631,64 +380,45 @@ int decode(const char *name_, bool adam7, uint64_t *stats, cvhip_device *dev, co
     CallScratch sc;
     Carver carve; // one allocation, carved
     const size_t pad = 32;
-    const size_t at_blob = carve.reserve(blob.size() + pad), at_status = carve.reserve(sizeof(Status)), at_win = carve.reserve((size_t)max_windows * WIN_WORDS * 8);
-    const size_t at_entry = carve.reserve((size_t)max_records * 8), at_count = carve.reserve(((size_t)max_records + 1) * 8);
+    const size_t at_blob = carve.reserve(blob.size() + pad), at_flags = carve.reserve(FLAGS * 4), at_win = carve.reserve((size_t)max_windows * WIN_SLOTS * 8);
+    const size_t at_entry = carve.reserve((size_t)max_records * 8), at_out = carve.reserve((size_t)max_records * 8), at_count = carve.reserve((size_t)max_records * 4);
     const size_t at_raw = carve.reserve((size_t)P.filtered), at_src = carve.reserve((size_t)P.filtered * 4 * 2);
+    const size_t at_streams = carve.reserve(3 * 8); // of the one stream: the end bit; the two Adler-32 sums
     uint8_t *arena = nullptr, *d_out = nullptr;
     hipError_t e = sc.alloc(&arena, carve.total);
     if (e == hipSuccess) e = sc.output(out, (size_t)bytes, &d_out);
     if (e != hipSuccess) return device_error(name_, e);
     uint8_t *d_blob = arena + at_blob, *raw = arena + at_raw;
-    Status *status = reinterpret_cast<Status *>(arena + at_status), h_status{};
-    uint32_t *flags = status->flags, *srcs[2] = {reinterpret_cast<uint32_t *>(arena + at_src), reinterpret_cast<uint32_t *>(arena + at_src) + P.filtered};
-    unsigned long long *values = status->values, *win = reinterpret_cast<unsigned long long *>(arena + at_win);
-    unsigned long long *rec_entry = reinterpret_cast<unsigned long long *>(arena + at_entry), *rec_count = reinterpret_cast<unsigned long long *>(arena + at_count);
-    const uint8_t *d_palette = d_blob, *d_stream = d_blob + stream_at;
+    uint32_t *flags = reinterpret_cast<uint32_t *>(arena + at_flags), h_flags[FLAGS] = {}; // read back in one copy
+    const uint8_t *d_palette = d_blob, *d_stream = d_blob + stream_at; // (stream_at is a multiple of 16)
     const IdatEntry *d_table = reinterpret_cast<const IdatEntry *>(d_blob + table_at);
-    const uint32_t *words = reinterpret_cast<const uint32_t *>(d_stream); // (stream_at is a multiple of 16)
     e = hipMemcpyAsync(d_blob, blob.data(), blob.size(), hipMemcpyHostToDevice, s);
     if (e == hipSuccess) e = hipMemsetAsync(d_blob + blob.size(), 0, pad, s);
-    if (e == hipSuccess) e = hipMemsetAsync(status, 0, sizeof(Status), s);
+    if (e == hipSuccess) e = hipMemsetAsync(flags, 0, FLAGS * 4, s);
+    if (e == hipSuccess) e = hipMemsetAsync(arena + at_streams, 0, 3 * 8, s);
     if (e != hipSuccess) return device_error(name_, e);
-    auto read_status = [&]() {
-        hipError_t r = hipGetLastError();
-        if (r == hipSuccess) r = hipMemcpyAsync(&h_status, status, sizeof(Status), hipMemcpyDeviceToHost, s);
-        if (r == hipSuccess) r = hipStreamSynchronize(s);
-        return r;
-    };
     const dim3 block(BLOCK);
     const uint8_t idat_name[4] = {'I', 'D', 'A', 'T'};
     hipLaunchKernelGGL(png_crc_kernel, dim3((uint32_t)n_idat), block, 0, s, d_stream, d_table, pc::crc32(idat_name, 4), flags);
-    hipLaunchKernelGGL(png_chain_kernel, dim3(1), block, 0, s, words, n, win, max_windows, rec_entry, rec_count, max_records, flags, values);
-    if ((e = read_status()) != hipSuccess) return device_error(name_, e);
     auto keep_stats = [&](uint64_t copy_rounds) {
-        const uint32_t *f = h_status.flags;
+        const uint32_t *f = h_flags;
         stats[0] = f[F_STORED], stats[1] = f[F_FIXED], stats[2] = f[F_DYNAMIC], stats[3] = f[F_SUBSEQUENCES], stats[4] = f[F_ROUNDS];
         stats[5] = f[F_WINDOWS], stats[6] = copy_rounds, stats[7] = f[F_SEGMENTS];
         if (adam7) stats[8] = h.passes, stats[9] = 0;
     };
-    keep_stats(0);
-    if (h_status.flags[F_ERR]) return file_error(name, h_status.flags[F_ERR], laced);
-    const unsigned long long n_win = h_status.flags[F_EMITTED], n_rec = h_status.flags[F_RECORDS];
-    if (n_win == 0) return file_error(name, ERR_SIZE, laced); // no output at all
-    launch_scan_u64(rec_count, n_rec, rec_count + n_rec, s);
-    hipLaunchKernelGGL(png_write_kernel, dim3((uint32_t)n_win), block, 0, s, words, n, win, rec_entry, rec_count, n_rec, raw, srcs[0], P.filtered, flags);
-    // ---- the copies: pointer doubling, a launch and one flag back per round (a chain of 2^31 copies takes 31 rounds and the one that changes nothing)
-    const dim3 byte_grid((uint32_t)((P.filtered + BLOCK - 1) / BLOCK));
-    uint32_t rounds = 0, from = 0;
-    for (;; from ^= 1u) {
-        if (rounds > 33) return fail(CVHIP_ERR_DEVICE, name + ": the copies did not resolve");
-        e = hipMemsetAsync(flags + F_CHANGED, 0, sizeof(uint32_t), s);
-        if (e != hipSuccess) return device_error(name_, e);
-        hipLaunchKernelGGL(png_resolve_kernel, byte_grid, block, 0, s, srcs[from], srcs[from ^ 1u], P.filtered, flags);
-        rounds++;
-        if ((e = read_status()) != hipSuccess) return device_error(name_, e);
-        if (h_status.flags[F_ERR] || !h_status.flags[F_CHANGED]) break;
-    }
+    InflateArgs A{};
+    A.file = d_stream, A.offsets = reinterpret_cast<const uint32_t *>(d_blob + streams_at), A.counts = A.offsets + 1, A.streams = 1;
+    A.layout = {(uint32_t)P.filtered, P.filtered}; // (below 2^31: parse has checked it)
+    A.win = reinterpret_cast<unsigned long long *>(arena + at_win), A.max_windows = max_windows;
+    A.rec_entry = reinterpret_cast<unsigned long long *>(arena + at_entry), A.rec_out = reinterpret_cast<unsigned long long *>(arena + at_out);
+    A.rec_count = reinterpret_cast<uint32_t *>(arena + at_count), A.max_records = max_records, A.raw = raw;
+    A.srcs[0] = reinterpret_cast<uint32_t *>(arena + at_src), A.srcs[1] = A.srcs[0] + P.filtered;
+    A.end_bit = reinterpret_cast<unsigned long long *>(arena + at_streams), A.sums = A.end_bit + 1, A.flags = flags;
+    uint32_t err = 0, rounds = 0;
+    const int stage = inflate_streams(name_, s, A, true, h_flags, err, rounds);
+    if (stage != CVHIP_OK) return stage;
     keep_stats(rounds);
-    if (h_status.flags[F_ERR]) return file_error(name, h_status.flags[F_ERR], laced);
-    hipLaunchKernelGGL(png_gather_kernel, byte_grid, block, 0, s, raw, srcs[from ^ 1u], P.filtered, values);
-    hipLaunchKernelGGL(png_finish_kernel, dim3(1), dim3(1), 0, s, d_stream, P.filtered, values, flags);
+    if (err) return file_error(name, err, laced);
     // the grid: a workgroup per row, of every pass
     if (laced) hipLaunchKernelGGL(png_unfilter_kernel<true>, dim3(h.pass_rows), dim3(UNFILTER_LANES), 0, s, raw, P.height, P.row_bytes, P.bpp, T, flags);
     else hipLaunchKernelGGL(png_unfilter_kernel<false>, dim3(P.height), dim3(UNFILTER_LANES), 0, s, raw, P.height, P.row_bytes, P.bpp, T, flags);
@@ -700,9 +430,12 @@ int decode(const char *name_, bool adam7, uint64_t *stats, cvhip_device *dev, co
     const dim3 out_grid((uint32_t)((lanes + BLOCK - 1) / BLOCK));
     if (laced) hipLaunchKernelGGL(png_convert_kernel<true>, out_grid, block, 0, s, raw, d_palette, P, T, channels, d_out, bytes, lead, flags);
     else hipLaunchKernelGGL(png_convert_kernel<false>, out_grid, block, 0, s, raw, d_palette, P, T, channels, d_out, bytes, lead, flags);
-    if ((e = read_status()) != hipSuccess) return device_error(name_, e);
+    e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(h_flags, flags, sizeof(h_flags), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) return device_error(name_, e);
     keep_stats(rounds);
-    if (h_status.flags[F_ERR]) return file_error(name, h_status.flags[F_ERR], laced);
+    if (h_flags[F_ERR]) return file_error(name, h_flags[F_ERR], laced);
     e = sc.copy_out(out, d_out, (size_t)bytes, s);
     if (e == hipSuccess) e = sc.drain(s);
     if (e != hipSuccess) return device_error(name_, e);

@@ -8,17 +8,10 @@
 // file's last has stream_bytes bytes, so a byte's stream is a division.
 //
 //   tiff_packbits_kernel, tiff_lzw_kernel   tiff_decompress.inc, a wave per stream: a tile is a strip to them
-//   tiffx_chain_kernel    a workgroup per zlib stream walks its chain of deflate blocks as png_chain_kernel walks the one PNG
-//                         stream (inflate_device.inc): the header by one lane, the tables in LDS, the self-synchronising decode
-//                         over subsequences of SUBSEQ_BITS bits in settle windows of 256.  A settled window's records get their
-//                         output positions at once, by a scan over the workgroup that carries the stream's running count, so the
-//                         positions restart at every stream; windows and records take the next free slots of two arrays shared
-//                         by all streams, whose sizes are the sums of the PNG path's bounds for each stream
-//   tiffx_write_kernel    a workgroup per window of any stream: the block's tables again, one more decode from the settled
-//                         states: literals, and per output byte its source index inside the stream (itself for a literal)
-//   tiffx_resolve_kernel  pointer doubling over the source indices, inside each stream, until a launch changes nothing
-//   tiffx_gather_kernel   every byte from its literal; the Adler-32 sums of every stream
-//   tiffx_finish_kernel   a lane per stream: the Adler-32 behind its final block against those sums
+//   inflate_streams       inflate_stage.inc, the stage the PNG reader runs on its one stream: a workgroup per zlib stream walks its
+//                         chain of deflate blocks, a workgroup per settled window writes literals and source indices, the copies
+//                         resolve inside each stream, and every stream's Adler-32 is checked.  The window and record arrays are
+//                         shared by all streams; their sizes are the sums of the PNG path's bounds for each stream
 //   tiffx_convert_kernel  a workgroup per result row, which gathers its bytes from tiles_across streams: Predictor 2 undone by
 //                         a scan per sample channel that restarts at every tile's left edge and carries across the 256-lane
 //                         chunks inside a tile, then the row's bytes as aligned dwords with single bytes at its ends
@@ -46,10 +39,9 @@ namespace strips {
 }
 namespace inflate {
 #include "inflate_device.inc"
+#include "inflate_stage.inc"
 }
 using namespace inflate;
-
-constexpr uint32_t WIN_SLOTS = 4; // a window: png_chain_kernel's three words, and its stream
 
 struct ExtParams {
     uint32_t width, height, spp, sample_bytes, predictor, from_file;
@@ -62,292 +54,6 @@ struct Status { // read back in one copy
     uint32_t flags[FLAGS];
     uint32_t strip_flags[strips::FLAGS];
 };
-
-// stream s decompresses to this many bytes
-__device__ __forceinline__ uint32_t stream_need(const ExtParams &X, uint32_t s)
-{
-    return (uint32_t)min((unsigned long long)X.stream_bytes, X.total - (unsigned long long)s * X.stream_bytes);
-}
-
-// ---- the chains of blocks: png_chain_kernel for stream blockIdx.x -------------------------------------------------------------------
-__global__ __launch_bounds__(BLOCK) void tiffx_chain_kernel(const uint8_t *__restrict__ file, const uint32_t *__restrict__ offsets,
-                                                            const uint32_t *__restrict__ counts, ExtParams X, unsigned long long *__restrict__ win,
-                                                            unsigned long long max_windows, unsigned long long *__restrict__ rec_entry,
-                                                            unsigned long long *__restrict__ rec_out, uint32_t *__restrict__ rec_count,
-                                                            unsigned long long max_records, uint32_t *__restrict__ flags,
-                                                            unsigned long long *__restrict__ end_bit)
-{
-    __shared__ Tables T;
-    __shared__ uint32_t s_stream[WINDOW_WORDS];
-    __shared__ unsigned long long s_exit[BLOCK], s_p, s_eob, s_wave[BLOCK / WAVE], s_slot[2];
-    __shared__ uint32_t s_err, s_btype, s_final, s_first, s_len;
-    const uint32_t tid = threadIdx.x, lane = tid % WAVE, wave = tid / WAVE, stream = blockIdx.x;
-    const uint32_t *words = reinterpret_cast<const uint32_t *>(file + offsets[stream]); // (the host lays every stream at a multiple of 4, 32 zero bytes behind it)
-    const unsigned long long n_bytes = counts[stream], total_bits = n_bytes * 8, need = stream_need(X, stream);
-    if (tid == 0) { // the zlib header
-        uint32_t err = 0;
-        if (n_bytes < 2) err = ERR_END;
-        else {
-            const uint32_t cmf = words[0] & 255u, flg = (words[0] >> 8) & 255u;
-            if ((cmf & 15u) != 8 || (cmf >> 4) > 7 || (flg & 32u) || ((cmf << 8 | flg) % 31u)) err = ERR_ZLIB;
-        }
-        s_err = err;
-    }
-    __syncthreads();
-    uint32_t err = s_err, stored = 0, fixed = 0, dynamic = 0, most_rounds = 0, subsequences = 0, windows = 0;
-    unsigned long long p = 16, out_pos = 0; // out_pos: the stream's output in front of the next record
-    bool final_seen = false;
-    // the next `records` records and the next window of the shared arrays -> s_slot, or ERR_ROOM
-    auto take = [&](unsigned long long records) -> bool {
-        __syncthreads();
-        if (tid == 0) s_slot[0] = atomicAdd(&flags[F_EMITTED], 1u), s_slot[1] = atomicAdd(&flags[F_RECORDS], (uint32_t)records);
-        __syncthreads();
-        return s_slot[0] + 1 <= max_windows && s_slot[1] + records <= max_records;
-    };
-    for (unsigned long long blocks = 0; !err && !final_seen && blocks <= total_bits; blocks++) {
-        const unsigned long long header = p;
-        __syncthreads();
-        if (tid == 0) {
-            uint32_t e = 0;
-            unsigned long long q = p + 3;
-            if (q > total_bits) e = ERR_END;
-            else {
-                const uint32_t b = peek(words, p);
-                s_final = b & 1u, s_btype = (b >> 1) & 3u;
-                if (s_btype == 3) e = ERR_BLOCK;
-                else if (s_btype == 0) {
-                    q = (q + 7) & ~7ull;
-                    if (q + 32 > total_bits) e = ERR_END;
-                    else {
-                        const uint32_t v = peek(words, q);
-                        s_len = v & 0xFFFFu;
-                        if ((s_len ^ 0xFFFFu) != (v >> 16)) e = ERR_BLOCK;
-                        q += 32;
-                        if (!e && q + 8ull * s_len > total_bits) e = ERR_END;
-                    }
-                }
-            }
-            s_err = e, s_p = q;
-        }
-        __syncthreads();
-        err = s_err;
-        if (err) break;
-        const uint32_t btype = s_btype;
-        final_seen = s_final != 0;
-        if (btype == 0) { // a stored block: a record per PIECE bytes
-            stored++;
-            const unsigned long long first_byte = s_p >> 3, length = s_len;
-            for (unsigned long long done = 0; done < length; done += (unsigned long long)BLOCK * PIECE) {
-                const unsigned long long pieces = min((unsigned long long)BLOCK, (length - done + PIECE - 1) / PIECE);
-                if (!take(pieces)) {
-                    err = ERR_ROOM;
-                    break;
-                }
-                const unsigned long long w = s_slot[0], r = s_slot[1];
-                if (tid < pieces) {
-                    const unsigned long long at = done + (unsigned long long)tid * PIECE;
-                    rec_entry[r + tid] = first_byte + at, rec_out[r + tid] = out_pos + at, rec_count[r + tid] = (uint32_t)min((unsigned long long)PIECE, length - at);
-                }
-                if (tid == 0) win[WIN_SLOTS * w] = header | pieces << 44, win[WIN_SLOTS * w + 1] = 0, win[WIN_SLOTS * w + 2] = r, win[WIN_SLOTS * w + 3] = stream;
-                windows++;
-            }
-            out_pos += length;
-            p = s_p + 8 * length;
-            continue;
-        }
-        if (btype == 1) fixed++;
-        else dynamic++;
-        const unsigned long long header_word = p >> 5;
-        for (uint32_t k = tid; k < HEADER_WORDS; k += BLOCK) s_stream[k] = header_word + k < (n_bytes + 32) / 4 ? words[header_word + k] : 0u;
-        __syncthreads();
-        err = load_tables(s_stream, header_word, p + 3, total_bits, btype, T, &s_err, &s_p);
-        if (err) break;
-        unsigned long long base = s_p, entry0 = s_p;
-        bool block_done = false;
-        while (!err && !block_done) { // a window of BLOCK subsequences
-            if (base >= total_bits) {
-                err = ERR_END;
-                break;
-            }
-            windows++;
-            const unsigned long long first_bit = base + (unsigned long long)tid * pd::SUBSEQ_BITS;
-            const bool active = first_bit < total_bits;
-            const unsigned long long end_bit_here = min(first_bit + pd::SUBSEQ_BITS, total_bits);
-            const unsigned long long n_active = min((unsigned long long)BLOCK, (total_bits - base + pd::SUBSEQ_BITS - 1) / pd::SUBSEQ_BITS);
-            const unsigned long long word_base = base >> 5, stream_words = (n_bytes + 32) / 4;
-#pragma unroll 8
-            for (uint32_t k = tid; k < WINDOW_WORDS; k += BLOCK) s_stream[k] = word_base + k < stream_words ? words[word_base + k] : 0u;
-            __syncthreads();
-            unsigned long long cur_entry = tid == 0 ? entry0 : first_bit, cur_exit = ENDED, count = 0, eob_after = 0;
-            if (active)
-                cur_exit = cur_entry >= end_bit_here
-                               ? cur_entry
-                               : decode_subsequence<false>(s_stream, word_base, T, cur_entry, end_bit_here, count, eob_after, nullptr, nullptr, 0, 0, nullptr);
-            s_exit[tid] = cur_exit;
-            if (tid == 0) s_first = BLOCK;
-            uint32_t rounds = 0;
-            for (uint32_t r = 0; r <= BLOCK; r++) { // lane k holds its true state after k rounds
-                __syncthreads();
-                unsigned long long want = (tid && active) ? s_exit[tid - 1] : cur_entry;
-                if (want == ENDED) want = cur_entry; // (png_chain_kernel says why)
-                const bool change = want != cur_entry;
-                if (!__syncthreads_or(change)) break;
-                if (change) {
-                    cur_entry = want, count = 0, eob_after = 0;
-                    cur_exit = cur_entry >= end_bit_here
-                                   ? cur_entry
-                                   : decode_subsequence<false>(s_stream, word_base, T, cur_entry, end_bit_here, count, eob_after, nullptr, nullptr, 0, 0, nullptr);
-                    s_exit[tid] = cur_exit;
-                }
-                rounds++;
-            }
-            most_rounds = max(most_rounds, rounds);
-            const bool ends_here = active && cur_exit == ENDED;
-            if (ends_here) atomicMin(&s_first, tid);
-            __syncthreads();
-            const uint32_t jend = s_first;
-            const unsigned long long emit = jend < BLOCK ? jend + 1 : n_active;
-            subsequences += (uint32_t)emit;
-            if (__syncthreads_or(tid < emit && count != 0)) { // (a window without output needs no write pass)
-                // the records' output positions: the counts scanned over the workgroup, behind the stream's count so far
-                const unsigned long long mine = tid < emit ? count : 0ull;
-                unsigned long long incl = mine;
-#pragma unroll
-                for (uint32_t d = 1; d < WAVE; d <<= 1) {
-                    const unsigned long long t = __shfl_up(incl, d);
-                    if (lane >= d) incl += t;
-                }
-                if (lane == WAVE - 1) s_wave[wave] = incl;
-                __syncthreads();
-                unsigned long long before = 0, all = 0;
-#pragma unroll
-                for (uint32_t k = 0; k < BLOCK / WAVE; k++) {
-                    if (k < wave) before += s_wave[k];
-                    all += s_wave[k];
-                }
-                if (!take(emit)) {
-                    err = ERR_ROOM;
-                    break;
-                }
-                const unsigned long long w = s_slot[0], r = s_slot[1];
-                if (tid < emit) rec_entry[r + tid] = cur_entry, rec_out[r + tid] = out_pos + before + incl - mine, rec_count[r + tid] = 0;
-                if (tid == 0)
-                    win[WIN_SLOTS * w] = header | (unsigned long long)btype << 40 | emit << 44, win[WIN_SLOTS * w + 1] = base, win[WIN_SLOTS * w + 2] = r,
-                                    win[WIN_SLOTS * w + 3] = stream;
-                out_pos += all;
-            }
-            if (jend < BLOCK) {
-                if (tid == jend) s_eob = eob_after;
-                __syncthreads();
-                p = s_eob;
-                if (p > total_bits) err = ERR_END;
-                block_done = true;
-            } else if (n_active < BLOCK) {
-                err = ERR_END;
-            } else {
-                entry0 = s_exit[BLOCK - 1];
-                base += (unsigned long long)BLOCK * pd::SUBSEQ_BITS;
-                __syncthreads();
-            }
-        }
-    }
-    if (!err && !final_seen) err = ERR_END;
-    if (!err && (p + 7) / 8 + 4 > n_bytes) err = ERR_END; // the stream ends inside the Adler-32
-    if (!err && out_pos != need) err = ERR_SIZE;          // not the strip's or tile's bytes: fewer, or more
-    if (tid == 0) {
-        if (err) atomicOr(&flags[F_ERR], err);
-        atomicAdd(&flags[F_STORED], stored), atomicAdd(&flags[F_FIXED], fixed), atomicAdd(&flags[F_DYNAMIC], dynamic);
-        atomicAdd(&flags[F_SUBSEQUENCES], subsequences), atomicAdd(&flags[F_WINDOWS], windows), atomicMax(&flags[F_ROUNDS], most_rounds);
-        end_bit[stream] = p;
-    }
-}
-
-// a workgroup per window: png_write_kernel on the window's stream, positions and source indices inside the stream
-__global__ __launch_bounds__(BLOCK) void tiffx_write_kernel(const uint8_t *__restrict__ file, const uint32_t *__restrict__ offsets,
-                                                            const uint32_t *__restrict__ counts, ExtParams X, const unsigned long long *__restrict__ win,
-                                                            const unsigned long long *__restrict__ rec_entry, const unsigned long long *__restrict__ rec_out,
-                                                            const uint32_t *__restrict__ rec_count, uint8_t *__restrict__ raw, uint32_t *__restrict__ src,
-                                                            uint32_t *__restrict__ flags)
-{
-    __shared__ Tables T;
-    __shared__ unsigned long long s_p;
-    __shared__ uint32_t s_err;
-    const uint32_t tid = threadIdx.x;
-    const unsigned long long *my = win + WIN_SLOTS * (unsigned long long)blockIdx.x;
-    const unsigned long long w0 = my[0], base = my[1], first = my[2];
-    const uint32_t stream = (uint32_t)my[3];
-    const unsigned long long header = w0 & ((1ull << 40) - 1ull), emit = w0 >> 44;
-    const uint32_t btype = (uint32_t)(w0 >> 40) & 3u;
-    const uint32_t *words = reinterpret_cast<const uint32_t *>(file + offsets[stream]);
-    const unsigned long long total_bits = 8ull * counts[stream], need = stream_need(X, stream), at = (unsigned long long)stream * X.stream_bytes;
-    raw += at, src += at;
-    if (btype == 0) {
-        if (tid >= emit) return;
-        const uint8_t *from = reinterpret_cast<const uint8_t *>(words) + rec_entry[first + tid];
-        const unsigned long long o = rec_out[first + tid], n = rec_count[first + tid];
-        for (unsigned long long k = 0; k < n && k < PIECE && o + k < need; k++) raw[o + k] = from[k], src[o + k] = (uint32_t)(o + k);
-        return;
-    }
-    if (load_tables(words, 0, header + 3, total_bits, btype, T, &s_err, &s_p)) return; // (the chain kernel has accepted the header)
-    if (tid >= emit) return;
-    const unsigned long long entry = rec_entry[first + tid];
-    const unsigned long long end_bit_here = min(base + (unsigned long long)(tid + 1) * pd::SUBSEQ_BITS, total_bits);
-    if (entry == ENDED || entry >= end_bit_here) return;
-    unsigned long long count = 0, eob_after = 0;
-    decode_subsequence<true>(words, 0, T, entry, end_bit_here, count, eob_after, raw, src, rec_out[first + tid], need, flags);
-}
-
-// png_resolve_kernel inside each stream: byte g of all streams is byte o = g - base of its own
-__global__ __launch_bounds__(BLOCK) void tiffx_resolve_kernel(const uint32_t *__restrict__ in, uint32_t *__restrict__ out, ExtParams X, uint32_t *__restrict__ flags)
-{
-    const unsigned long long g = (unsigned long long)blockIdx.x * BLOCK + threadIdx.x;
-    if (g >= X.total) return;
-    const unsigned long long base = g / X.stream_bytes * X.stream_bytes;
-    const uint32_t o = (uint32_t)(g - base);
-    uint32_t s = in[g];
-    if (s < o) {
-        const uint32_t t = in[base + s];
-        if (t < s) s = t, flags[F_CHANGED] = 1u;
-    }
-    out[g] = s;
-}
-
-// raw[g] = its literal; sums[2 s], sums[2 s + 1] += the Adler-32 sums of stream s (png_gather_kernel's)
-__global__ __launch_bounds__(BLOCK) void tiffx_gather_kernel(uint8_t *__restrict__ raw, const uint32_t *__restrict__ src, ExtParams X,
-                                                             unsigned long long *__restrict__ sums)
-{
-    const unsigned long long g = (unsigned long long)blockIdx.x * BLOCK + threadIdx.x;
-    const bool inside = g < X.total;
-    const uint32_t stream = (uint32_t)((inside ? g : X.total - 1) / X.stream_bytes);
-    unsigned long long a = 0, b = 0;
-    if (inside) {
-        const unsigned long long base = (unsigned long long)stream * X.stream_bytes;
-        const uint32_t o = (uint32_t)(g - base), s = src[g];
-        const uint8_t d = raw[base + (s < o ? s : o)]; // (a literal's position holds its own byte)
-        if (s < o) raw[g] = d;
-        a = d, b = (unsigned long long)((stream_need(X, stream) - o) % pc::ADLER_MOD) * d;
-    }
-    // a wave inside one stream adds its sums up first; one that spans a stream's end adds lane by lane
-    const uint32_t first = __shfl(stream, 0);
-    if (__all(stream == first)) {
-        for (int step = WAVE / 2; step; step >>= 1) a += __shfl_down(a, step), b += __shfl_down(b, step);
-        if ((threadIdx.x & (WAVE - 1u)) != 0) return;
-    }
-    if (a | b) atomicAdd(&sums[2ull * stream], a), atomicAdd(&sums[2ull * stream + 1], b);
-}
-
-__global__ __launch_bounds__(BLOCK) void tiffx_finish_kernel(const uint8_t *__restrict__ file, const uint32_t *__restrict__ offsets, uint32_t streams, ExtParams X,
-                                                             const unsigned long long *__restrict__ end_bit, const unsigned long long *__restrict__ sums,
-                                                             uint32_t *__restrict__ flags)
-{
-    const uint32_t s = blockIdx.x * BLOCK + threadIdx.x;
-    if (s >= streams) return;
-    const uint8_t *stream = file + offsets[s];
-    const unsigned long long at = (end_bit[s] + 7) / 8; // (the chain kernel has checked that four bytes follow)
-    const uint32_t want = (uint32_t)stream[at] << 24 | (uint32_t)stream[at + 1] << 16 | (uint32_t)stream[at + 2] << 8 | stream[at + 3];
-    const pc::AdlerSums whole = {(uint32_t)(sums[2ull * s] % pc::ADLER_MOD), (uint32_t)(sums[2ull * s + 1] % pc::ADLER_MOD)};
-    if (pc::adler_value(whole, stream_need(X, s)) != want) atomicOr(&flags[F_ERR], ERR_ADLER);
-}
 
 // ---- the pixels -----------------------------------------------------------------------------------------------------------------
 // where pixel x of image row y lies: in its stream's decompressed bytes (or, stored, in the rows with Predictor 2 undone), or in
@@ -583,35 +289,18 @@ extern "C" int cvhip_tiff_ext_decode(cvhip_device *dev, const uint8_t *file, uin
     const dim3 block(BLOCK);
     uint32_t rounds = 0;
     if (deflate) {
-        unsigned long long *win = reinterpret_cast<unsigned long long *>(arena + at_win), *rec_entry = reinterpret_cast<unsigned long long *>(arena + at_entry);
-        unsigned long long *rec_out = reinterpret_cast<unsigned long long *>(arena + at_out), *end_bit = reinterpret_cast<unsigned long long *>(arena + at_streams);
-        unsigned long long *sums = end_bit + streams;
-        uint32_t *rec_count = reinterpret_cast<uint32_t *>(arena + at_count);
-        uint32_t *srcs[2] = {reinterpret_cast<uint32_t *>(arena + at_src), reinterpret_cast<uint32_t *>(arena + at_src) + X.total};
-        hipLaunchKernelGGL(tiffx_chain_kernel, dim3(streams), block, 0, s, d_file, d_offsets, d_counts, X, win, max_windows, rec_entry, rec_out, rec_count,
-                           max_records, flags, end_bit);
-        if ((e = read_status()) != hipSuccess) return device_error("tiff_ext_decode", e);
-        keep_stats(0);
-        if (h_status.flags[F_ERR]) return file_error(h_status.flags[F_ERR]);
-        const uint32_t n_win = h_status.flags[F_EMITTED];
-        if (n_win == 0) return file_error(ERR_SIZE); // no output at all
-        hipLaunchKernelGGL(tiffx_write_kernel, dim3(n_win), block, 0, s, d_file, d_offsets, d_counts, X, win, rec_entry, rec_out, rec_count, raw, srcs[0], flags);
-        // ---- the copies: pointer doubling, a launch and one flag back per round
-        const dim3 byte_grid((uint32_t)((X.total + BLOCK - 1) / BLOCK));
-        uint32_t from = 0;
-        for (;; from ^= 1u) {
-            if (rounds > 33) return fail(CVHIP_ERR_DEVICE, "tiff_ext_decode: the copies did not resolve");
-            e = hipMemsetAsync(flags + F_CHANGED, 0, sizeof(uint32_t), s);
-            if (e != hipSuccess) return device_error("tiff_ext_decode", e);
-            hipLaunchKernelGGL(tiffx_resolve_kernel, byte_grid, block, 0, s, srcs[from], srcs[from ^ 1u], X, flags);
-            rounds++;
-            if ((e = read_status()) != hipSuccess) return device_error("tiff_ext_decode", e);
-            if (h_status.flags[F_ERR] || !h_status.flags[F_CHANGED]) break;
-        }
+        InflateArgs A{};
+        A.file = d_file, A.offsets = d_offsets, A.counts = d_counts, A.streams = streams, A.layout = {X.stream_bytes, X.total};
+        A.win = reinterpret_cast<unsigned long long *>(arena + at_win), A.max_windows = max_windows;
+        A.rec_entry = reinterpret_cast<unsigned long long *>(arena + at_entry), A.rec_out = reinterpret_cast<unsigned long long *>(arena + at_out);
+        A.rec_count = reinterpret_cast<uint32_t *>(arena + at_count), A.max_records = max_records, A.raw = raw;
+        A.srcs[0] = reinterpret_cast<uint32_t *>(arena + at_src), A.srcs[1] = A.srcs[0] + X.total;
+        A.end_bit = reinterpret_cast<unsigned long long *>(arena + at_streams), A.sums = A.end_bit + streams, A.flags = flags;
+        uint32_t err = 0;
+        const int stage = inflate_streams("tiff_ext_decode", s, A, false, h_status.flags, err, rounds);
+        if (stage != CVHIP_OK) return stage;
         keep_stats(rounds);
-        if (h_status.flags[F_ERR]) return file_error(h_status.flags[F_ERR]);
-        hipLaunchKernelGGL(tiffx_gather_kernel, byte_grid, block, 0, s, raw, srcs[from ^ 1u], X, sums);
-        hipLaunchKernelGGL(tiffx_finish_kernel, dim3((streams + BLOCK - 1) / BLOCK), block, 0, s, d_file, d_offsets, streams, X, end_bit, sums, flags);
+        if (err) return file_error(err);
     } else if (h.compression == tc::COMPRESSION_LZW) {
         hipLaunchKernelGGL(strips::tiff_lzw_kernel, dim3(streams), dim3(strips::WAVE), 0, s, d_file, d_offsets, d_counts, P, raw, strip_flags);
     } else if (h.compression == tc::COMPRESSION_PACKBITS) {
