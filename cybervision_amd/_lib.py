@@ -120,6 +120,18 @@ SIGNATURES = {
     # max_points: (n, max_points, seed, points, tracks, m_cams, out_rows, out_points, out_tracks, out_n); (keys, n, m, out_rows, out_n)
     "cvhip_surface_subset": (C.c_int, [_vp, C.c_uint64, C.c_uint64, C.c_uint64, _vp, _vp, _u32, _vp, _vp, _vp, C.POINTER(C.c_uint64)]),
     "cvhip_select_smallest_u64": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint64, _vp, C.POINTER(C.c_uint64)]),
+    # the dense track table in device memory: (dev, m, reserve_rows, out); (t, out_rows, out_capacity, out_m, out_device_rows);
+    # (t, rows, n); (t, first, n, out); (t, ctx, image1, image2, max_dimension2, out_counts[3]);
+    # (t, image_index, width, height, out_stats[4]); (src, columns, k, out); (t, rows, k, out)
+    "cvhip_tracks_create": (C.c_int, [_vp, _u32, C.c_uint64, C.POINTER(_vp)]),
+    "cvhip_tracks_destroy": (None, [_vp]),
+    "cvhip_tracks_info": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(_u32), C.POINTER(_vp)]),
+    "cvhip_tracks_assign": (C.c_int, [_vp, _vp, C.c_uint64]),
+    "cvhip_tracks_read": (C.c_int, [_vp, C.c_uint64, C.c_uint64, _vp]),
+    "cvhip_tracks_extend": (C.c_int, [_vp, _vp, _u32, _u32, _u32, _vp]),
+    "cvhip_tracks_merge": (C.c_int, [_vp, _u32, _u32, _u32, _vp]),
+    "cvhip_tracks_select_columns": (C.c_int, [_vp, _vp, _u32, C.POINTER(_vp)]),
+    "cvhip_tracks_gather": (C.c_int, [_vp, _vp, C.c_uint64, _vp]),
     # the mesh stage; the surface is (points, tracks, n, m, projection, r, t, image_dims) in every entry
     "cvhip_mesh_set_wide_threshold": (C.c_int, [_vp, _u32]),
     "cvhip_mesh_camera_points": (C.c_int, [_vp, _vp, _vp, C.c_uint64, _u32, _vp, _vp, _vp, _vp, _u32, _vp, _vp, C.c_uint64,

@@ -24,7 +24,7 @@ LIB = PKG / "libcvhip.so"
 SOURCES = ["cvhip_api.hip", "corr_kernels.hip", "orb_kernels.hip", "ransac_kernels.hip", "track_kernels.hip", "resize_kernels.hip", "cvhip_rccl.hip",
            "triangulation_kernels.hip", "pose_kernels.hip", "mesh_kernels.hip", "mesh_output_kernels.hip", "mesh_obj_kernels.hip", "delaunay_kernels.hip",
            "png_kernels.hip", "jpeg_kernels.hip", "tiff_kernels.hip", "png_decode_kernels.hip", "subset_kernels.hip",
-           "jpeg_encode_kernels.hip", "tiff_encode_kernels.hip", "jpeg_prog_kernels.hip", "tiff_ext_kernels.hip"]
+           "jpeg_encode_kernels.hip", "tiff_encode_kernels.hip", "jpeg_prog_kernels.hip", "tiff_ext_kernels.hip", "track_table_kernels.hip"]
 FLAGS = [
     "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC",
     "-ffp-contract=off", "-fno-fast-math", "-fhip-fp32-correctly-rounded-divide-sqrt",

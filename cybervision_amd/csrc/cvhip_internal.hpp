@@ -164,10 +164,11 @@ void launch_triangulate_affine(const uint32_t *cells, uint32_t lw, uint32_t lh, 
 void launch_scan_u32(uint32_t *data, uint32_t n, uint32_t *total, hipStream_t s);
 // the same of n u64 (mesh_obj_kernels.hip): sums of bytes, which pass 2^32
 void launch_scan_u64(unsigned long long *data, unsigned long long n, unsigned long long *total, hipStream_t s);
-// Triangulation::extend_tracks on the forward grid (track_kernels.hip)
+// Triangulation::extend_tracks on the forward grid (track_kernels.hip).  stride: int2 elements between the image-1 points
+// of consecutive tracks - 1 for a column of its own, m for a column of the n x m table read in place
 void launch_extend_tracks_match(const uint32_t *cells, uint32_t lw, uint32_t lh, uint32_t k, uint32_t gw, uint32_t gh,
                                 const int2 *track_p1, unsigned long long n_tracks, uint32_t radius, int2 *out_p2,
-                                uint8_t *removed, uint32_t *oob, hipStream_t s);
+                                uint8_t *removed, uint32_t *oob, hipStream_t s, uint32_t stride = 1);
 void launch_extend_tracks_new(const uint32_t *cells, uint32_t lw, uint32_t lh, uint32_t k, uint32_t gw, uint32_t gh,
                               const uint8_t *removed, uint32_t *block_counts, uint32_t *total, uint32_t *out_new_p1,
                               uint32_t *out_new_p2, unsigned long long cap, hipStream_t s);

@@ -111,6 +111,7 @@ class PointCorrelations { // correlation/mod.rs:63-245, GPU branch
     PointCorrelations &operator=(const PointCorrelations &) = delete;
 
     const std::string &get_selected_hardware() const { return selected_hardware_; }
+    cvhip_ctx *handle() const { return ctx_; } // (for the entries that read the device-resident grid: mesh::TrackTable::extend)
 
     // correlate_images (mod.rs:217-245): forward, reverse, cross-check x2, first_pass = false
     void correlate_images(const Grid<uint8_t> &img1, const Grid<uint8_t> &img2, float scale)
@@ -502,6 +503,81 @@ inline Surface surface_subset(GpuDevice &dev, const Surface &s, uint64_t max_poi
     if (rows) *rows = std::move(kept);
     return out;
 }
+
+// The dense track table in device memory (cvhip_tracks): n x m x 2 int32, (-1, -1) = None - what
+// PerspectiveTriangulation keeps in `tracks` (triangulation.rs:604-617), owned by the library, so that extend_tracks, merge_tracks
+// and the survivors' rows never cross to the host.  It belongs to the GpuDevice it was made with and is destroyed before it.
+// device_rows() is valid until the next call that changes the table (assign, extend, merge); a call that throws leaves the
+// table as it was.
+class TrackTable {
+  public:
+    struct ExtendCounts {
+        uint64_t matched, filled, appended;
+    };
+    struct MergeStats { // cvhip_merge_tracks' out_stats
+        uint64_t present, cells, rejected, empty_area;
+    };
+    TrackTable(GpuDevice &dev, uint32_t m, uint64_t reserve_rows = 0) { check(cvhip_tracks_create(dev.handle(), m, reserve_rows, &t_), "cvhip_tracks_create"); }
+    ~TrackTable() { cvhip_tracks_destroy(t_); }
+    TrackTable(const TrackTable &) = delete;
+    TrackTable &operator=(const TrackTable &) = delete;
+    TrackTable(TrackTable &&o) noexcept : t_(o.t_) { o.t_ = nullptr; }
+    cvhip_tracks *handle() const { return t_; }
+    uint64_t rows() const { return info().rows; }
+    uint64_t capacity() const { return info().capacity; }
+    uint32_t m() const { return info().m; }
+    const int32_t *device_rows() const { return info().device_rows; }
+    void assign(const std::vector<int32_t> &rows) { check(cvhip_tracks_assign(t_, rows.data(), rows.size() / (2 * (size_t)m())), "cvhip_tracks_assign"); }
+    // rows [first, first + n) on the host (n = UINT64_MAX: to the last row)
+    std::vector<int32_t> read(uint64_t first = 0, uint64_t n = UINT64_MAX) const
+    {
+        const Info i = info();
+        if (n == UINT64_MAX) n = i.rows > first ? i.rows - first : 0;
+        std::vector<int32_t> out((size_t)n * i.m * 2);
+        check(cvhip_tracks_read(t_, first, n, out.data()), "cvhip_tracks_read");
+        return out;
+    }
+    // extend_tracks (triangulation.rs:1330-1419) with the device-resident grid of `pc`, fill rule and append included
+    ExtendCounts extend(PointCorrelations &pc, uint32_t image1, uint32_t image2, uint32_t max_dimension2)
+    {
+        uint64_t c[3] = {0, 0, 0};
+        check(cvhip_tracks_extend(t_, pc.handle(), image1, image2, max_dimension2, c), "cvhip_tracks_extend");
+        return {c[0], c[1], c[2]};
+    }
+    MergeStats merge(uint32_t image_index, uint32_t width, uint32_t height) // merge_tracks (:1421-1540)
+    {
+        uint64_t s[4] = {0, 0, 0, 0};
+        check(cvhip_tracks_merge(t_, image_index, width, height, s), "cvhip_tracks_merge");
+        return {s[0], s[1], s[2], s[3]};
+    }
+    TrackTable select_columns(const std::vector<uint32_t> &columns) const // prune_projections (:913-938)
+    {
+        cvhip_tracks *out = nullptr;
+        check(cvhip_tracks_select_columns(t_, columns.data(), (uint32_t)columns.size(), &out), "cvhip_tracks_select_columns");
+        return TrackTable(out);
+    }
+    std::vector<int32_t> gather(const std::vector<uint64_t> &rows) const // out[j] = row rows[j]
+    {
+        std::vector<int32_t> out(rows.size() * (size_t)m() * 2);
+        check(cvhip_tracks_gather(t_, rows.data(), rows.size(), out.data()), "cvhip_tracks_gather");
+        return out;
+    }
+
+  private:
+    struct Info {
+        uint64_t rows = 0, capacity = 0;
+        uint32_t m = 0;
+        const int32_t *device_rows = nullptr;
+    };
+    explicit TrackTable(cvhip_tracks *t) : t_(t) {}
+    Info info() const
+    {
+        Info i;
+        check(cvhip_tracks_info(t_, &i.rows, &i.capacity, &i.m, &i.device_rows), "cvhip_tracks_info");
+        return i;
+    }
+    cvhip_tracks *t_ = nullptr;
+};
 
 struct Polygon { // output.rs:49-53
     uint32_t camera_i;

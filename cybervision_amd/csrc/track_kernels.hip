@@ -17,14 +17,15 @@ namespace cvhip {
 
 __global__ __launch_bounds__(256) void extend_tracks_match_kernel(const uint32_t *__restrict__ cells, uint32_t lw, uint32_t lh,
                                                                    uint32_t k, uint32_t gw, uint32_t gh,
-                                                                   const int2 *__restrict__ track_p1,
+                                                                   const int2 *__restrict__ track_p1, uint32_t stride,
                                                                    unsigned long long n_tracks, uint32_t radius,
                                                                    int2 *__restrict__ out_p2, uint8_t *__restrict__ removed,
                                                                    uint32_t *__restrict__ oob)
 {
     const unsigned long long t = (unsigned long long)blockIdx.x * 256 + threadIdx.x;
     if (t >= n_tracks) return;
-    const int2 p = track_p1[t];
+    // track t's image-1 point: a column of its own (stride 1), or column image1 of the n x m table in place (stride m)
+    const int2 p = track_p1[t * stride];
     int2 res = make_int2(-1, -1);
     if (p.x >= 0 && p.y >= 0) { // track.get(image1_index)?
         const uint32_t px = (uint32_t)p.x, py = (uint32_t)p.y;
@@ -106,11 +107,11 @@ __global__ __launch_bounds__(256) void extend_tracks_write_kernel(const uint32_t
 
 void launch_extend_tracks_match(const uint32_t *cells, uint32_t lw, uint32_t lh, uint32_t k, uint32_t gw, uint32_t gh,
                                 const int2 *track_p1, unsigned long long n_tracks, uint32_t radius, int2 *out_p2,
-                                uint8_t *removed, uint32_t *oob, hipStream_t s)
+                                uint8_t *removed, uint32_t *oob, hipStream_t s, uint32_t stride)
 {
     if (!n_tracks) return;
     hipLaunchKernelGGL(extend_tracks_match_kernel, dim3((unsigned)((n_tracks + 255) / 256)), dim3(256), 0, s, cells, lw, lh, k,
-                       gw, gh, track_p1, n_tracks, radius, out_p2, removed, oob);
+                       gw, gh, track_p1, stride, n_tracks, radius, out_p2, removed, oob);
 }
 
 void launch_extend_tracks_new(const uint32_t *cells, uint32_t lw, uint32_t lh, uint32_t k, uint32_t gw, uint32_t gh,

@@ -42,14 +42,26 @@ class VertexMode(enum.IntEnum):
 
 
 def _p(a):
+    if hasattr(a, "data_ptr"):  # a device tensor (_surface_array)
+        return C.c_void_p(a.data_ptr()) if a.numel() else None
     return C.c_void_p(a.ctypes.data) if a is not None and a.size else None
+
+
+def _surface_array(a, dtype):
+    """A surface's points or tracks as the entries take them: a contiguous device tensor as it is - its address goes to the
+    library, which takes device pointers there -, anything else as a contiguous numpy array of `dtype`."""
+    if hasattr(a, "data_ptr") and a.is_cuda and a.is_contiguous():
+        return a
+    if hasattr(a, "data_ptr"):
+        a = a.cpu().numpy()
+    return np.ascontiguousarray(a, dtype=dtype)
 
 
 def _surface_args(surface, image_shapes):
     """(points, tracks, n, m, projection, r, t, image_dims) as every cvhip_mesh_* entry takes them, and the arrays kept
     alive."""
-    pts = np.ascontiguousarray(surface.points, dtype=np.float64).reshape(-1, 3)
-    tracks = np.ascontiguousarray(surface.tracks, dtype=np.int32)
+    pts = _surface_array(surface.points, np.float64).reshape(-1, 3)
+    tracks = _surface_array(surface.tracks, np.int32)
     m = len(surface.cameras)
     P = np.ascontiguousarray(np.stack([np.asarray(c.projection, dtype=np.float64).reshape(12) for c in surface.cameras])) \
         if m else np.zeros((0, 12))
@@ -178,8 +190,8 @@ def _image_args(images):
 
 def _writer_args(surface, polygons, out_scale, images):
     """(points, tracks [n, m, 2], polygons [p, 3], out_scale, m) as cvhip_mesh_ply and cvhip_mesh_obj take them."""
-    pts = np.ascontiguousarray(surface.points, dtype=np.float64).reshape(-1, 3)
-    tracks = np.ascontiguousarray(surface.tracks, dtype=np.int32)
+    pts = _surface_array(surface.points, np.float64).reshape(-1, 3)
+    tracks = _surface_array(surface.tracks, np.int32)
     if tracks.ndim != 3:
         tracks = tracks.reshape(len(pts), -1, 2)
     poly = np.ascontiguousarray(polygons, dtype=np.uint32).reshape(-1, 3)
@@ -275,7 +287,7 @@ def write_obj(path, device, surface, polygons, camera, images=None, vertex_mode=
     sections = []
     obj(device, surface, polygons, camera, images, vertex_mode, out_scale, stem=path.stem, sections=sections).tofile(path)
     if int(vertex_mode) == VertexMode.Texture:
-        m = np.asarray(surface.tracks).reshape(len(surface.points), -1, 2).shape[1] if len(surface.points) else len(images or [])
+        m = _surface_array(surface.tracks, np.int32).reshape(len(surface.points), -1, 2).shape[1] if len(surface.points) else len(images or [])
         (path.parent / (path.stem + ".mtl")).write_bytes(obj_mtl(path.stem, m))
         if save_textures:
             write_obj_textures(path, device, images)

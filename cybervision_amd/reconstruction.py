@@ -228,6 +228,19 @@ def reconstruct_pairs(device, pyramids, projection_mode: ProjectionMode = Projec
     return {"keypoints": keypoints, "pairs": pairs, "timings_ms": dict(rec.timings_ms)}
 
 
+def _resident_grid(device, shape, resident: bool) -> dict:
+    """complete()'s outputs for a pair of the perspective tail: none (host arrays) - or, with the resident track table, device
+    tensors of the image-1 grid `shape` = (width, height), so that nothing of the grid crosses to the host."""
+    if not resident:
+        return {}
+    import torch
+
+    from .triangulation import _device_tensor
+
+    w, h = shape
+    return {"out_xy": _device_tensor(device, (h, w, 2), torch.int32), "out_corr": _device_tensor(device, (h, w), torch.float32)}
+
+
 def match_count(xy) -> int:
     """Number of Some cells of a dense grid (host array or device tensor)."""
     if hasattr(xy, "data_ptr"):
@@ -236,7 +249,8 @@ def match_count(xy) -> int:
 
 
 def reconstruct_perspective_surface(device, pyramids, pairs_result, cameras, bundle_adjustment: bool = True,
-                                    progress=None, merge_tracks: bool = False, max_points=None, max_points_seed: int = 0):
+                                    progress=None, merge_tracks: bool = False, max_points=None, max_points_seed: int = 0,
+                                    resident_tracks: bool = False):
     """The perspective tail of `reconstruct` for n views: reconstruct_dense's pair loop (reconstruction.rs:668-730) -
     for img1 in order, for every later img2 whose pair has an F in `pairs_result` (reconstruct_pairs' output; its
     dense grids are not needed, dense=False is enough), the dense correlation and extend_tracks into one track table
@@ -248,13 +262,16 @@ def reconstruct_perspective_surface(device, pyramids, pairs_result, cameras, bun
     subset (:837-843) right behind it, on the device - triangulation.subset with max_points_seed.
     -> dict: surface (triangulation.Surface), tracks (the whole table), timings_ms per stage (dense,
     tracks, merge, triangulate); with merge_tracks, merges (per image: PerspectiveTriangulation.merge_tracks' counts); with
-    max_points, surface is the subset, subset its info (triangulation.subset's) and timings_ms["subset"] its time."""
+    max_points, surface is the subset, subset its info (triangulation.subset's) and timings_ms["subset"] its time.
+    resident_tracks=True: as in reconstruct_perspective."""
     from . import triangulation
 
     rec = ImageReconstruction(device, ProjectionMode.Perspective)
     n = len(pyramids)
     shapes = [(int(p[0].shape[1]), int(p[0].shape[0])) for p in pyramids]
-    tri = triangulation.PerspectiveTriangulation(n, shapes, bundle_adjustment=bundle_adjustment)
+    tri = triangulation.PerspectiveTriangulation(n, shapes, bundle_adjustment=bundle_adjustment, resident_tracks=resident_tracks)
+    if resident_tracks:
+        tri.complete_sparse_triangulation(device)  # (no sparse half here: the empty dense table, in device memory)
     mode = correlation.ProjectionMode(int(ProjectionMode.Perspective))
     merges = []
     for i in range(n):
@@ -269,7 +286,7 @@ def reconstruct_perspective_surface(device, pyramids, pairs_result, cameras, bun
                     for s in range(steps + 1):
                         k = steps - s
                         pc.correlate_images(pi[k], pj[k], 1.0 / float(1 << k))
-                    return pc.complete()
+                    return pc.complete(**_resident_grid(device, shapes[i], resident_tracks))
 
                 rec._timed("dense", run)
                 rec._timed("tracks", lambda pc=pc, i=i, j=j: tri.add_image_pair_dense(i, j, pc))
@@ -314,7 +331,8 @@ def recover_camera_poses(device, tri, seed: int = 0, log=None):
 
 
 def reconstruct_perspective(device, pyramids, K, bundle_adjustment: bool = True, seed: int = 0, pairs_result=None,
-                            progress=None, merge_tracks: bool = False, max_points=None, max_points_seed: int = 0):
+                            progress=None, merge_tracks: bool = False, max_points=None, max_points_seed: int = 0,
+                            resident_tracks: bool = False):
     """The perspective `reconstruct` in the reference's order for n views (reconstruction.rs:261-277, 380-395, 627-752):
     the sparse stage per pair (ORB, matcher, RANSAC - reconstruct_pairs with dense=False, or the caller's `pairs_result`),
     add_image_pair_sparse for every pair with an F (a pair that fails is skipped), recover_camera_poses, the dense
@@ -326,7 +344,11 @@ def reconstruct_perspective(device, pyramids, K, bundle_adjustment: bool = True,
     -> dict: surface, camera_order, poses (per recover call), initial_pair, sparse ({pair: (p2, score, the short tracks scored)}), sparse_tracks (the
     table before complete_sparse_triangulation), tracks, cameras, projections, pairs, timings_ms; with merge_tracks, merges
     (per linked image: PerspectiveTriangulation.merge_tracks' counts); with max_points, surface is the subset, subset its info
-    (triangulation.subset's) and timings_ms["subset"] its time."""
+    (triangulation.subset's) and timings_ms["subset"] its time.
+    resident_tracks=True: the dense track table lives in device memory from extend_tracks to the surface - a
+    pair's complete() writes into device tensors, extend_tracks' fill rule and append, merge_tracks, the column selection and the
+    survivors' rows all run on a triangulation.DeviceTrackTable, which is out["tracks"] (`.numpy()` brings it down), and the
+    surface's points and tracks are device tensors (its track_index a host array); every value equals the default path's."""
     from . import triangulation
 
     n = len(pyramids)
@@ -335,7 +357,8 @@ def reconstruct_perspective(device, pyramids, K, bundle_adjustment: bool = True,
         pairs_result = reconstruct_pairs(device, pyramids, ProjectionMode.Perspective, seed=seed, dense=False)
     rec = ImageReconstruction(device, ProjectionMode.Perspective)
     shapes = [(int(p[0].shape[1]), int(p[0].shape[0])) for p in pyramids]
-    tri = triangulation.PerspectiveTriangulation(n, shapes, bundle_adjustment=bundle_adjustment, calibration=Ks)
+    tri = triangulation.PerspectiveTriangulation(n, shapes, bundle_adjustment=bundle_adjustment, calibration=Ks,
+                                                 resident_tracks=resident_tracks)
     from . import _lib
 
     sparse = {}
@@ -351,6 +374,8 @@ def reconstruct_perspective(device, pyramids, K, bundle_adjustment: bool = True,
     initial = tri.best_initial_pair
     sparse_tracks = tri.tracks.copy()
     order, poses = rec._timed("poses", lambda: recover_camera_poses(device, tri, seed=seed))
+    if resident_tracks:
+        tri.complete_sparse_triangulation(device)  # (the sparse table is gone: the empty dense table, in device memory)
     linked = set(order)
     mode = correlation.ProjectionMode(int(ProjectionMode.Perspective))
     merges = []
@@ -368,7 +393,7 @@ def reconstruct_perspective(device, pyramids, K, bundle_adjustment: bool = True,
                     for s in range(steps + 1):
                         k = steps - s
                         pc.correlate_images(pi[k], pj[k], 1.0 / float(1 << k))
-                    return pc.complete()
+                    return pc.complete(**_resident_grid(device, shapes[i], resident_tracks))
 
                 rec._timed("dense", run)
                 rec._timed("tracks", lambda pc=pc, i=i, j=j: tri.add_image_pair_dense(i, j, pc))

@@ -5,6 +5,8 @@ adjustment - in one call of cvhip_triangulate_perspective - and the sparse half 
 recover_pose run on the device - and merge_tracks (:1421-1540, cvhip_merge_tracks), which reconstruct_dense runs after
 each linked image's pairs.  `subset` is triangulate_all's max_points (:837-843, cvhip_surface_subset): a seeded random subset
 of a surface's rows, selected and gathered on the device.
+`DeviceTrackTable` is the dense table in device memory (cvhip_tracks): with resident_tracks=True the table
+stays there from extend_tracks to the surface, whose points and tracks are device tensors.
 `affine_surface` is the Surface of AffineTriangulation::triangulate (:268-330) around cvhip_triangulate_affine's points.
 No compute in Python - the track table's bookkeeping and the calls only.
 """
@@ -35,7 +37,8 @@ class Camera:
 class Surface:
     """Surface (triangulation.rs:142-150) as the device returns it: points[i] belongs to track row track_index[i] of the
     table (tracks[i] is that row); one camera per image.  ba_*: what the bundle adjustment did (iterations, accept (1) /
-    reject (0) per iteration, |residual| before and after; NaN without bundle adjustment)."""
+    reject (0) per iteration, |residual| before and after; NaN without bundle adjustment).  points and tracks are numpy
+    arrays, or - from a resident track table - device tensors; track_index is always a host array."""
     points: np.ndarray
     track_index: np.ndarray
     tracks: np.ndarray
@@ -132,14 +135,146 @@ def subset(device, surface: Surface, max_points: int, seed: int = 0):
     return out, {"rows_in": n, "rows_out": k, "seed": seed, "rows": rows}
 
 
-class PerspectiveTriangulation:
-    """PerspectiveTriangulation: tracks [n, images_count, 2] int32, (-1, -1) = no point; the sparse half places the cameras."""
+def _device_tensor(device, shape, dtype):
+    """An uninitialised tensor on the GPU of the handle `device` (what the library writes a device output into)."""
+    import torch
 
-    def __init__(self, images_count: int, image_shapes, bundle_adjustment: bool = True, calibration=None):
+    ordinal = int(getattr(device, "ordinal", -1))
+    return torch.empty(shape, dtype=dtype, device=torch.device("cuda", ordinal) if ordinal >= 0 else "cuda")
+
+
+class DeviceTrackTable:
+    """The dense track table in device memory (cvhip_tracks): [rows, m, 2] int32, (-1, -1) = no point, owned
+    by a handle of the library - the table the existing entries take through `data_ptr`.  It belongs to `device`, works on its
+    stream and is closed before it.  data_ptr is valid until the next call that changes the table (assign, extend, merge,
+    close); a call that raises leaves the table as it was.  No arithmetic here: every method is one entry of the library."""
+
+    def __init__(self, device, m: int, reserve_rows: int = 0, _handle=None):
+        self.device = device
+        self._h = C.c_void_p()
+        if _handle is not None:
+            self._h = _handle
+        else:
+            _lib.check(_lib.lib().cvhip_tracks_create(device.handle, int(m), int(reserve_rows), C.byref(self._h)),
+                       "cvhip_tracks_create")
+
+    def _info(self):
+        rows, cap, m, ptr = C.c_uint64(0), C.c_uint64(0), C.c_uint32(0), C.c_void_p()
+        _lib.check(_lib.lib().cvhip_tracks_info(self._h, C.byref(rows), C.byref(cap), C.byref(m), C.byref(ptr)), "cvhip_tracks_info")
+        return int(rows.value), int(cap.value), int(m.value), int(ptr.value or 0)
+
+    @property
+    def handle(self):
+        return self._h
+
+    @property
+    def rows(self) -> int:
+        return self._info()[0]
+
+    @property
+    def capacity(self) -> int:
+        return self._info()[1]
+
+    @property
+    def m(self) -> int:
+        return self._info()[2]
+
+    @property
+    def data_ptr(self) -> int:
+        """The device address of row 0 (0 while the table has no capacity)."""
+        return self._info()[3]
+
+    def __len__(self) -> int:
+        return self.rows
+
+    def numpy(self, first: int = 0, n=None) -> np.ndarray:
+        """Rows [first, first + n) (to the last row by default) as a host array [n, m, 2] int32."""
+        rows, _cap, m, _ptr = self._info()
+        n = rows - int(first) if n is None else int(n)
+        out = np.empty((max(n, 0), m, 2), dtype=np.int32)
+        _lib.check(_lib.lib().cvhip_tracks_read(self._h, int(first), n, _array_ptr(out) if out.size else None), "cvhip_tracks_read")
+        return out
+
+    def assign(self, rows):
+        """The table becomes `rows`: a numpy array or a contiguous int32 device tensor, [n, m, 2]."""
+        if not hasattr(rows, "data_ptr"):
+            rows = np.ascontiguousarray(rows, dtype=np.int32)
+        elif not rows.is_contiguous():
+            raise ValueError("rows: a contiguous tensor")
+        if rows.ndim != 3 or tuple(rows.shape[1:]) != (self.m, 2):
+            raise ValueError("rows: [n, m, 2]")
+        n = int(rows.shape[0])
+        _lib.check(_lib.lib().cvhip_tracks_assign(self._h, _array_ptr(rows) if n else None, n), "cvhip_tracks_assign")
+
+    def extend(self, pc, image1_index: int, image2_index: int, max_dimension: int) -> dict:
+        """extend_tracks (triangulation.rs:1330-1419) with the grid of the pair's PointCorrelations `pc`, fill rule and append
+        included (cvhip_tracks_extend) -> {matched, filled, appended}."""
+        counts = np.zeros(3, dtype=np.uint64)
+        _lib.check(_lib.lib().cvhip_tracks_extend(self._h, pc._h, int(image1_index), int(image2_index), int(max_dimension),
+                                                  _array_ptr(counts)), "cvhip_tracks_extend")
+        return {"matched": int(counts[0]), "filled": int(counts[1]), "appended": int(counts[2])}
+
+    def merge(self, image_index: int, width: int, height: int) -> dict:
+        """merge_tracks for image `image_index` of width x height (cvhip_tracks_merge) -> PerspectiveTriangulation.merge_tracks'
+        dict."""
+        n = self.rows
+        stats = np.zeros(4, dtype=np.uint64)
+        _lib.check(_lib.lib().cvhip_tracks_merge(self._h, int(image_index), int(width), int(height), _array_ptr(stats)),
+                   "cvhip_tracks_merge")
+        return {"image": int(image_index), "rows_in": n, "rows_out": self.rows, "present": int(stats[0]), "cells": int(stats[1]),
+                "rejected": int(stats[2]), "empty_area": int(stats[3])}
+
+    def select_columns(self, columns) -> "DeviceTrackTable":
+        """A new table of the listed columns (strictly increasing) of every row (prune_projections, :913-938)."""
+        cols = np.ascontiguousarray(columns, dtype=np.uint32).reshape(-1)
+        out = C.c_void_p()
+        _lib.check(_lib.lib().cvhip_tracks_select_columns(self._h, _array_ptr(cols) if len(cols) else None, len(cols), C.byref(out)),
+                   "cvhip_tracks_select_columns")
+        return DeviceTrackTable(self.device, len(cols), _handle=out)
+
+    def gather(self, rows, out=None):
+        """out[j] = row rows[j].  rows: a numpy array or a contiguous device tensor of 64-bit integers; out: a numpy array or a
+        contiguous int32 device tensor [k, m, 2] (by default a device tensor).  -> out."""
+        if not hasattr(rows, "data_ptr"):
+            rows = np.ascontiguousarray(rows, dtype=np.uint64).reshape(-1)
+        elif not rows.is_contiguous() or rows.element_size() != 8 or rows.dim() != 1:
+            raise ValueError("rows: a contiguous one-dimensional tensor of 64-bit integers")
+        k = int(rows.shape[0])
+        if out is None:
+            import torch
+
+            out = _device_tensor(self.device, (k, self.m, 2), torch.int32)
+        elif (hasattr(out, "data_ptr") and not out.is_contiguous()) or tuple(out.shape) != (k, self.m, 2):
+            raise ValueError("out: contiguous, [k, m, 2]")
+        _lib.check(_lib.lib().cvhip_tracks_gather(self._h, _array_ptr(rows) if k else None, k, _array_ptr(out) if k else None),
+                   "cvhip_tracks_gather")
+        return out
+
+    def close(self):
+        if getattr(self, "_h", None):
+            _lib.lib().cvhip_tracks_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class PerspectiveTriangulation:
+    """PerspectiveTriangulation: tracks [n, images_count, 2] int32, (-1, -1) = no point; the sparse half places the cameras.
+    resident_tracks=True: after complete_sparse_triangulation the dense table is a DeviceTrackTable - add_image_pair_dense,
+    merge_tracks and triangulate_all[_recovered] work on it in device memory (they take the device handle then), and the
+    Surface's points and tracks are device tensors.  The sparse half keeps its host table."""
+
+    def __init__(self, images_count: int, image_shapes, bundle_adjustment: bool = True, calibration=None,
+                 resident_tracks: bool = False):
         """image_shapes: (width, height) per image; calibration: K per image (set_image_data, :604-617, 700-703)."""
         self.images_count = int(images_count)
         self.image_shapes = [tuple(int(v) for v in s) for s in image_shapes]
         self.bundle_adjustment = bool(bundle_adjustment)
+        self.resident_tracks = bool(resident_tracks)
         self.tracks = np.full((0, self.images_count, 2), -1, dtype=np.int32)
         n = self.images_count
         self.calibration = [None if calibration is None else np.ascontiguousarray(calibration[i], dtype=np.float64)
@@ -280,16 +415,68 @@ class PerspectiveTriangulation:
         self.triangulate_tracks(device)
         return [best]
 
-    def complete_sparse_triangulation(self):
-        """complete_sparse_triangulation (:813-815): the tracks go, the cameras stay."""
+    def complete_sparse_triangulation(self, device=None):
+        """complete_sparse_triangulation (:813-815): the tracks go, the cameras stay.  With resident_tracks the dense table
+        that takes their place is a DeviceTrackTable of `device` (without a device here, the first dense call makes it)."""
         self.tracks = np.full((0, self.images_count, 2), -1, dtype=np.int32)
         self.points = np.zeros((0, 3))
         self.points_ok = np.zeros(0, dtype=bool)
+        if self.resident_tracks and device is not None:
+            self._resident_table(device)
+
+    def _resident_table(self, device) -> DeviceTrackTable:
+        """The dense table in device memory: made on first use, from the rows the host table holds then."""
+        if not isinstance(self.tracks, DeviceTrackTable):
+            table = DeviceTrackTable(device, self.images_count)
+            if len(self.tracks):
+                table.assign(self.tracks)
+            self.tracks = table
+        return self.tracks
+
+    def _triangulate_resident(self, device, keep, call) -> Surface:
+        """triangulate_all on the resident table: the kept columns selected on the device, the entry `call(tracks pointer, n,
+        m, outputs...)` run on the table's device rows with device outputs, and the survivors' rows gathered on the device.
+        The Surface's points and tracks are device tensors.  track_index stays a host array: it is bookkeeping that no kernel
+        reads, and the one n_kept x 8 B array that still comes down."""
+        import torch
+
+        sel = self._resident_table(device).select_columns(keep)
+        try:
+            m, n = len(keep), sel.rows
+            pts = _device_tensor(device, (max(n, 1), 3), torch.float64)
+            idx = _device_tensor(device, (max(n, 1),), torch.int64)  # (the entry's uint64 rows: below 2^32)
+            out_r, out_t, out_p = np.zeros((m, 3)), np.zeros((m, 3)), np.zeros((m, 3, 4))
+            out_n, iters = C.c_uint64(0), C.c_uint32(0)
+            history = np.zeros(BUNDLE_ADJUSTMENT_MAX_ITERATIONS, dtype=np.uint8)
+            norms = np.zeros(2)
+            p = lambda a: C.c_void_p(a.ctypes.data)  # noqa: E731
+            call(C.c_void_p(sel.data_ptr) if n else None, n, m, _array_ptr(pts), _array_ptr(idx), p(out_r), p(out_t), p(out_p),
+                 C.byref(out_n), C.byref(iters), p(history), p(norms))
+            k = out_n.value
+            index = idx[:k]
+            tracks = sel.gather(index)
+            return Surface(points=pts[:k], track_index=index.cpu().numpy(), tracks=tracks,
+                           cameras=[Camera(out_r[j].copy(), out_t[j].copy(), out_p[j].copy()) for j in range(m)],
+                           ba_iterations=int(iters.value), ba_history=[int(h) for h in history[:iters.value]],
+                           ba_residual_norms=(float(norms[0]), float(norms[1])))
+        finally:
+            sel.close()
 
     def triangulate_all_recovered(self, device, progress=None) -> Surface:
         """triangulate_all (:817-865) with the recovered cameras and projections (cvhip_triangulate_perspective_cameras);
-        images without a camera are pruned (prune_projections, :913-938)."""
+        images without a camera are pruned (prune_projections, :913-938).  With resident_tracks: _triangulate_resident."""
         keep = [i for i in range(self.images_count) if self.projections[i] is not None]
+        if self.resident_tracks:
+            K = np.ascontiguousarray(np.stack([self.cameras[i][0].reshape(9) for i in keep]))
+            R = np.ascontiguousarray(np.stack([self.cameras[i][1].reshape(3) for i in keep]))
+            t = np.ascontiguousarray(np.stack([self.cameras[i][2].reshape(3) for i in keep]))
+            P = np.ascontiguousarray(np.stack([self.projections[i] for i in keep]))
+            cb = _lib.PROGRESS_FN(lambda _user, pos: progress(pos)) if progress is not None else _lib.NULL_PROGRESS
+            a = lambda v: C.c_void_p(v.ctypes.data)  # noqa: E731
+            return self._triangulate_resident(device, keep, lambda tracks, n, m, *outs: _lib.check(
+                _lib.lib().cvhip_triangulate_perspective_cameras(device.handle, tracks, n, m, a(K), a(R), a(t), a(P),
+                                                                 int(self.bundle_adjustment), *outs, cb, None),
+                "cvhip_triangulate_perspective_cameras"))
         tracks = np.ascontiguousarray(self.tracks[:, keep])
         m, n = len(keep), len(tracks)
         K = np.ascontiguousarray(np.stack([self.cameras[i][0].reshape(9) for i in keep]))
@@ -318,8 +505,11 @@ class PerspectiveTriangulation:
     def add_image_pair_dense(self, image1_index: int, image2_index: int, pc):
         """extend_tracks (:1330-1419) with the completed grid of a pair's PointCorrelations `pc`: every track with a point
         in image 1 gets the nearest match - Track::add only fills an empty slot (:370-375) - and every remaining match
-        becomes a new track, appended in scan order."""
+        becomes a new track, appended in scan order.  With resident_tracks all of it is one call on the table in device
+        memory (DeviceTrackTable.extend, on pc's device), whose counts it returns."""
         max_dimension = max(self.image_shapes[image2_index])
+        if self.resident_tracks:
+            return self._resident_table(pc.device).extend(pc, image1_index, image2_index, max_dimension)
         tp2, new_p1, new_p2 = pc.extend_tracks(self.tracks[:, image1_index], max_dimension)
         fill = (self.tracks[:, image2_index, 0] < 0) & (tp2[:, 0] >= 0)
         self.tracks[fill, image2_index] = tp2[fill]
@@ -333,9 +523,12 @@ class PerspectiveTriangulation:
         becomes one copy of the highest row of every kept cell of that image, in row-major order of the cells; tracks
         without a point in the image are dropped.  The trailing triangulate_tracks (:1538) is not run: triangulate_all
         re-triangulates every track first (:822), and the dense stage keeps no points (`self.points` stays as it is).
-        -> {image, rows_in, rows_out, present, cells, rejected, empty_area}."""
+        -> {image, rows_in, rows_out, present, cells, rejected, empty_area}.  With resident_tracks the table is merged in
+        device memory (DeviceTrackTable.merge): the same dict."""
         n, m = len(self.tracks), self.images_count
         w, h = self.image_shapes[image_index]
+        if self.resident_tracks:
+            return self._resident_table(device).merge(image_index, w, h)
         tr = np.ascontiguousarray(self.tracks)
         out = np.empty((max(n, 1), m, 2), dtype=np.int32)
         out_n = C.c_uint64(0)
@@ -357,7 +550,18 @@ class PerspectiveTriangulation:
     def triangulate_all(self, device, cameras, progress=None) -> Surface:
         """triangulate_all (:817-865) with the given cameras [(K, R, t)] (None = no camera for that image).  max_points
         (:837-843, a random subset) is `subset`, applied to the surface this returns.  Raises CvhipError with the reference's
-        TriangulationError message (CVHIP_ERR_NO_SURFACE) when the bundle adjustment fails."""
+        TriangulationError message (CVHIP_ERR_NO_SURFACE) when the bundle adjustment fails.  With resident_tracks:
+        _triangulate_resident."""
+        if self.resident_tracks:
+            keep = [i for i, cam in enumerate(cameras) if cam is not None]
+            K = np.ascontiguousarray(np.stack([np.asarray(cameras[i][0], dtype=np.float64).reshape(9) for i in keep]))
+            R = np.ascontiguousarray(np.stack([np.asarray(cameras[i][1], dtype=np.float64).reshape(9) for i in keep]))
+            t = np.ascontiguousarray(np.stack([np.asarray(cameras[i][2], dtype=np.float64).reshape(3) for i in keep]))
+            cb = _lib.PROGRESS_FN(lambda _user, pos: progress(pos)) if progress is not None else _lib.NULL_PROGRESS
+            a = lambda v: C.c_void_p(v.ctypes.data)  # noqa: E731
+            return self._triangulate_resident(device, keep, lambda tracks, n, m, *outs: _lib.check(
+                _lib.lib().cvhip_triangulate_perspective(device.handle, tracks, n, m, a(K), a(R), a(t), int(self.bundle_adjustment),
+                                                         *outs, cb, None), "cvhip_triangulate_perspective"))
         cams, tracks = self.prune_projections(cameras)
         m = len(cams)
         n = len(tracks)

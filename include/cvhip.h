@@ -284,6 +284,62 @@ int cvhip_select_smallest_u64(cvhip_device *dev, const uint64_t *keys, uint64_t 
                               uint64_t *out_n);
 
 /* ------------------------------------------------------------------------------------------
+ * The dense track table in device memory: n x m x 2 int32, row-major, (-1, -1) = no point - what
+ * cvhip_extend_tracks, cvhip_merge_tracks, cvhip_triangulate_perspective[_cameras], cvhip_surface_subset and the
+ * cvhip_mesh_* entries take as `tracks` - owned by an opaque handle, so that the table never crosses to the host between
+ * a pair's correlation grid and the surface.  A table belongs to one cvhip_device, does all its work on that handle's
+ * stream, and is destroyed before it.  m <= CVHIP_TRIANGULATE_MAX_CAMERAS (CVHIP_ERR_UNSUPPORTED above), fewer than
+ * 2^32 - 1 rows (CVHIP_ERR_UNSUPPORTED).  The capacity grows geometrically (at least doubling), keeps the rows, and is
+ * never smaller than asked.
+ * POINTER LIFETIME: the address cvhip_tracks_info gives out is valid until the next call that changes the table
+ * (assign, extend, merge, destroy): any of them may move the rows.
+ * UNCHANGED ON ERROR: an entry that returns an error leaves the table's rows, row count and contents as they were.
+ * Integer only: every entry is bit-exact, and equal to the host-table path around the entries above. */
+typedef struct cvhip_tracks cvhip_tracks;
+
+/* An empty table of m images with room for reserve_rows rows.  CVHIP_ERR_INVALID for a NULL dev or out, or m = 0 (checked
+ * before any device call). */
+int cvhip_tracks_create(cvhip_device *dev, uint32_t m, uint64_t reserve_rows, cvhip_tracks **out);
+void cvhip_tracks_destroy(cvhip_tracks *t); /* NULL: nothing */
+
+/* *out_rows = n, *out_capacity (rows), *out_m, *out_device_rows = the device address of row 0 (see POINTER LIFETIME; NULL
+ * while the capacity is 0).  Each may be NULL. */
+int cvhip_tracks_info(const cvhip_tracks *t, uint64_t *out_rows, uint64_t *out_capacity, uint32_t *out_m,
+                      const int32_t **out_device_rows);
+
+/* assign: the table becomes the n rows at `rows` (n x m x 2 int32).  read: rows [first, first + n) into `out`;
+ * CVHIP_ERR_INVALID when the range passes the end.  rows, out: host or device pointers. */
+int cvhip_tracks_assign(cvhip_tracks *t, const int32_t *rows, uint64_t n);
+int cvhip_tracks_read(const cvhip_tracks *t, uint64_t first, uint64_t n, int32_t *out);
+
+/* extend_tracks (triangulation.rs:1330-1419) of the pair (image1, image2) on the table, from ctx's forward grid - what
+ * cvhip_extend_tracks and its caller's bookkeeping do, in one call: the search of cvhip_extend_tracks runs ONCE, reading
+ * column image1 of the table in place; a track's match fills slot image2 only where that slot is empty (x < 0; Track::add,
+ * :370-375); the removal map is marked for every track that found a match, filled or not; every remaining Some cell is
+ * appended as a new row in scan order - the cell in slot image1, its match in slot image2, (-1, -1) elsewhere.
+ * out_counts[3] (may be NULL): tracks whose search found a match, slots filled, rows appended.  A ctx with nothing
+ * correlated fills and appends nothing.  max_dimension2 as for cvhip_extend_tracks.
+ * Errors (table unchanged: the matches go to a scratch column, and the table is written only once the flag is known to be
+ * clear): CVHIP_ERR_INVALID for image1 == image2, an image index >= m, a ctx of another cvhip_device than the table's, and
+ * "Index out of bounds" (a merged match lies outside the image-1 grid), as cvhip_extend_tracks has it.  Uses the context's
+ * per-pass scratch: call it between pairs. */
+int cvhip_tracks_extend(cvhip_tracks *t, cvhip_ctx *ctx, uint32_t image1, uint32_t image2, uint32_t max_dimension2,
+                        uint64_t *out_counts);
+
+/* cvhip_merge_tracks' out_tracks becomes the table (the same launches and rules; the result goes to a second device buffer
+ * and the two are exchanged).  out_stats[4] (may be NULL) as there.  Errors as there, table unchanged. */
+int cvhip_tracks_merge(cvhip_tracks *t, uint32_t image_index, uint32_t width, uint32_t height, uint64_t *out_stats);
+
+/* prune_projections (triangulation.rs:913-938): *out = a new table (the caller destroys it) of the k listed columns of every
+ * row of src, in that order.  columns: k u32 in host memory, strictly increasing and < m (CVHIP_ERR_INVALID otherwise, or
+ * for k = 0).  The new table shares nothing with src. */
+int cvhip_tracks_select_columns(const cvhip_tracks *src, const uint32_t *columns, uint32_t k, cvhip_tracks **out);
+
+/* out[j] = row rows[j] for j < k (k x m x 2 int32).  rows (u64) and out: host or device pointers.  A row >= n is
+ * CVHIP_ERR_INVALID and nothing is written: the rows are checked on the device before the copy. */
+int cvhip_tracks_gather(const cvhip_tracks *t, const uint64_t *rows, uint64_t k, int32_t *out);
+
+/* ------------------------------------------------------------------------------------------
  * Pose recovery, perspective pipeline (sparse stage).  All f64 on the device (csrc/pose_kernels.hip).
  * tracks: n x m x 2 int32, (-1, -1) = no point; m <= CVHIP_TRIANGULATE_MAX_CAMERAS.  projections: m x 12 row-major
  * (3 x 4, calibrated), used where has_projection[j] != 0.  Host pointers unless stated. */
