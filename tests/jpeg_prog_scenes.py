@@ -1,8 +1,8 @@
 """The progressive JPEG files of the decoder's tests: (a) files that Pillow (libjpeg-turbo) writes with
 progressive=True - libjpeg's default script has all four scan kinds -, (b) files from `write`, a small progressive writer
 from quantised coefficients, a scan script and restart intervals, one DHT in front of every scan, which forces what an
-encoder does not give on demand, and (c) the files that are refused.  tests/test_jpeg_prog_ref.py checks that each forced
-file reaches its case."""
+encoder does not give on demand - SEAMS: the files that sit on the seams of the kernels' units -, and (c) the files that are
+refused.  tests/test_jpeg_prog_ref.py checks that each forced file reaches its case."""
 import functools
 
 import numpy as np
@@ -264,8 +264,229 @@ def forced_eob16384():
     return write(1024, 1024, coef, QUANT_PLAIN, _script_default(1, al=0), components=1)
 
 
+# ---- the seams of the kernels' units (Tests): 64-byte chunks and 256-lane workgroups of the byte kernels, 1024-bit
+# subsequences 256 to a workgroup, a wave per restart interval, correction fields in 16-bit pieces.  Every seed below was found by
+# the bounded search its builder still holds; the search starts at the seed written down, so a test pays for one try.
+CHUNK, GROUP = 64, 256
+
+
+def forced_dense_history():
+    """48 x 16 grey, 12 blocks, every AC coefficient a history coefficient (|v| >= 2) of the band's last refinement (Al = 0) but for the
+    exceptions: blocks 0, 1 - none, an EOB run of two whose blocks each read the whole band's 63 correction bits as one field, the
+    second from inside the run; blocks 2 .. 8 - a new coefficient (|v| = 1) behind exactly 16, 17, 32, 33, 48, 49 and 62 history
+    coefficients (the last at 63); block 9 - H H 0 sixteen times from 1 on, history to 54, a new coefficient at 55: the writer's ZRL
+    runs over 16 zero-history positions with 32 history coefficients between them; block 10 - new coefficients behind fields of 16 and
+    then 17; block 11 - none (the scan ends inside an EOB run)."""
+    rng = np.random.RandomState(41)
+    coef = np.zeros((12, 64), dtype=np.int64)
+    coef[:, 0] = rng.randint(-60, 60, size=12)
+    history = rng.choice([-1, 1], size=(12, 64)) * rng.randint(2, 8, size=(12, 64))
+    for b in range(12):
+        for k in range(1, 64):
+            coef[b, ref_jpeg.ZIGZAG[k]] = history[b, k]
+    for b, n in zip(range(2, 9), (16, 17, 32, 33, 48, 49, 62)):
+        coef[b, ref_jpeg.ZIGZAG[n + 1]] = 1 if b & 1 else -1
+    for k in range(3, 49, 3):
+        coef[9, ref_jpeg.ZIGZAG[k]] = 0
+    coef[9, ref_jpeg.ZIGZAG[55]] = -1
+    coef[10, ref_jpeg.ZIGZAG[17]], coef[10, ref_jpeg.ZIGZAG[35]] = 1, -1
+    return write(48, 16, coef, QUANT_PLAIN, _script_default(1), components=1)
+
+
+DC_SLOTS = {"420": (128, (2, 2), 1), "422": (96, (2, 1), 8), "444": (80, (1, 1), 0)}   # sampling -> (size, factors, the seed found)
+
+
+def _dc_slots_file(size, sampling, seed):
+    coef = _small_coef(_blocks(size, size, sampling), seed)
+    coef[:, 0] = np.random.RandomState(1000 + seed).randint(-1000, 1000, size=len(coef))
+    return write(size, size, coef, QUANT_PLAIN, _script_default(3, al=0), sampling=sampling)
+
+
+def _dc_entry_slots(data):
+    met = {}
+    ref_jpeg_prog.entropy_decode(ref_jpeg_prog.parse(data), met)
+    return met["dc_entry_slots"]
+
+
+def dc_slots_ok(slots, sampling):
+    """At least three distinct slots at the subsequences' first blocks, a chroma slot among them and a luma slot above 0 (4:4:4 has
+    the one luma slot: there the three are all there are)."""
+    luma = sampling[0] * sampling[1]
+    return len(slots) >= 3 and any(s >= luma for s, _ in slots) and (luma == 1 or any(0 < s < luma for s, _ in slots))
+
+
+def forced_dc_slots(key):
+    """size x size colour, DC values from -1000 .. 999 (differences of up to 11 bits), small AC; the interleaved DC-first scan is longer
+    than three subsequences and their first blocks lie at three slots of the MCU at least: the first of 64 seeds from the one found."""
+    size, sampling, first = DC_SLOTS[key]
+    for seed in range(first, first + 64):
+        data = _dc_slots_file(size, sampling, seed)
+        if dc_slots_ok(_dc_entry_slots(data), sampling):
+            return data
+    raise AssertionError("no seed gives the slots")
+
+
+def _rst_every_block_coef():
+    return _small_coef(289, 43)
+
+
+def forced_rst_every_block(fill=0):
+    """136 x 136 grey, 17 x 17 blocks, DRI 1: 289 restart intervals in each of the 6 scans."""
+    return write(136, 136, _rst_every_block_coef(), QUANT_PLAIN, _script_default(1), components=1, restart=1, fill=fill)
+
+
+WIDE_FIRST = {False: (384, 0), True: (216, 5)}   # 16-bit codes or not -> (size, the seed found)
+
+
+def _wide_first_file(size, seed, long_codes):
+    """Half the blocks carry all 63 AC coefficients in -12 .. 12 without a zero, the others DC alone (EOB runs between them)."""
+    rng = np.random.RandomState(seed)
+    n = (size // 8) ** 2
+    coef = np.zeros((n, 64), dtype=np.int64)
+    coef[:, 0] = rng.randint(-60, 60, size=n)
+    full = rng.randint(0, 2, size=n).astype(bool)
+    values = rng.choice([-1, 1], size=(n, 63)) * rng.randint(1, 13, size=(n, 63))
+    coef[full, 1:] = values[full]
+    script = [dict(s, long=long_codes and s["ss"] > 0 and s["ah"] == 0) for s in _script_default(1)]
+    return write(size, size, coef, QUANT_PLAIN, script, components=1)
+
+
+def wide_first_seams(data):
+    """The file's band 6 .. 63 first scan: (subsequences, a multiple of 256 of the first scans' lane order strictly inside one of
+    its intervals, the three seam counts)."""
+    h = ref_jpeg_prog.parse(data)
+    met = {}
+    ref_jpeg_prog.entropy_decode(h, met)
+    k = [s[1:4] for s in met["scans"]].index((6, 63, 0))
+    lane = sum(n for s, n in zip(met["scans"][:k], met["subsequences"][:k]) if s[3] == 0)   # (no DRI: an interval each)
+    inside = any(lane < g < lane + met["subsequences"][k] for g in range(SYNC_LANES, lane + met["subsequences"][k], SYNC_LANES))
+    return met["subsequences"][k], inside, tuple(met[key][k] for key in ("eob_run_ends_subsequence", "symbol_straddles_subsequence", "eobn_straddles_subsequence"))
+
+
+def forced_wide_first(long_codes=False):
+    size, first = WIDE_FIRST[long_codes]
+    for seed in range(first, first + 64):
+        data = _wide_first_file(size, seed, long_codes)
+        subs, inside, counts = wide_first_seams(data)
+        if subs > SYNC_LANES and inside and all(counts):
+            return data
+    raise AssertionError("no seed gives the seams")
+
+
+def chunk_seams(data):
+    """Where the bytes of the scans behind the first lie relative to the byte kernels' units, restated from the parsed file: virtual
+    byte = the scan's vfirst (the running sum of the scans' lengths, each rounded up to 64, an empty scan 64) + the offset in the scan.
+    -> the set of seams met: ("ff00" | "rst" | "fill", 64 | 256) for an FF 00 pair's FF, an RSTn's own FF, or a fill FF in front of an
+    RSTn, as the last byte of a 64-byte chunk that ends no workgroup, or of a 256-byte workgroup; ("length", 0 | 1) for a scan of a
+    multiple of 64 bytes, or one more."""
+    h = ref_jpeg_prog.parse(data)
+    met, vfirst = set(), 0
+    for number, scan in enumerate(h["scans"]):
+        s0, s1 = scan["range"]
+        b = data[s0:s1]
+        if number:
+            if len(b) and len(b) % CHUNK in (0, 1):
+                met.add(("length", len(b) % CHUNK))
+            for i in range(len(b) - 1):
+                v = vfirst + i
+                if b[i] != 0xFF or v % CHUNK != CHUNK - 1:
+                    continue
+                unit = GROUP if v % GROUP == GROUP - 1 else CHUNK
+                q = i + 1
+                while q < len(b) and b[q] == 0xFF:
+                    q += 1
+                if b[i + 1] == 0:
+                    met.add(("ff00", unit))
+                elif 0xD0 <= b[i + 1] <= 0xD7:
+                    met.add(("rst", unit))
+                elif q < len(b) and 0xD0 <= b[q] <= 0xD7:
+                    met.add(("fill", unit))
+        vfirst += -(-len(b) // CHUNK) * CHUNK if len(b) else CHUNK
+    return met
+
+
+CHUNK_SEAMS = {("ff00", 64), ("ff00", 256), ("rst", 64), ("rst", 256), ("fill", 64), ("length", 0), ("length", 1)}
+CHUNK_SEAMS_FILE = (9, 66)   # blocks across and down, the seed: what a search over sides 6 up, 300 seeds each, found first
+
+
+def _chunk_seams_file(side, seed):
+    """side x side grey blocks, DRI 1, FF FF fill: an interval of a DC-refinement scan is one bit and seven pad bits, the byte 7F, or FF 00
+    where the bit is set, so the two low bits of the DC values lay out the two DC-refinement scans (Al = 1 and 0) byte by byte; they
+    are random by the seed, and the last blocks' are then set or cleared until the scan's length is 0, and the last scan's 1, modulo 64
+    (the last scan holds the two fill bytes in front of EOI)."""
+    n = side * side
+    rng = np.random.RandomState(seed)
+    coef = _small_coef(n, 49)
+    coef[:, 1:] *= 4   # (the AC first scans are at Al = 3)
+    low = rng.randint(0, 2, size=(2, n))
+    for row, want, tail in ((low[0], 0, 0), (low[1], 1, 2)):
+        length = lambda: n + int(row.sum()) + 4 * (n - 1) + tail   # noqa: E731
+        more = (want - length()) % CHUNK
+        flip, value = (more, 1) if more <= n - int(row.sum()) else (CHUNK - more, 0)   # (where neither can be had the search goes on)
+        row[[k for k in range(n - 1, -1, -1) if row[k] != value][:flip]] = value
+    coef[:, 0] = 4 * rng.randint(-15, 15, size=n) + 2 * low[0] + low[1]
+    return write(8 * side, 8 * side, coef, QUANT_PLAIN, _script_default(1, al=2), components=1, restart=1, fill=2)
+
+
+def forced_chunk_seams():
+    side, first = CHUNK_SEAMS_FILE
+    for seed in range(first, first + 10000):
+        data = _chunk_seams_file(side, seed)
+        if chunk_seams(data) >= CHUNK_SEAMS:
+            return data
+    raise AssertionError("no seed gives the seams")
+
+
+def forced_mozjpeg_420_rst(restart):
+    return write(33, 47, _small_coef(_blocks(33, 47, (2, 2)), 21), QUANT_PLAIN, _script_mozjpeg(3), sampling=(2, 2), restart=restart)
+
+
+REFINE_TAILS = [8 * n - 3 for n in range(1, 18)] + [8, 64, 72, 128, 136]   # the bits of each block's interval in the last refinement
+
+
+def forced_refine_tails():
+    """One row of 22 grey blocks, DRI 1.  Block b's coefficients 1 .. m are all non-zero, new ones (|v| = 1: a 2-bit code and a sign)
+    and history (|v| = 2, 3: a correction bit), the last of them history, then zeros: the interval of the last refinement (Al = 0) is
+    3 new + history + 2 (EOB) bits long, REFINE_TAILS[b] - 1 .. 17 bytes, and five of them end on their last correction bit."""
+    rng = np.random.RandomState(47)
+    coef = np.zeros((len(REFINE_TAILS), 64), dtype=np.int64)
+    coef[:, 0] = rng.randint(-60, 60, size=len(coef))
+    for b, bits in enumerate(REFINE_TAILS):
+        new = max(0, -(-(bits - 2 - 62) // 2))   # 3 new + history = bits - 2 in at most 62 positions ...
+        new += int(rng.randint(0, (bits - 3) // 3 - new + 1))   # ... and a history coefficient at least
+        kinds = [1] * new + [0] * (bits - 2 - 3 * new - 1)
+        rng.shuffle(kinds)
+        for k, is_new in enumerate(kinds + [0], 1):
+            coef[b, ref_jpeg.ZIGZAG[k]] = int(rng.choice([-1, 1])) * (1 if is_new else int(rng.randint(2, 4)))
+    return write(8 * len(coef), 8, coef, QUANT_PLAIN, _script_default(1), components=1, restart=1)
+
+
+AL_HIGH = (5, 6)   # the Al of the DC's and of the AC bands' first scans
+
+
+def forced_al_high():
+    """32 x 32 grey: the rounded forward DCT of a two-level noise picture under a quantisation table of ones - an encoder's magnitudes, up to
+    category 9 -, the DC sent at Al = 5 and refined five times, the AC bands at Al = 6 and refined six times."""
+    k = np.arange(8)
+    d = np.sqrt(0.25) * np.cos((2 * k[None, :] + 1) * k[:, None] * np.pi / 16)
+    d[0] = np.sqrt(0.125)
+    pixels = np.random.RandomState(48).choice([0.0, 255.0], size=(32, 32)) - 128   # two-level noise: AC magnitudes past 255
+    coef = np.array([np.rint(d @ pixels[y:y + 8, x:x + 8] @ d.T).reshape(64) for y in range(0, 32, 8) for x in range(0, 32, 8)]).astype(np.int64)
+    dc_al, ac_al = AL_HIGH
+    script = [S([0], 0, 0, 0, dc_al), S([0], 1, 5, 0, ac_al), S([0], 6, 63, 0, ac_al)]
+    script += [S([0], 1, 63, ah, ah - 1) for ah in range(ac_al, 0, -1)] + [S([0], 0, 0, ah, ah - 1) for ah in range(dc_al, 0, -1)]
+    return write(32, 32, coef, [1] * 64, script, components=1)
+
+
 FORCED = {"p_mozjpeg_420": forced_mozjpeg_420, "p_y_then_chroma_422": forced_y_then_chroma_422, "p_refine_444": forced_refine_444,
           "p_refine_grey_rst": forced_refine_grey_rst, "p_codes16": forced_codes16, "p_eob16384": forced_eob16384}
+SEAMS = {"p_dense_history": forced_dense_history, "p_dc_slots_420": lambda: forced_dc_slots("420"), "p_dc_slots_422": lambda: forced_dc_slots("422"),
+         "p_dc_slots_444": lambda: forced_dc_slots("444"), "p_rst_every_block": forced_rst_every_block,
+         "p_rst_every_block_fill": lambda: forced_rst_every_block(fill=1), "p_wide_first": forced_wide_first,
+         "p_wide_first_codes16": lambda: forced_wide_first(True), "p_mozjpeg_420_rst5": lambda: forced_mozjpeg_420_rst(5),
+         "p_mozjpeg_420_rst1": lambda: forced_mozjpeg_420_rst(1), "p_refine_tails": forced_refine_tails, "p_al_high": forced_al_high,
+         "p_chunk_seams": forced_chunk_seams}
+FORCED.update(SEAMS)
 # the writer's files with every coefficient sent down to Al = 0: the same coefficients make a baseline file
 COEFFICIENTS = {
     "p_mozjpeg_420": lambda: (33, 47, _small_coef(_blocks(33, 47, (2, 2)), 21), dict(sampling=(2, 2))),
@@ -316,7 +537,7 @@ ENCODED = {
     "q_flat256_420": lambda: _pillow(256, 256, "flat", quality=90, subsampling=2),
 }
 FOCAL = {"q_exif": 28}
-IN_ENCODER_RANGE = ("p_mozjpeg_420", "p_y_then_chroma_422", "p_refine_444", "p_refine_grey_rst", "p_codes16", "p_eob16384")
+IN_ENCODER_RANGE = ("p_mozjpeg_420", "p_y_then_chroma_422", "p_refine_444", "p_refine_grey_rst", "p_codes16", "p_eob16384") + tuple(sorted(SEAMS))
 
 
 def names():
@@ -378,4 +599,41 @@ def refused():
     good = w(full)
     body = good.rindex(b"\xff\xda") + 10   # the last scan's first entropy byte
     out["scan_cut_short"] = (good[:body + (len(good) - 2 - body) // 2], I)
+    return out
+
+
+def _scan_range(data, ss, ah, al):
+    return next(s["range"] for s in ref_jpeg_prog.parse(data)["scans"] if (s["ss"], s["ah"], s["al"]) == (ss, ah, al))
+
+
+REFUSED_SEAMS = ("cut_in_a_63_bit_field", "cut_on_a_subsequence_boundary", "misnumbered_rst_257")   # refused_seams()'s names, without building it
+
+
+@functools.lru_cache(maxsize=None)
+def refused_seams():
+    """name -> (file, code): the seam scenes broken at their seams; the scans behind the broken one stay, so the progression is whole."""
+    out = {}
+    # the band's last refinement cut 4 bytes in: an EOB1 code, its bit, and the data ends inside block 0's 63-bit correction field
+    dense = scene("p_dense_history")
+    s0, s1 = _scan_range(dense, 1, 1, 0)
+    assert 0xFF not in dense[s0:s0 + 4]
+    out["cut_in_a_63_bit_field"] = (dense[:s0 + 4] + dense[s1:], ref_jpeg.INVALID)
+    # the band 6 .. 63 first scan cut behind half its data bytes rounded down to a multiple of 128: the data ends on a subsequence
+    # boundary with blocks missing
+    wide = scene("p_wide_first")
+    s0, s1 = _scan_range(wide, 6, 0, 2)
+    clean = len(wide[s0:s1].replace(b"\xff\x00", b"\xff"))
+    want, at, seen = clean // 2 // 128 * 128, s0, 0
+    while seen < want:
+        at += 2 if wide[at] == 0xFF else 1
+        seen += 1
+    assert want >= 128 * SYNC_LANES // 2 and len(wide[s0:at].replace(b"\xff\x00", b"\xff")) == want
+    out["cut_on_a_subsequence_boundary"] = (wide[:at] + wide[s1:], ref_jpeg.INVALID)
+    # marker 257 (counted from 0: RST1) of the fourth scan numbered RST2
+    rst = scene("p_rst_every_block")
+    s0, s1 = ref_jpeg_prog.parse(rst)["scans"][3]["range"]
+    markers = [i for i in range(s0, s1 - 1) if rst[i] == 0xFF and 0xD0 <= rst[i + 1] <= 0xD7]
+    assert len(markers) == 288 and rst[markers[257] + 1] == 0xD1
+    out["misnumbered_rst_257"] = (rst[:markers[257] + 1] + b"\xd2" + rst[markers[257] + 2:], ref_jpeg.INVALID)
+    assert tuple(sorted(out)) == REFUSED_SEAMS
     return out

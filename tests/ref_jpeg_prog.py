@@ -288,7 +288,7 @@ def intervals(data, scan):
 
 class _Bits:
     def __init__(self, seg, met):
-        self.buf, self.p, self.nbits, self.met = seg + PAD, 0, 8 * len(seg), met
+        self.buf, self.p, self.nbits, self.met, self.last_correction = seg + PAD, 0, 8 * len(seg), met, -1
 
     def get(self, n):
         if n == 0:
@@ -328,8 +328,16 @@ def _refine_block(bits, row, ss, se, al, lut, eobrun, met):
 
     def correct(z):
         v = row[z]
-        if bits.get(1) and (v & p1) == 0:
+        bit = bits.get(1)
+        bits.last_correction = bits.p
+        if bit and (v & p1):
+            met["correction_on_set_bit"] += 1
+        if bit and (v & p1) == 0:
             row[z] = _wrap16(v + p1 if v >= 0 else v - p1)
+
+    def field(n):   # what correct_wave reads at once: the corrections between the walk's position and its target
+        if n:
+            met["correction_field_bits"].add(n)
 
     if eobrun == 0:
         while k <= se:
@@ -349,6 +357,7 @@ def _refine_block(bits, row, ss, se, al, lut, eobrun, met):
             else:
                 met["zrl_in_refinement"] = True
             # skip r zero-history coefficients, a correction bit for every non-zero one on the way; stop AT the next zero one
+            p0 = bits.p
             while True:
                 if k > se:
                     _fail(INVALID, "a run past Se")
@@ -356,12 +365,16 @@ def _refine_block(bits, row, ss, se, al, lut, eobrun, met):
                 if row[z]:
                     if s == 0:
                         met["zrl_over_history"] = True
+                        met["zrl_history_between"] = max(met["zrl_history_between"], bits.p - p0 + 1)
                     correct(z)
                 else:
                     r -= 1
                     if r < 0:
                         break
                 k += 1
+            field(bits.p - p0)
+            if bits.p - p0:
+                met["correction_field_bits_before_new" if s else "correction_field_bits_before_zrl"].add(bits.p - p0)
             if s:
                 row[ZIGZAG[k]] = value
                 placed = True
@@ -374,6 +387,9 @@ def _refine_block(bits, row, ss, se, al, lut, eobrun, met):
             if row[ZIGZAG[k]]:
                 correct(ZIGZAG[k])
             k += 1
+        field(bits.p - p0)
+        if entered_in_run and bits.p - p0:
+            met["correction_field_bits_in_eob_run"].add(bits.p - p0)
         if entered_in_run and bits.p > p0:
             met["corrections_in_eob_run"] = True
         eobrun -= 1
@@ -385,7 +401,19 @@ def entropy_decode(h, met=None):
     met = {} if met is None else met
     met.update({"scans": [], "longest_eob_run": 0, "zrl_in_refinement": False, "zrl_over_history": False, "new_at_se_in_refinement": False,
                 "history_after_last_new": False, "corrections_in_eob_run": False, "eob_run_ends_scan": False, "subsequences": [],
-                "intervals": 0, "longest_code": 0})
+                "intervals": 0, "longest_code": 0,
+                # the seams of DESIGN.md 4.22's units.  Sets of widths of the fields correct_wave reads at once (all; in front of a new
+                # coefficient; in front of a ZRL's target; by a block entered inside an EOB run); a correction bit 1 on a set bit
+                "correction_field_bits": set(), "correction_field_bits_before_new": set(), "correction_field_bits_before_zrl": set(),
+                "correction_field_bits_in_eob_run": set(), "correction_on_set_bit": 0, "zrl_history_between": 0,
+                # (slot, blocks of the scan MCU) at which a subsequence behind an interval's first begins in an interleaved DC-first scan
+                "dc_entry_slots": set(),
+                # per scan (0 where it is not an AC-first scan): EOBn, n >= 1, whose last bit is the last in front of a subsequence
+                # boundary inside its interval; symbols with their value bits, and EOBn with their run bits, on both sides of one
+                "eob_run_ends_subsequence": [], "symbol_straddles_subsequence": [], "eobn_straddles_subsequence": [],
+                # the byte lengths of the intervals of the file's last AC-refinement scan; the AC-refinement intervals whose last
+                # correction bit is the last bit of their last byte (no pad bit)
+                "refine_interval_bytes": set(), "refine_interval_without_pad": 0})
     n_blocks = h["mcus_x"] * h["mcus_y"] * h["bpm"]
     coef = [[0] * 64 for _ in range(n_blocks)]
     data = h["data"]
@@ -399,15 +427,27 @@ def entropy_decode(h, met=None):
         subs = 0
         parts = intervals(data, scan)
         met["intervals"] += len(parts)
+        seams = {"eob_run_ends_subsequence": 0, "symbol_straddles_subsequence": 0, "eobn_straddles_subsequence": 0}
+        if ss > 0 and ah:
+            met["refine_interval_bytes"] = {len(seg) for seg, _ in parts}
+        per_mcu = len(mcu_blocks(h, comps, 0, scan["across"]))
         for j, (seg, _where) in enumerate(parts):
             subs += max(1, -(-8 * len(seg) // SUBSEQ_BITS))
             bits = _Bits(seg, met)
             pred = {c: 0 for c in comps}
             eobrun = 0
             last_in_run = False
+            boundary = SUBSEQ_BITS   # the first bit of the interval's next subsequence
+
+            def crosses(p0, p1):   # bits p0 .. p1 - 1 lie on both sides of a subsequence boundary of the interval
+                return p0 // SUBSEQ_BITS != (p1 - 1) // SUBSEQ_BITS
+
             for m in range(j * ri, min((j + 1) * ri, scan["mcus"])):
-                for c, idx in mcu_blocks(h, comps, m, scan["across"]):
+                for slot, (c, idx) in enumerate(mcu_blocks(h, comps, m, scan["across"])):
                     row = coef[idx]
+                    if ss == 0 and ah == 0 and len(comps) > 1 and boundary <= bits.p < bits.nbits:
+                        met["dc_entry_slots"].add((slot, per_mcu))   # the lane of this subsequence starts at this block
+                        boundary = (bits.p // SUBSEQ_BITS + 1) * SUBSEQ_BITS
                     if ss == 0 and ah == 0:
                         s = bits.symbol(dc_lut[c])
                         pred[c] += _extend(bits.get(s), s)
@@ -422,6 +462,7 @@ def entropy_decode(h, met=None):
                         else:
                             k = ss
                             while k <= se:
+                                p0 = bits.p
                                 sym = bits.symbol(ac_lut)
                                 r, s = sym >> 4, sym & 15
                                 if s:
@@ -429,6 +470,7 @@ def entropy_decode(h, met=None):
                                     if k > se:
                                         _fail(INVALID, "a run past Se")
                                     row[ZIGZAG[k]] = _wrap16(_extend(bits.get(s), s) * (1 << al))
+                                    seams["symbol_straddles_subsequence"] += crosses(p0, bits.p)
                                     k += 1
                                 elif r == 15:
                                     if k + 16 > se + 1:
@@ -437,6 +479,9 @@ def entropy_decode(h, met=None):
                                 else:
                                     eobrun = (1 << r) + bits.get(r)
                                     met["longest_eob_run"] = max(met["longest_eob_run"], eobrun)
+                                    if r:
+                                        seams["eobn_straddles_subsequence"] += crosses(p0, bits.p)
+                                        seams["eob_run_ends_subsequence"] += bits.p % SUBSEQ_BITS == 0 and bits.p < bits.nbits
                                     eobrun -= 1
                                     break
                     else:
@@ -446,7 +491,11 @@ def entropy_decode(h, met=None):
                         _fail(INVALID, "the data ends before the scan's last block")
             if ss > 0 and j + 1 == len(parts) and last_in_run and eobrun == 0:
                 met["eob_run_ends_scan"] = True
+            if ss > 0 and ah and bits.nbits and bits.p == bits.nbits == bits.last_correction:
+                met["refine_interval_without_pad"] += 1
         met["subsequences"].append(subs)
+        for key, n in seams.items():
+            met[key].append(int(n))
     return np.array(coef, dtype=np.int64).astype(np.int16), met
 
 

@@ -44,7 +44,11 @@ def test_pixels_are_the_restated_pixels(gpu_device, name):
     whose AC-first scan has more than 256 subsequences, a flat 256 x 256 image (long EOB runs); and the writer's files: DC
     scans per component and three refinement passes, Y alone and then Cb + Cr with DRI changing between scans, the refinement
     cases (ZRL over history, a new coefficient at Se, history behind the last new one, correction bits inside an EOB run, a
-    run that ends on the scan's last block) with and without restart intervals, 16-bit codes, an EOB run of 16384 blocks.
+    run that ends on the scan's last block) with and without restart intervals, 16-bit codes, an EOB run of 16384 blocks; and
+    the seam scenes (jpeg_prog_scenes.SEAMS; tests/test_jpeg_prog_ref.py proves each reaches its seam): correction fields of every
+    piece count, subsequences of an interleaved DC scan that begin inside the MCU, 289 restart intervals in every scan, a
+    workgroup seam inside a later first scan with EOB runs, the byte kernels' 64- and 256-byte edges in later scans, per-component
+    DC scans of a 4:2:0 file under DRI 5 and 1, refinement intervals of 1 .. 17 bytes, Al = 5 and 6.
     The counts of the last decode are the restatement's."""
     data = jpeg_prog_scenes.scene(name)
     want = jpeg_prog_scenes.restated(name)
@@ -69,6 +73,26 @@ def test_the_noise_scene_needs_more_than_one_workgroup(gpu_device):
     assert stats["intervals"] == stats["scans"] and stats["subsequences"] > 256 and stats["sync_launches"] >= 2 and stats["workgroup_rounds"] >= 1
     image.decode_jpeg_progressive(gpu_device, jpeg_prog_scenes.scene("q_8x8_444"), "L")
     assert image.jpeg_progressive_last_stats()["sync_launches"] == 1
+
+
+@pytest.mark.parametrize("name", ["p_wide_first", "p_wide_first_codes16"])
+def test_the_wide_first_scenes_need_more_than_one_workgroup(gpu_device, name):
+    """The workgroup seam lies inside the band 6 .. 63 first scan, behind the DC and band 1 .. 5 scans' lanes, where an EOB run's
+    blocks are counted across it."""
+    image.decode_jpeg_progressive(gpu_device, jpeg_prog_scenes.scene(name), "L")
+    stats = image.jpeg_progressive_last_stats()
+    assert stats["intervals"] == stats["scans"] == 6 and stats["subsequences"] > 256 and stats["sync_launches"] >= 2 and stats["workgroup_rounds"] >= 1
+    assert stats["longest_eob_run"] == jpeg_prog_scenes.restated(name)["met"]["longest_eob_run"] >= 4
+
+
+def test_a_restart_interval_per_block_in_every_scan(gpu_device):
+    """289 intervals in each of 6 scans: the interval and scan searches, the marker numbering and the segment kernel past one workgroup
+    of intervals, 578 refinement waves in two launches; with and without a fill byte."""
+    for name in ("p_rst_every_block", "p_rst_every_block_fill"):
+        assert same(image.decode_jpeg_progressive(gpu_device, jpeg_prog_scenes.scene(name), "L"), jpeg_prog_scenes.restated(name)["luma"])
+        stats = image.jpeg_progressive_last_stats()
+        assert stats["intervals"] == 1734 and stats["subsequences"] == 1734 and stats["scans"] == 6
+        assert (stats["ac_refinement_scans"], stats["ac_refinement_launches"]) == (2, 2)
 
 
 def _call(device, data, fmt, drop, out, cap):
@@ -128,18 +152,14 @@ def test_one_scene_every_way_out(gpu_device):
         assert _call(gpu_device, data, fmt, 0, p, size) == (0, size) and same(buf.reshape(pixels.shape), pixels)
 
 
-@pytest.mark.parametrize("name", sorted(jpeg_prog_scenes.refused()))
-def test_refused_files_leave_the_buffer_alone(gpu_device, name):
-    """Incomplete progressions, a multi-scan SOF0 file and a baseline file (UNSUPPORTED: outside SOF2), scan headers outside
-    T.81 G.1, s = 2 in a refinement, a scan cut short, a misnumbered and a missing RSTn (INVALID): the code, and not a byte of `out` written."""
+def _refused_leaves_the_buffer_alone(gpu_device, data, code, size=1 << 16):
     import torch
 
-    data, code = jpeg_prog_scenes.refused()[name]
-    buf = np.full(1 << 16, 0xA5, dtype=np.uint8)
+    buf = np.full(size, 0xA5, dtype=np.uint8)
     for fmt in (ref_jpeg_prog.LUMA8, ref_jpeg_prog.RGB8):
         assert _call(gpu_device, data, fmt, 0, C.c_void_p(buf.ctypes.data), buf.size)[0] == code
         assert (buf == 0xA5).all()
-    d_out = torch.full((1 << 16,), 0x5A, dtype=torch.uint8, device="cuda")
+    d_out = torch.full((size,), 0x5A, dtype=torch.uint8, device="cuda")
     torch.cuda.synchronize()
     assert _call(gpu_device, data, ref_jpeg_prog.RGB8, 0, C.c_void_p(d_out.data_ptr()), d_out.numel())[0] == code
     torch.cuda.synchronize()
@@ -147,6 +167,27 @@ def test_refused_files_leave_the_buffer_alone(gpu_device, name):
     with pytest.raises(_lib.CvhipError) as raised:
         image.decode_jpeg_progressive(gpu_device, data, "RGB")
     assert raised.value.code == code
+
+
+@pytest.mark.parametrize("name", sorted(jpeg_prog_scenes.refused()))
+def test_refused_files_leave_the_buffer_alone(gpu_device, name):
+    """Incomplete progressions, a multi-scan SOF0 file and a baseline file (UNSUPPORTED: outside SOF2), scan headers outside
+    T.81 G.1, s = 2 in a refinement, a scan cut short, a misnumbered and a missing RSTn (INVALID): the code, and not a byte of `out` written."""
+    _refused_leaves_the_buffer_alone(gpu_device, *jpeg_prog_scenes.refused()[name])
+
+
+@pytest.mark.parametrize("name", jpeg_prog_scenes.REFUSED_SEAMS)
+def test_refused_seams_leave_the_buffer_alone(gpu_device, name):
+    """A refinement scan that ends inside a 63-bit correction field, a first scan that ends on a subsequence boundary with blocks
+    missing, marker 257 of a later scan misnumbered (INVALID): the code, and not a byte of `out` written.  The walk accepts these
+    files, so the sizing call answers, and the buffers hold the whole RGB8 image and 16 bytes more: the capacity check passes and the
+    refusal is the kernels'."""
+    data, code = jpeg_prog_scenes.refused_seams()[name]
+    info = ref_jpeg_prog.info(data)
+    rgb_bytes = info["width"] * info["height"] * 3
+    assert _call(gpu_device, data, ref_jpeg_prog.RGB8, 0, None, 0) == (0, rgb_bytes)
+    assert _call(gpu_device, data, ref_jpeg_prog.LUMA8, 0, None, 0) == (0, rgb_bytes // 3)
+    _refused_leaves_the_buffer_alone(gpu_device, data, code, size=rgb_bytes + 16)
 
 
 @pytest.mark.parametrize("name", sorted(jpeg_prog_scenes.COEFFICIENTS))

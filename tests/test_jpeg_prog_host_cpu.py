@@ -82,6 +82,19 @@ def test_refused_files(exe, tmp_path):
         assert got["code"] == code or (got["code"] == 0 and got["decode"] == code), name   # (the program's walk cuts the intervals too)
 
 
+def test_refused_seams(exe, tmp_path):
+    """The seam scenes broken at their seams: the walk takes the misnumbered RSTn when it cuts the intervals, the two cut scans walk
+    and their entropy decode refuses them."""
+    for name, (data, code) in sorted(jpeg_prog_scenes.refused_seams().items()):
+        (tmp_path / "in.jpg").write_bytes(data)
+        got = json.loads(_run(exe, "parse", tmp_path / "in.jpg"))
+        ref_jpeg_prog.parse(data)
+        if name == "misnumbered_rst_257":
+            assert got["code"] == code and got["reason"] == "a misnumbered or surplus RSTn"
+        else:
+            assert got["code"] == 0 and got["decode"] == code, name
+
+
 @pytest.mark.parametrize("name", ["q_17x9_420", "p_refine_grey_rst"])
 def test_truncations_and_corruptions(exe, tmp_path, name):
     data = jpeg_prog_scenes.scene(name)
